@@ -6,7 +6,11 @@ One "step" = one full WaveGlow.forward over one synthetic batch already resident
 including the per-forward weight-norm recompute + weight packing the reference also pays
 (torch.nn.utils.weight_norm hooks, reference glow.py:123-151).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line; `--dump-outputs DIR` then also writes what the
+last timed step returned (rank 0) as DIR/<name>.npy.  Everything else this script measures (the gate GEMM roofline, the train
+blocks, WaveGlow infer, Tacotron, the CPU baseline) runs only with `--full`.
 
 For N > 1 either the driver launches one rank per GPU with torch.distributed.run, or - when the
 command above is run directly (no RANK in the environment) - this script starts
@@ -15,10 +19,10 @@ touches the GPU and exits with the child's code (the reference ships the same ki
 waveglow/distributed.py:145-170).  The forward pass of independent batches needs no collective, so
 ranks only meet at the timing barriers ("weak" scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fused in+cond+gate GEMM),
+Prints ONE JSON line (rank 0).  With --full: `roofline` is for the dominant kernel (the fused in+cond+gate GEMM),
 timed live with HIP events on the launch stream; `cpu_baseline` is the CPU oracle (a port of the
 reference's torch op sequence) timed on this host at N=1 with BASELINE.md section 4's protocol.
-Extra blocks on the same line: `tacotron` (mel-frames/s, the second half of BASELINE.json's metric),
+Extra blocks on the same line (--full): `tacotron` (mel-frames/s, the second half of BASELINE.json's metric),
 `waveglow_train` / `tacotron_train` (BASELINE configs[3] / configs[1] train steps at N=1) and, at
 N > 1, `waveglow_train_dp` (the data-parallel train step over RCCL, BASELINE configs[3]).
 """
@@ -44,24 +48,71 @@ def log(msg):
     print("[bench] " + msg, file=sys.stderr, flush=True)
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--segment", type=int, default=16000)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: gate GEMM roofline, train blocks, WaveGlow infer, "
+                         "Tacotron, CPU baseline (the --no-* options below drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all (a fixed seeded sample of each array beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tacotron", action="store_true", help="skip the Tacotron mel-frames/s block (N=1 only)")
     ap.add_argument("--no-train", action="store_true", help="skip the train-step blocks")
-    ap.add_argument("--event-stride", type=int, default=7,
+    ap.add_argument("--event-stride", type=int, default=None,
                     help="time every n-th gate-GEMM launch with a HIP event pair inside the timed region (roofline.avg_launch_ms); "
-                         "1 = every launch, 0 = none (no roofline block).  7 is coprime with the 8 layers of a flow, so every layer / dilation "
-                         "is sampled; an event pair around EVERY launch costs 0.66 ms per forward (3.6 percent), every 7th 0.1 ms")
+                         "1 = every launch, 0 = none (no roofline block); default 7 with --full, 0 without.  7 is coprime with the 8 "
+                         "layers of a flow, so every layer / dilation is sampled; an event pair around EVERY launch costs 0.66 ms per "
+                         "forward (3.6 percent), every 7th 0.1 ms")
     ap.add_argument("--mode", choices=["forward", "train"], default="forward",
                     help="forward: the headline metric (default); train: value = zero_grad+forward+loss+backward+Adam, "
                          "data-parallel over RCCL when launched with N > 1 ranks (BASELINE configs[3])")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.event_stride is None:
+        args.event_stride = 7 if args.full else 0
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def output_arrays(mode, out):
+    """What a caller of the timed step receives, by name: forward -> z, log_s per flow, log_det_W per flow; train -> the loss."""
+    if mode == "train":
+        return {"loss": out}
+    z, log_s, log_det_w = out
+    arrays = {"z": z}
+    arrays.update(("log_s_%02d" % i, t) for i, t in enumerate(log_s))
+    arrays.update(("log_det_W_%02d" % i, t) for i, t in enumerate(log_det_w))
+    return arrays
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each tensor as path/<name>.npy (float64 stays float64, anything else becomes float32).  When the arrays hold more
+    than `limit` bytes, every one is cut to the same fraction of its elements: a sorted sample of its flattened values drawn
+    with a fixed seed, so that two runs of the same command write the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    room = limit - 256 * len(host)          # .npy headers
+    total = sum(a.nbytes for a in host.values())
+    frac = 1.0 if total <= room else room / total
+    for i, (name, a) in enumerate(host.items()):
+        if frac < 1.0:
+            n = int(a.size * frac)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(1000 + i).choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("wrote %d arrays to %s%s" % (len(host), path, "" if frac == 1.0 else " (sampled: %.3g of each)" % frac))
 
 
 def self_launch(args):
@@ -376,7 +427,7 @@ def main():
         return step
 
     def fwd_step():
-        model((mel, audio))
+        return model((mel, audio))
 
     def max_over_ranks(dt):
         if dist is None:
@@ -386,6 +437,11 @@ def main():
         return float(tt.item())
 
     step = make_train_step() if args.mode == "train" else fwd_step
+    last = {}
+
+    def headline_step():        # keeps what the step returned: after the timed loop, the last step's outputs (--dump-outputs)
+        out = step()
+        last["out"] = out.detach() if args.mode == "train" else out        # the loss without its graph
     # the gate GEMM's HIP events are recorded on the launch stream during the timed steps only
     eng.gemm_events = None
     with torch.enable_grad() if args.mode == "train" else torch.no_grad():
@@ -394,10 +450,13 @@ def main():
     torch.cuda.synchronize()
     eng.gemm_events = [] if (rank == 0 and args.mode == "forward" and args.event_stride > 0) else None
     eng.gemm_event_stride = max(1, args.event_stride)
-    dt = max_over_ranks(run_steps(step, args.steps, 0, dist, args.mode == "train"))
+    dt = max_over_ranks(run_steps(headline_step, args.steps, 0, dist, args.mode == "train"))
     evs = eng.gemm_events or []
     eng.gemm_events = None
     log("rank %d: %d steps in %.3f s" % (rank, args.steps, dt))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, output_arrays(args.mode, last["out"]))
+    last.clear()
 
     out = None
     if rank == 0:
@@ -459,7 +518,7 @@ def main():
             out["collective"] = eng.grad_sync.stats()
     # ---- data-parallel WaveGlow train step (BASELINE configs[3]) next to the forward figure, every rank takes part ----
     train_block, train_key = None, None
-    if args.mode == "forward" and not args.no_train:
+    if args.full and args.mode == "forward" and not args.no_train:
         train_key = "waveglow_train" if world == 1 else "waveglow_train_dp"
 
         def give_up():      # a collective that never completes must not cost the headline line: print it, leave non-zero
@@ -522,7 +581,7 @@ def main():
             out["rehearsal"] = "NOT A MEASUREMENT: %d ranks share %d GPU(s), collectives over %s" % (world, torch.cuda.device_count(), rehearse)
         if train_block is not None:
             out[train_key] = train_block
-        if args.gpus == 1 and args.mode == "forward":
+        if args.full and args.gpus == 1 and args.mode == "forward":
             if not args.no_tacotron:
                 # the vocoder direction (BASELINE configs[4] back half): B = 1, reverse flow, weights packed once
                 try:

@@ -85,3 +85,43 @@ def test_avg_op_follows_the_groups_backend():
     from text2speech_amd import distributed as D
     assert D._avg_op("nccl") == dist.ReduceOp.AVG
     assert D._avg_op("gloo") == dist.ReduceOp.SUM
+
+
+def test_bench_plain_run_is_lean_and_full_keeps_the_extras():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline only: no gate-GEMM events in the timed region and
+    no extra blocks; --full brings back today's roofline sampling (every 7th launch)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.event_stride, a.dump_outputs) == (5, 2, False, 0, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert (a.full, a.event_stride, a.dump_outputs) == (True, 7, "d")
+    assert bench.parse_args(["--event-stride", "3"]).event_stride == 3
+
+
+def test_bench_dump_outputs_names_dtypes_and_limit(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    gen = torch.Generator().manual_seed(3)
+    z = torch.randn(2, 8, 100, generator=gen)
+    log_s = [torch.randn(2, 4, 100, generator=gen), torch.randn(2, 3, 100, generator=gen).double()]
+    log_det = [torch.tensor(1.5), torch.tensor(-2.0)]
+    arrays = bench.output_arrays("forward", (z, log_s, log_det))
+    assert list(arrays) == ["z", "log_s_00", "log_s_01", "log_det_W_00", "log_det_W_01"]
+    bench.dump_outputs(str(tmp_path / "full"), arrays)
+    got = {n: np.load(str(tmp_path / "full" / (n + ".npy"))) for n in arrays}
+    assert got["z"].dtype == np.float32 and got["log_s_01"].dtype == np.float64 and got["log_det_W_00"].shape == ()
+    assert np.array_equal(got["z"], z.numpy()) and float(got["log_det_W_01"]) == -2.0
+    # over the limit: every array becomes the same fixed sample of its flattened values, within the limit, run after run
+    limit = 4000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    files = sorted(os.listdir(str(tmp_path / "s1")))
+    assert files == sorted(n + ".npy" for n in arrays)
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in files) <= limit
+    zs = np.load(str(tmp_path / "s1" / "z.npy"))
+    assert 0 < zs.size < z.numel() and np.isin(zs, z.numpy().reshape(-1)).all()
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "s1" / f)), np.load(str(tmp_path / "s2" / f)))
+    assert list(bench.output_arrays("train", torch.tensor(0.25))) == ["loss"]

@@ -18,5 +18,5 @@ python3 tools/bench_e2e.py > "$OUT/e2e.json" 2> /dev/null
 python3 tools/bench_tacotron.py > "$OUT/bench_tacotron.json" 2> /dev/null
 python3 tools/bench_tacotron_train.py > "$OUT/bench_tacotron_train.json" 2> /dev/null
 python3 tools/prof_ops.py tacotron_train > "$OUT/ops_tacotron_train.txt" 2> /dev/null
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "wrote $OUT"

@@ -8,7 +8,7 @@ R=$(pwd)
 OUT=$(realpath -m "${1:-$R/gpurun_out/collect}")
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-tacotron --no-train"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-tacotron --no-train"
 rocprofv3 --kernel-trace --stats -d "$OUT/fwd" -o fw -- $B --steps 5 --warmup 1 > "$OUT/fwd_under_rocprof.json" 2> "$OUT/fwd.err"
 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o f -- $B --steps 2 --warmup 1 > /dev/null 2> "$OUT/pmc_f.err"
 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o w -- $B --steps 2 --warmup 1 > /dev/null 2> "$OUT/pmc_w.err"
@@ -33,7 +33,7 @@ python3 tools/bench_infer_lengths.py > "$OUT/infer_lengths.json" 2> /dev/null
 python3 tools/microbench/sbgemm_bench.py > "$OUT/sbgemm_bench.json" 2> /dev/null
 python3 tools/prof_ops.py waveglow_train > "$OUT/ops_waveglow_train.txt" 2> /dev/null
 python3 tools/prof_ops.py tacotron_train > "$OUT/ops_tacotron_train.txt" 2> /dev/null
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 # round 4: the B = 1 decode chain (streamed gates / folded prenet / location term one launch early, each against its switch), the
 # operand-format A/B and - when the diagnostic builds exist (python -m text2speech_amd.build --variant ...) - the role ablation and the
 # in-kernel stamps of the attention role

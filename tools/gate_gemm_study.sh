@@ -5,7 +5,7 @@ set -uo pipefail
 R=$(pwd)
 OUT=$R/gpurun_out/gg_study
 mkdir -p "$OUT"
-B="python3 $R/bench.py --no-cpu-baseline --no-tacotron --no-train --steps 10 --warmup 2"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-tacotron --no-train --steps 10 --warmup 2"
 line() { python3 -c "
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']
