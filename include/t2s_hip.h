@@ -247,7 +247,9 @@ int t2s_bn_running_update(const float* mean, const float* var, float* running_me
 int t2s_zero_fill(void* p, size_t bytes, void* stream);
 
 /* Encoder BiLSTM recurrence with packed-sequence semantics (tacotron.py:199-207).  gx[B][T][8H] = W_ih x + b_ih + b_hh
- * for both directions (fwd gates then reverse gates), whhT_* = W_hh^T [H][4H]; out[B][T_out][2H]; 4H must be 1024. */
+ * for both directions (fwd gates then reverse gates), whhT_* = W_hh^T [H][4H]; out[B][T_out][2H]; 4H must be 1024.
+ * lengths[b] (NULL: all T) is cut to T_out (<= T): an entry longer than out's rows runs over its first T_out positions, as if its
+ * length were T_out (all four recurrence entry points).  Rows of gates_save / c_save past an entry's length are not written. */
 int t2s_taco_encoder_lstm(const float* gx, const float* whhT_fwd, const float* whhT_rev, const int* lengths, float* out,
                           int B, int T, int H, int T_out, float* gates_save /* [B][T][2][4H] or NULL */,
                           float* c_save /* [B][T][2][H] or NULL */, void* stream);
@@ -262,8 +264,9 @@ int t2s_taco_encoder_lstm_split(const float* gx, const float* whhT_fwd, const fl
                                 int B, int T, int H, int T_out, float* gates_save, float* c_save, void* xbuf, unsigned epoch,
                                 void* stream);
 long t2s_taco_lstm_xbuf_bytes(int B);
-/* BPTT of that recurrence: d_out[B][T_out][2H] -> dgx[B][T][8H] (zero beyond each length), hprev[B][T][2H] (the h each
- * step consumed; the X operand of the W_hh weight-gradient GEMM); whh_* are the natural [4H][H] matrices */
+/* BPTT of that recurrence: d_out[B][T_out][2H] -> dgx[B][T][8H], hprev[B][T][2H] (the h each step consumed; the X operand of
+ * the W_hh weight-gradient GEMM); rows past each length (cut to T_out as above) are not written - the caller clears them.  whh_*
+ * are the natural [4H][H] matrices */
 int t2s_taco_encoder_lstm_bwd(const float* d_out, const float* out, const float* gates_save, const float* c_save,
                               const float* whh_fwd, const float* whh_rev, const int* lengths, float* dgx, float* hprev,
                               int B, int T, int H, int T_out, void* stream);

@@ -78,6 +78,70 @@ def encoder(sd, hp, ids, lengths=None, training=False, masks=None):
     return out
 
 
+def bilstm_recurrence(gx, whh_f, whh_r, lengths, T_out, d_out=None):
+    """The encoder BiLSTM's recurrence alone (packed-sequence semantics, gate order i, f, g, o), in float64 and in the layouts the
+    library's recurrence kernels take and produce (t2s_taco_encoder_lstm[_split], t2s_taco_encoder_lstm_bwd[_split]).
+
+    gx [B][T][8H]: W_ih x + b_ih + b_hh, the forward direction's 4H gate rows then the reverse direction's.  whh_f / whh_r [4H][H]
+    (torch's weight_hh layout).  lengths: B entries, each <= T_out <= T (None: every entry T long).
+    Returns a dict of float64 tensors:
+      out    [B][T_out][2H]  h of both directions, zero past each entry's length;
+      gates  [B][T][2][4H]   post-activation gates (sigmoid i, sigmoid f, tanh g, sigmoid o) per position and direction;
+      c      [B][T][2][H]    cell state;
+      valid  [B][T]          True below each entry's length (the kernels leave the gates / c rows past it unwritten).
+    With d_out [B][T_out][2H] the same call also differentiates sum(out * d_out):
+      dgx    [B][T][8H]      its gradient w.r.t. gx (zero past the lengths);
+      hprev  [B][T][2H]      the h each step's recurrent product read: the direction's previous step, zero at its first step
+                             and past the length."""
+    gx = gx.detach().double().requires_grad_(d_out is not None)
+    B, T, G = gx.shape
+    H = G // 8
+    lens = torch.full((B,), T, dtype=torch.long) if lengths is None else torch.as_tensor(lengths).long().cpu()
+    assert 0 < T_out <= T and 0 < int(lens.max()) <= T_out and int(lens.min()) >= 0
+    S = int(lens.max())
+    bi = torch.arange(B)
+    tt = torch.arange(T)
+    valid = tt[None, :] < lens[:, None]                                         # [B][T]
+    outs, gates, cs = [], [], []
+    for d, w in enumerate((whh_f, whh_r)):
+        w = w.detach().double()
+        h = gx.new_zeros(B, H)
+        c = gx.new_zeros(B, H)
+        hs, gs, cl = [], [], []
+        # the input of step s: position s (forward) / len_b - 1 - s (reverse); one gather, unbound per step (an index per step
+        # would cost a full-size gradient per step in the backward)
+        at = tt[None, :S].expand(B, S) if d == 0 else (lens[:, None] - 1 - tt[None, :S]).clamp(min=0)
+        xs = torch.gather(gx[..., d * 4 * H:(d + 1) * 4 * H], 1, at[..., None].expand(B, S, 4 * H)).unbind(1)
+        for s in range(S):
+            z = xs[s] + h @ w.t()
+            gi, gf = torch.sigmoid(z[:, :H]), torch.sigmoid(z[:, H:2 * H])
+            gg, go = torch.tanh(z[:, 2 * H:3 * H]), torch.sigmoid(z[:, 3 * H:])
+            c2 = gf * c + gi * gg
+            h2 = go * torch.tanh(c2)
+            act = (s < lens)[:, None]                                           # (entries past their length keep h, c)
+            h, c = torch.where(act, h2, h), torch.where(act, c2, c)
+            hs.append(h2)
+            gs.append(torch.cat((gi, gf, gg, go), 1))
+            cl.append(c2)
+        # position t of entry b is step t (forward) / len_b - 1 - t (reverse) of its direction
+        step = (tt[None, :].expand(B, T) if d == 0 else lens[:, None] - 1 - tt[None, :]).clamp(0, S - 1)
+        pick = lambda seq: torch.stack(seq, 0)[step, bi[:, None]] * valid[..., None]
+        outs.append(pick(hs)[:, :T_out])
+        gates.append(pick(gs))
+        cs.append(pick(cl))
+    res = dict(out=torch.cat(outs, 2), gates=torch.stack(gates, 2), c=torch.stack(cs, 2), valid=valid)
+    if d_out is not None:
+        (res["out"] * d_out.double()).sum().backward()
+        res["dgx"] = gx.grad
+        o = res["out"].detach()
+        o = torch.cat((o, o.new_zeros(B, T + 1 - T_out, 2 * H)), 1)              # [B][T + 1][2H], zero rows past T_out
+        hp_f = torch.cat((o.new_zeros(B, 1, H), o[:, :T - 1, :H]), 1)            # forward: step t read h(t - 1)
+        hp_r = o[:, 1:T + 1, H:]                                                  # reverse: step t read h(t + 1), zero at len - 1
+        res["hprev"] = torch.cat((hp_f, hp_r), 2) * valid[..., None]
+        res["out"] = res["out"].detach()
+    return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in res.items()}
+
+
 def prenet(sd, x, mask):
     """Prenet.forward (reference modules.py:19-22); mask [..., 2, prenet_dim] in {0,1}, p = 0.5."""
     for i in range(2):

@@ -134,24 +134,24 @@ def _seeded_masks(B, T_in, T_out, gen):
     return tm, pm, masks
 
 
-@pytest.mark.parametrize("B,T_in,T_out", [
-    (12, 22, 20),     # > 8 items: f32 matrix-core cells (csrc/sbgemm.hip); T_in % 4 != 0: in-loop d_memory accumulation
-    (32, 64, 64),     # BASELINE configs[1] batch (train.py:216-225): two 16-item groups per sbgemm workgroup, deferred d_memory
-])
-def test_step_vs_oracle(B, T_in, T_out):
-    """Loss, the four outputs and every parameter gradient against CPU autograd through the oracle, seeded masks, ragged
-    lengths."""
+def _step_vs_oracle(B, T_in, T_out, in_lens, out_lens, seed=5, max_len=None):
+    """One training step (training-mode forward -> Tacotron2Loss -> backward) against CPU autograd through the oracle, seeded
+    masks: loss, the four outputs (rel 1e-3) and every parameter gradient (rel 5e-3).  max_len: the batch tuple's max_len (default
+    the longest input); the oracle runs on the input lengths clamped to it.  Returns the model (its engine's exchange buffers
+    are checked by the callers)."""
     from oracle import tacotron_oracle as O
     from text2speech_amd.tacotron import Tacotron
     _lib.load()
-    gen = torch.Generator().manual_seed(5)
-    text, in_len, mel_t, gate_t, out_len = _ragged(B, T_in, T_out, gen, din=lambda i: (i * 3) // 2 if B == 12 else i)
+    gen = torch.Generator().manual_seed(seed)
+    text, in_len, mel_t, gate_t, out_len = _ragged(B, T_in, T_out, gen, din=lambda i: T_in - int(in_lens[i]),
+                                                   dout=lambda i: T_out - int(out_lens[i]))
     tm, pm, masks = _seeded_masks(B, T_in, T_out, gen)
     sd = synth.tacotron_state()
     m = Tacotron(HP, 80, num_speakers=2)
     m.load_state_dict(sd, strict=True)
     m = m.to(DEV).train()
-    out = m((text.to(DEV), in_len.to(DEV), mel_t.to(DEV), int(in_len.max()), torch.zeros(B, device=DEV), out_len.to(DEV)),
+    ml = int(in_len.max()) if max_len is None else max_len
+    out = m((text.to(DEV), in_len.to(DEV), mel_t.to(DEV), ml, torch.zeros(B, device=DEV), out_len.to(DEV)),
             prenet_masks=pm, train_masks=tm)
     mt, gt = mel_t.to(DEV), gate_t.to(DEV)
     loss = torch.nn.functional.mse_loss(out[0], mt) + torch.nn.functional.mse_loss(out[1], mt) + \
@@ -160,11 +160,12 @@ def test_step_vs_oracle(B, T_in, T_out):
     torch.cuda.synchronize()
     got = {n: p.grad.detach().cpu() for n, p in m.named_parameters() if p.grad is not None}
     sd_cpu = {k: (v.clone().requires_grad_(True) if v.is_floating_point() else v) for k, v in sd.items()}
-    oo = O.tacotron_forward(sd_cpu, HP, text, in_len, mel_t, out_len, masks, training=True)
+    oo = O.tacotron_forward(sd_cpu, HP, text, in_len.clamp(max=ml), mel_t, out_len, masks, training=True)
     lo = O.tacotron_loss(oo, mel_t, gate_t)
     lo.backward()
     assert abs(float(loss) - float(lo)) < 2e-4 * max(1.0, abs(float(lo)))
     for k in range(4):
+        assert tuple(out[k].shape) == tuple(oo[k].shape), k
         assert _rel(out[k], oo[k].detach()) < 1e-3, k
     worst = []
     for n, v in sd_cpu.items():
@@ -175,6 +176,90 @@ def test_step_vs_oracle(B, T_in, T_out):
         worst.append((0.0 if diff < 2e-5 else _rel(got[n], v.grad), n))
     worst.sort(reverse=True)
     assert worst[0][0] < 5e-3, worst[:6]
+    return m
+
+
+def _edge_lengths(B, T_in, T_out):
+    """Ragged input lengths from T_in down, the last entry 3 long; output lengths from T_out down to 2."""
+    in_len = torch.tensor([T_in - i for i in range(B - 1)] + [3])
+    out_len = torch.tensor([T_out - (i * (T_out - 2)) // max(1, B - 1) for i in range(B)])
+    return in_len, out_len
+
+
+@pytest.mark.parametrize("B,T_in,T_out", [
+    (12, 22, 20),     # > 8 items: f32 matrix-core cells (csrc/sbgemm.hip); T_in % 4 != 0: in-loop d_memory accumulation
+    (32, 64, 64),     # BASELINE configs[1] batch (train.py:216-225): two 16-item groups per sbgemm workgroup, deferred d_memory
+    (32, 512, 12),    # 512 blocks of the one-launch attention forward and of att_bwd_fused (+ the folded attention cell): two rounds
+    (40, 96, 24),     # split encoder BiLSTM past one residency round (320 blocks); a third 16-item group in the matrix-core cells
+    (12, 513, 10),    # just past 512 encoder positions: two-launch attention forward, BPTT without the folded cell; a 1-wide chunk
+])
+def test_step_vs_oracle(B, T_in, T_out):
+    """Loss, the four outputs and every parameter gradient against CPU autograd through the oracle, seeded masks, ragged
+    lengths (the new edge shapes: one 3-long input, outputs down to 2 frames); then no bounded wait of the step expired."""
+    if (B, T_in, T_out) in ((12, 22, 20), (32, 64, 64)):
+        in_len = torch.tensor([T_in - ((i * 3) // 2 if B == 12 else i) for i in range(B)])
+        out_len = torch.tensor([T_out - i for i in range(B)])
+    else:
+        in_len, out_len = _edge_lengths(B, T_in, T_out)
+    m = _step_vs_oracle(B, T_in, T_out, in_len, out_len)
+    m._eng().check_lstm_xbuf()
+
+
+def test_stale_max_len_truncates_inputs():
+    """A batch tuple whose max_len is below the longest input length (the reference ignores max_len; here it sizes the encoder
+    output): those inputs are cut to max_len positions - eval forward and a training step against the oracle on
+    in_len.clamp(max=max_len).  Before the recurrence kernels clamped their lengths to the output's rows this wrote past
+    the encoder output."""
+    from oracle import tacotron_oracle as O
+    from text2speech_amd.tacotron import Tacotron
+    B, T_in, T_out = 12, 40, 14
+    in_len = torch.tensor([40, 39, 38, 37, 36, 35, 34, 30, 22, 17, 9, 3])
+    out_len = torch.tensor([T_out - i for i in range(B)])
+    max_len = int(in_len.max()) - 5
+    # eval
+    gen = torch.Generator().manual_seed(71)
+    text = torch.randint(2, 80, (B, T_in), generator=gen)
+    mel = torch.randn(B, 80, T_out, generator=gen)
+    for b in range(B):
+        text[b, in_len[b]:] = 0
+        mel[b, :, out_len[b]:] = 0
+    pm = (torch.rand(T_out + 1, B, 2, 256, generator=gen) < 0.5).to(torch.uint8)
+    _lib.load()
+    m = Tacotron(HP, 80, num_speakers=2)
+    m.load_state_dict(synth.tacotron_state(), strict=True)
+    m = m.to(DEV).eval()
+    with torch.no_grad():
+        out = m((text.to(DEV), in_len.to(DEV), mel.to(DEV), max_len, torch.zeros(B, device=DEV), out_len.to(DEV)), prenet_masks=pm)
+        want = O.tacotron_forward(synth.tacotron_state(), HP, text, in_len.clamp(max=max_len), mel, out_len, {"prenet": pm.float()})
+    for name, a, b in zip(("mel", "mel_post", "gate", "align"), out, want):
+        assert tuple(a.shape) == tuple(b.shape), name
+        assert _rel(a, b) < 1e-3, (name, _rel(a, b))
+    m._eng().check_lstm_xbuf()
+    # training step with its gradients
+    m = _step_vs_oracle(B, T_in, T_out, in_len, out_len, seed=73, max_len=max_len)
+    m._eng().check_lstm_xbuf()
+
+
+def test_check_lstm_xbuf_reads_bptt_exchange_words():
+    """check_lstm_xbuf() covers the backward's attention exchange buffer (t2s_taco_bptt::att_xbuf, T_in <= 512): its error word
+    (granule B * ceil(T_in / 32) * 128) and its pace-error word (+ 2), written here from the host."""
+    in_len = torch.tensor([24 - i for i in range(12)])
+    out_len = torch.tensor([8 - i // 2 for i in range(12)])
+    m = _step_vs_oracle(12, 24, 8, in_len, out_len, seed=79)
+    eng = m._eng()
+    eng.check_lstm_xbuf()
+    buf, e = eng.__dict__["_last_bptt_xbuf"]
+    assert e == 12 * 1 * 128
+    words = buf.view(torch.int64)
+    assert words.numel() == e + 3
+    for w in (e, e + 2):
+        words[w] = 1
+        torch.cuda.synchronize()
+        with pytest.raises(_lib.T2SError):
+            eng.check_lstm_xbuf()
+        words[w] = 0
+        torch.cuda.synchronize()
+        eng.check_lstm_xbuf()
 
 
 def test_three_adam_steps_vs_oracle_batch32():

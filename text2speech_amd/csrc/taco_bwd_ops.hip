@@ -1526,7 +1526,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_kernel(const float* __restr
     const int tid = threadIdx.x;
     const int b = blockIdx.x, dir = blockIdx.y;
     const float* W = dir ? whh_r : whh_f;
-    const int len = lengths ? lengths[b] : T;
+    const int len = min(lengths ? lengths[b] : T, T_out);   // (T_out <= T: as the forward, cut to the rows of out / d_out)
     float dc = 0.f;
     if (tid < H) s_dh[tid] = 0.f;
     __syncthreads();
@@ -1603,7 +1603,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_split_kernel(const float* _
     const int b = group >> 1, dir = group & 1;
     const int kk = tid & 63, jq = tid >> 6;
     const float* W = dir ? whh_r : whh_f;                    // [4H][H]
-    const int len = lengths ? lengths[b] : T;
+    const int len = min(lengths ? lengths[b] : T, T_out);   // (T_out <= T: as the forward, cut to the rows of out / d_out)
     float wr[64];
 #pragma unroll
     for (int i = 0; i < 64; ++i) wr[i] = W[(size_t)(64 * jq + i) * H + 64 * q + kk];

@@ -1887,7 +1887,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_kernel(const float* __restrict_
     int maxlen = 0;
 #pragma unroll
     for (int i = 0; i < BT; ++i) {
-        len[i] = (b0 + i < B) ? (lengths ? lengths[b0 + i] : T) : 0;
+        len[i] = (b0 + i < B) ? min(lengths ? lengths[b0 + i] : T, T_out) : 0;     // (T_out <= T: rows past T_out are not out's)
         maxlen = max(maxlen, len[i]);
     }
     float c[BT];
@@ -2049,7 +2049,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_split_kernel(const float* __res
     const int r = tid & 255, g = r >> 6, ul = r & 63, kq = tid >> 8;
     const int j = g * H + 64 * q + ul;                       // this thread's gate row
     const float* WT = dir ? whhT_r : whhT_f;                 // [H][4H]
-    const int len = lengths ? lengths[b] : T;
+    const int len = min(lengths ? lengths[b] : T, T_out);   // (T_out <= T: a longer entry is cut to the rows of out)
     float wr[64];
 #pragma unroll
     for (int i = 0; i < 64; ++i) wr[i] = WT[(size_t)(64 * kq + i) * 4 * H + j];

@@ -578,7 +578,8 @@ class _TacoEngine:
         return ent[0], ent[1]
 
     def check_lstm_xbuf(self):
-        """Synchronises; raises if a bounded wait of the split BiLSTM kernels ever expired on one of this engine's buffers."""
+        """Synchronises; raises if a bounded wait of the split BiLSTM kernels ever expired on one of this engine's buffers, or one
+        of the last teacher-forced decode or of the last backward's attention exchange."""
         for key, (buf, _) in self.__dict__.get("_xbufs", {}).items():
             if int(buf[-1].item()) != 0:
                 raise _lib.T2SError("split BiLSTM recurrence %s: a hand-off wait expired (results of that launch are invalid)" % (key,))
@@ -590,6 +591,15 @@ class _TacoEngine:
                 t = S.get(name)
                 if t is not None and any(float(t.view(-1)[w].item()) != 0.0 for w in words):
                     raise _lib.T2SError("teacher-forced decode: a bounded wait on %s expired (results of that call are invalid)" % name)
+        # ... and of the last backward's attention exchange buffer (t2s_taco_bptt::att_xbuf: 8-byte granule E = B * ceil(T_in / 32)
+        # * att_dim is raised by a bounded wait of the folded attention cell that expired, E + 2 by one of the paced helper chain)
+        last = self.__dict__.get("_last_bptt_xbuf")
+        if last is not None:
+            buf, e = last
+            words = buf.view(torch.int64)
+            for w, what in ((e, "the folded attention cell's exchange"), (e + 2, "the paced helper chain")):
+                if int(words[w].item()) != 0:
+                    raise _lib.T2SError("decoder BPTT: a bounded wait of %s expired (gradients of that step are invalid)" % what)
 
     def _gemv(self, W, x, rows, items, K, y, act=0, mask=None, smask=0, mask_scale=1.0, bias=None, sy_item=None,
               sx=None):
