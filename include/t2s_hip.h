@@ -316,16 +316,16 @@ typedef struct t2s_taco_decoder {
     float *dec_gates_all, *dec_c_all;    /* same for the decoder LSTM */
     float *att_h_all;                    /* [T][B][H] attention-LSTM output after dropout */
     float *q_all, *wcum_all;             /* [T][B][att_dim] queries, [T][B][T_in] cumulative weights after the step */
-    /* ABI v4.  [3][B][4H] scratch, ZERO before step 0, or NULL.  Autoregressive decode at B <= 4 (T2S_DECODE_STREAM_MAXB) with
+    /* ABI v4.  [3][B][4H] scratch, ZERO before step 0, or NULL.  Autoregressive decode at B <= 4 with
      * att_rnn_dim = dec_rnn_dim = 1024: the fused attention launch of step t also streams W_hh_dec . h_dec(t-1), W_ih_dec[:, :att_rnn] . h_att(t) and
      * W_hh_att . h_att(t) on the CUs the attention leaves idle and keeps the products here; the decoder cell of step t and the
      * attention cell of step t+1 then add them instead of streaming those 50 MB themselves.  State like h / c: carried between
-     * calls that continue one utterance.  NULL (or T2S_DECODE_STREAM=0): every cell streams its own weights (ABI v3 behaviour). */
+     * calls that continue one utterance.  NULL: every cell streams its own weights (ABI v3 behaviour). */
     float *gate_part;
     /* ABI v4.  [prenet][prenet] TRANSPOSE of w_pre2, or NULL.  With gate_part: the prenet's second layer (modules.py:19-22) is
      * folded into the attention cell's launch - every workgroup recomputes its 256 outputs from pre1, as a sparse product (pre1 is
      * ~3/4 exact zeros after ReLU and dropout: one coalesced row of the transpose per nonzero) - instead of a GEMV launch of its own
-     * on the serial chain.  NULL (or T2S_DECODE_FOLD_PRE2=0): the separate launch. */
+     * on the serial chain.  NULL: the separate launch. */
     const float *w_pre2T;
     /* ABI v4.  [B][T_in][att_dim] scratch, ZERO before step 0, or NULL.  With gate_part: the location term of the attention
      * (location_dense o location_conv of the current weights / cumulative weights, tacotron.py:96-107) is computed one launch EARLIER,
@@ -333,40 +333,36 @@ typedef struct t2s_taco_decoder {
      * only adds the query and the processed memory to it: the two exact-f32 matrix-core stages leave the one workgroup the whole
      * launch waits for (4 us at 128 encoder positions, growing linearly with T_in).  State like gate_part. */
     float *ploc;
-    /* ABI v4.  [16][B][4 * dec_rnn] scratch (not state: written before it is read inside one call), or NULL.  Teacher forced at 9+ items
-     * with att_h_all: the decoder cells run a chunk of 16 steps behind the attention chain (helper stream), so the input half of
-     * their pre-activations, W_ih_dec . [h_att(s) | ctx(s)], is ONE matrix product per chunk over 16 x B items - its 25 MB of
-     * weights read once per 16 steps instead of once per step - and the per-step cell streams only W_hh_dec (17 of 42 MB).
-     * Used only with T2S_DECODE_CHUNK_GEMM=1 (measured no faster); otherwise, or NULL: every decoder
-     * cell streams all of [W_ih | W_hh]. */
+    /* ABI v4.  Ignored: kept so that the layout stays v4 (a chunk-GEMM decode path that used it was measured no faster and removed,
+     * DESIGN.md section 5d).  Every decoder cell streams all of [W_ih | W_hh]; pass NULL. */
     float *dec_in_part;
     /* ABI v4.  (B * T_in + 1) 8-byte words, ZERO before step 0 of a sequence (state like gate_part: tags are step numbers), or NULL.
      * At 9+ items with attention_dim 128, 32 location filters, T_in <= 512 and enc_dim a multiple of 64, the
      * energies launch also does softmax, cumulative weights and context: the workgroups of a batch element exchange their energies
      * through tagged granules here instead of ending the launch.  The last word is raised if a bounded wait expires.  A buffer
      * serves every step INDEX once per zeroing (the tag of step s is s + 1): callers that revisit step indices pass NULL.
-     * NULL (or T2S_ATT_ONE_LAUNCH=0): energies and softmax + context stay two launches. */
+     * NULL: energies and softmax + context stay two launches. */
     void *att_xbuf;
     /* ABI v4.  16 bytes (a step counter and an error word), ZERO before step 0 of a sequence, or NULL.  Teacher forced at 9+ items with
      * att_h_all: instead of running a chunk of 16 steps behind, the helper stream's decoder cell of step s - 1 is released by a word
      * the attention cell's launch of step s stores as it starts, so that it runs beside the attention launch of step s (whose
-     * workgroups share a CU with it) and is over when the next attention cell needs the chip.  NULL (or T2S_DECODE_PACED=0): chunks. */
+     * workgroups share a CU with it) and is over when the next attention cell needs the chip.  NULL: chunks (as with the environment variable T2S_DECODE_PACED=0, for tools that serialise
+     * kernels across streams). */
     void *pace_flag;
 } t2s_taco_decoder;
 
 /* Enqueue decoder steps [step0, step0+n_steps) (Decoder.decode, tacotron.py:355-393, plus in autoregressive mode
  * the projection and the prenet of the next step, tacotron.py:447-461) on `stream` without host synchronisation.
  * Teacher-forced with att_h_all and hc_all given (training): the decoder LSTM cells - which feed nothing but the next decoder cell
- * and the projection after the loop - are enqueued on a library-owned helper stream, T2S_DECODE_CHUNK (16) steps behind the
- * attention chain, reading h_att / ctx from those saves; `stream` has been made to wait for the helper when the call returns
- * (T2S_DECODE_SPLIT=0: everything on `stream`). */
+ * and the projection after the loop - are enqueued on a library-owned helper stream, 16 steps behind the
+ * attention chain, reading h_att / ctx from those saves; `stream` has been made to wait for the helper when the call returns. */
 int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, void* stream);
 
 /* ABI v4.  One call of the location-sensitive attention alone (Attention.forward, tacotron.py:145-166, with the state update of
  * Decoder.decode around it, tacotron.py:371-379): query = w_query . h_att, energies from the location features of (w, w_cum) and
  * the processed memory, masked softmax over T, context.  IN PLACE: w [B][T] holds the previous weights on entry and the new ones on
  * return, w_cum [B][T] is incremented by them, ctx [B][enc] receives the context.  q_scratch [B][att_dim], e_scratch [B][T].
- * lengths [B] int32 or NULL.  Same kernels as t2s_taco_decode_steps (one fused launch up to T2S_ATT_FUSED_MAXB items, else
+ * lengths [B] int32 or NULL.  Same kernels as t2s_taco_decode_steps (one fused launch up to 8 items, else
  * query GEMV + energies + softmax/context). */
 int t2s_taco_attention(const float* h_att, const float* memory, const float* pmem, const int* lengths, float* w, float* w_cum,
                        float* ctx, float* q_scratch, float* e_scratch, const float* w_query, const float* w_loc_conv,
@@ -455,7 +451,7 @@ int t2s_wgrad_gemm_flat(const void* A_hi, const void* A_lo, const void* X_hi, co
  *   bstride  = u16 elements between batch entries (0 for constants such as the all-ones bias chunk).
  * out = [nsplit][M][ldp] f32 slabs (ldp >= N floats per row; columns N .. ldp-1 are scratch) over K-blocks [k0, k1) of 32 plane
  * rows of each of the B batch entries, as t2s_wgrad_gemm_flat.  ldp % 4 == 0 (and out 16-byte aligned) selects the ping-pong
- * kernel, whose epilogue stores 16-byte pieces; any other ldp the round-2 lockstep kernel (also: env T2S_WGRAD_PP=0).
+ * kernel, whose epilogue stores 16-byte pieces; any other ldp the round-2 lockstep kernel.
  * Every K-block is a WHOLE block of 32 plane rows starting at row 32 k (+ the shift folded into the pointer): the caller makes
  * sure rows [32 k0 - max shift, 32 k1 + max shift) exist in every plane (halo % 32 == 0 does, text2speech_amd/glow.py geom()).
  * bias_cols != 0 (ping-pong kernel only, ldp >= N + 4): columns N .. N+3 of every slab also receive four partial sums of the
@@ -590,13 +586,13 @@ typedef struct t2s_taco_bptt {
      * a 32-position chunk computes for itself, slots 1 / 2 the parts reaching in from the chunk to the right / left. */
     const float *ctx_all; long s_ctx_step, s_ctx_item;
     float *dw_c2, *dwc_c2;
-    /* ABI v4.  (B * ceil(T_in / 32) * 128 + 3) 8-byte words (the last three: error word, pace word, pace error word), ZERO before a BPTT pass, or NULL.  With the one-launch attention backward
+    /* ABI v4.  (B * ceil(T_in / 32) * 128 + 3) 8-byte words (the last three: the error word and two unused words), ZERO before a BPTT pass, or NULL.  With the one-launch attention backward
      * (ctx_all ...) and T_in <= 512: the attention LSTMCell's pointwise backward (with W_query^T d_q) runs inside that launch - the
      * chunk workgroups of a batch element exchange their partial d_q through tagged granules here (tag = step + 1), each then takes its
-     * share of the hidden units.  The last word is raised if a bounded wait expires.  NULL (or T2S_BPTT_FOLD_CELL=0): a launch of its own. */
+     * share of the hidden units.  The last word is raised if a bounded wait expires.  NULL: a launch of its own. */
     void *att_xbuf;
 } t2s_taco_bptt;
-/* Launch sequencing only.  Unless T2S_BPTT_ONE_STREAM is set, the decoder-cell chain and the location-conv part of the
+/* Launch sequencing only.  The decoder-cell chain and the location-conv part of the
  * attention backward run on two library-owned non-blocking streams (created on first use on the current device, kept for the
  * life of the process), ordered against `stream` with events; everything this call enqueues is complete, as seen from
  * `stream`, once the call's last wait has been passed.  Not re-entrant across host threads for the same device. */

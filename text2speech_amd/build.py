@@ -28,7 +28,6 @@ def needs_build():
 
 def _compile(hipcc, src, obj, verbose):
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, src), "-o", obj]
-    cmd[1:1] = os.environ.get("T2S_BUILD_DEFINES", "").split()      # e.g. -DT2S_GEMM_ABLATE for the timing-only ablations
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -39,7 +38,7 @@ def _compile(hipcc, src, obj, verbose):
 
 def build(force=False, verbose=False):
     """Compile what is out of date (a source newer than its object, or any header newer than it), a few files at a time, and
-    link.  T2S_BUILD_DEFINES changes what an object means, so diagnostic builds always pass force=True (tools/ do)."""
+    link.  Diagnostic builds (extra -D defines) go through build_variant() into build/<name>/, never into csrc/."""
     if not force and not needs_build():
         return LIB
     from concurrent.futures import ThreadPoolExecutor
@@ -47,7 +46,6 @@ def build(force=False, verbose=False):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
               [os.path.join(os.path.dirname(HERE), "include", "t2s_hip.h")]
     hdr_t = _newest(headers)
-    force = force or bool(os.environ.get("T2S_BUILD_DEFINES", "").strip())
     jobs, objs = [], []
     for src in SOURCES:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
@@ -67,7 +65,7 @@ def build(force=False, verbose=False):
 
 
 def build_variant(name, defines):
-    """A diagnostic build next to the shipped one: every source compiled with `defines` (e.g. "-DT2S_ATTSTREAM_ABLATE") into
+    """A diagnostic build next to the shipped one: every source compiled with `defines` (e.g. "-DT2S_GEMM_STAMPS") into
     build/<name>/ and linked to build/<name>/libt2s_hip.so (git-ignored, travels with gpurun).  Load it with T2S_LIB_PATH."""
     from concurrent.futures import ThreadPoolExecutor
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

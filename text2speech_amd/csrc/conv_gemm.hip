@@ -32,16 +32,6 @@
 #include "t2s_common.h"
 #include "t2s_kernels.h"
 
-#include <stdlib.h>
-
-// Timing-only ablations (results are wrong): build with -DT2S_GEMM_ABLATE and set env T2S_DBG_GEMM to
-// 1 (no DMA inside the K loop), 2 (no MFMA) or 3.  Compiled out of the product build.
-#ifdef T2S_GEMM_ABLATE
-#define T2S_ABLATE(a) ((a).dbg)
-#else
-#define T2S_ABLATE(a) 0
-#endif
-
 #define B_PLANE_BYTES 16384          // one B (activation) plane tile: 256 rows x 64 B
 
 static __device__ __forceinline__ int swz4(int rb) {      // {0,2,3,1}[rb]
@@ -54,20 +44,15 @@ static __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 }
 
 // MT = rows of the M (output-channel) tile: 256, or 128 for short GEMMs that would otherwise leave CUs idle.
-// WN = waves along N (time): 4 -> 8 waves of 128 x 64 (two per SIMD); 2 -> 4 waves of 128 x 128 (one per SIMD, 256
-// accumulator registers): a third fewer LDS fragment bytes per MFMA, the resource this kernel runs out of first.
-// BD = B operand direct: the activation fragments go global -> registers (in the plane layout a 16-row x 32-channel fragment
-// is one contiguous KiB, so the loads are perfectly coalesced and need no swizzle), one K-step ahead; LDS then only carries A.
 // SH = shared B tile (gate GEMM, taps == 3, dilation <= 32): the three taps of a 32-channel block read rows t0-d.., t0..,
 // t0+d.. of the SAME activation plane, so one extended tile of 256 + 2d rows is filled once per block and the three K-steps
 // read it at row offsets 0, d, 2d - 40 KB of B per block instead of 96 KB.  The K order becomes block-major for the tap part
 // (A is indexed tap*xc + c as packed, no repack); the conditioning part keeps the one-tile-per-step scheme.
-// EF = early free: a wave reads ALL fragments of the current stage into registers (96 VGPRs), a barrier frees the stage, and
-// the DMA for step k+2 goes into it at once - the fill gets two K-steps to land instead of one (2 LDS stages as before).
 // NS = LDS stages of the plain main loop: 2, or 3 where the stage is small enough (128-row tiles: 3 x 48 KB) - those GEMMs have
 // K-steps of ~0.7 us of MFMA against a ~1.7 us fill turnaround, so the fill must be issued two steps ahead.
-template <int EPI, int MT, int WN, bool BD = false, bool SH = false, bool EF = false, int NS = 2>
-__global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs a) {
+template <int EPI, int MT, bool SH = false, int NS = 2>
+__global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
+    constexpr int WN = 4;                            // waves along N (time): 8 waves of 128 x 64, two per SIMD
     constexpr int NTH = 128 * WN;                    // threads per workgroup
     constexpr int NWT = 16 / WN;                     // 16-column MFMA tiles per wave
     constexpr int CALL_BYTES = NTH * 16;             // bytes one workgroup-wide global_load_lds moves
@@ -156,21 +141,10 @@ __global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs 
             glds16(ah + j * CALL_BYTES, dst + j * CALL_BYTES);
             glds16(al + j * CALL_BYTES, dst + A_PLANE + j * CALL_BYTES);
         }
-        if (!BD) {
 #pragma unroll
-            for (int j = 0; j < B_PLANE_BYTES / CALL_BYTES; ++j) {
-                glds16(bh + j * CALL_BYTES, dst + 2 * A_PLANE + j * CALL_BYTES);
-                glds16(bl + j * CALL_BYTES, dst + 2 * A_PLANE + B_PLANE_BYTES + j * CALL_BYTES);
-            }
-        }
-    };
-    // BD: this lane's 16 bytes of B fragment n of the tile whose DMA source would be (bh, bl)
-    const long bd_adj = (long)((wc * (NWT * 16) + (lane & 15)) * 64 + (lane >> 4) * 16) - (long)thr_off;
-    auto b_direct = [&](const char* bh, const char* bl, bf16x8 (&rh)[NWT], bf16x8 (&rl)[NWT]) {
-#pragma unroll
-        for (int n = 0; n < NWT; ++n) {
-            rh[n] = *(const bf16x8*)(bh + bd_adj + n * 1024);
-            rl[n] = *(const bf16x8*)(bl + bd_adj + n * 1024);
+        for (int j = 0; j < B_PLANE_BYTES / CALL_BYTES; ++j) {
+            glds16(bh + j * CALL_BYTES, dst + 2 * A_PLANE + j * CALL_BYTES);
+            glds16(bl + j * CALL_BYTES, dst + 2 * A_PLANE + B_PLANE_BYTES + j * CALL_BYTES);
         }
     };
 
@@ -189,11 +163,7 @@ __global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs 
     // the K loop, and ride out their latency under it.  Ablations (tools/res_gemm_study.sh) put 25 of the kernel's 38 us outside
     // MFMA and fill: every CU reading, then writing, its 128 x 256 tile of x at the same moment (33 + 33 MB in one burst).  With the
     // read half moved under the loop only the write burst is left.  64 VGPRs; 256-row tiles have no room for it.
-#ifdef T2S_NO_PREX
-    constexpr bool PREX = false;
-#else
     constexpr bool PREX = EPI == EPI_RESSKIP && MT == 128;
-#endif
     u16x4 pre_h[PREX ? MW : 1][PREX ? NWT : 1], pre_l[PREX ? MW : 1][PREX ? NWT : 1];
     typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
     if constexpr (PREX) {
@@ -245,12 +215,8 @@ __global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs 
 
     // GATE_BWD on 128-row tiles (K = 32 steps, a 43 us loop): its epilogue reads the layer's saved gate output and sigmoid - 4 planes,
     // 66 MB per launch - and writes 66 MB of d_pre: half of the kernel's time was that read-then-write burst after the loop.  As
-    // for RESSKIP above, the reads are requested HERE and ride out their latency under the K loop (128 VGPRs; -DT2S_NO_PREG: off).
-#ifdef T2S_NO_PREG
-    constexpr bool PREG = false;
-#else
+    // for RESSKIP above, the reads are requested HERE and ride out their latency under the K loop (128 VGPRs).
     constexpr bool PREG = EPI == EPI_GATE_BWD && MT == 128;
-#endif
     u16x4 pg_th[PREG ? MW : 1][PREG ? NWT : 1], pg_tl[PREG ? MW : 1][PREG ? NWT : 1];
     u16x4 pg_gh[PREG ? MW : 1][PREG ? NWT : 1], pg_gl[PREG ? MW : 1][PREG ? NWT : 1];
     if constexpr (PREG) {
@@ -272,55 +238,14 @@ __global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs 
         }
     }
 
-  if constexpr (EF) {
-    const int nk = nk_split;
-    const char *nbh = nullptr, *nbl = nullptr;
-    if (nk > 0) { b_source(0, nbh, nbl); issue(0, 0, nbh, nbl); }
-    if (nk > 1) { b_source(1, nbh, nbl); issue(1, 1, nbh, nbl); }
-    if (nk > 2) b_source(2, nbh, nbl);
-    for (int ks = 0; ks < nk; ++ks) {
-        const int cur = ks & 1;
-        const char* sb = smem + cur * STAGE;
-        // stage ks has landed once at most the newer DMA group (step ks+1: 8 instructions per wave) is outstanding
-        if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        bf16x8 fah[MW], fal[MW], fbh[NWT], fbl[NWT];
-#pragma unroll
-        for (int n = 0; n < NWT; ++n) {
-            fbh[n] = *(const bf16x8*)(sb + b_frag + n * 1024);
-            fbl[n] = *(const bf16x8*)(sb + b_frag + B_PLANE_BYTES + n * 1024);
-        }
-#pragma unroll
-        for (int m = 0; m < MW; ++m) {
-            fah[m] = *(const bf16x8*)(sb + a_frag + m * 1024);
-            fal[m] = *(const bf16x8*)(sb + a_frag + A_PLANE + m * 1024);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __syncthreads();                                     // every wave holds its fragments: the stage is free
-        if (ks + 2 < nk) {
-            issue(ks + 2, cur, nbh, nbl);
-            if (ks + 3 < nk) b_source(ks + 3, nbh, nbl);
-        }
-#pragma unroll
-        for (int m = 0; m < MW; ++m) {
-#pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(fal[m], fbh[n], acc[m][n], 0, 0, 0);
-#pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(fah[m], fbl[n], acc[m][n], 0, 0, 0);
-#pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(fah[m], fbh[n], acc[m][n], 0, 0, 0);
-        }
-    }
-  } else if constexpr (!SH) {
-    constexpr int DMA_PER_ISSUE = 2 * (A_PLANE / CALL_BYTES) + (BD ? 0 : 2 * (B_PLANE_BYTES / CALL_BYTES));
+  if constexpr (!SH) {
+    constexpr int DMA_PER_ISSUE = 2 * (A_PLANE / CALL_BYTES) + 2 * (B_PLANE_BYTES / CALL_BYTES);
     const int nk = nk_split;
     const char *nbh = nullptr, *nbl = nullptr;       // B sources of the next stage to issue, computed one step ahead
-    bf16x8 bh[NWT], bl[NWT], bhn[NWT], bln[NWT];
+    bf16x8 bh[NWT], bl[NWT];
     if (nk > 0) {
         b_source(0, nbh, nbl);
         issue(0, 0, nbh, nbl);
-        if (BD) b_direct(nbh, nbl, bh, bl);
     }
     if (NS == 3 && nk > 1) {
         b_source(1, nbh, nbl);
@@ -340,19 +265,14 @@ __global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs 
         // previous step (measured: issuing it after the fragment reads instead costs 6 us per launch); (2) the fragment
         // reads the first MFMAs need; (3) the scalar address arithmetic for the next issue, hidden under the MFMAs.  The A
         // fragments of m-tile m+1 are fetched while m's 12 MFMAs issue.
-        const bool issued = ks + NS - 1 < nk && !(T2S_ABLATE(a) & 1);
-        if (issued) {
-            issue(ks + NS - 1, nxt, nbh, nbl);
-            if (BD) b_direct(nbh, nbl, bhn, bln);
-        }
+        const bool issued = ks + NS - 1 < nk;
+        if (issued) issue(ks + NS - 1, nxt, nbh, nbl);
         bf16x8 ah = *(const bf16x8*)(sb + a_frag);
         bf16x8 al = *(const bf16x8*)(sb + a_frag + A_PLANE);
-        if (!BD) {
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) {
-                bh[n] = *(const bf16x8*)(sb + b_frag + n * 1024);
-                bl[n] = *(const bf16x8*)(sb + b_frag + B_PLANE_BYTES + n * 1024);
-            }
+        for (int n = 0; n < NWT; ++n) {
+            bh[n] = *(const bf16x8*)(sb + b_frag + n * 1024);
+            bl[n] = *(const bf16x8*)(sb + b_frag + B_PLANE_BYTES + n * 1024);
         }
         if (ks + NS < nk) b_source(ks + NS, nbh, nbl);
 #pragma unroll
@@ -362,26 +282,18 @@ __global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs 
                 ah_n = *(const bf16x8*)(sb + a_frag + (m + 1) * 1024);
                 al_n = *(const bf16x8*)(sb + a_frag + A_PLANE + (m + 1) * 1024);
             }
-            if (!(T2S_ABLATE(a) & 2)) {
 #pragma unroll
-                for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(al, bh[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(al, bh[n], acc[m][n], 0, 0, 0);
 #pragma unroll
-                for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bl[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bl[n], acc[m][n], 0, 0, 0);
 #pragma unroll
-                for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bh[n], acc[m][n], 0, 0, 0);
-            } else {
-                asm volatile("" :: "v"(al), "v"(ah));
-            }
+            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bh[n], acc[m][n], 0, 0, 0);
             ah = ah_n;
             al = al_n;
         }
         // the next step's stage must have landed; with three stages the group issued in THIS step may still be in flight
         if (NS == 3 && issued) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_ISSUE) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (BD) {
-#pragma unroll
-            for (int n = 0; n < NWT; ++n) { bh[n] = bhn[n]; bl[n] = bln[n]; }
-        }
         __syncthreads();
         cur = cur + 1 == NS ? 0 : cur + 1;
     }
@@ -772,50 +684,35 @@ __global__ __launch_bounds__(128 * WN) void conv_gemm_kernel(const ConvGemmArgs 
     }
 }
 
-template <int EPI, int MT, int WN = 4, bool BD = false, bool SH = false, bool EF = false, int NS = 2>
+template <int EPI, int MT, bool SH = false, int NS = 2>
 static hipError_t launch_one(const ConvGemmArgs& a, hipStream_t stream) {
     const int nwg = a.n_mtiles * a.n_ttiles * a.B;
     constexpr size_t lds = SH ? 2 * (2 * MT * 64) + 4 * 320 * 64 : NS * (2 * MT * 64 + 2 * B_PLANE_BYTES);
     static std::atomic<unsigned long long> attr_mask{0};        // per instantiation; bit d = raised on device d
-    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, WN, BD, SH, EF, NS>, (int)lds, attr_mask);
+    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, SH, NS>, (int)lds, attr_mask);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, WN, BD, SH, EF, NS>), dim3(nwg), dim3(128 * WN), lds, stream, a);
+    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, SH, NS>), dim3(nwg), dim3(512), lds, stream, a);
     return hipGetLastError();
 }
 
 // a.n_mtiles must have been computed for the same tile height `mt_rows` (256 or 128)
-hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a_in, int epi, hipStream_t stream, int mt_rows) {
-    static const int dbg = getenv("T2S_DBG_GEMM") ? atoi(getenv("T2S_DBG_GEMM")) : 0;
-    ConvGemmArgs a = a_in;
-    a.dbg = dbg;
+hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows) {
     if (mt_rows == 128) {
-        static const int ns3 = getenv("T2S_GEMM_NS3") ? atoi(getenv("T2S_GEMM_NS3")) : 0;     // 1 = three stages (measured slower)
-        if (epi == EPI_RESSKIP && ns3) return launch_one<EPI_RESSKIP, 128, 4, false, false, false, 3>(a, stream);
-        if (epi == EPI_GATE_BWD && ns3) return launch_one<EPI_GATE_BWD, 128, 4, false, false, false, 3>(a, stream);
         if (epi == EPI_RESSKIP) return launch_one<EPI_RESSKIP, 128>(a, stream);
         if (epi == EPI_GATE_BWD) return launch_one<EPI_GATE_BWD, 128>(a, stream);
         if (epi == EPI_GATE && a.ksplit <= 1 && a.k0 == 0 && a.kflat == 0) return launch_one<EPI_GATE, 128>(a, stream);
         // small grids (Tacotron encoder / postnet at B = 1: 2-8 workgroups walking 80 K-steps): each step is one exposed fill
         // latency with two stages; three stages of the 48 KB tile keep two fills in flight
-        if (epi == EPI_BIAS_ACT && a.ksplit <= 1 && a.k0 == 0 && a.kflat == 0)
-            return launch_one<EPI_BIAS_ACT, 128, 4, false, false, false, 3>(a, stream);
+        if (epi == EPI_BIAS_ACT && a.ksplit <= 1 && a.k0 == 0 && a.kflat == 0) return launch_one<EPI_BIAS_ACT, 128, false, 3>(a, stream);
         return hipErrorInvalidValue;
     }
-    // default gate GEMM: the ping-pong schedule (csrc/gate_gemm_pp.hip); T2S_GEMM_PP=0 falls back to the lockstep kernels below
-    static const int pp = getenv("T2S_GEMM_PP") ? atoi(getenv("T2S_GEMM_PP")) : 1;
-    if (epi == EPI_GATE && pp && a.ksplit <= 1 && a.k0 == 0 && a.kflat == 0 && a.nk == a.nk_x + a.sc && a.nk_x == a.taps * a.xc &&
+    // gate GEMM: the ping-pong schedule (csrc/gate_gemm_pp.hip) where its K order applies, else the shared-B or plain lockstep kernel
+    if (epi == EPI_GATE && a.ksplit <= 1 && a.k0 == 0 && a.kflat == 0 && a.nk == a.nk_x + a.sc && a.nk_x == a.taps * a.xc &&
         a.a_bstride == 0 && (a.taps >> 1) * a.dil <= a.halo)
         return t2s_launch_gate_gemm_pp(a, stream);
-    static const int wn2 = getenv("T2S_GEMM_WN2") ? atoi(getenv("T2S_GEMM_WN2")) : 0;
-    static const int bdir = getenv("T2S_GEMM_BD") ? atoi(getenv("T2S_GEMM_BD")) : 0;
-    if (epi == EPI_GATE && wn2) return launch_one<EPI_GATE, 256, 2>(a, stream);
-    if (epi == EPI_GATE && bdir) return launch_one<EPI_GATE, 256, 4, true>(a, stream);
-    static const int ef = getenv("T2S_GEMM_EF") ? atoi(getenv("T2S_GEMM_EF")) : 0;
-    if (epi == EPI_GATE && ef) return launch_one<EPI_GATE, 256, 4, false, false, true>(a, stream);
-    static const int shb = getenv("T2S_GEMM_SH") ? atoi(getenv("T2S_GEMM_SH")) : 1;      // default on; 0 = one B tile per K-step
-    if (epi == EPI_GATE && shb && a.taps == 3 && a.dil <= 32 && a.dil <= a.halo && a.nk_x == 3 * a.xc && a.ksplit <= 1 &&
+    if (epi == EPI_GATE && a.taps == 3 && a.dil <= 32 && a.dil <= a.halo && a.nk_x == 3 * a.xc && a.ksplit <= 1 &&
         a.k0 == 0 && a.kflat == 0 && a.nk == a.nk_x + a.sc)
-        return launch_one<EPI_GATE, 256, 4, false, true>(a, stream);
+        return launch_one<EPI_GATE, 256, true>(a, stream);
     if (epi == EPI_GATE) return launch_one<EPI_GATE, 256>(a, stream);
     if (epi == EPI_RESSKIP) return launch_one<EPI_RESSKIP, 256>(a, stream);
     if (epi == EPI_GATE_BWD) return launch_one<EPI_GATE_BWD, 256>(a, stream);

@@ -38,18 +38,8 @@ constexpr int PP_PLANE = 16384;          // one plane tile: 256 rows x 64 B
 constexpr int PP_HALF = 8192;            // 128 rows
 constexpr int PP_BUF = 4 * PP_PLANE;     // A_hi, A_lo, B_hi, B_lo
 
-// 8-byte plane store.  Measured negative (profiles/r02_summary.md): making these stores write-through (sc1, -DT2S_PP_SC1_STORES:
-// the bytes leave the XCD's L2 during the epilogue instead of at the end-of-kernel release) costs 1.4 % on the gate GEMM and
-// 1.1 % on the forward - 8-byte sc1 stores run at 0.54-0.70 x the 16-byte rate and the residual GEMM that follows no longer
-// finds the gate outputs in L2.  Plain stores are the default.
-__device__ __forceinline__ void pp_store8(u16* dst, u16x4 v) {
-#ifdef T2S_PP_SC1_STORES
-    __hip_atomic_store((unsigned long long*)dst, __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-#else
-    *(u16x4*)dst = v;
-#endif
-}
+// 8-byte plane store.  Plain stores: write-through (sc1) ones measured 1.4 % slower on the gate GEMM.
+__device__ __forceinline__ void pp_store8(u16* dst, u16x4 v) { *(u16x4*)dst = v; }
 
 __device__ __forceinline__ int pp_swz4(int rb) { return (0x78 >> (rb * 2)) & 3; }      // {0,2,3,1}[rb]
 
@@ -64,7 +54,6 @@ __device__ __forceinline__ void pp_glds16(const void* gsrc, void* lds_dst) {
 // fabric again: 218 MB fetched per launch against 83 MB of operands).  The packed weights stay tap-major, so the A chunk is
 // addressed through the cursor (aoff) instead of by the K-step number; then come the conditioning planes.  All state is
 // wave-uniform (scalar registers); the per-thread part of the address is inside the base pointers.
-// -DT2S_PP_TAP_MAJOR restores the tap-major walk (and with it the round-1 summation order) for A/B runs.
 struct BCursor {
     long off;       // bytes from the X (or S) base
     long aoff;      // bytes from the A base: packed K-chunk index * Mpad * 64
@@ -74,8 +63,6 @@ struct BCursor {
 
 }  // namespace
 
-// ABL: timing-only ablations of the main loop (results are wrong), instantiated only under -DT2S_GEMM_ABLATE and selected with
-// env T2S_DBG_GEMM: bit 0 = no DMA, bit 1 = no MFMA, bit 2 = no LDS fragment reads.
 #ifdef T2S_GEMM_STAMPS
 // Diagnostic build only (cdna_hip_programming.md section 7, in-kernel stamps): s_memtime / s_memrealtime of wave 0 of every
 // workgroup at four points, written to a buffer nothing else reads.  [wg][0..3] = shader-clock stamps (kernel entry, loop
@@ -99,7 +86,7 @@ __device__ unsigned long long t2s_pp_stamps[1024 * 8];
 // (t2s_wg_bwd_gate_dgrad).  Those GEMMs have M = C = 512, two 256-row tiles: alone they fill half the chip, but the backward
 // runs them next to the weight-gradient stream, and what counts there is the time a CU spends per unit of work - 2.1 us per
 // 256 x 256 x 32 step on this schedule against 2 x 1.33 us on the lockstep 128-row tiles.
-template <int ABL, bool PH, int EPI = EPI_GATE>
+template <bool PH, int EPI = EPI_GATE>
 __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -174,13 +161,8 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
     auto cursor_at = [&](int ks) {
         BCursor c;
         if (ks < a.nk_x) {
-#ifdef T2S_PP_TAP_MAJOR
-            c.tap = ks / a.xc;
-            c.kc = ks - c.tap * a.xc;
-#else
             c.kc = ks / a.taps;
             c.tap = ks - c.kc * a.taps;
-#endif
             c.in_s = false;
             c.off = (long)c.kc * (long)x_cstride + (long)((c.tap - (a.taps >> 1)) * a.dil) * 64;
             c.aoff = (long)(c.tap * a.xc + c.kc) * (long)a_kstride;
@@ -193,24 +175,6 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         }
         return c;
     };
-#ifdef T2S_PP_TAP_MAJOR
-    auto advance = [&](BCursor& c) {
-        c.kc += 1;
-        c.off += c.in_s ? (long)s_cstride : (long)x_cstride;
-        c.aoff += (long)a_kstride;
-        if (!c.in_s && c.kc == a.xc) {
-            c.kc = 0;
-            c.tap += 1;
-            if (c.tap == a.taps) {
-                c.in_s = true;
-                c.off = 0;
-                if (PH) c.aoff = 0;
-            } else {
-                c.off = (long)((c.tap - (a.taps >> 1)) * a.dil) * 64;
-            }
-        }
-    };
-#else
     const long tap_step = (long)a.dil * 64;
     const long a_tap_step = (long)a.xc * (long)a_kstride;
     auto advance = [&](BCursor& c) {
@@ -237,7 +201,6 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
             }
         }
     };
-#endif
     auto stage_a = [&](int ks, const BCursor& c, int half) {
         char* dst = lds_wave + (ks & 1) * PP_BUF + half * PP_HALF;
         const long off = c.aoff + (long)half * PP_HALF;
@@ -282,14 +245,10 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();          // group 1 runs one barrier behind group 0
 
-#define PP_MFMA(ACC, AH, AL, BH, BL)                                                 \
-    if (!(ABL & 2)) {                                                                \
-        ACC = T2S_MFMA32(AL, BH, ACC, 0, 0, 0);         \
-        ACC = T2S_MFMA32(AH, BL, ACC, 0, 0, 0);         \
-        ACC = T2S_MFMA32(AH, BH, ACC, 0, 0, 0);         \
-    } else {                                                                         \
-        asm volatile("" ::"v"(AH), "v"(AL), "v"(BH), "v"(BL));                       \
-    }
+#define PP_MFMA(ACC, AH, AL, BH, BL)            \
+    ACC = T2S_MFMA32(AL, BH, ACC, 0, 0, 0);         \
+    ACC = T2S_MFMA32(AH, BL, ACC, 0, 0, 0);         \
+    ACC = T2S_MFMA32(AH, BH, ACC, 0, 0, 0);
 
     // One phase = read segment, barrier, matrix segment, barrier.  `MAIN` K-steps issue a stage in every phase and wait
     // with a counted vmcnt(6); the last two K-steps have nothing (or less) left to stage and drain with vmcnt(0).
@@ -297,7 +256,6 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         constexpr bool MAIN = decltype(main_tag)::value;
         const char* sb = smem + (ks & 1) * PP_BUF;
         // ------------------------------------------------ phase 0: A half 0 x B half 0
-        if (!(ABL & 4) || !MAIN) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             b0h[n] = *(const bf16x8*)(sb + b_frag + n * 1024);
@@ -308,9 +266,8 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
             afh[m] = *(const bf16x8*)(sb + a_frag + m * 1024);
             afl[m] = *(const bf16x8*)(sb + a_frag + PP_PLANE + m * 1024);
         }
-        }
-        if ((MAIN && !(ABL & 1)) || (!MAIN && ks + 1 < nk)) stage_b(ks + 1, c1, 1);
-        if (MAIN && !(ABL & 1)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN || ks + 1 < nk) stage_b(ks + 1, c1, 1);
+        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -326,15 +283,13 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         // ------------------------------------------------ phase 1: A half 0 x B half 1
-        if (!(ABL & 4) || !MAIN) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             b1h[n] = *(const bf16x8*)(sb + b_frag + PP_HALF + n * 1024);
             b1l[n] = *(const bf16x8*)(sb + b_frag + PP_HALF + PP_PLANE + n * 1024);
         }
-        }
-        if ((MAIN && !(ABL & 1)) || (!MAIN && ks + 1 < nk)) stage_a(ks + 1, c1, 1);
-        if (MAIN && !(ABL & 1)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN || ks + 1 < nk) stage_a(ks + 1, c1, 1);
+        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -350,15 +305,13 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         // ------------------------------------------------ phase 2: A half 1 x B half 1
-        if (!(ABL & 4) || !MAIN) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             afh[m] = *(const bf16x8*)(sb + a_frag + PP_HALF + m * 1024);
             afl[m] = *(const bf16x8*)(sb + a_frag + PP_HALF + PP_PLANE + m * 1024);
         }
-        }
-        if ((MAIN && !(ABL & 1)) || (!MAIN && ks + 2 < nk)) stage_a(ks + 2, c2, 0);
-        if (MAIN && !(ABL & 1)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN || ks + 2 < nk) stage_a(ks + 2, c2, 0);
+        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -374,8 +327,8 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         // ------------------------------------------------ phase 3: A half 1 x B half 0 (fragments still in registers)
-        if ((MAIN && !(ABL & 1)) || (!MAIN && ks + 2 < nk)) stage_b(ks + 2, c2, 0);
-        if (MAIN && !(ABL & 1)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN || ks + 2 < nk) stage_b(ks + 2, c2, 0);
+        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -753,22 +706,22 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
     PP_RSTAMP(5)
 }
 
-template <int ABL, bool PH = false, int EPI = EPI_GATE>
+template <bool PH = false, int EPI = EPI_GATE>
 static hipError_t launch_pp(const ConvGemmArgs& a, hipStream_t stream) {
     const int nwg = PH ? a.n_mtiles * a.ph_P * a.ph_nft * ((a.B + a.ph_bper - 1) / a.ph_bper) : a.n_mtiles * a.n_ttiles * a.B;
     constexpr int lds = 2 * PP_BUF;
     static std::atomic<unsigned long long> attr_mask{0};
-    const hipError_t e = t2s_raise_lds_limit((const void*)gate_gemm_pp_kernel<ABL, PH, EPI>, lds, attr_mask);
+    const hipError_t e = t2s_raise_lds_limit((const void*)gate_gemm_pp_kernel<PH, EPI>, lds, attr_mask);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gate_gemm_pp_kernel<ABL, PH, EPI>), dim3(nwg), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((gate_gemm_pp_kernel<PH, EPI>), dim3(nwg), dim3(512), lds, stream, a);
     return hipGetLastError();
 }
 
 // the accumulate / gate-backward GEMMs of the training backward on the ping-pong schedule (256-row tiles); the caller has checked
 // t2s_pp_shape_ok(a)
 hipError_t t2s_launch_bwd_gemm_pp(const ConvGemmArgs& a, int epi, hipStream_t stream) {
-    if (epi == EPI_RESSKIP) return launch_pp<0, false, EPI_RESSKIP>(a, stream);
-    if (epi == EPI_GATE_BWD) return launch_pp<0, false, EPI_GATE_BWD>(a, stream);
+    if (epi == EPI_RESSKIP) return launch_pp<false, EPI_RESSKIP>(a, stream);
+    if (epi == EPI_GATE_BWD) return launch_pp<false, EPI_GATE_BWD>(a, stream);
     return hipErrorInvalidValue;
 }
 bool t2s_pp_shape_ok(const ConvGemmArgs& a) {
@@ -783,19 +736,6 @@ extern "C" int t2s_debug_read_pp_stamps(unsigned long long* host_out, int n_word
 #endif
 
 hipError_t t2s_launch_gate_gemm_pp(const ConvGemmArgs& a, hipStream_t stream) {
-#ifdef T2S_GEMM_ABLATE
-    static const int dbg = getenv("T2S_DBG_GEMM") ? atoi(getenv("T2S_DBG_GEMM")) : 0;
-    switch (dbg & 7) {
-        case 1: return launch_pp<1>(a, stream);
-        case 2: return launch_pp<2>(a, stream);
-        case 3: return launch_pp<3>(a, stream);
-        case 4: return launch_pp<4>(a, stream);
-        case 5: return launch_pp<5>(a, stream);
-        case 6: return launch_pp<6>(a, stream);
-        case 7: return launch_pp<7>(a, stream);
-        default: break;
-    }
-#endif
-    if (a.ph_P > 0) return launch_pp<0, true>(a, stream);
-    return launch_pp<0>(a, stream);
+    if (a.ph_P > 0) return launch_pp<true>(a, stream);
+    return launch_pp<false>(a, stream);
 }

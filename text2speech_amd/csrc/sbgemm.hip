@@ -12,7 +12,6 @@
 // Epilogues: plain (bias / activation, GemvArgs semantics) and the fused LSTMCell update (LstmCellArgs semantics,
 // reference tacotron.py:366-370,380-385): there the 16 rows of a workgroup are the four gates of four hidden
 // units, ordered so that one lane's four accumulators are (i, f, g, o) of one (unit, item).
-#include <stdlib.h>
 #include "t2s_common.h"
 #include "t2s_kernels.h"
 #include "tacotron_ops.h"
@@ -27,78 +26,7 @@ struct SbOperands {
     int items;
 };
 
-#ifdef T2S_SBGEMM_VGPR      // round-1 operand path (register ring), kept for A/B builds
-struct SbFrag {
-    f32x4 a[4], b0[4], b1[4];
-};
-
-// Loads the operands of (up to) four consecutive 16-wide K steps starting at step s (steps >= s_end give zeros).
-static __device__ __forceinline__ void sb_load(SbFrag& f, const SbOperands& o, int s, int s_end, size_t grow, bool row_ok,
-                                               int item0, int q) {
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int st = s + u;
-        if (st < s_end) {                                   // wave-uniform
-            const int k = st * 16;
-            const float* wp = k < o.k1 ? o.W1 + grow * o.ld1 + k : o.W2 + grow * o.ld2 + (k - o.k1);
-            f.a[u] = row_ok ? *(const f32x4*)(wp + q * 4) : zero;
-            const float* xp;                                // no dynamic indexing of the segment arrays (scratch)
-            long sx;
-            if (k < o.n0) { xp = o.x0 + k; sx = o.sx0; }
-            else if (k < o.n0 + o.n1) { xp = o.x1 + (k - o.n0); sx = o.sx1; }
-            else { xp = o.x2 + (k - o.n0 - o.n1); sx = o.sx2; }
-            xp += q * 4;
-            f.b0[u] = item0 < o.items ? *(const f32x4*)(xp + (size_t)item0 * sx) : zero;
-            f.b1[u] = item0 + 16 < o.items ? *(const f32x4*)(xp + (size_t)(item0 + 16) * sx) : zero;
-        } else {
-            f.a[u] = zero; f.b0[u] = zero; f.b1[u] = zero;
-        }
-    }
-}
-
-static __device__ __forceinline__ void sb_mma(const SbFrag& f, f32x4& acc0, f32x4& acc1) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[u][j], f.b0[u][j], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[u][j], f.b1[u][j], acc1, 0, 0, 0);
-        }
-}
-
-// One workgroup's 16 rows x 32 items; partial sums of the 8 waves end in s_part[wave][half][reg][lane].
-template <int KW>
-static __device__ __forceinline__ void sb_core(const SbOperands& o, size_t grow, bool row_ok, int item_base,
-                                               float (*s_part)[2][4][64], char*, size_t, size_t) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = lane >> 4, item0 = item_base + (lane & 15);
-    const int nsteps = o.K >> 4;
-    const int s0 = (wave * nsteps) >> 3, s1 = ((wave + 1) * nsteps) >> 3;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    // ring of three operand groups (4 K-steps each): two groups of loads stay in flight behind the MFMAs of the third
-    SbFrag f0, f1, f2;
-    sb_load(f0, o, s0, s1, grow, row_ok, item0, q);
-    sb_load(f1, o, s0 + 4, s1, grow, row_ok, item0, q);
-    sb_load(f2, o, s0 + 8, s1, grow, row_ok, item0, q);
-    for (int s = s0; s < s1; s += 12) {
-        sb_mma(f0, acc0, acc1);
-        sb_load(f0, o, s + 12, s1, grow, row_ok, item0, q);
-        if (s + 4 < s1) sb_mma(f1, acc0, acc1);
-        sb_load(f1, o, s + 16, s1, grow, row_ok, item0, q);
-        if (s + 8 < s1) sb_mma(f2, acc0, acc1);
-        sb_load(f2, o, s + 20, s1, grow, row_ok, item0, q);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        s_part[wave][0][r][lane] = acc0[r];
-        s_part[wave][1][r][lane] = acc1[r];
-    }
-    __syncthreads();
-}
-
-#else
-// Operand ring in LDS, filled by LDS-DMA (round 2).  The register ring above never had more than ~5 loads in flight per lane:
+// Operand ring in LDS, filled by LDS-DMA (round 2).  The round-1 register ring never had more than ~5 loads in flight per lane:
 // hipcc puts a branch and a `vmcnt(0)` around each conditional operand load (18 full waits for 82 loads), and both rewrites
 // with unconditional loads lost more to extra instructions than they won (profiles/r02_summary.md).  `global_load_lds` takes no
 // VGPRs and no compiler-inserted waits: every wave owns SB_R slots of 3 KB - the A, B0 and B1 fragments of one 16-wide K-step,
@@ -122,24 +50,12 @@ static __device__ __forceinline__ void sb_glds16(const void* gsrc, void* lds_dst
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
-// the weight rows: read once per launch by ONE workgroup - the textbook case for nt (MI355X_MICROARCH.md nt-weights, aux = 2), and
-// measured NEGATIVE here (-DT2S_SB_NT_WEIGHTS, profiles/r04_cache_policy_ab.txt, same box, alternating): teacher-forced forward at
-// B = 32 35.98 / 35.86 against 34.35 / 34.54 ms, train step 93.5 / 92.7 against 89.3 / 90.1 ms.  Default policy is what ships.
-#ifdef T2S_SB_NT_WEIGHTS
-#define SB_W_AUX 2
-#else
-#define SB_W_AUX 0
-#endif
-static __device__ __forceinline__ void sb_glds16w(const void* gsrc, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_dst, 16, 0, SB_W_AUX);
-}
-
+// the weight rows use the default cache policy too: nt loads (read once per launch by ONE workgroup) measured slower
 // HALF: the workgroup takes 16 items instead of 32 (no second B fragment): for launches whose row count fills less than half the
 // chip - the per-CU fill is what bounds the kernel, and two workgroups with half the input vectors each pull 2/3 of the bytes per CU
 template <int KW, bool HALF = false>
 static __device__ __forceinline__ void sb_core(const SbOperands& o, size_t grow_of_r16, bool row_ok, int item_base,
-                                               float (*s_part)[2][4][64], char* ring, size_t grow_lo8, size_t grow_hi8) {
+                                               char* ring, size_t grow_lo8, size_t grow_hi8) {
     constexpr int SB_R = SbCfg<KW>::R, SB_SLOT = SbCfg<KW>::SLOT;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -169,12 +85,12 @@ static __device__ __forceinline__ void sb_core(const SbOperands& o, size_t grow_
         else { xp = o.x2 + (k - o.n0 - o.n1); sx = o.sx2; }
         char* dst = my + slot_in * SB_SLOT;
         if constexpr (KW == 16) {
-            sb_glds16w(wbase + grow_of_r16 * wld + dp * 4, dst);
+            sb_glds16(wbase + grow_of_r16 * wld + dp * 4, dst);
             sb_glds16(xp + dp * 4 + ia0 * sx, dst + 1024);
             if constexpr (!HALF) sb_glds16(xp + dp * 4 + ib0 * sx, dst + 2048);
         } else {
-            sb_glds16w(wbase + grow_lo8 * wld + dp * 4, dst);
-            sb_glds16w(wbase + grow_hi8 * wld + dp * 4, dst + 1024);
+            sb_glds16(wbase + grow_lo8 * wld + dp * 4, dst);
+            sb_glds16(wbase + grow_hi8 * wld + dp * 4, dst + 1024);
             sb_glds16(xp + dp * 4 + ia0 * sx, dst + 2048);
             sb_glds16(xp + dp * 4 + ia1 * sx, dst + 3072);
             if constexpr (!HALF) {
@@ -215,15 +131,10 @@ static __device__ __forceinline__ void sb_core(const SbOperands& o, size_t grow_
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         slot_out = slot_out + 1 == SB_R ? 0 : slot_out + 1;
         // the slot read in the PREVIOUS iteration is free (its reads were waited for there): refill it
-#if !defined(SB_ABL) || !(SB_ABL & 1)
         if (issued < nmine) issue(s0 + issued++);
-#else
-        if (issued < nmine) issued++;                      // timing-only ablation: no fill after the prologue (results are wrong)
-#endif
         if (!row_ok) { fa = zero; ga = zero; }
         if (!v0) { fb0 = zero; gb0 = zero; }
         if (!v1) { fb1 = zero; gb1 = zero; }
-#if !defined(SB_ABL) || !(SB_ABL & 2)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[j], fb0[j], acc0, 0, 0, 0);
@@ -236,9 +147,6 @@ static __device__ __forceinline__ void sb_core(const SbOperands& o, size_t grow_
                 if constexpr (!HALF) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[j], gb1[j], acc1, 0, 0, 0);
             }
         }
-#else
-        asm volatile("" ::"v"(fa), "v"(fb0), "v"(fb1), "v"(ga), "v"(gb0), "v"(gb1));    // timing-only ablation: no MFMA
-#endif
     }
     // this wave's slots are drained (every fragment read above was waited for): its partial sums go into its own first slot
     float* part = (float*)my;
@@ -249,35 +157,20 @@ static __device__ __forceinline__ void sb_core(const SbOperands& o, size_t grow_
     }
     __syncthreads();
 }
-#endif
 
 // tile row r (0..15) of item it (0..31 within the group): D[row][col]: lane = (row/4)*16 + col%16, reg = row%4, half = col/16
-#ifdef T2S_SBGEMM_VGPR
 template <int KW>
-static __device__ __forceinline__ float sb_sum(float (*s_part)[2][4][64], const char*, int r, int it) {
-    const int ln = (r >> 2) * 16 + (it & 15), half = it >> 4, reg = r & 3;
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) s += s_part[w][half][reg][ln];
-    return s;
-}
-#define SB_DECL_PART __shared__ float s_part[8][2][4][64];
-#else
-template <int KW>
-static __device__ __forceinline__ float sb_sum(float (*)[2][4][64], const char* ring, int r, int it) {
+static __device__ __forceinline__ float sb_sum(const char* ring, int r, int it) {
     const int ln = (r >> 2) * 16 + (it & 15), half = it >> 4, reg = r & 3;
     float s = 0.f;
 #pragma unroll
     for (int w = 0; w < 8; ++w) s += ((const float*)(ring + w * (SbCfg<KW>::R * SbCfg<KW>::SLOT)))[(half * 4 + reg) * 64 + ln];
     return s;
 }
-#define SB_DECL_PART float (*s_part)[2][4][64] = nullptr;
-#endif
 
 // ---- plain epilogue: GemvArgs semantics (no split_row) -------------------------------------------------------
 template <int KW, bool HALF = false>
 __global__ __launch_bounds__(512) void sbgemm_plain_kernel(const GemvArgs a) {
-    SB_DECL_PART
     extern __shared__ __attribute__((aligned(16))) char sb_ring[];
     SbOperands o;
     o.W1 = a.W1; o.ld1 = a.ld1; o.k1 = a.k1; o.W2 = a.W2; o.ld2 = a.ld2;
@@ -288,15 +181,11 @@ __global__ __launch_bounds__(512) void sbgemm_plain_kernel(const GemvArgs a) {
     const int lrow = row0 + (threadIdx.x & 15);
     auto clampr = [&](int r) { return (size_t)(r < a.rows ? r : a.rows - 1); };       // DMA sources stay inside the matrix
     const int dr = (threadIdx.x & 63) >> 3;
-#ifdef T2S_SBGEMM_VGPR
-    sb_core<KW>(o, clampr(lrow), lrow < a.rows, item_base, s_part, sb_ring, clampr(row0 + dr), clampr(row0 + dr + 8));
-#else
-    sb_core<KW, HALF>(o, clampr(lrow), lrow < a.rows, item_base, s_part, sb_ring, clampr(row0 + dr), clampr(row0 + dr + 8));
-#endif
+    sb_core<KW, HALF>(o, clampr(lrow), lrow < a.rows, item_base, sb_ring, clampr(row0 + dr), clampr(row0 + dr + 8));
     const int r = threadIdx.x & 15, it = threadIdx.x >> 4;          // 512 threads = 16 rows x 32 items
     const int row = row0 + r, item = item_base + it;
     if (row < a.rows && item < a.items && (!HALF || it < 16)) {
-        float y = sb_sum<KW>(s_part, sb_ring, r, it) + (a.bias1 ? a.bias1[row] : 0.f) + (a.bias2 ? a.bias2[row] : 0.f);
+        float y = sb_sum<KW>(sb_ring, r, it) + (a.bias1 ? a.bias1[row] : 0.f) + (a.bias2 ? a.bias2[row] : 0.f);
         if (a.act == ACT_RELU) y = fmaxf(y, 0.f);
         else if (a.act == ACT_TANH) y = tanhf(y);
         if (a.mask) y *= a.mask[(size_t)item * a.smask_item + row] ? a.mask_scale : 0.f;      // dropout draw (the hoisted prenet)
@@ -318,45 +207,31 @@ bool t2s_sbgemm_plain_ok(const GemvArgs& a) {
 
 template <int KW, typename Args, int VARIANT = 0>         // VARIANT: distinct kernels of one (KW, Args) each get their own flag
 static hipError_t sb_launch(void (*kern)(const Args), const Args& a, dim3 grid, hipStream_t stream) {
-#ifdef T2S_SBGEMM_VGPR
-    constexpr int lds = 0;
-#else
     constexpr int lds = sb_ring_bytes<KW>();
     static std::atomic<unsigned long long> attr_mask{0};         // one per (KW, Args, VARIANT) instantiation = per kernel
     const hipError_t e = t2s_raise_lds_limit((const void*)kern, lds, attr_mask);
     if (e != hipSuccess) return e;
-#endif
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, a);
     return hipGetLastError();
 }
-// whole 128-byte lines per fragment row where every operand segment is a multiple of 32 (T2S_SB_STEP=16 forces the 64-byte form)
-static bool sb_wide_ok(int K, int k1, int n0, int n1, int n2) {
-    static const int force = getenv("T2S_SB_STEP") ? atoi(getenv("T2S_SB_STEP")) : 0;
-    if (force == 16) return false;
-    return !((K | k1 | n0 | n1 | n2) & 31);
-}
+// whole 128-byte lines per fragment row where every operand segment is a multiple of 32
+static bool sb_wide_ok(int K, int k1, int n0, int n1, int n2) { return !((K | k1 | n0 | n1 | n2) & 31); }
 
 hipError_t t2s_launch_sbgemm_plain(const GemvArgs& a, hipStream_t stream) {
     dim3 grid((a.rows + 15) / 16, (a.items + 31) / 32);
-#ifndef T2S_SBGEMM_VGPR
-    // 16 items per workgroup where twice the workgroups still fit one round of the chip (T2S_SB_HALF=0: never): the attention
-    // cell's transposed GEMM of the BPTT loop (1792 rows = 112 workgroups at 32 items) pulls 512 instead of 768 KB per CU
-    static const bool half_ok = !(getenv("T2S_SB_HALF") && atoi(getenv("T2S_SB_HALF")) == 0);
-    const bool half = half_ok && !a.no_half && a.items > 16 && (long)grid.x * ((a.items + 15) / 16) <= 256;
+    // 16 items per workgroup where twice the workgroups still fit one round of the chip: the attention cell's transposed GEMM of
+    // the BPTT loop (1792 rows = 112 workgroups at 32 items) pulls 512 instead of 768 KB per CU
+    const bool half = a.items > 16 && (long)grid.x * ((a.items + 15) / 16) <= 256;
     if (half) grid.y = (a.items + 15) / 16;
-    if (!a.narrow_ring && sb_wide_ok(a.n1 + a.n2 + a.n3, a.k1, a.n1, a.n2, a.n3))
+    if (sb_wide_ok(a.n1 + a.n2 + a.n3, a.k1, a.n1, a.n2, a.n3))
         return half ? sb_launch<32, GemvArgs, 1>(sbgemm_plain_kernel<32, true>, a, grid, stream) : sb_launch<32>(sbgemm_plain_kernel<32>, a, grid, stream);
     return half ? sb_launch<16, GemvArgs, 1>(sbgemm_plain_kernel<16, true>, a, grid, stream) : sb_launch<16>(sbgemm_plain_kernel<16>, a, grid, stream);
-#else
-    return sb_launch<16>(sbgemm_plain_kernel<16>, a, grid, stream);
-#endif
 }
 
 // ---- fused LSTMCell epilogue: LstmCellArgs semantics ---------------------------------------------------------------
 // Workgroup = hidden units u0..u0+3; tile row r = unit*4 + gate  ->  weight row gate*H + u0 + unit.
 template <int KW>
 __global__ __launch_bounds__(512) void sbgemm_lstm_kernel(const LstmCellArgs a) {
-    SB_DECL_PART
     extern __shared__ __attribute__((aligned(16))) char sb_ring[];
     if (a.sig_ptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)       // "this launch has started" (LstmCellArgs::sig_ptr)
         __hip_atomic_store(a.sig_ptr, a.sig_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -374,8 +249,7 @@ __global__ __launch_bounds__(512) void sbgemm_lstm_kernel(const LstmCellArgs a) 
     __shared__ float s_hq[4][32];
     f32x4 wq = {0.f, 0.f, 0.f, 0.f};
     if (a.q_part) wq = *(const f32x4*)(a.w_q + (size_t)(threadIdx.x & 127) * a.H + u0);
-    // partial pre-activations (LstmCellArgs::pre_a, [B][4H]: the input half of the product, computed for a whole chunk of steps by
-    // one GEMM - t2s_taco_decoder::dec_in_part): requested in front of the K loop, added in the epilogue
+    // partial pre-activations (LstmCellArgs::pre_a, [B][4H], optional): requested in front of the K loop, added in the epilogue
     float pre[4] = {0.f, 0.f, 0.f, 0.f};
     if (a.pre_a && threadIdx.x < 128) {
         const int item = item_base + (threadIdx.x >> 2), u = u0 + (threadIdx.x & 3);
@@ -384,7 +258,7 @@ __global__ __launch_bounds__(512) void sbgemm_lstm_kernel(const LstmCellArgs a) 
             for (int gi = 0; gi < 4; ++gi) pre[gi] = a.pre_a[(size_t)item * 4 * a.H + (size_t)gi * a.H + u];
         }
     }
-    sb_core<KW>(o, wrow(threadIdx.x & 15), true, item_base, s_part, sb_ring, wrow(dr), wrow(dr + 8));
+    sb_core<KW>(o, wrow(threadIdx.x & 15), true, item_base, sb_ring, wrow(dr), wrow(dr + 8));
     if (threadIdx.x < 128) s_hq[threadIdx.x & 3][threadIdx.x >> 2] = 0.f;
     if (threadIdx.x < 128) {
         const int ul = threadIdx.x & 3, it = threadIdx.x >> 2;
@@ -393,7 +267,7 @@ __global__ __launch_bounds__(512) void sbgemm_lstm_kernel(const LstmCellArgs a) 
             float g[4];
 #pragma unroll
             for (int gi = 0; gi < 4; ++gi)
-                g[gi] = (sb_sum<KW>(s_part, sb_ring, ul * 4 + gi, it) + pre[gi]) + (a.b_ih[gi * a.H + u] + a.b_hh[gi * a.H + u]);
+                g[gi] = (sb_sum<KW>(sb_ring, ul * 4 + gi, it) + pre[gi]) + (a.b_ih[gi * a.H + u] + a.b_hh[gi * a.H + u]);
             const size_t idx = (size_t)item * a.H + u;
             const float gi_ = sb_sigmoid(g[0]), gf = sb_sigmoid(g[1]), gg = tanhf(g[2]), go_ = sb_sigmoid(g[3]);
             const float c2 = gf * a.c[idx] + gi_ * gg;
@@ -439,8 +313,6 @@ bool t2s_sbgemm_lstm_ok(const LstmCellArgs& a) {
 
 hipError_t t2s_launch_sbgemm_lstm(const LstmCellArgs& a, hipStream_t stream) {
     dim3 grid(a.H / 4, (a.B + 31) / 32);
-#ifndef T2S_SBGEMM_VGPR
     if (sb_wide_ok(a.n1 + a.n2 + a.H, a.n1 + a.n2, a.n1, a.n2, a.H)) return sb_launch<32>(sbgemm_lstm_kernel<32>, a, grid, stream);
-#endif
     return sb_launch<16>(sbgemm_lstm_kernel<16>, a, grid, stream);
 }

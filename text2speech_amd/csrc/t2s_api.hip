@@ -202,8 +202,6 @@ int t2s_wg_endfold_weights(const t2s_endfold_job* jobs, int n_jobs, int C, void*
 // Gate GEMM tile height for a shape: 256-row tiles (the ping-pong kernel) unless they leave at least half of the chip's 256 CUs
 // without a workgroup - short utterances at B = 1 - where 128-row tiles give twice the workgroups at half the work each.
 static int gate_tile_rows(int B, int C, int L) {
-    static const int force = getenv("T2S_GATE_TILE") ? atoi(getenv("T2S_GATE_TILE")) : 0;      // 128 / 256: A/B switch
-    if (force == 128 || force == 256) return (force == 128 && C % 64 == 0) ? 128 : 256;
     const long wg256 = (long)cdiv(C, 128) * cdiv(L, 256) * B;
     return (wg256 <= 128 && C % 64 == 0) ? 128 : 256;
 }
@@ -323,15 +321,11 @@ int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const
     a.xc = cdiv(C, 32); a.sc = 0; a.oc = cdiv(C, 32);
     a.taps = 1; a.dil = 1; a.nk_x = a.xc; a.nk = a.xc;
     a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    // T2S_RES_TILE=256 (with T2S_RES_PAIR8=0: the 16-byte epilogue exists for 128-row tiles only): 256-row tiles, half the
-    // workgroups - the A/B behind DESIGN.md section 8 item 3
-    static const int tile_env = getenv("T2S_RES_TILE") ? atoi(getenv("T2S_RES_TILE")) : 0;
-    const int rows = (tile_env == 256 && !pair8) ? 256 : 128;
-    a.n_mtiles = cdiv(C, rows); a.n_ttiles = cdiv(L, 256);
+    a.n_mtiles = cdiv(C, 128); a.n_ttiles = cdiv(L, 256);
     a.C = 0; a.n_res = C;
     if (pair8 && C % 32) return T2S_EINVAL;
     a.pair8 = pair8 ? 1 : 0;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream, rows));
+    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream, 128));
     return T2S_OK;
 }
 
@@ -374,8 +368,7 @@ int t2s_conv_bias_act(const void* A_hi, const void* A_lo, const float* bias, con
     a.nk_x = taps * a.xc; a.nk = a.nk_x;
     a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
     // a grid of at most 64 workgroups is latency-bound per K-step: 128-row tiles with three LDS stages (conv_gemm.hip)
-    static const int tile_env = getenv("T2S_CONV_TILE") ? atoi(getenv("T2S_CONV_TILE")) : 0;      // 128 / 256: A/B switch
-    const int rows = tile_env == 128 || tile_env == 256 ? tile_env : ((long)cdiv(Cout, 256) * cdiv(L, 256) * B <= 64 ? 128 : 256);
+    const int rows = (long)cdiv(Cout, 256) * cdiv(L, 256) * B <= 64 ? 128 : 256;
     a.n_mtiles = cdiv(Cout, rows); a.n_ttiles = cdiv(L, 256);
     a.C = Cout; a.act = act; a.f32_cl = f32_channel_last;
     T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_BIAS_ACT, (hipStream_t)stream, rows));

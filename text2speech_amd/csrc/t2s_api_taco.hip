@@ -16,6 +16,13 @@ extern "C" int t2s_internal_fail_hip(int e);   // defined in t2s_api.hip (record
 
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// one fused attention launch per step (one workgroup per batch element) up to this batch; beyond it the three-kernel form
+constexpr int ATT_FUSED_MAX_B = 8;
+// streamed gate partials (t2s_taco_decoder::gate_part) up to this batch
+constexpr int DECODE_STREAM_MAX_B = 4;
+// teacher-forced decode with the decoder cells on the helper stream, unpaced: attention-chain steps per event
+constexpr int DECODE_CHUNK = 16;
+
 static int gemv_args_ok(const GemvArgs& a) {
     if (!a.W1 || !a.x1 || !a.y || a.rows <= 0 || a.items <= 0) return 0;
     const int K = a.n1 + a.n2 + a.n3;
@@ -157,8 +164,7 @@ int t2s_taco_attention(const float* h_att, const float* memory, const float* pme
     aa.lengths = lengths; aa.w_prev = w; aa.w_cum = w_cum; aa.energies = e_scratch; aa.ctx = ctx;
     aa.B = B; aa.T = T; aa.att_dim = att_dim; aa.enc_dim = enc_dim; aa.loc_f = loc_filters; aa.loc_ks = loc_kernel;
     aa.w_query = w_query; aa.h_att = h_att; aa.w_loc_denseT = w_loc_denseT; aa.att_rnn = att_rnn;
-    static const int fused_max_b = getenv("T2S_ATT_FUSED_MAXB") ? atoi(getenv("T2S_ATT_FUSED_MAXB")) : 8;
-    if (B <= fused_max_b && T <= 512 && w_loc_denseT && enc_dim <= 512 && att_rnn <= 1024) {
+    if (B <= ATT_FUSED_MAX_B && T <= 512 && w_loc_denseT && enc_dim <= 512 && att_rnn <= 1024) {
         T2S_CHECK_HIP(t2s_launch_att_fused(aa, stream));
         return T2S_OK;
     }
@@ -197,9 +203,8 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
     // softmax + context), whose next prenet input is given.  So it runs on the library's helper stream from the saved copies
     // of h_att[s] and ctx[s] (att_h_all, hc_all), a chunk of steps behind the attention chain, and drops out of the serial chain.
     // With one event per STEP this measured equal (128.0 vs 128.2 ms per train step, profiles/r03_taco_timeline_fwd_split.md: the
-    // record opens a 7 us gap on the critical stream); with one event per 16 steps: 95.7 -> 91.9 ms.  T2S_DECODE_SPLIT=0: off.
-    static const bool want_split = !(getenv("T2S_DECODE_SPLIT") && atoi(getenv("T2S_DECODE_SPLIT")) == 0);
-    const bool split = d->teacher_forced && d->att_h_all && d->hc_all && want_split;
+    // record opens a 7 us gap on the critical stream); with one event per 16 steps: 95.7 -> 91.9 ms.
+    const bool split = d->teacher_forced && d->att_h_all && d->hc_all;
     T2sHelperStream hs;
     if (split) T2S_CHECK_HIP(t2s_helper_stream_acquire(hs));
     struct Join {           // whatever happens below, the caller's stream waits for the helper before this call returns
@@ -208,24 +213,16 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
             if (on && hipEventRecord(hs.ev_join, hs.side) == hipSuccess) (void)hipStreamWaitEvent(stream, hs.ev_join, 0);
         }
     } join{hs, stream, split};
-    // Streamed gate partials (ABI v4, t2s_taco_decoder::gate_part): autoregressive small-batch decode only.  T2S_DECODE_STREAM=0: off.
-    static const bool want_stream = !(getenv("T2S_DECODE_STREAM") && atoi(getenv("T2S_DECODE_STREAM")) == 0);
+    // Streamed gate partials (ABI v4, t2s_taco_decoder::gate_part): autoregressive small-batch decode only.
     const size_t GP = (size_t)B * 4 * A;                   // one [B][4H] block of gate_part
-    // Decoder cells a chunk behind the chain (split): the input half of their pre-activations as ONE product per chunk
-    // (t2s_taco_decoder::dec_in_part, 16 steps of scratch).  Built and measured NEGATIVE (profiles/r04_taco_chunk_gemm_ab.txt, same
-    // box, alternating: teacher-forced forward at B = 32 35.5 / 35.6 with it against 35.0 / 34.7 ms, train step equal): the small-batch
-    // GEMM kernel re-reads its 16 weight rows per group of 32 items and the 32 input vectors per 16 rows (1.2 GB of L2 reads per
-    // 512-item chunk), which costs what the per-step cells save.  Off unless T2S_DECODE_CHUNK_GEMM=1.
-    static const bool want_chunk_gemm = getenv("T2S_DECODE_CHUNK_GEMM") && atoi(getenv("T2S_DECODE_CHUNK_GEMM")) != 0;
     // Paced decoder cells (t2s_taco_decoder::pace_flag): the helper stream's cell of step s - 1 is released by a word the attention
     // cell's launch of step s stores as it STARTS, i.e. when the attention of step s - 1 is complete.  It is enqueued ~4 us later, finds
     // the chip held by that attention cell, and runs as its workgroups retire - beside the attention launch of step s, whose small
     // workgroups share a CU with it - and is over when the next attention cell needs the CUs.  In bursts of 16 (the chunked form) the
-    // helper's cells kept the chain's next attention cell from starting: their time ADDED to the chain's.  T2S_DECODE_PACED=0: chunks.
+    // helper's cells kept the chain's next attention cell from starting: their time ADDED to the chain's.  T2S_DECODE_PACED=0: chunks
+    // (for tools that serialise kernels across streams, which would otherwise wait out every bounded spin).
     static const bool want_paced = !(getenv("T2S_DECODE_PACED") && atoi(getenv("T2S_DECODE_PACED")) == 0);
     const bool paced = split && want_paced && d->pace_flag && B > 8 && !((uintptr_t)d->pace_flag & 7);
-    const bool chunk_gemm = split && !paced && want_chunk_gemm && d->dec_in_part && B > 8 && !((A | D | E) & 31);
-    int part_c0 = 0;                                       // first step of the chunk whose products dec_in_part holds
     auto body = [&](int s, bool do_att, bool do_dec) -> int {
         float* ah_in = (s & 1) ? d->att_h1 : d->att_h0;
         float* ah_out = (s & 1) ? d->att_h0 : d->att_h1;
@@ -245,8 +242,7 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
         if (d->att_drop) { ca.drop_mask = d->att_drop + (size_t)s * B * A; ca.drop_scale = d->att_drop_scale; }
         // one fused attention launch per step (one workgroup per batch element) up to this batch; beyond it the three-kernel
         // form (query GEMV, energies, softmax + context) fills the chip better (measured at B = 32, T_in = 256: no difference)
-        static const int fused_max_b = getenv("T2S_ATT_FUSED_MAXB") ? atoi(getenv("T2S_ATT_FUSED_MAXB")) : 8;
-        const bool fused_att = B <= fused_max_b && T <= 512 && d->w_loc_denseT && d->att_dim <= 128;
+        const bool fused_att = B <= ATT_FUSED_MAX_B && T <= 512 && d->w_loc_denseT && d->att_dim <= 128;
         if (d->att_gates_all) { ca.gates_out = d->att_gates_all + (size_t)s * B * 4 * A; ca.c_out = d->att_c_all + (size_t)s * B * A; }
         if (d->att_h_all) { ca.h_copy = d->att_h_all + (size_t)s * B * A; ca.s_copy = A; }
         // small batch: the attention cell's workgroups emit partial queries (their own hidden units' columns of W_query), so
@@ -255,11 +251,9 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
         const int units = ca.gates_out ? 2 : 4;             // hidden units per workgroup of lstm_cell_kernel (training / eval)
         if (q_parts) { ca.w_q = d->w_query; ca.q_part = d->q_part; ca.q_dim = d->att_dim; }
         // large batch (matrix-core cells): the same idea - every cell workgroup (4 hidden units) leaves a partial query and the
-        // energies kernel sums the A / 4 = 256 of them - takes the query GEMM off the serial chain.  T2S_QPART_BIG=0: the GEMM.
-        static const bool want_qbig = !(getenv("T2S_QPART_BIG") && atoi(getenv("T2S_QPART_BIG")) == 0);
-        static const bool att_valu = getenv("T2S_ATT_VALU") != nullptr;
+        // energies kernel sums the A / 4 = 256 of them - takes the query GEMM off the serial chain.
         bool q_big = false;
-        if (!fused_att && !q_parts && want_qbig && !att_valu && d->q_part && A == 1024 && d->att_dim == 128 && d->loc_filters == 32 &&
+        if (!fused_att && !q_parts && d->q_part && A == 1024 && d->att_dim == 128 && d->loc_filters == 32 &&
             d->loc_kernel <= 31 && d->w_loc_denseT) {
             ca.w_q = d->w_query; ca.q_part = d->q_part; ca.q_dim = d->att_dim;
             q_big = t2s_sbgemm_lstm_ok(ca);
@@ -267,9 +261,8 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
         }
         // streamed gates: W_hh_att . h_att(s-1) was left in gate_part[2] by the previous step's attention launch (zero at step 0)
         // (up to 4 items: the role's dot products and reductions are per item - at B = 8 the launch takes longer than the two cells save,
-        // 73.9 vs 67.4 us per step; B = 4: 48.2 vs 49.9, B = 2: 36.2 vs 42.0, B = 1: 29.6 vs 37.3.  T2S_DECODE_STREAM_MAXB overrides)
-        static const int stream_max_b = getenv("T2S_DECODE_STREAM_MAXB") ? atoi(getenv("T2S_DECODE_STREAM_MAXB")) : 4;
-        if (want_stream && d->gate_part && B <= stream_max_b && !d->teacher_forced && fused_att && q_parts && !ca.gates_out && A == 1024 &&
+        // 73.9 vs 67.4 us per step; B = 4: 48.2 vs 49.9, B = 2: 36.2 vs 42.0, B = 1: 29.6 vs 37.3)
+        if (d->gate_part && B <= DECODE_STREAM_MAX_B && !d->teacher_forced && fused_att && q_parts && !ca.gates_out && A == 1024 &&
             D == 1024) {
             gs.W0 = d->dec_w_hh; gs.ld0 = D; gs.x0 = dh_in; gs.out0 = d->gate_part;
             gs.W1 = d->dec_w_ih; gs.ld1 = A + E; gs.out1 = d->gate_part + GP;
@@ -289,9 +282,8 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
             if (!sig_by_kernel) T2S_CHECK_HIP(t2s_launch_pace_signal(ca.sig_ptr, ca.sig_val, stream));
         }
         // ... and with it the prenet's second layer folded into this launch (every workgroup recomputes the 256 outputs from
-        // pre1 and W_pre2 out of L2) instead of a GEMV launch of its own at the end of the previous step.  T2S_DECODE_FOLD_PRE2=0: off
-        static const bool want_fold = !(getenv("T2S_DECODE_FOLD_PRE2") && atoi(getenv("T2S_DECODE_FOLD_PRE2")) == 0);
-        fold_pre2 = stream_gates && want_fold && d->w_pre2T && P == 256 && E == 512 && s < d->mask_steps;
+        // pre1 and W_pre2 out of L2) instead of a GEMV launch of its own at the end of the previous step
+        fold_pre2 = stream_gates && d->w_pre2T && P == 256 && E == 512 && s < d->mask_steps;
         if (fold_pre2) {
             ca.x1 = nullptr; ca.w_p2 = d->w_pre2T; ca.p1 = d->pre1;
             ca.p2_mask = d->prenet_masks + (size_t)s * B * 2 * P + P; ca.s_p2_mask = 2 * P; ca.p2_scale = 2.0f;
@@ -313,9 +305,8 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
         if (fused_att) {
             // small batch: one fused launch per step (one workgroup per batch element)
             if (stream_gates && !t2s_att_fused_stream_ok(aa, gs)) return T2S_EINVAL;
-            // the location term of this step came out of the previous step's projection launch (zero at step 0).  T2S_DECODE_PLOC=0: off
-            static const bool want_ploc = !(getenv("T2S_DECODE_PLOC") && atoi(getenv("T2S_DECODE_PLOC")) == 0);
-            use_ploc = stream_gates && want_ploc && d->ploc && d->att_dim == 128 && d->loc_filters == 32 && d->loc_kernel <= 31 && !aa.q_save &&
+            // the location term of this step came out of the previous step's projection launch (zero at step 0)
+            use_ploc = stream_gates && d->ploc && d->att_dim == 128 && d->loc_filters == 32 && d->loc_kernel <= 31 && !aa.q_save &&
                        !aa.wcum_save;
             if (use_ploc) aa.ploc = d->ploc;
             T2S_CHECK_HIP(t2s_launch_att_fused(aa, stream, stream_gates ? &gs : nullptr));
@@ -329,10 +320,9 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
             if (q_big) { aa.q_part = d->q_part; aa.n_part = A / 4; aa.q_out = qa.y; aa.q_save = nullptr; }
             else T2S_CHECK_HIP(t2s_launch_gemv(qa, stream));
             // energies, softmax, cumulative weights and context in ONE launch where the shape allows (t2s_taco_decoder::att_xbuf: the
-            // tiles of an element exchange their energies through tagged granules).  T2S_ATT_ONE_LAUNCH=0: two launches.
-            static const bool want_one = !(getenv("T2S_ATT_ONE_LAUNCH") && atoi(getenv("T2S_ATT_ONE_LAUNCH")) == 0);
+            // tiles of an element exchange their energies through tagged granules)
             bool one = false;
-            if (want_one && d->att_xbuf) {
+            if (d->att_xbuf) {
                 aa.xbuf = (unsigned long long*)d->att_xbuf; aa.tag = (unsigned)s + 1u;
                 one = t2s_att_energy_ctx_ok(aa);
                 if (!one) { aa.xbuf = nullptr; aa.tag = 0; }
@@ -359,11 +349,6 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
             // came out of the attention launch as gate_part[0], gate_part[1]
             cd.W_ih = d->dec_w_ih + A; cd.ld_ih = A + E; cd.x1 = d->ctx; cd.n1 = E; cd.sx1 = E; cd.x2 = nullptr; cd.n2 = 0; cd.sx2 = 0;
             cd.h_in = nullptr; cd.pre_a = d->gate_part; cd.pre_b = d->gate_part + GP;
-        }
-        if (chunk_gemm) {
-            // W_ih . [h_att(s) | ctx(s)] is in dec_in_part[s - part_c0]: only W_hh . h_dec(s-1) is left to stream (17 of 42 MB)
-            cd.x1 = nullptr; cd.n1 = 0; cd.sx1 = 0; cd.x2 = nullptr; cd.n2 = 0; cd.sx2 = 0;
-            cd.pre_a = d->dec_in_part + (size_t)(s - part_c0) * B * 4 * D;
         }
         if (d->dec_drop) { cd.drop_mask = d->dec_drop + (size_t)s * B * D; cd.drop_scale = d->dec_drop_scale; }
         if (d->teacher_forced) { cd.h_copy = d->hc_all + (size_t)s * B * (D + E); cd.s_copy = D + E; }
@@ -438,26 +423,12 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
         { const int rd = body(step0 + n_steps - 1, false, true); if (rd != T2S_OK) return rd; }
     } else if (split) {
         // the attention chain of `chunk` steps, ONE event, then the decoder cells of those steps on the helper stream while the
-        // caller's stream goes on with the next chunk (T2S_DECODE_CHUNK, default 16)
-        static const int chunk_env = getenv("T2S_DECODE_CHUNK") ? atoi(getenv("T2S_DECODE_CHUNK")) : 16;
-        int chunk = chunk_env > 0 ? chunk_env : 1;
-        if (chunk_gemm && chunk > 16) chunk = 16;          // (dec_in_part holds 16 steps)
-        for (int c0 = step0; c0 < step0 + n_steps; c0 += chunk) {
-            const int c1 = c0 + chunk < step0 + n_steps ? c0 + chunk : step0 + n_steps;
+        // caller's stream goes on with the next chunk
+        for (int c0 = step0; c0 < step0 + n_steps; c0 += DECODE_CHUNK) {
+            const int c1 = c0 + DECODE_CHUNK < step0 + n_steps ? c0 + DECODE_CHUNK : step0 + n_steps;
             for (int s = c0; s < c1; ++s) { const int rc = body(s, true, false); if (rc != T2S_OK) return rc; }
             T2S_CHECK_HIP(hipEventRecord(hs.ev_step, stream));        // h_att, ctx of the chunk saved (and all earlier work of the caller)
             T2S_CHECK_HIP(hipStreamWaitEvent(hs.side, hs.ev_step, 0));
-            if (chunk_gemm) {
-                GemvArgs g;
-                memset(&g, 0, sizeof(g));
-                g.W1 = d->dec_w_ih; g.ld1 = A + E; g.k1 = A + E;
-                g.x1 = d->att_h_all + (size_t)c0 * B * A; g.n1 = A; g.sx1 = A;
-                g.x2 = d->hc_all + (size_t)c0 * B * (D + E) + D; g.n2 = E; g.sx2 = D + E;
-                g.y = d->dec_in_part; g.sy_item = 4 * D; g.sy_row = 1; g.rows = 4 * D; g.items = (c1 - c0) * B; g.mask_scale = 1.f;
-                if (!gemv_args_ok(g)) return T2S_EINVAL;
-                T2S_CHECK_HIP(t2s_launch_gemv(g, hs.side));
-                part_c0 = c0;
-            }
             for (int s = c0; s < c1; ++s) { const int rc = body(s, false, true); if (rc != T2S_OK) return rc; }
         }
     } else {

@@ -4,7 +4,6 @@
 #include "taco_bwd_ops.h"
 #include "tacotron_ops.h"
 
-#include <stdlib.h>
 #include <string.h>
 
 #include <mutex>
@@ -16,15 +15,15 @@ extern "C" int t2s_internal_fail_hip(int e);
         if (_e != hipSuccess) return t2s_internal_fail_hip((int)_e); \
     } while (0)
 
-// The one piece of library-owned state (documented in include/t2s_hip.h): the BPTT driver overlaps three dependent
-// chains on three streams.  The caller hands over ONE stream, so the two helpers and their events belong to the library:
+// The one piece of library-owned state (documented in include/t2s_hip.h): the BPTT driver overlaps two dependent
+// chains on two streams.  The caller hands over ONE stream, so the helper and its events belong to the library:
 // one set per device, created on first use on THAT device, and a per-device mutex held while a call enqueues (two autograd
 // threads may call into the same device; the call only enqueues work, it never blocks on the GPU).
 namespace {
 struct BpttStreams {
     std::mutex mu;
-    hipStream_t side = nullptr, side2 = nullptr;
-    hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_energy = nullptr, ev_conv = nullptr, ev_join = nullptr;
+    hipStream_t side = nullptr;
+    hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_join = nullptr;
     bool ready = false;
 };
 constexpr int kMaxDevices = 64;
@@ -33,17 +32,12 @@ BpttStreams g_bptt[kMaxDevices];
 hipError_t bptt_streams_init(BpttStreams& s) {      // caller holds s.mu; the current device is the one s belongs to
     if (s.ready) return hipSuccess;
     hipError_t e;
-    // T2S_HELPER_PRIO: stream priority of the helpers (HIP: lower number = higher priority; the range is clamped to the device's).
-    // The helpers carry the chains nothing waits for per step (decoder cells), so a LOWER priority than the caller's stream lets the
-    // serial chain's workgroups go first whenever both have some pending.
+    // priority 0, clamped to the device's range (HIP: lower number = higher priority); a lower priority measured equal
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);         // lo = least (largest number), hi = greatest
-    int prio = getenv("T2S_HELPER_PRIO") ? atoi(getenv("T2S_HELPER_PRIO")) : 0;
-    prio = prio > lo ? lo : (prio < hi ? hi : prio);
+    const int prio = 0 > lo ? lo : (0 < hi ? hi : 0);
     if ((e = hipStreamCreateWithPriority(&s.side, hipStreamNonBlocking, prio)) != hipSuccess) return e;
-    if ((e = hipStreamCreateWithPriority(&s.side2, hipStreamNonBlocking, prio)) != hipSuccess) return e;
-    if (getenv("T2S_HELPER_PRIO")) fprintf(stderr, "[t2s] helper streams at priority %d (device range %d .. %d)\n", prio, hi, lo);
-    hipEvent_t* evs[] = {&s.ev_main, &s.ev_side, &s.ev_energy, &s.ev_conv, &s.ev_join};
+    hipEvent_t* evs[] = {&s.ev_main, &s.ev_side, &s.ev_join};
     for (hipEvent_t* ev : evs)
         if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return e;
     s.ready = true;
@@ -64,6 +58,9 @@ hipError_t t2s_helper_stream_acquire(T2sHelperStream& h) {
     h.side = S.side; h.ev_step = S.ev_main; h.ev_join = S.ev_join;
     return hipSuccess;
 }
+
+// steps of the decoder-cell chain enqueued per cross-stream wait (8 and 32 measured equal)
+constexpr int BPTT_CHUNK = 16;
 
 extern "C" {
 
@@ -141,76 +138,42 @@ int t2s_taco_bptt_steps(const t2s_taco_bptt* p, int t_hi, int t_lo, void* stream
         return T2S_EINVAL;
     // Two chains, two streams.  The decoder-cell chain of step t (pointwise backward, then [W_ih | W_hh]^T dgates) needs only
     // the decoder-cell chain of step t+1: h_dec feeds the next decoder cell and the projection, never the attention.  The
-    // attention / attention-cell chain of step t consumes its output out_d[t].  So the former runs ahead on a side stream and
-    // signals one event per step; its ~27 us per step hide behind the ~78 us of the attention chain.
-    // A third stream takes the last part of the attention backward (location-conv backward): it only feeds the NEXT step's
-    // carries and the kernel gradient, so it runs beside this step's attention-cell backward and GEMM.
-    static const bool two_streams = !getenv("T2S_BPTT_ONE_STREAM");
-    // The location-conv backward stays on the caller's stream: with the matrix-core kernels it takes 10 us, while the event
-    // record on the critical stream and the wait for a third stream cost ~7 + ~5 us per step on this runtime
-    // (profiles/r03_taco_timeline_bwd.md; 128.7 -> 122.4 ms per train step).  T2S_BPTT_CONV_MAIN=0: the round-2 three-stream form.
-    static const bool conv_main = !getenv("T2S_BPTT_CONV_MAIN") || atoi(getenv("T2S_BPTT_CONV_MAIN"));
+    // attention / attention-cell chain of step t consumes its output out_d[t].  So the former runs ahead on a side stream; its
+    // ~27 us per step hide behind the ~78 us of the attention chain.  The location-conv backward stays on the caller's stream:
+    // with the matrix-core kernels it takes 10 us, while the event record on the critical stream and the wait for a third stream
+    // cost ~7 + ~5 us per step on this runtime (profiles/r03_taco_timeline_bwd.md; 128.7 -> 122.4 ms per train step).
     int device = 0;
     T2S_CHECK_HIP(hipGetDevice(&device));
     if (device < 0 || device >= kMaxDevices) return T2S_EINVAL;
     BpttStreams& S = g_bptt[device];
     std::unique_lock<std::mutex> lock(S.mu);
-    if (two_streams) T2S_CHECK_HIP(bptt_streams_init(S));
-    hipStream_t side = S.side, side2 = S.side2;
-    hipEvent_t ev_main = S.ev_main, ev_side = S.ev_side, ev_energy = S.ev_energy, ev_conv = S.ev_conv;
+    T2S_CHECK_HIP(bptt_streams_init(S));
+    const hipStream_t side = S.side;
     // Whatever happens below (including a failed launch), the caller's stream is made to wait for everything already
-    // enqueued on the two helper streams before this call returns: the caller may recycle the scratch buffers as soon as
+    // enqueued on the helper stream before this call returns: the caller may recycle the scratch buffers as soon as
     // ITS stream has passed this point.
     struct Join {
-        BpttStreams& S; hipStream_t stream; bool on;
+        BpttStreams& S; hipStream_t stream;
         ~Join() {
-            if (!on) return;
             if (hipEventRecord(S.ev_join, S.side) == hipSuccess) (void)hipStreamWaitEvent(stream, S.ev_join, 0);
-            if (hipEventRecord(S.ev_join, S.side2) == hipSuccess) (void)hipStreamWaitEvent(stream, S.ev_join, 0);
         }
-    } join{S, stream, two_streams};
-    bool conv_pending = false;
-    hipStream_t dstream = two_streams ? side : stream;
-    if (two_streams) {                                   // everything enqueued so far (d_hc, the saves) precedes the side chain
-        T2S_CHECK_HIP(hipEventRecord(ev_main, stream));
-        T2S_CHECK_HIP(hipStreamWaitEvent(side, ev_main, 0));
-    }
-    // The decoder-cell chain never waits for the attention chain, so it is enqueued `chunk` steps at a time and the caller's
+    } join{S, stream};
+    // everything enqueued so far (d_hc, the saves) precedes the side chain
+    T2S_CHECK_HIP(hipEventRecord(S.ev_main, stream));
+    T2S_CHECK_HIP(hipStreamWaitEvent(side, S.ev_main, 0));
+    // The decoder-cell chain never waits for the attention chain, so it is enqueued BPTT_CHUNK steps at a time and the caller's
     // stream waits once per chunk: a cross-stream wait costs ~6 us on the critical stream (profiles/r03_taco_timeline_bwd_fused.md).
-    static const int chunk_env = getenv("T2S_BPTT_CHUNK") ? atoi(getenv("T2S_BPTT_CHUNK")) : 16;
-    const int chunk = two_streams ? (chunk_env > 0 ? chunk_env : 1) : 1;
-    // Two streams, 9+ items: the transposed decoder-cell GEMM [KD = A + E + D rows] x [4 D] of every step is
-    // split by consumer - the D rows of d h_dec(t-1), which the next decoder-cell step needs, per step; the A + E rows of d h_att /
-    // d ctx, which only the attention chain reads (a chunk of steps later), as ONE launch over the chunk's (steps x batch) items
-    // (-1 % of the train step: 88.45 / 88.2 / 87.8 / 88.2 against 89.4 / 89.7 / 89.5 / 89.5 ms in three same-box sessions,
-    // profiles/r04_taco_bptt_streams_ab.txt, r04_taco_bptt_narrow_ab.txt, r04_taco_chunk_gemm_ab.txt.  T2S_BPTT_SPLIT_ROWS=0: off)
-    static const bool want_split_rows = !(getenv("T2S_BPTT_SPLIT_ROWS") && atoi(getenv("T2S_BPTT_SPLIT_ROWS")) == 0);
-    // T2S_BPTT_SIDE_NARROW=1: the decoder-cell chain's GEMM (helper stream) on the 96 KB ring, so that the attention chain's
-    // att_bwd_fused workgroups (61 KB of LDS) can share its CUs instead of queueing behind it.  Measured NEGATIVE: 96.6 / 96.3
-    // against 89.5 / 90.0 ms per train step (profiles/r04_taco_bptt_narrow_ab.txt) - the 64-byte fragment rows cost the GEMM more
-    // CU time than the sharing returns; the loop is the sum of its kernels' CU time.  Off.
-    static const bool want_narrow = getenv("T2S_BPTT_SIDE_NARROW") && atoi(getenv("T2S_BPTT_SIDE_NARROW")) != 0;
-    const bool side_narrow = want_narrow && two_streams;
-    const bool split_rows = want_split_rows && two_streams && chunk > 1 && B > 8 && ((A + E) & 15) == 0 && (D & 15) == 0;
-    // Paced helper chain (T2S_BPTT_PACED=1; needs att_xbuf, whose tail holds the word): the decoder-cell chain's step m (counted from
-    // t_hi - 1) is released by a word the attention backward's launch of step m - chunk stores as it starts, and its GEMM takes the
-    // 96 KB ring - so that it runs BESIDE that launch (61 KB of LDS) instead of holding the CUs the chain's next launch needs.
-    // Built after the forward's pacing paid (section 5b of DESIGN.md) and measured NEGATIVE here: 77.8 / 78.0 ms per train step with
-    // the 96 KB ring, 78.9 / 78.7 with the 144 KB one, against 74.2 / 73.9 unpaced (profiles/r04_bptt_paced_ab.txt; every gradient test
-    // green with it on).  The forward pairs a GEMM with a 14 KB kernel; here the partner is a 61 KB / 185-VGPR kernel and the GEMM has to
-    // take the slower ring to fit beside it.  Off.
-    static const bool want_bpaced = getenv("T2S_BPTT_PACED") && atoi(getenv("T2S_BPTT_PACED")) != 0;
-    static const bool bpaced_narrow = !(getenv("T2S_BPTT_PACED_NARROW") && atoi(getenv("T2S_BPTT_PACED_NARROW")) == 0);
-    const bool bpaced = want_bpaced && two_streams && chunk > 1 && p->att_xbuf && p->ctx_all && p->dw_c2 && p->dwc_c2 && conv_main &&
-                        Tin <= 512 && ad == 128;
-    unsigned* const pace_word = bpaced ? (unsigned*)((unsigned long long*)p->att_xbuf + (size_t)B * ((Tin + 31) / 32) * ad + 1) : nullptr;
-    unsigned long long* const pace_err = bpaced ? (unsigned long long*)p->att_xbuf + (size_t)B * ((Tin + 31) / 32) * ad + 2 : nullptr;
+    constexpr int chunk = BPTT_CHUNK;
+    // 9+ items: the transposed decoder-cell GEMM [KD = A + E + D rows] x [4 D] of every step is split by consumer - the D rows of
+    // d h_dec(t-1), which the next decoder-cell step needs, per step; the A + E rows of d h_att / d ctx, which only the attention
+    // chain reads (a chunk of steps later), as ONE launch over the chunk's (steps x batch) items (-1 % of the train step: 88.45 /
+    // 88.2 / 87.8 / 88.2 against 89.4 / 89.7 / 89.5 / 89.5 ms in three same-box sessions, profiles/r04_taco_bptt_streams_ab.txt,
+    // r04_taco_bptt_narrow_ab.txt, r04_taco_chunk_gemm_ab.txt)
+    const bool split_rows = B > 8 && ((A + E) & 15) == 0 && (D & 15) == 0;
     for (int tc = t_hi - 1; tc >= t_lo; tc -= chunk) {
     const int tl = tc - chunk + 1 > t_lo ? tc - chunk + 1 : t_lo;
     for (int t = tc; t >= tl; --t) {
         const bool nxt = t + 1 < T;
-        if (bpaced && t_hi - 1 - t >= chunk)
-            T2S_CHECK_HIP(t2s_launch_pace_wait(pace_word, (unsigned)(t_hi - 1 - t - chunk) + 1u, pace_err, dstream));
         // decoder LSTMCell: dh = d[h_dec] from the projection + from step t+1's decoder cell (through W_hh)
         LstmBwdArgs cd;
         cd.dh1 = p->d_hc + (size_t)t * B * DE; cd.s1 = DE;
@@ -221,22 +184,17 @@ int t2s_taco_bptt_steps(const t2s_taco_bptt* p, int t_hi, int t_lo, void* stream
         cd.c_prev = t > 0 ? p->dec_c_all + (size_t)(t - 1) * B * D : nullptr;
         cd.dc_carry = p->dc_d; cd.dgates = p->dg_d + (size_t)t * B * 4 * D; cd.B = B; cd.H = D;
         cd.wq = nullptr; cd.dq = nullptr; cd.q_dim = 0; cd.dq_part = nullptr; cd.dq_nchunk = 0; cd.dq_out = nullptr;
-        T2S_CHECK_HIP(t2s_launch_lstm_cell_bwd(cd, dstream));
+        T2S_CHECK_HIP(t2s_launch_lstm_cell_bwd(cd, side));
         GemvArgs g;
         memset(&g, 0, sizeof(g));
         g.W1 = p->W_dT; g.ld1 = 4 * D; g.k1 = 4 * D; g.x1 = cd.dgates; g.n1 = 4 * D; g.sx1 = 4 * D;
         g.y = p->out_d + (size_t)t * B * KD; g.sy_item = KD; g.sy_row = 1; g.rows = KD; g.items = B; g.mask_scale = 1.f;
-        g.narrow_ring = (side_narrow || (bpaced && bpaced_narrow)) ? 1 : 0;
-        static const bool side_full = getenv("T2S_BPTT_SIDE_FULL") && atoi(getenv("T2S_BPTT_SIDE_FULL")) != 0;
-        // (A/B: 32 items per workgroup on the helper chain's per-step GEMM - fewer, longer workgroups: 77.1 / 77.6 against
-        // 73.5 / 73.7 ms per train step, profiles/r04_bptt_side_full_ab.txt; off)
-        g.no_half = (side_full && two_streams) ? 1 : 0;
         if (split_rows) {
             // only the rows the NEXT decoder-cell step reads (d h_dec(t-1) = rows A + E .. KD of [W_ih | W_hh]^T dgates) stay per step;
             // the d h_att / d ctx rows, which the attention chain reads a chunk later, are one GEMM over the chunk's items below
             g.W1 = p->W_dT + (size_t)(A + E) * 4 * D; g.y += A + E; g.rows = D;
         }
-        T2S_CHECK_HIP(t2s_launch_gemv(g, dstream));
+        T2S_CHECK_HIP(t2s_launch_gemv(g, side));
     }
     if (split_rows) {
         GemvArgs g;
@@ -244,12 +202,11 @@ int t2s_taco_bptt_steps(const t2s_taco_bptt* p, int t_hi, int t_lo, void* stream
         g.W1 = p->W_dT; g.ld1 = 4 * D; g.k1 = 4 * D; g.x1 = p->dg_d + (size_t)tl * B * 4 * D; g.n1 = 4 * D; g.sx1 = 4 * D;
         g.y = p->out_d + (size_t)tl * B * KD; g.sy_item = KD; g.sy_row = 1; g.rows = A + E; g.items = (tc - tl + 1) * B;
         g.mask_scale = 1.f;
-        T2S_CHECK_HIP(t2s_launch_gemv(g, dstream));
+        T2S_CHECK_HIP(t2s_launch_gemv(g, side));
     }
-    if (two_streams) {       // out_d[tl .. tc] are ready: the wait below binds to THIS record, so one event object serves every chunk
-        T2S_CHECK_HIP(hipEventRecord(ev_side, side));
-        T2S_CHECK_HIP(hipStreamWaitEvent(stream, ev_side, 0));
-    }
+    // out_d[tl .. tc] are ready: the wait below binds to THIS record, so one event object serves every chunk
+    T2S_CHECK_HIP(hipEventRecord(S.ev_side, side));
+    T2S_CHECK_HIP(hipStreamWaitEvent(stream, S.ev_side, 0));
     for (int t = tc; t >= tl; --t) {
         const bool nxt = t + 1 < T;
         GemvArgs g;
@@ -270,13 +227,13 @@ int t2s_taco_bptt_steps(const t2s_taco_bptt* p, int t_hi, int t_lo, void* stream
         if (p->dctx_all) { ab.dctx_out = p->dctx_all + (size_t)t * B * E; ab.d_memory = nullptr; }
         ab.B = B; ab.T = Tin; ab.att_dim = ad; ab.enc_dim = E; ab.loc_f = p->loc_filters; ab.loc_ks = p->loc_kernel;
         bool fused = false;
-        if (p->ctx_all && p->dw_c2 && p->dwc_c2 && (!two_streams || conv_main)) {
+        if (p->ctx_all && p->dw_c2 && p->dwc_c2) {
             // one launch: reads the carries of parity t, writes those of parity t - 1; d_q stays in per-chunk partials
             ab.ctx = p->ctx_all + (size_t)t * p->s_ctx_step; ab.s_ctx = p->s_ctx_item;
             if (t & 1) { ab.dw_carry = p->dw_c2; ab.dwc_carry = p->dwc_c2; ab.dw_carry_out = p->dw_c; ab.dwc_carry_out = p->dwc_c; }
             else { ab.dw_carry_out = p->dw_c2; ab.dwc_carry_out = p->dwc_c2; }
             fused = t2s_att_bwd_fused_ok(ab);
-            if (!fused) {                           // shape not covered (or T2S_ATTB_FUSED=0): the three-launch form, carries in place
+            if (!fused) {                           // shape not covered: the three-launch form, carries in place
                 ab.ctx = nullptr; ab.dw_carry = p->dw_c; ab.dwc_carry = p->dwc_c; ab.dw_carry_out = nullptr; ab.dwc_carry_out = nullptr;
             }
         }
@@ -287,34 +244,20 @@ int t2s_taco_bptt_steps(const t2s_taco_bptt* p, int t_hi, int t_lo, void* stream
         ca.dh3 = nullptr; ca.s3 = 0;
         ca.wq = p->w_query; ca.dq = ab.d_q; ca.q_dim = ad;           // + W_query^T d_q, fused
         ca.dq_part = nullptr; ca.dq_nchunk = 0; ca.dq_out = nullptr;
-        if (fused || (two_streams && !conv_main)) {       // d_q is not folded yet: sum the per-chunk partials here
-            ca.dq_part = p->dq_part; ca.dq_nchunk = (Tin + 31) / 32;
-            if (fused) ca.dq_out = ab.d_q;
+        if (fused) {                                       // d_q is not folded yet: sum the per-chunk partials here
+            ca.dq_part = p->dq_part; ca.dq_nchunk = (Tin + 31) / 32; ca.dq_out = ab.d_q;
         }
         ca.drop_mask = p->att_drop ? p->att_drop + (size_t)t * B * A : nullptr; ca.drop_scale = p->att_drop_scale;
         ca.gates = p->att_gates_all + (size_t)t * B * 4 * A; ca.c_new = p->att_c_all + (size_t)t * B * A;
         ca.c_prev = t > 0 ? p->att_c_all + (size_t)(t - 1) * B * A : nullptr;
         ca.dc_carry = p->dc_a; ca.dgates = p->dg_a + (size_t)t * B * 4 * A; ca.B = B; ca.H = A;
-        // ... folded into the one-launch attention backward where it runs (t2s_taco_bptt::att_xbuf; T2S_BPTT_FOLD_CELL=0: a launch of its own)
-        static const bool want_fold = !(getenv("T2S_BPTT_FOLD_CELL") && atoi(getenv("T2S_BPTT_FOLD_CELL")) == 0);
-        const bool fold_cell = fused && want_fold && p->att_xbuf && Tin <= 512 && ad == 128;
+        // ... folded into the one-launch attention backward where it runs (t2s_taco_bptt::att_xbuf)
+        const bool fold_cell = fused && p->att_xbuf && Tin <= 512 && ad == 128;
         if (fused) {
             AttBwdFoldArgs fa;
             memset(&fa, 0, sizeof(fa));
             if (fold_cell) { fa.cell = ca; fa.xbuf = (unsigned long long*)p->att_xbuf; fa.tag = (unsigned)t + 1u; }
-            if (bpaced) { fa.sig_ptr = pace_word; fa.sig_val = (unsigned)(t_hi - 1 - t) + 1u; }
-            T2S_CHECK_HIP(t2s_launch_att_bwd_fused(ab, stream, (fold_cell || bpaced) ? &fa : nullptr));
-        } else if (two_streams && conv_main) {
-            if (bpaced) T2S_CHECK_HIP(t2s_launch_pace_signal(pace_word, (unsigned)(t_hi - 1 - t) + 1u, stream));
-            T2S_CHECK_HIP(t2s_launch_att_bwd(ab, stream));
-        } else if (two_streams) {
-            if (conv_pending) T2S_CHECK_HIP(hipStreamWaitEvent(stream, ev_conv, 0));   // carries of step t+1 are in place
-            T2S_CHECK_HIP(t2s_launch_att_bwd_front(ab, stream));
-            T2S_CHECK_HIP(hipEventRecord(ev_energy, stream));
-            T2S_CHECK_HIP(hipStreamWaitEvent(side2, ev_energy, 0));
-            T2S_CHECK_HIP(t2s_launch_att_bwd_conv(ab, side2));
-            T2S_CHECK_HIP(hipEventRecord(ev_conv, side2));
-            conv_pending = true;
+            T2S_CHECK_HIP(t2s_launch_att_bwd_fused(ab, stream, fold_cell ? &fa : nullptr));
         } else {
             T2S_CHECK_HIP(t2s_launch_att_bwd(ab, stream));
         }
@@ -325,7 +268,6 @@ int t2s_taco_bptt_steps(const t2s_taco_bptt* p, int t_hi, int t_lo, void* stream
         T2S_CHECK_HIP(t2s_launch_gemv(g, stream));
     }
     }
-    if (conv_pending) T2S_CHECK_HIP(hipStreamWaitEvent(stream, ev_conv, 0));       // dq_all, carries, dK complete for the caller
     return T2S_OK;
 }
 

@@ -16,24 +16,19 @@ extern "C" int t2s_internal_fail_hip(int e);
 
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-#include <stdlib.h>
 // The accumulate / gate-backward GEMMs of the training backward: 256-row tiles on the ping-pong schedule (csrc/gate_gemm_pp.hip)
 // once they give at least ~100 workgroups - M = 512 at 8 x 16000 is 128, half the chip, and the rest is taken by the
 // weight-gradient stream that runs beside them - else the lockstep kernels on 128-row tiles (twice the workgroups).
-// T2S_BWD_PP256=0 restores the round-2 choice for A/B runs.
 static bool bwd_pp256(const ConvGemmArgs& a, int rows) {
-    static const int on = getenv("T2S_BWD_PP256") ? atoi(getenv("T2S_BWD_PP256")) : 1;
-    return on && t2s_pp_shape_ok(a) && (long)cdiv(rows, 256) * a.n_ttiles * a.B >= 100;
+    return t2s_pp_shape_ok(a) && (long)cdiv(rows, 256) * a.n_ttiles * a.B >= 100;
 }
 
 static int planes_ok(const void* a, const void* b) { return a && b && al16(a) && al16(b); }
 
 // Can the backward GEMM with `rows` output rows over B x L columns take PERM_PAIR8-packed operands (16-byte epilogue pieces)?  Only
-// the 256-row ping-pong kernels have that epilogue: the grid rule of bwd_pp256 above, whole 32-row groups.  T2S_BWD_PAIR8=0: never.
+// the 256-row ping-pong kernels have that epilogue: the grid rule of bwd_pp256 above, whole 32-row groups.
 extern "C" int t2s_wg_bwd_pair8_ok(int B, int rows, int L) {
-    static const int on = getenv("T2S_BWD_PAIR8") ? atoi(getenv("T2S_BWD_PAIR8")) : 1;
-    static const int pp = getenv("T2S_BWD_PP256") ? atoi(getenv("T2S_BWD_PP256")) : 1;
-    if (!on || !pp || B <= 0 || rows <= 0 || L <= 0 || rows % 32) return 0;
+    if (B <= 0 || rows <= 0 || L <= 0 || rows % 32) return 0;
     return (long)cdiv(rows, 256) * cdiv(L, 256) * B >= 100 ? 1 : 0;
 }
 

@@ -60,7 +60,6 @@ struct ConvGemmArgs {
     int ph_bper;           // batch entries per tile = 256 / ph_FT
     int ph_nft;            // frame tiles per batch entry
     int ph_Fp;             // rows of the mel-window planes S[B][sc][ph_Fp][32]
-    int dbg;               // timing-only ablations (env T2S_DBG_GEMM): 1 = no DMA in the K loop, 2 = no MFMA; results are wrong
 };
 
 hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows = 256);

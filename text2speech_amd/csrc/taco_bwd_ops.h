@@ -55,8 +55,8 @@ struct AttBwdFoldArgs {
     LstmBwdArgs cell;
     unsigned long long* xbuf;
     unsigned tag;
-    // optional: the first thread of the launch stores sig_val to *sig_ptr as the kernel starts (pacing of the helper stream's
-    // decoder-cell chain: t2s_launch_pace_wait, csrc/tacotron_ops.h)
+    // optional: the first thread of the launch stores sig_val to *sig_ptr as the kernel starts (t2s_launch_pace_wait,
+    // csrc/tacotron_ops.h; no caller sets it now - kept so that the kernel stays as measured)
     unsigned* sig_ptr; unsigned sig_val;
 };
 

@@ -797,14 +797,8 @@ static __device__ __forceinline__ float attf_carry(const float* c, size_t BT, si
 }
 #define ATTF_SP 130
 #define ATTF_SPIN_MAX (1 << 22)
-#ifdef T2S_ATTB_LB2             // A/B build: two workgroups per CU by registers (128 VGPRs instead of 185, 188 bytes of scratch per thread):
-                                // 89.3 / 90.3 against 74.1 / 73.8 ms per train step (profiles/r04_attb_lb2_ab.txt) - the spills cost far more
-                                // than sharing CUs with the helper chain's GEMMs could return
-#define ATTB_LB __launch_bounds__(512, 4)
-#else
-#define ATTB_LB __launch_bounds__(512)
-#endif
-__global__ ATTB_LB void att_bwd_fused_kernel(const AttBwdArgs a, const AttBwdFoldArgs fold) {
+// (one workgroup per CU by registers, 185 VGPRs: a 128-VGPR bound spilled and measured much slower)
+__global__ __launch_bounds__(512) void att_bwd_fused_kernel(const AttBwdArgs a, const AttBwdFoldArgs fold) {
     constexpr int AD = 128, F = 32, SP = ATTF_SP, SD = 34, SG = 34;
     __shared__ __attribute__((aligned(16))) float s_all[128 + 64 * 48 + ATTB_CH * 33 + 32 * 144 + ATTB_CH * ATTF_SP + ATTB_CH * 34 + 1024 + 2 * ATTB_CH + 16];
     float* s_cat = s_all;                          // [2][64]    window of [w_prev ; wc_prev]: entry i <-> t0 - pad + i
@@ -824,9 +818,6 @@ __global__ ATTB_LB void att_bwd_fused_kernel(const AttBwdArgs a, const AttBwdFol
     // block number -> (batch element, chunk): id = 8 s + x is chunk s % n_chunks of element 8 (s / n_chunks) + x - the chunks of an
     // element share one XCD's L2 (workgroups go round the 8 XCDs by block number) and are neighbours in dispatch order (they wait
     // for one another when the cell backward is folded in, below)
-#ifdef T2S_ATTB_SETPRIO
-    __builtin_amdgcn_s_setprio(3);                 // (A/B build: this kernel is the backward's serial chain)
-#endif
     if (fold.sig_ptr && blockIdx.x == 0 && threadIdx.x == 0)          // "this launch has started"
         __hip_atomic_store(fold.sig_ptr, fold.sig_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int n_chunks = (a.T + ATTB_CH - 1) / ATTB_CH;
@@ -1272,9 +1263,8 @@ hipError_t t2s_launch_att_bwd_front(const AttBwdArgs& a, hipStream_t stream) {
     if (!att_bwd_ok(a)) return hipErrorInvalidValue;
     const dim3 grid((a.T + ATTB_CH - 1) / ATTB_CH, a.B);
     hipLaunchKernelGGL(att_bwd_dw_kernel, grid, dim3(256), 0, stream, a);
-    // matrix-core form for the reference's shape (T2S_ATTB_VALU bit 0 / bit 1: the VALU energies / convolution kernel, for A/B runs)
-    static const int valu = getenv("T2S_ATTB_VALU") ? atoi(getenv("T2S_ATTB_VALU")) : 0;
-    if (!(valu & 1) && a.att_dim == 128 && a.loc_f == 32 && a.loc_ks <= 31) {
+    // matrix-core form for the reference's shape, the VALU kernels for the others
+    if (a.att_dim == 128 && a.loc_f == 32 && a.loc_ks <= 31) {
         hipLaunchKernelGGL(att_bwd_energy_mfma_kernel, grid, dim3(512), 0, stream, a);
     } else {
         hipLaunchKernelGGL(att_bwd_energy_kernel, grid, dim3(512), 0, stream, a);
@@ -1284,16 +1274,14 @@ hipError_t t2s_launch_att_bwd_front(const AttBwdArgs& a, hipStream_t stream) {
 hipError_t t2s_launch_att_bwd_conv(const AttBwdArgs& a, hipStream_t stream) {
     if (!att_bwd_ok(a)) return hipErrorInvalidValue;
     const dim3 grid((a.T + ATTB_CH - 1) / ATTB_CH, a.B);
-    static const int valu = getenv("T2S_ATTB_VALU") ? atoi(getenv("T2S_ATTB_VALU")) : 0;
-    if (!(valu & 2) && a.loc_f == 32 && a.loc_ks <= 31)
+    if (a.loc_f == 32 && a.loc_ks <= 31)
         hipLaunchKernelGGL(att_bwd_conv_mfma_kernel, grid, dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL(att_bwd_conv_kernel, grid, dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 bool t2s_att_bwd_fused_ok(const AttBwdArgs& a) {
-    static const int off = getenv("T2S_ATTB_FUSED") ? !atoi(getenv("T2S_ATTB_FUSED")) : 0;
-    return !off && att_bwd_ok(a) && a.att_dim == 128 && a.loc_f == 32 && a.loc_ks <= 31 && a.ctx && a.dw_carry_out &&
+    return att_bwd_ok(a) && a.att_dim == 128 && a.loc_f == 32 && a.loc_ks <= 31 && a.ctx && a.dw_carry_out &&
            a.dwc_carry_out && a.dctx_out && !a.d_memory && a.dw_carry_out != a.dw_carry && a.dwc_carry_out != a.dwc_carry;
 }
 hipError_t t2s_launch_att_bwd_fused(const AttBwdArgs& a, hipStream_t stream, const AttBwdFoldArgs* fold) {

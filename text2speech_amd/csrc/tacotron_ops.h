@@ -30,11 +30,6 @@ struct GemvArgs {
     float* y2; long sy2_item; long sy2_row;
     int act2;
     const unsigned char* mask2; long smask2_item; float mask2_scale;
-    // small-batch GEMM only: the 96 KB operand ring (64-byte fragment rows) instead of the 144 KB one, so that a 61 KB workgroup of
-    // another stream's kernel (att_bwd_fused_kernel) fits on the same CU - for launches on a helper stream with slack
-    int narrow_ring;
-    // small-batch GEMM only: never the 16-items-per-workgroup form (helper-stream launches: fewer, longer workgroups cost less CU time)
-    int no_half;
 };
 
 struct LstmCellArgs {
@@ -85,8 +80,6 @@ struct GateStreamArgs {
     const float* W2; int ld2; float* out2;                    // out2[b][r] = W2[r][:H] . x12[b][:H]
     const float* x12;
     int rows, H, B;                                           // rows = 4H of each block, H = 1024
-    int dbg;                                                  // -DT2S_ATTSTREAM_ABLATE builds only: 1 = attention role returns at once,
-                                                              // 2 = gate-stream role returns at once (timing only, results garbage)
 };
 
 struct AttArgs {
@@ -119,7 +112,7 @@ struct AttArgs {
     // positions, growing linearly) and only adds q and the processed memory
     const float* ploc;
     float* wcum_save;          // optional [B][T]: cumulative weights after this step (training)
-    int tile_major;            // att_energy_mfma_kernel: block -> (tile, item) in launch order instead of item-per-XCD (A/B: T2S_ENERGY_XCD=0)
+    int tile_major;            // att_energy_mfma_kernel: block -> (tile, item) in launch order instead of item-per-XCD (always 0 now; kept so that the kernel stays as measured)
     // one-launch form of energies + softmax + context (t2s_launch_att_energy with xbuf set; t2s_att_energy_ctx_ok says whether the
     // shape is covered): [B][T] 8-byte granules + 1 error word, zero before step 0; tag = step + 1 (never 0)
     unsigned long long* xbuf;

@@ -305,21 +305,11 @@ hipError_t t2s_launch_gemv_with_loc(const GemvArgs& a, const LocPreArgs& lp_in, 
 // UNITS = hidden units per workgroup (4 -> 1024 threads, 2 -> 512 threads); SAVE = keep gates / cell state (training)
 // weight-row loads of the LSTM cell: each row is streamed once per step by ONE workgroup, so they are non-temporal
 // (MI355X_MICROARCH.md nt-weights; same box, alternating: 39.26 / 39.01 vs 39.60 / 39.66 us per step at B = 1).
-// -DT2S_LSTM_PLAIN_LOADS restores default-policy loads.
-#ifdef T2S_LSTM_PLAIN_LOADS
-#define T2S_WLOAD(p) (*(p))
-#else
 #define T2S_WLOAD(p) __builtin_nontemporal_load(p)
-#endif
 // With the streamed gate partials (LstmCellArgs::pre_a) a cell reads 8-13 MB per step, and those columns are better loaded with the
 // default policy while the attention launch's 50 MB stream stays nt: 29.04 / 29.04 vs 29.70 / 29.33 us per step at B = 1, same box
 // (profiles/r04_cache_policy_ab.txt; all-plain: 31.4 / 31.3; the unstreamed chain prefers nt in the cells: 37.5-37.7 vs 38.3-38.7).
-// -DT2S_CELL_NT_LOADS: nt in the streamed cells too (the A/B's other side).
-#ifdef T2S_CELL_NT_LOADS
-#define T2S_CLOAD(p) T2S_WLOAD(p)
-#else
 #define T2S_CLOAD(p) (*(p))
-#endif
 
 template <int NVW, int UNITS, bool SAVE, bool STREAMED = false>
 __global__ __launch_bounds__(UNITS * 256) void lstm_cell_kernel(const LstmCellArgs a) {
@@ -812,10 +802,8 @@ __global__ __launch_bounds__(512, 2) void att_energy_mfma_kernel(const AttArgs a
     // that the item's 128 KB of partial queries cross the fabric once and its other tiles find them in that XCD's L2 - with the
     // plain (tile, item) grid every XCD pulled every item's partials (32 MB per launch at B = 32, T = 256 instead of 4 MB).
     // this kernel is the serial chain; what shares its CUs (a decoder cell's GEMM workgroup on the helper stream) is not: its waves
-    // ask for issue priority (T2S_ATT_SETPRIO=0 at build time: -DT2S_ATT_NO_SETPRIO)
-#ifndef T2S_ATT_NO_SETPRIO
+    // ask for issue priority
     __builtin_amdgcn_s_setprio(3);
-#endif
     const int n_tiles = (a.T + ATT_MQ - 1) / ATT_MQ;
     const int slot = blockIdx.x >> 3;
     int b = (slot / n_tiles) * 8 + (blockIdx.x & 7), tile = slot - (slot / n_tiles) * n_tiles;
@@ -1082,25 +1070,21 @@ __global__ __launch_bounds__(512, 2) void att_energy_mfma_kernel(const AttArgs a
 // multiple of 64 (workgroup `tile` takes the context chunks tile, tile + n_tiles, ...), a row of weights within 2 KB of LDS (so that
 // the workgroup still fits beside a small-batch GEMM workgroup)
 bool t2s_att_energy_ctx_ok(const AttArgs& a) {
-    static const bool no_mfma = getenv("T2S_ATT_VALU") != nullptr;
-    static const bool plain = getenv("T2S_ENERGY_XCD") && atoi(getenv("T2S_ENERGY_XCD")) == 0;
-    if (no_mfma || plain || a.att_dim != 128 || a.loc_f != 32 || a.loc_ks > 31 || !a.w_loc_denseT) return false;
+    if (a.att_dim != 128 || a.loc_f != 32 || a.loc_ks > 31 || !a.w_loc_denseT) return false;
     if (a.q_part && a.n_part != 256) return false;
     const int n_tiles = (a.T + ATT_MQ - 1) / ATT_MQ;
     (void)n_tiles;                                           // (fewer tiles than context chunks: a workgroup takes several)
     return a.T <= 512 && (a.enc_dim & 63) == 0 && a.tag != 0;
 }
 hipError_t t2s_launch_att_energy(const AttArgs& a, hipStream_t stream) {
-    // T2S_ATT_VALU set: the VALU kernel (A/B switch, shared with the fused small-batch form)
-    static const bool no_mfma = getenv("T2S_ATT_VALU") != nullptr;
-    if (!no_mfma && a.att_dim == 128 && a.loc_f == 32 && a.loc_ks <= 31 && a.w_loc_denseT) {
+    // other shapes: the VALU kernel below
+    if (a.att_dim == 128 && a.loc_f == 32 && a.loc_ks <= 31 && a.w_loc_denseT) {
         if (a.q_part && a.n_part != 256) return hipErrorInvalidValue;
-        static const bool plain = getenv("T2S_ENERGY_XCD") && atoi(getenv("T2S_ENERGY_XCD")) == 0;
         AttArgs aa = a;
-        aa.tile_major = plain ? 1 : 0;
+        aa.tile_major = 0;
         dim3 grid(8 * ((a.B + 7) / 8) * ((a.T + ATT_MQ - 1) / ATT_MQ));
         if (a.xbuf) {
-            if (plain || !t2s_att_energy_ctx_ok(a)) return hipErrorInvalidValue;
+            if (!t2s_att_energy_ctx_ok(a)) return hipErrorInvalidValue;
             hipLaunchKernelGGL(att_energy_mfma_kernel<true>, grid, dim3(512), (size_t)a.T * sizeof(float), stream, aa);
             return hipGetLastError();
         }
@@ -1431,16 +1415,10 @@ template <bool STREAM, bool PLOC = false>
 __global__ __launch_bounds__(1024) void att_fused_mfma_kernel(const AttArgs a, const GateStreamArgs gs) {
     if constexpr (STREAM) {
         if ((int)blockIdx.x >= a.B) {           // whole workgroups take this branch: no barrier of the attention role is skipped
-#ifdef T2S_ATTSTREAM_ABLATE
-            if (gs.dbg == 2) return;
-#endif
             extern __shared__ __attribute__((aligned(16))) float s_role[];
             gate_stream_role(gs, (int)blockIdx.x - a.B, (int)gridDim.x - a.B, s_role);
             return;
         }
-#ifdef T2S_ATTSTREAM_ABLATE
-        if (gs.dbg == 1) return;
-#endif
     }
     PROBE_BEGIN(301)
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];   // s_f [max(Tp*33, 4096)] | s_e [Tp] | s_ep [8][Tp] | s_kb [KP][48]
@@ -1784,10 +1762,7 @@ __global__ __launch_bounds__(1024) void att_fused_mfma_kernel(const AttArgs a, c
     PROBE_END()
 }
 
-static bool att_fused_mfma_form(const AttArgs& a) {
-    static const bool no_mfma = getenv("T2S_ATT_VALU") != nullptr;       // A/B switch: the VALU form
-    return a.loc_f == 32 && a.att_dim == 128 && !no_mfma;
-}
+static bool att_fused_mfma_form(const AttArgs& a) { return a.loc_f == 32 && a.att_dim == 128; }
 
 // Workgroups of the gate-stream role for a launch with B attention workgroups on this device: one workgroup per CU, and the role's
 // ONE pass needs 3 or 4 row units per wave (3 * 16 * blocks <= n_units <= 4 * 16 * blocks).  0: this device has too few CUs - the
@@ -1833,11 +1808,7 @@ hipError_t t2s_launch_att_fused(const AttArgs& a, hipStream_t stream, const Gate
             const int blocks = gate_stream_blocks(a.B, 3 * gs->rows);
             if (blocks == 0) return hipErrorInvalidValue;
             const size_t lds1 = lds > 84 * 1024 ? lds : 84 * 1024;      // more than half a CU's LDS: never two workgroups on one CU
-            GateStreamArgs g2 = *gs;
-#ifdef T2S_ATTSTREAM_ABLATE
-            static const int dbg = getenv("T2S_DBG_ATTSTREAM") ? atoi(getenv("T2S_DBG_ATTSTREAM")) : 0;
-            g2.dbg = dbg;
-#endif
+            const GateStreamArgs& g2 = *gs;
             if (a.ploc) {
                 if (!a.q_part || (a.n_part & 31) || a.n_part > 256) return hipErrorInvalidValue;
                 static std::atomic<unsigned long long> attr_mask4{0};
@@ -1981,9 +1952,8 @@ hipError_t t2s_launch_lstm_seq(const float* gx, const float* whhT_f, const float
     if (4 * H != 1024) return hipErrorInvalidValue;
     // elements per workgroup: the recurrent matrix (1 MB per direction) is re-streamed by every workgroup each step, the
     // FMAs scale with the elements it carries - 2 per workgroup up to 128 elements (<= 128 workgroups), then 4
-    // resident rows (T2S_LSTM_SEQ_RESIDENT=0: none, the round-3 kernel): 64 / 24 / 16 in registers (by elements per workgroup: the
+    // resident rows: 64 / 24 / 16 in registers (by elements per workgroup: the
     // 128-VGPR cap of a 1024-thread workgroup) + 36 / 36 / 32 in LDS (144 / 128 KB) of the 256
-    static const bool resident = !(getenv("T2S_LSTM_SEQ_RESIDENT") && atoi(getenv("T2S_LSTM_SEQ_RESIDENT")) == 0);
 #define LSEQ(BT_, KR_, KL_, GRID)                                                                                      \
     do {                                                                                                               \
         static std::atomic<unsigned long long> am{0};                                                                  \
@@ -1992,13 +1962,9 @@ hipError_t t2s_launch_lstm_seq(const float* gx, const float* whhT_f, const float
         hipLaunchKernelGGL((lstm_seq_kernel<BT_, KR_, KL_>), GRID, dim3(1024), KL_ * 4096, stream, gx, whhT_f, whhT_r, \
                            lengths, out, B, T, H, T_out, gates_save, c_save);                                          \
     } while (0)
-    if (B > 128) {
-        if (resident) LSEQ(4, 16, 32, dim3((B + 3) / 4, 2)); else LSEQ(4, 0, 0, dim3((B + 3) / 4, 2));
-    } else if (B >= 8) {
-        if (resident) LSEQ(2, 24, 36, dim3((B + 1) / 2, 2)); else LSEQ(2, 0, 0, dim3((B + 1) / 2, 2));
-    } else {
-        if (resident) LSEQ(1, 64, 36, dim3(B, 2)); else LSEQ(1, 0, 0, dim3(B, 2));
-    }
+    if (B > 128) LSEQ(4, 16, 32, dim3((B + 3) / 4, 2));
+    else if (B >= 8) LSEQ(2, 24, 36, dim3((B + 1) / 2, 2));
+    else LSEQ(1, 64, 36, dim3(B, 2));
 #undef LSEQ
     return hipGetLastError();
 }

@@ -454,8 +454,7 @@ hipError_t t2s_launch_upsample_squeeze(const float* mel, const float* W, const f
                                        int frames, int ksize, int stride, int n_group, int L, int Lp, int halo,
                                        u16* S_hi, u16* S_lo, hipStream_t stream) {
     const int nchunks = (n_mel * n_group + 31) / 32;
-    static const bool valu_only = getenv("T2S_UPSAMPLE_VALU") != nullptr;      // A/B switch
-    if (!valu_only && n_group == 8 && ksize == 4 * stride && stride % 64 == 0 && n_mel % 4 == 0) {
+    if (n_group == 8 && ksize == 4 * stride && stride % 64 == 0 && n_mel % 4 == 0) {
         // frames that reach plane rows < L: f <= (8 * L - 1) / stride
         const int nf = (8 * L - 1) / stride + 1;
         const int tiles_per_b = (nf + 15) / 16;

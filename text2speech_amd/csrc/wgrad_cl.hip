@@ -212,8 +212,8 @@ __global__ __launch_bounds__(512) void wgrad_cl_kernel(const WgradClArgs a) {
 
 
 // ------------------------------------------------------------------------------------------------------------------------
-// The same GEMM on the ping-pong schedule of csrc/gate_gemm_pp.hip (round 3; the kernel above is the round-2 lockstep loop,
-// T2S_WGRAD_PP=0).  What carries over unchanged: the 256 x 256 tile, 32-step K-blocks, the LDS image and its half-row swap, the
+// The same GEMM on the ping-pong schedule of csrc/gate_gemm_pp.hip (round 3; the kernel above is the round-2 lockstep loop, still
+// taken where ldp % 4 != 0).  What carries over unchanged: the 256 x 256 tile, 32-step K-blocks, the LDS image and its half-row swap, the
 // DMA pieces, split-bf16 products.  What changes:
 //  * waves 0-3 / 4-7 form two groups (one wave of each on every SIMD) that run one barrier apart: in every barrier interval one
 //    wave of a SIMD issues its 24 MFMAs while its partner reads LDS (transposed 8-byte reads) and issues the fill;
@@ -513,9 +513,8 @@ __global__ __launch_bounds__(512) void wgrad_cl_pp_kernel(const WgradClArgs a) {
 hipError_t t2s_launch_wgrad_cl(const WgradClArgs& a, hipStream_t stream) {
     const int nwg = a.n_mtiles * a.n_ntiles * a.nslab;
     constexpr int lds = 2 * WG_STAGE;
-    static const int pp = getenv("T2S_WGRAD_PP") ? atoi(getenv("T2S_WGRAD_PP")) : 1;
-    if (a.bias_cols && !(pp && a.ldp % 4 == 0 && a.ldp >= a.N + 4)) return hipErrorInvalidValue;    // only the ping-pong kernel has it
-    if (pp && a.ldp % 4 == 0) {
+    if (a.bias_cols && !(a.ldp % 4 == 0 && a.ldp >= a.N + 4)) return hipErrorInvalidValue;    // only the ping-pong kernel has it
+    if (a.ldp % 4 == 0) {
         static std::atomic<unsigned long long> attr_mask_pp{0};
         const hipError_t e = t2s_raise_lds_limit((const void*)wgrad_cl_pp_kernel, lds, attr_mask_pp);
         if (e != hipSuccess) return e;

@@ -217,7 +217,7 @@ class _Engine:
         """res_pair8: pack the residual rows of every res/skip convolution in the 8-consecutive-channels order the folded no-grad
         path's residual GEMM wants (t2s_wg_res_only(pair8 = 1)); the training path keeps the identity order."""
         m = self.m
-        res_pair8 = bool(res_pair8) and self.geom()["C"] % 32 == 0 and os.environ.get("T2S_RES_PAIR8") != "0"
+        res_pair8 = bool(res_pair8) and self.geom()["C"] % 32 == 0
         key = tuple(p._version for p in m.parameters()) + (str(device), res_pair8)
         if not force and self.packed is not None and self.packed_key == key:
             return self.packed
@@ -533,8 +533,6 @@ class _Engine:
         main = torch.cuda.current_stream(dev)
         side = self.side_stream if getattr(self, "side_stream", None) is not None else torch.cuda.Stream(device=dev)
         self.side_stream = side
-        if os.environ.get("T2S_NO_SIDE_STREAM"):          # A/B switch: everything on the caller's stream
-            side = main
         audio32 = _f32c(audio)
         z = torch.empty(B, G, L, dtype=torch.float32, device=dev)
         log_s_list, log_det_list = [], []
@@ -564,14 +562,11 @@ class _Engine:
         # hides under the GEMMs of the flows before it.
         pack_s = self.pack_stream if getattr(self, "pack_stream", None) is not None else torch.cuda.Stream(device=dev)
         self.pack_stream = pack_s
-        if os.environ.get("T2S_NO_SIDE_STREAM") or os.environ.get("T2S_PACK_OVERLAP") == "0":
-            pack_s = main                   # A/B switch: the whole pack in front of flow 0 on the caller's stream (round 1)
         pack_events = []
         pack_s.wait_stream(main)
         with torch.cuda.stream(pack_s):
             self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=self.use_fold)
-        if side is not main:
-            main.wait_event(ev_inputs)
+        main.wait_event(ev_inputs)
         st = _lib.current_stream()
         for k in range(m.n_flows):
             main.wait_event(pack_events[k])

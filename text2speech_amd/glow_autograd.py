@@ -11,7 +11,6 @@ resident as split-bf16 planes (~105 MB per layer, 10.1 GB per step at 8 x 16000;
 recomputed.
 """
 import ctypes
-import os
 
 import torch
 
@@ -19,6 +18,8 @@ from . import _lib
 from .glow import _f32c, _vg
 
 L_ = _lib
+# workgroups a weight-gradient launch aims for: the gate convolution's, the res/skip convolution's
+WGRAD_FILL2, WGRAD_FILL1 = 256, 128
 
 
 def _ptr(t):
@@ -51,7 +52,7 @@ def _alloc_train(eng, B, L, dev):
     # 128-row tiles) + what the backward needs: every layer's input x, gate output and sigmoid.  The skip sum is never formed in
     # the forward; the backward rebuilds it once per flow from the saved gate outputs (t2s_wg_skip_sum), which is why the gate
     # outputs of a flow's layers sit side by side in ONE plane set (layer i = chunks [xc i, xc (i + 1)) of every batch entry).
-    st.fold_train = C % 16 == 0 and eng.use_fold and not os.environ.get("T2S_TRAIN_NO_FOLD")
+    st.fold_train = C % 16 == 0 and eng.use_fold
     st.act_bchunks = nl * xc if st.fold_train else 0
     st.layers, st.AF, st.GF = [], [], []
     for k in range(m.n_flows):
@@ -107,17 +108,16 @@ def _alloc_train(eng, B, L, dev):
             ns -= 1
         return ns
     # (its K-blocks are whole 32-row blocks shifted by up to +-halo rows: in bounds only when halo % 32 == 0, which geom() ensures)
-    st.cl_ok = C % 32 == 0 and g["n_cond"] % 32 == 0 and g["halo"] % 32 == 0 and not os.environ.get("T2S_WGRAD_TM")
+    st.cl_ok = C % 32 == 0 and g["n_cond"] % 32 == 0 and g["halo"] % 32 == 0
     assert not st.cl_ok or (st.k0 * 32 >= g["halo"] and st.k1 * 32 + g["halo"] <= Lp), "wgrad_cl K-blocks leave the plane"
     # res/skip weight gradient: N = C + 1 with the bias as an all-ones column would open another column of 256-wide tiles for
     # that one column whenever C % 256 == 0; the ping-pong kernel computes the bias gradient as row sums instead (bias_cols:
     # four partial-sum columns C .. C+3) and the GEMM is exactly C wide
-    st.bias_cols = 1 if (st.cl_ok and C % 256 == 0 and os.environ.get("T2S_WGRAD_PP", "1") != "0"
-                         and os.environ.get("T2S_WGRAD_BIAS_COL") != "ones") else 0
+    st.bias_cols = 1 if st.cl_ok and C % 256 == 0 else 0
     st.N1g = C if st.bias_cols else st.N1                  # columns of the GEMM proper
-    # workgroups a weight-gradient launch aims for (T2S_WGRAD_FILL2 / _FILL1: the gate / the res-skip convolution's): next to the
-    # data-gradient stream what counts is CU-time per unit of work, and half the slabs are half the partial-sum traffic
-    fill2, fill1 = int(os.environ.get("T2S_WGRAD_FILL2", "256")), int(os.environ.get("T2S_WGRAD_FILL1", "128"))
+    # workgroups a weight-gradient launch aims for (the gate / the res-skip convolution's): next to the data-gradient stream what
+    # counts is CU-time per unit of work, and half the slabs are half the partial-sum traffic
+    fill2, fill1 = WGRAD_FILL2, WGRAD_FILL1
     st.ks2, st.ks1 = nsplit(2 * C, st.N2, fill2), nsplit(2 * C, st.N1g, fill1)
     # the last layer of a flow has no residual rows (M = C): twice the slabs of half the height, the same slab buffer
     st.ks1_last = nsplit(C, st.N1g, fill1) if st.cl_ok and nsplit(C, st.N1g, fill1) * C <= st.ks1 * 2 * C else st.ks1
@@ -216,8 +216,6 @@ def forward_train(eng, mel, audio):
     main = torch.cuda.current_stream(dev)
     pack_s = eng.pack_stream if getattr(eng, "pack_stream", None) is not None else torch.cuda.Stream(device=dev)
     eng.pack_stream = pack_s
-    if os.environ.get("T2S_NO_SIDE_STREAM") or os.environ.get("T2S_PACK_OVERLAP") == "0":
-        pack_s = main
     pack_events = []
     log_det = torch.empty(m.n_flows, dtype=torch.float32, device=dev)
     Ws = [_f32c(m.convinv[k].conv.weight) for k in range(m.n_flows)]
@@ -344,17 +342,12 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
     # chain updates DX in place; every layer has its own slice of the flow-wide d_pre planes, which the next flow reuses only
     # after the two streams have joined).  The split-K slabs belong to the side stream alone.
     main_s = torch.cuda.current_stream(dev)
-    two = not os.environ.get("T2S_WG_BWD_ONE_STREAM")
     side_s = getattr(eng, "bwd_side_stream", None)
-    if two and side_s is None:
-        # T2S_WG_SIDE_PRIO=-1: the weight-gradient stream at high priority (it is the longer of the two chains)
-        side_s = eng.bwd_side_stream = torch.cuda.Stream(device=dev, priority=int(os.environ.get("T2S_WG_SIDE_PRIO", "0")))
-    if not two:
-        side_s = main_s
+    if side_s is None:
+        side_s = eng.bwd_side_stream = torch.cuda.Stream(device=dev)
     st2 = _lib.c_vp(side_s.cuda_stream)
     side_s.wait_stream(main_s)
     cl = ts.cl_ok       # weight-gradient GEMMs straight from the channel-last planes (no time-major copies)
-    cl_third_ok = cl
     if not cl:
         # conditioning rows + the ones row of the in/cond weight-gradient GEMM are the same for every layer
         _lib.call("t2s_plane_transpose", _ptr(ts.S_planes[0]), _ptr(ts.S_planes[1]), B, sc, sc, Lp, 0, _ptr(ts.TM_x[0]),
@@ -363,7 +356,6 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
         _lib.call("t2s_tm_ones_row", _ptr(ts.TM_act[0]), _ptr(ts.TM_act[1]), B, Lp, halo, L, ts.N1pad, C, st2)
     dsp_init = 1
     side_done = {}                          # flow -> event: the weight-gradient stream has finished that flow
-    per_layer_cond = bool(os.environ.get("T2S_WCOND_PER_LAYER"))
     keep = []
 
     def new(*shape):
@@ -418,22 +410,9 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
         keep.append(v32)
         return v32, saved
 
-    # T2S_WG_P1_MAIN=0: the res/skip weight gradient on the weight-gradient stream (the round-3 start)
-    p1_main = two and os.environ.get("T2S_WG_P1_MAIN", "1") != "0"
     p1_count, p1_free = [0], [None, None]
-    # T2S_WG_P1_THIRD=1 (experimental): the res/skip weight gradient on a THIRD stream, started beside the gate backward - both
-    # are 128-workgroup launches that only READ DX / DS, so together they fill the chip; the chain waits for it only in front of
-    # W_in^T's in-place update of DX
-    p1_third = p1_main and cl_third_ok and os.environ.get("T2S_WG_P1_THIRD", "0") == "1"
-    p1_s = None
-    if p1_third:
-        p1_s = getattr(eng, "bwd_p1_stream", None)
-        if p1_s is None:
-            p1_s = eng.bwd_p1_stream = torch.cuda.Stream(device=dev)
-        p1_s.wait_stream(main_s)
-    st3 = _lib.c_vp(p1_s.cuda_stream) if p1_third else None
-    ev_p1_done = None
-    wcond_side = two and cl and not per_layer_cond and os.environ.get("T2S_WG_WCOND_SIDE", "1") == "1"
+    # d_spect's conditioning-gradient GEMM on the weight-gradient stream (it feeds the upsampler's gradient only, not the chain)
+    wcond_side = cl
     for k in reversed(range(m.n_flows)):
         c_off, n_rem, n_half = eng._flow_geom(k)
         wn = m.WN[k]
@@ -500,11 +479,10 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
             conv_rs, conv_in, conv_c = wn.res_skip_layers[i], wn.in_layers[i], wn.cond_layers[i]
             # 1. d_pre = gate'(T,G) * (W_rs^T [dx ; dS])                                                     [main]
             A_rsT, A_inT, A_cT = ts.A_rsT[k][i], ts.A_inT[k][i], ts.A_cT[k]
-            # (one event per layer on the data-gradient stream when the res/skip weight gradient runs there: each record is a ~7 us
-            # bubble in front of the next kernel of the recording stream; T2S_WG_FEW_EVENTS=0: one per consumer as before)
-            few_ev = cl and p1_main and os.environ.get("T2S_WG_FEW_EVENTS", "1") != "0"
+            # (one event per layer on the data-gradient stream when the res/skip weight gradient runs there (cl): each record is a
+            # ~7 us bubble in front of the next kernel of the recording stream)
             ev_in = None
-            if not few_ev:
+            if not cl:
                 ev_in = torch.cuda.Event()      # DX / DS of this layer are final (last written on the main stream)
                 ev_in.record(main_s)
             # this layer's slice of the flow-wide d_pre planes (bytes from the start of each plane)
@@ -512,40 +490,18 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
             dp_h, dp_l = _lib.c_vp(DP[0].data_ptr() + dp_off), _lib.c_vp(DP[1].data_ptr() + dp_off)
             a_h, a_l = _act_ptrs(ts, k, i, "A")
             g_h, g_l = _act_ptrs(ts, k, i, "G")
-            ev_dx = None
-            if p1_third:
-                ev_dx = torch.cuda.Event()          # DX / DS of this layer are final: the third stream's res/skip weight gradient may read them
-                ev_dx.record(main_s)
             _lib.call("t2s_wg_bwd_gate_dgrad", _ptr(A_rsT[0]), _ptr(A_rsT[1]), _ptr(zb),
                       None if last else _ptr(ts.DX[0]), None if last else _ptr(ts.DX[1]), _ptr(DS[0]), _ptr(DS[1]),
                       a_h, a_l, g_h, g_l, ts.act_bchunks, dp_h, dp_l, ts.dp_chunks, B, C, L, Lp, halo, ts.Mc, ts.p8_x, st)
             ev_dp = None
-            if not few_ev:
+            if not cl:
                 ev_dp = torch.cuda.Event()
                 ev_dp.record(main_s)
             # 2. dW_rs = [dx ; dS] . acts^T  (+ bias column)                                                 [side, or main]
             d = 2 ** i
             P1 = ts.P1
             ev_tdrs = None
-            if cl and p1_third:
-                # third stream: needs DX / DS final (the record sits in front of the gate backward on the main stream) and a free slab set
-                ta1, tb1, ta2, tb2 = _cl_tables(ts, (k, i), sv, last, xc, sc, ks, d, dev, i)
-                ks1 = ts.ks1_last if last else ts.ks1
-                pb = p1_count[0] & 1
-                p1_count[0] += 1
-                P1 = ts.P1b if pb else ts.P1
-                p1_s.wait_event(ev_dx)
-                if p1_free[pb] is not None:
-                    p1_s.wait_event(p1_free[pb])
-                _lib.call("t2s_wgrad_cl", _ptr(ta1), ta1.size(0), _ptr(tb1), tb1.size(0), _ptr(P1), B, rows2, ts.N1g, ts.ld1,
-                          ts.k0, ts.k1, ks1, ts.bias_cols, st3)
-                ev_p1_done = torch.cuda.Event()
-                ev_p1_done.record(p1_s)
-                side_s.wait_event(ev_p1_done)
-                ev_p1 = torch.cuda.Event()          # d_pre of this layer is final (gate backward): the weight-gradient stream's cue
-                ev_p1.record(main_s)
-                side_s.wait_event(ev_p1)
-            elif cl and p1_main:
+            if cl:
                 # On the data-gradient stream, between the two GEMMs that bracket it there: the chain then never waits for the
                 # weight-gradient stream before it updates DX (that wait was 135 us of the 463 us a layer took,
                 # profiles/r03_wg_train_timeline_before.md), and 74 us of half-chip work leave the longer stream.  Its slab
@@ -562,14 +518,6 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
                 ev_p1 = torch.cuda.Event()
                 ev_p1.record(main_s)
                 side_s.wait_event(ev_p1)
-            elif cl:
-                side_s.wait_event(ev_in)
-                ta1, tb1, ta2, tb2 = _cl_tables(ts, (k, i), sv, last, xc, sc, ks, d, dev, i)
-                ks1 = ts.ks1_last if last else ts.ks1
-                _lib.call("t2s_wgrad_cl", _ptr(ta1), ta1.size(0), _ptr(tb1), tb1.size(0), _ptr(ts.P1), B, rows2, ts.N1g, ts.ld1,
-                          ts.k0, ts.k1, ks1, ts.bias_cols, st2)
-                ev_tdrs = torch.cuda.Event()        # DX / DS have been read: the chain may update DX in place
-                ev_tdrs.record(side_s)
             else:
                 side_s.wait_event(ev_in)
                 if not last:
@@ -585,12 +533,12 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
                           _ptr(zb), _ptr(ts.P1), B, rows2, ts.N1, Mrs, ts.N1pad, nt, ts.k0, ts.k1, ts.ks1, st2)
             wn_grads(conv_rs, P1, (ts.ks1_last if last else ts.ks1) if cl else ts.ks1, rows2, ts.ld1, 0, 0, C, rows2, C, 1,
                      stream=st2, nb=4 if ts.bias_cols and cl else 1)
-            if cl and p1_main:
+            if cl:
                 p1_free[pb] = torch.cuda.Event()
                 p1_free[pb].record(side_s)
             # 3. dW_in, dW_cond = d_pre . [x taps | spect | 1]^T                                             [side]
             if ev_dp is not None:
-                side_s.wait_event(ev_dp)        # (few_ev: the wait for ev_p1 above covers d_pre too - recorded later on the same stream)
+                side_s.wait_event(ev_dp)        # (cl: the wait for ev_p1 above covers d_pre too - recorded later on the same stream)
             if cl:
                 _lib.call("t2s_wgrad_cl", _ptr(ta2), ta2.size(0), _ptr(tb2), tb2.size(0), _ptr(ts.P2), B, 2 * C, ts.N2, ts.ld2,
                           ts.k0, ts.k1, ts.ks2, 0, st2)
@@ -607,25 +555,16 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
             # 4. dx (+)= W_in^T (*) d_pre ;  d_spect += W_cond^T d_pre                                       [main]
             if ev_tdrs is not None:
                 main_s.wait_event(ev_tdrs)  # (events of one stream complete in order: this covers every earlier read of DX too)
-            if p1_third and ev_p1_done is not None:
-                main_s.wait_event(ev_p1_done)       # the third stream has read DX: W_in^T may update it in place
             _lib.call("t2s_conv_accumulate", _ptr(A_inT[0]), _ptr(A_inT[1]), _ptr(zb), dp_h, dp_l, ts.dp_chunks,
                       _ptr(ts.DX[0]), _ptr(ts.DX[1]), B, 2 * C, C, ks, d, 1 if last else 0, L, Lp, halo, ts.Mc, ts.p8_x, st)
-            # (W_cond,i^T sits in K-chunks [2 xc i, 2 xc (i + 1)) of the flow's conditioning-gradient operand A_cT)
-            if per_layer_cond:          # A/B switch (T2S_WCOND_PER_LAYER=1): the round-2 form, one accumulate per layer
-                a_off = 2 * i * 2 * xc * ts.Ms * 32
-                _lib.call("t2s_conv_accumulate", _lib.c_vp(A_cT[0].data_ptr() + a_off), _lib.c_vp(A_cT[1].data_ptr() + a_off),
-                          _ptr(zb), dp_h, dp_l, ts.dp_chunks, _ptr(ts.DSp[0]), _ptr(ts.DSp[1]), B, 2 * C, n_cond, 1, 1, dsp_init,
-                          L, Lp, halo, ts.Ms, ts.p8_c, st)
-                dsp_init = 0
         # d_spect (+)= [W_cond,0^T | ... | W_cond,nl-1^T] [d_pre_0 ; ... ; d_pre_nl-1]: one GEMM per flow, K = nl * 2C       [main]
-        if not per_layer_cond:
-            # (T2S_WG_WCOND_SIDE=1: on the weight-gradient stream - it feeds the upsampler's gradient only, not the chain; that
-            # stream has waited for every d_pre of the flow by now, and it owns the d_pre planes' reuse through side_done)
-            _lib.call("t2s_conv_accumulate", _ptr(ts.A_cT[k][0]), _ptr(ts.A_cT[k][1]), _ptr(zb), _ptr(DP[0]), _ptr(DP[1]), 0,
-                      _ptr(ts.DSp[0]), _ptr(ts.DSp[1]), B, nl * 2 * C, n_cond, 1, 1, dsp_init, L, Lp, halo, ts.Ms, ts.p8_c,
-                      st2 if wcond_side else st)
-            dsp_init = 0
+        # (W_cond,i^T sits in K-chunks [2 xc i, 2 xc (i + 1)) of the flow's conditioning-gradient operand A_cT.  With wcond_side on
+        # the weight-gradient stream, which has waited for every d_pre of the flow by now and owns the d_pre planes' reuse through
+        # side_done)
+        _lib.call("t2s_conv_accumulate", _ptr(ts.A_cT[k][0]), _ptr(ts.A_cT[k][1]), _ptr(zb), _ptr(DP[0]), _ptr(DP[1]), 0,
+                  _ptr(ts.DSp[0]), _ptr(ts.DSp[1]), B, nl * 2 * C, n_cond, 1, 1, dsp_init, L, Lp, halo, ts.Ms, ts.p8_c,
+                  st2 if wcond_side else st)
+        dsp_init = 0
         # ---- WN.start ----
         dW_eff = new(C, n_half)
         db_start = bucket.take(C)

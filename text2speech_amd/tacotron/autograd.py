@@ -14,7 +14,6 @@ Structure of the backward (all through the C ABI of libt2s_hip.so):
   encoder  : BiLSTM BPTT, convolutions, embedding
 """
 import ctypes
-import os
 
 import torch
 
@@ -68,8 +67,8 @@ def _ru(a, b):
     return -(-a // b) * b
 
 
-import os as _os
-_IW_WGS = int(_os.environ.get("T2S_IW_WGS", "4096"))
+# target number of workgroups of an items weight-gradient GEMM (with its split-K slabs)
+_IW_WGS = 4096
 
 
 class _Bwd:
@@ -113,9 +112,7 @@ class _Bwd:
         return torch.zeros(*shape, dtype=torch.float32, device=self.dev)
 
     def close(self):
-        """Join the helper stream; remember the arena size this pass needed (the next pass of this engine allocates it)."""
-        if self.__dict__.get("side_used"):
-            torch.cuda.current_stream(self.dev).wait_stream(self.side_stream())
+        """Remember the arena size this pass needed (the next pass of this engine allocates it)."""
         self.eng.zero_arena_elems = max(getattr(self.eng, "zero_arena_elems", 0), self._za_need)
 
     def bf(self, *shape, tag=None, extent=()):
@@ -164,7 +161,7 @@ class _Bwd:
             _lib.call("t2s_rows_to_tm", ptr, ld, items, items_pad, shift, C, _p(X[0]), _p(X[1]), Npad, off, self.st)
         _lib.call("t2s_tm_ones_row", _p(X[0]), _p(X[1]), 1, items_pad, 0, items, Npad, N_cols, self.st)
         # split-K slabs: 16 where the item count allows.  Fewer for the products that are many output tiles already (the LSTM cells':
-        # 176 / 128 tiles, 16 slabs of 4096 x 2561 floats = 671 MB written and read back) measured EQUAL - T2S_IW_WGS = target number
+        # 176 / 128 tiles, 16 slabs of 4096 x 2561 floats = 671 MB written and read back) measured EQUAL - _IW_WGS = target number
         # of workgroups, 256 / 768 / 1536 / 4096: 82.2-83.5 ms per train step for all of them (profiles/r04_iw_split_ab.txt)
         tiles = -(-M4 // 256) * -(-N // 256)
         ks = max(1, min(16, nch, -(-_IW_WGS // tiles)))
@@ -186,21 +183,10 @@ class _Bwd:
         self.keep.append(w)
 
     # ------------------------------------------------------------------ conv + BatchNorm stack (postnet / encoder)
-    def side_stream(self):
-        """The engine's helper stream for work nothing on the backward's dependent chain waits for (joined in close())."""
-        side = getattr(self.eng, "enc_side_stream", None)
-        if side is None:
-            side = self.eng.enc_side_stream = torch.cuda.Stream(device=self.dev)
-        return side
-
-    def conv_bn_stack_backward(self, saves, dout_f32=None, dout_planes=None, wgrad_side=False):
+    def conv_bn_stack_backward(self, saves, dout_f32=None, dout_planes=None):
         """Backward of [conv -> BN(batch stats) -> act -> dropout] x n.  The gradient of the stack's output comes as f32
-        [B][C_last][T] or as planes.  Returns the gradient w.r.t. the stack's input as planes (hi, lo).
-        wgrad_side: the weight gradients (nothing downstream needs them) go to the helper stream, layer by layer behind an
-        event - for the postnet they then run beside the decoder's BPTT loop, which leaves most of the chip idle."""
+        [B][C_last][T] or as planes.  Returns the gradient w.r.t. the stack's input as planes (hi, lo)."""
         d_planes = dout_planes
-        main_t = torch.cuda.current_stream(self.dev)
-        side_t = self.side_stream() if wgrad_side else None
         for i in reversed(range(len(saves))):
             s = saves[i]
             conv, bn, layer = s["seq"][0].conv, s["seq"][1], s["layer"]
@@ -234,12 +220,6 @@ class _Bwd:
             Npad = _ru(N, 256)
             A = (self.bf(B, nt, Mpad, 32, tag=("cs_Ah", cs_), extent=ex), self.bf(B, nt, Mpad, 32, tag=("cs_Al", cs_), extent=ex))
             X = (self.bf(B, nt, Npad, 32, tag=("cs_Xh", cs_), extent=ex), self.bf(B, nt, Npad, 32, tag=("cs_Xl", cs_), extent=ex))
-            st_main = self.st
-            if side_t is not None:          # dconv is final: the weight-gradient sequence of this layer moves to the helper stream
-                ev = torch.cuda.Event()
-                ev.record(main_t)
-                side_t.wait_event(ev)
-                self.st = _lib.c_vp(side_t.cuda_stream)
             _lib.call("t2s_plane_transpose", _p(dconv[0]), _p(dconv[1]), B, occ, occ, Lp, 0, _p(A[0]), _p(A[1]), Mpad, 0, self.st)
             icc = Cin_pad // 32
             for tap in range(Kt):
@@ -252,9 +232,6 @@ class _Bwd:
                       Npad, nt, 0, nt, 1, self.st)
             self.slab_to_grad(P, B, M4, N, conv.weight, Cout, Cin, 0, conv.bias, Kt=Kt, tap_stride=Cin_pad)
             self.keep += [A, X, P]
-            if side_t is not None:
-                self.st = st_main
-                self.side_used = True
             # data gradient: convolution of dconv with the transposed, tap-mirrored weight
             w32 = _f32(conv.weight)
             Opad = _ru(Cout, 32)
@@ -286,7 +263,7 @@ class _Bwd:
         g_mel_post = self.zeros(B, n_mel, T) if g_mel_post is None else g_mel_post.to(torch.float32).contiguous()
         g_gate = self.zeros(B, T) if g_gate is None else g_gate.to(torch.float32).contiguous()
         # ---- postnet: mel_post = mel + postnet(mel) ----
-        d_in = self.conv_bn_stack_backward(sv["post_convs"], g_mel_post, wgrad_side=os.environ.get("T2S_POSTNET_WGRAD_SIDE", "0") == "1")
+        d_in = self.conv_bn_stack_backward(sv["post_convs"], g_mel_post)
         d_mel = self.new(B, n_mel, T)
         _lib.call("t2s_add3", _p(g_mel), _p(g_mel_post), None, d_mel.numel(), _p(d_mel), st)
         s0 = sv["post_convs"][0]
@@ -368,7 +345,7 @@ class _Bwd:
             if T_in <= 512 and ad == 128:
                 # exchange buffer of the attention cell's backward folded into the attention backward's launch (t2s_taco_bptt::att_xbuf):
                 # 8-byte granules as f32 pairs, zero = no tag matches
-                att_xbuf = self.zeros(2 * (B * nch * ad + 3))       # (+ error word, pace word, pace error word)
+                att_xbuf = self.zeros(2 * (B * nch * ad + 3))       # (+ the error word and two unused words: ABI v4 size)
                 bp.att_xbuf = _p(att_xbuf)
                 self.keep.append(att_xbuf)
                 self.eng.__dict__["_last_bptt_xbuf"] = (att_xbuf, B * nch * ad)     # (check_lstm_xbuf reads its error words)
@@ -404,9 +381,8 @@ class _Bwd:
         d_mem_tot = self.new(B, T_in, E)
         _lib.call("t2s_add3", _p(d_memory), _p(d_mem2), None, d_mem_tot.numel(), _p(d_mem_tot), st)
         self.d_memory = d_mem_tot
-        if os.environ.get("T2S_ENC_BWD_SIDE", "1") != "0":
-            from .autograd_encoder import encoder_lstm_backward
-            self.enc_pending = encoder_lstm_backward(self, d_mem_tot)
+        from .autograd_encoder import encoder_lstm_backward
+        self.enc_pending = encoder_lstm_backward(self, d_mem_tot)
         # ---- weight gradients over all (step, batch) items ----
         ar = dec.attention_rnn
         Pa, ks, M4, N = self.items_wgrad(items, [(_p(dg_a), 4 * A, 4 * A, 0, 0)],

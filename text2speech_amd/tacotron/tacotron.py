@@ -559,12 +559,9 @@ class _TacoEngine:
         return memory, len32
 
     def _lstm_xbuf(self, which, B, dev):
-        """Exchange buffer of the split BiLSTM recurrence (t2s_taco_encoder_lstm_split / _bwd_split) and this launch's epoch, or None
-        (T2S_LSTM_SEQ_SPLIT=0: the one-workgroup kernels).  One buffer per direction of use (forward / backward: the two may be in
-        flight on different streams), engine-owned, zeroed once; `check_lstm_xbuf()` reads the error words."""
-        import os
-        if os.environ.get("T2S_LSTM_SEQ_SPLIT", "1") == "0":
-            return None
+        """Exchange buffer of the split BiLSTM recurrence (t2s_taco_encoder_lstm_split / _bwd_split) and this launch's epoch.  One
+        buffer per direction of use (forward / backward: the two may be in flight on different streams), engine-owned, zeroed once;
+        `check_lstm_xbuf()` reads the error words."""
         bufs = self.__dict__.setdefault("_xbufs", {})
         key = (which, int(B), str(dev))
         ent = bufs.get(key)
@@ -592,14 +589,13 @@ class _TacoEngine:
                 if t is not None and any(float(t.view(-1)[w].item()) != 0.0 for w in words):
                     raise _lib.T2SError("teacher-forced decode: a bounded wait on %s expired (results of that call are invalid)" % name)
         # ... and of the last backward's attention exchange buffer (t2s_taco_bptt::att_xbuf: 8-byte granule E = B * ceil(T_in / 32)
-        # * att_dim is raised by a bounded wait of the folded attention cell that expired, E + 2 by one of the paced helper chain)
+        # * att_dim is raised by a bounded wait of the folded attention cell that expired)
         last = self.__dict__.get("_last_bptt_xbuf")
         if last is not None:
             buf, e = last
-            words = buf.view(torch.int64)
-            for w, what in ((e, "the folded attention cell's exchange"), (e + 2, "the paced helper chain")):
-                if int(words[w].item()) != 0:
-                    raise _lib.T2SError("decoder BPTT: a bounded wait of %s expired (gradients of that step are invalid)" % what)
+            if int(buf.view(torch.int64)[e].item()) != 0:
+                raise _lib.T2SError("decoder BPTT: a bounded wait of the folded attention cell's exchange expired (gradients of that "
+                                    "step are invalid)")
 
     def _gemv(self, W, x, rows, items, K, y, act=0, mask=None, smask=0, mask_scale=1.0, bias=None, sy_item=None,
               sx=None):
@@ -897,9 +893,6 @@ class _TacoEngine:
             # off the serial chain (helper stream, a chunk of steps behind the attention chain: t2s_taco_decode_steps) exactly as in
             # training - the only save that path needs besides hc_all
             extra["att_h_all"] = torch.empty(T_out, B, dec.attention_rnn_dim, dtype=torch.float32, device=dev)
-        if B > 8 and extra.get("att_h_all") is not None:
-            # scratch of the decoder cells' per-chunk input product (t2s_taco_decoder::dec_in_part: 16 steps x B items x 4 D)
-            extra["dec_in_part"] = torch.empty(16, B, 4 * D, dtype=torch.float32, device=dev)
         d, S = self._decoder_struct(memory, len32, T_out, True, extra)
         if m.training:
             d.att_drop_scale = 1.0 / (1.0 - dec.p_attention_dropout)

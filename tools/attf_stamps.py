@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Diagnostic: where one launch of the one-launch attention backward (att_bwd_fused_kernel) spends its time.  Needs a library built
-with -DT2S_ATTF_STAMPS (recompile csrc/taco_bwd_ops.hip with that define, link it with the other objects of csrc/ into e.g.
-text2speech_amd/libt2s_hip_stamps.so - never over the shipped library - and point T2S_LIB_PATH at it): workgroup (0, 0) records the 100 MHz clock at its phase boundaries; this runs
-a few Tacotron train steps (B = 32, T_in = 256) and prints the deltas of the last launch in us."""
+"""Diagnostic: where one launch of the one-launch attention backward (att_bwd_fused_kernel) spends its time.  Workgroup (0, 0) of the
+stamps build records the 100 MHz clock at its phase boundaries; this runs a few Tacotron train steps (B = 32, T_in = 256) and prints
+the deltas of the last launch in us.  Needs that build, run through T2S_LIB_PATH:
+    python -m text2speech_amd.build --variant attf_stamps "-DT2S_ATTF_STAMPS"
+    T2S_LIB_PATH=build/attf_stamps/libt2s_hip.so python3 tools/attf_stamps.py"""
 import ctypes
 import os
 import sys

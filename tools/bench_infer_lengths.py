@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """WaveGlow.infer at B=1 for several utterance lengths (config.json defaults, synthetic weights): ms per call and samples/s.
-Short utterances leave most of the chip idle with 256-row gate tiles; T2S_GATE_TILE=256 / 128 forces a tile height for A/B."""
+Short utterances leave most of the chip idle with 256-row gate tiles: the library picks 128-row tiles for them."""
 import json
 import os
 import sys
@@ -19,7 +19,7 @@ def main():
     m = WaveGlow(**cfg)
     m.load_state_dict(synth.waveglow_state(cfg))
     m = m.cuda().eval()
-    out = {"gate_tile": os.environ.get("T2S_GATE_TILE", "auto")}
+    out = {}
     for frames in (100, 200, 256, 300, 400, 1000):
         mel = torch.randn(1, 80, frames, generator=torch.Generator().manual_seed(frames)).cuda()
         for _ in range(2):

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Diagnostic (library built with T2S_BUILD_DEFINES=-DT2S_CLOCK_PROBE): per launch of the B=1 decoder chain, the body time
-of workgroup 0 (100 MHz real-time counter), the in-kernel shader clock (s_memtime / s_memrealtime) and the gap between the end
-of one launch's workgroup 0 and the start of the next one's."""
+"""Diagnostic: per launch of the B=1 decoder chain, the body time of workgroup 0 (100 MHz real-time counter), the in-kernel shader
+clock (s_memtime / s_memrealtime) and the gap between the end of one launch's workgroup 0 and the start of the next one's.  Needs
+the probe build, run through T2S_LIB_PATH:
+    python -m text2speech_amd.build --variant probe "-DT2S_CLOCK_PROBE"
+    T2S_LIB_PATH=build/probe/libt2s_hip.so python3 tools/decode_probe.py 128"""
 import ctypes
 import json
 import os

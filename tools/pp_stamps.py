@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Diagnostic (needs a library built with T2S_BUILD_DEFINES=-DT2S_GEMM_STAMPS): where one launch of the ping-pong gate GEMM
-spends its cycles - prologue / main loop / epilogue per workgroup, and the in-kernel clock (s_memtime vs s_memrealtime)."""
+"""Diagnostic: where one launch of the ping-pong gate GEMM spends its cycles - prologue / main loop / epilogue per workgroup, and
+the in-kernel clock (s_memtime vs s_memrealtime).  Needs the stamps build, run through T2S_LIB_PATH:
+    python -m text2speech_amd.build --variant stamps "-DT2S_GEMM_STAMPS"
+    T2S_LIB_PATH=build/stamps/libt2s_hip.so python3 tools/pp_stamps.py"""
 import ctypes
 import json
 import os
