@@ -240,27 +240,31 @@ def test_stale_max_len_truncates_inputs():
     m._eng().check_lstm_xbuf()
 
 
-def test_check_lstm_xbuf_reads_bptt_error_word():
-    """check_lstm_xbuf() covers the backward's attention exchange buffer (t2s_taco_bptt::att_xbuf, T_in <= 512): its error word
-    (granule B * ceil(T_in / 32) * 128), written here from the host.  The two words after it are unused (no kernel writes them
-    since the paced helper chain was removed): a BPTT pass leaves them zero."""
+def test_check_lstm_xbuf_reads_every_error_word():
+    """check_lstm_xbuf() covers every exchange buffer of a B = 12 training step: the split BiLSTM buffers of the forward and the
+    backward, the teacher-forced decode's att_xbuf and pace_flag, and the backward's attention exchange buffer
+    (t2s_taco_bptt::att_xbuf, T_in <= 512, error word = granule B * ceil(T_in / 32) * 128).  Each error word is written here from
+    the host.  The two words after the BPTT one are unused (no kernel writes them since the paced helper chain was removed): a
+    BPTT pass leaves them zero."""
     in_len = torch.tensor([24 - i for i in range(12)])
     out_len = torch.tensor([8 - i // 2 for i in range(12)])
     m = _step_vs_oracle(12, 24, 8, in_len, out_len, seed=79)
     eng = m._eng()
     eng.check_lstm_xbuf()
-    buf, e = eng.__dict__["_last_bptt_xbuf"]
+    assert sorted(eng.xbuf_errs) == ["BPTT att_xbuf", "decoder att_xbuf", "decoder pace_flag",
+                                     "split BiLSTM bwd B=12 %s" % DEV, "split BiLSTM fwd B=12 %s" % DEV]
+    words, e = eng.xbuf_errs["BPTT att_xbuf"]
     assert e == 12 * 1 * 128
-    words = buf.view(torch.int64)
     assert words.numel() == e + 3
     assert int(words[e + 1].item()) == 0 and int(words[e + 2].item()) == 0
-    words[e] = 1
-    torch.cuda.synchronize()
-    with pytest.raises(_lib.T2SError):
+    for name, (words, e) in eng.xbuf_errs.items():
+        words[e] = 1
+        torch.cuda.synchronize()
+        with pytest.raises(_lib.T2SError, match=name):
+            eng.check_lstm_xbuf()
+        words[e] = 0
+        torch.cuda.synchronize()
         eng.check_lstm_xbuf()
-    words[e] = 0
-    torch.cuda.synchronize()
-    eng.check_lstm_xbuf()
 
 
 def test_three_adam_steps_vs_oracle_batch32():

@@ -2,6 +2,7 @@
 #include "../../include/t2s_hip.h"
 #include "t2s_kernels.h"
 #include "tacotron_ops.h"
+#include "t2s_handoff.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -120,12 +121,12 @@ int t2s_taco_encoder_lstm(const float* gx, const float* whhT_fwd, const float* w
     return T2S_OK;
 }
 
-long t2s_taco_lstm_xbuf_bytes(int B) { return B > 0 ? ((long)2 * B * 2 * 256 + 1) * 8 : -1; }
+long t2s_taco_lstm_xbuf_bytes(int B) { return B > 0 ? (long)(split_lstm_err_word(B) + 1) * 8 : -1; }
 
 int t2s_taco_encoder_lstm_split(const float* gx, const float* whhT_fwd, const float* whhT_rev, const int* lengths, float* out,
                                 int B, int T, int H, int T_out, float* gates_save, float* c_save, void* xbuf, unsigned epoch,
                                 void* stream) {
-    if (!gx || !whhT_fwd || !whhT_rev || !out || !xbuf || B <= 0 || T <= 0 || T >= 4095 || T_out <= 0 || T_out > T || H != 256 ||
+    if (!gx || !whhT_fwd || !whhT_rev || !out || !xbuf || B <= 0 || T <= 0 || T >= SPLIT_LSTM_T_LIMIT || T_out <= 0 || T_out > T || H != 256 ||
         ((uintptr_t)xbuf & 7))
         return T2S_EINVAL;
     if ((gates_save == nullptr) != (c_save == nullptr)) return T2S_EINVAL;

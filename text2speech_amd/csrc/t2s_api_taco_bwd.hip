@@ -3,6 +3,7 @@
 #include "t2s_kernels.h"
 #include "taco_bwd_ops.h"
 #include "tacotron_ops.h"
+#include "t2s_handoff.h"
 
 #include <string.h>
 
@@ -316,7 +317,7 @@ int t2s_taco_encoder_lstm_bwd_split(const float* d_out, const float* out, const 
                                     const float* whh_fwd, const float* whh_rev, const int* lengths, float* dgx, float* hprev,
                                     int B, int T, int H, int T_out, void* xbuf, unsigned epoch, void* stream) {
     if (!d_out || !out || !gates_save || !c_save || !whh_fwd || !whh_rev || !dgx || !hprev || !xbuf || B <= 0 || T <= 0 ||
-        T >= 4095 || H != 256 || T_out <= 0 || T_out > T || ((uintptr_t)xbuf & 7))
+        T >= SPLIT_LSTM_T_LIMIT || H != 256 || T_out <= 0 || T_out > T || ((uintptr_t)xbuf & 7))
         return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_lstm_seq_bwd_split(d_out, out, gates_save, c_save, whh_fwd, whh_rev, lengths, dgx, hprev, B, T, T_out,
                                                 (unsigned long long*)xbuf, epoch, (hipStream_t)stream));

@@ -48,15 +48,15 @@ struct AttBwdArgs {
 };
 
 // Optional second argument of the one-launch attention backward: the attention LSTMCell's pointwise backward (with W_query^T d_q)
-// folded into the same launch.  The chunk workgroups of a batch element exchange their partial d_q through tagged 8-byte granules
-// (xbuf: [B][ceil(T/32)][128] + 1 error word, zero before a BPTT pass; tag = step + 1), each then does the cell backward of its share
-// of the hidden units.  T <= 512.
+// folded into the same launch.  The chunk workgroups of a batch element exchange their partial d_q through the granules of
+// t2s_handoff.h (xbuf: [B][ceil(T/32)][128] + 1 error word, zero before a BPTT pass; tag = step + 1), each then does the cell
+// backward of its share of the hidden units.  T <= 512.
 struct AttBwdFoldArgs {
     LstmBwdArgs cell;
     unsigned long long* xbuf;
     unsigned tag;
-    // optional: the first thread of the launch stores sig_val to *sig_ptr as the kernel starts (t2s_launch_pace_wait,
-    // csrc/tacotron_ops.h; no caller sets it now - kept so that the kernel stays as measured)
+    // optional: the first thread of the launch stores sig_val to *sig_ptr as the kernel starts (pace_signal, t2s_handoff.h; no
+    // caller sets it now - kept so that the kernel stays as measured)
     unsigned* sig_ptr; unsigned sig_val;
 };
 

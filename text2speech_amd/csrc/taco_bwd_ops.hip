@@ -9,6 +9,7 @@
 #include "t2s_common.h"
 #include "t2s_kernels.h"
 #include "taco_bwd_ops.h"
+#include "t2s_handoff.h"
 
 #include <stdlib.h>
 
@@ -796,7 +797,6 @@ static __device__ __forceinline__ float attf_carry(const float* c, size_t BT, si
     return v;
 }
 #define ATTF_SP 130
-#define ATTF_SPIN_MAX (1 << 22)
 // (one workgroup per CU by registers, 185 VGPRs: a 128-VGPR bound spilled and measured much slower)
 __global__ __launch_bounds__(512) void att_bwd_fused_kernel(const AttBwdArgs a, const AttBwdFoldArgs fold) {
     constexpr int AD = 128, F = 32, SP = ATTF_SP, SD = 34, SG = 34;
@@ -819,7 +819,7 @@ __global__ __launch_bounds__(512) void att_bwd_fused_kernel(const AttBwdArgs a, 
     // element share one XCD's L2 (workgroups go round the 8 XCDs by block number) and are neighbours in dispatch order (they wait
     // for one another when the cell backward is folded in, below)
     if (fold.sig_ptr && blockIdx.x == 0 && threadIdx.x == 0)          // "this launch has started"
-        __hip_atomic_store(fold.sig_ptr, fold.sig_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pace_signal(fold.sig_ptr, fold.sig_val);
     const int n_chunks = (a.T + ATTB_CH - 1) / ATTB_CH;
     const int bsl = blockIdx.x >> 3;
     const int b = (bsl / n_chunks) * 8 + (blockIdx.x & 7), chunk = bsl - (bsl / n_chunks) * n_chunks, t0 = chunk * ATTB_CH;
@@ -1062,8 +1062,7 @@ __global__ __launch_bounds__(512) void att_bwd_fused_kernel(const AttBwdArgs a, 
             a.dq_part[slot * AD + ach] = dq;
             a.dv_part[slot * AD + ach] = dv_old + dvs;
             if (fold.xbuf)                         // this chunk's partial d_q for the other chunks of the element (read at the end)
-                __hip_atomic_store(fold.xbuf + slot * AD + ach, ((unsigned long long)fold.tag << 32) | (unsigned long long)__float_as_uint(dq),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                handoff_publish(fold.xbuf + slot * AD + ach, fold.tag, dq);
         }
     }
     ATTF_STAMP(7)
@@ -1186,19 +1185,13 @@ __global__ __launch_bounds__(512) void att_bwd_fused_kernel(const AttBwdArgs a, 
         float* s_ee = s_q + AD;                    // [4][128]
         bool ok = true;
         for (int i = tid; i < n_chunks * AD; i += 512) {
-            const unsigned long long* g = fold.xbuf + ((size_t)b * n_chunks) * AD + i;
-            bool got = false;
-            for (int it = 0; it < ATTF_SPIN_MAX; ++it) {
-                const unsigned long long v = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((unsigned)(v >> 32) == fold.tag) { s_x[i] = __uint_as_float((unsigned)v); got = true; break; }
-                __builtin_amdgcn_s_sleep(1);
-            }
+            const bool got = handoff_await(fold.xbuf + ((size_t)b * n_chunks) * AD + i, fold.tag, s_x[i]);
             ok = ok && got;
         }
         if (!ok) s_fail = 1;
         __syncthreads();
         if (s_fail) {
-            if (tid == 0) __hip_atomic_store(fold.xbuf + (size_t)a.B * n_chunks * AD, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) handoff_raise(fold.xbuf + (size_t)a.B * n_chunks * AD);
             return;
         }
         if (tid < AD) {
@@ -1572,9 +1565,8 @@ hipError_t t2s_launch_lstm_seq_bwd(const float* d_out, const float* out, const f
 // (batch element, direction); workgroup q owns the 64 outputs d_h[64 q .. 64 q + 63] and keeps W_hh[:, those 64 columns] (256 KB)
 // in registers - thread (jq, kk) the 64 rows 64 jq .. of column 64 q + kk.  Per step every workgroup redoes the pointwise part for
 // all 256 units (a few hundred flops; its 8 loads per unit are requested one step ahead), multiplies its quarter, and exchanges 64
-// values with the other three through tagged 8-byte granules.  The one-workgroup kernel above streams 1 MB per step through one CU
-// (25 us per step at B = 32: 6.5 ms of a train step, behind which the encoder's whole backward waits).
-#define LSEQB_SPIN_MAX (1 << 22)
+// values with the other three through tagged 8-byte granules (t2s_handoff.h).  The one-workgroup kernel above streams 1 MB per step
+// through one CU (25 us per step at B = 32: 6.5 ms of a train step, behind which the encoder's whole backward waits).
 __global__ __launch_bounds__(1024) void lstm_seq_bwd_split_kernel(const float* __restrict__ d_out, const float* __restrict__ out,
                                                                   const float* __restrict__ gates, const float* __restrict__ csave,
                                                                   const float* __restrict__ whh_f, const float* __restrict__ whh_r,
@@ -1598,7 +1590,6 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_split_kernel(const float* _
     if (tid < H) s_dh[tid] = 0.f;
     if (tid == 0) s_fail = 0;
     unsigned long long* xg = xbuf + (size_t)group * 2 * H;
-    const unsigned tag0 = epoch << 12;
     const int pu = tid >= 64 && tid < 256 ? ((tid - 64) < 64 * q ? (tid - 64) : tid) : 0;
     const bool mine = tid < H && (tid >> 6) == q;            // the units whose dgx / hprev rows this workgroup writes
     // operands of the pointwise part of step s, requested one step ahead (thread u < 256)
@@ -1656,28 +1647,17 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_split_kernel(const float* _
             float v = 0.f;
 #pragma unroll
             for (int w = 0; w < 16; w += 4) v += (s_part[w][tid] + s_part[w + 1][tid]) + (s_part[w + 2][tid] + s_part[w + 3][tid]);
-            const unsigned long long g = ((unsigned long long)(tag0 + (unsigned)s + 1u) << 32) | (unsigned long long)__float_as_uint(v);
-            __hip_atomic_store(xg + (size_t)(s & 1) * H + 64 * q + tid, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            handoff_publish(xg + (size_t)(s & 1) * H + 64 * q + tid, split_lstm_tag(epoch, s), v);
             s_dh[64 * q + tid] = v;
         } else if (tid < 256) {
             float v = 0.f;
-            bool ok = true;
-            if (s + 1 < len) {
-                ok = false;
-                const unsigned want = tag0 + (unsigned)s + 1u;
-                const unsigned long long* slot = xg + (size_t)(s & 1) * H + pu;
-                for (int it = 0; it < LSEQB_SPIN_MAX; ++it) {
-                    const unsigned long long g = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((unsigned)(g >> 32) == want) { v = __uint_as_float((unsigned)g); ok = true; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
+            const bool ok = s + 1 < len ? handoff_await(xg + (size_t)(s & 1) * H + pu, split_lstm_tag(epoch, s), v) : true;
             if (!ok) s_fail = 1;
             s_dh[pu] = v;
         }
         __syncthreads();
         if (s_fail) {
-            if (tid == 0) __hip_atomic_store(xbuf + (size_t)2 * B * 2 * H, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) handoff_raise(xbuf + split_lstm_err_word(B));
             break;
         }
     }
@@ -1685,9 +1665,9 @@ __global__ __launch_bounds__(1024) void lstm_seq_bwd_split_kernel(const float* _
 hipError_t t2s_launch_lstm_seq_bwd_split(const float* d_out, const float* out, const float* gates, const float* csave,
                                          const float* whh_f, const float* whh_r, const int* lengths, float* dgx, float* hprev,
                                          int B, int T, int T_out, unsigned long long* xbuf, unsigned epoch, hipStream_t stream) {
-    if (T >= 4095) return hipErrorInvalidValue;
+    if (T >= SPLIT_LSTM_T_LIMIT) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lstm_seq_bwd_split_kernel, dim3(((2 * B + 7) / 8) * 32), dim3(1024), 0, stream, d_out, out, gates, csave,
-                       whh_f, whh_r, lengths, dgx, hprev, B, T, T_out, xbuf, epoch & 0xFFFFFu);
+                       whh_f, whh_r, lengths, dgx, hprev, B, T, T_out, xbuf, epoch & SPLIT_LSTM_EPOCH_MASK);
     return hipGetLastError();
 }
 

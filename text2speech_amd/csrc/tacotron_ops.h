@@ -59,13 +59,14 @@ struct LstmCellArgs {
     // (modules.py:19-22, the prenet's second Linear + ReLU + always-on dropout; w_p2 = the TRANSPOSED weight, walked sparsely:
     // lstm_cell_p2_kernel)
     const float* w_p2; const float* p1; const unsigned char* p2_mask; long s_p2_mask; float p2_scale;
-    // matrix-core form only: the first thread of the launch stores sig_val to *sig_ptr (agent scope) as the kernel STARTS - i.e. when
-    // everything in front of it on its stream has completed.  A helper stream's t2s_launch_pace_wait on that word then releases work
-    // that should run beside what FOLLOWS this launch (the teacher-forced decoder cell beside the attention launch).
+    // matrix-core form only: the first thread of the launch stores sig_val to *sig_ptr as the kernel STARTS (pace_signal,
+    // t2s_handoff.h) - i.e. when everything in front of it on its stream has completed.  A helper stream's t2s_launch_pace_wait on
+    // that word then releases work that should run beside what FOLLOWS this launch (the teacher-forced decoder cell beside the
+    // attention launch).
     unsigned* sig_ptr; unsigned sig_val;
 };
-// one wave that polls *flag (bounded) until it has reached `val`; the launches behind it on `stream` start then.  err: a word that is
-// raised if the wait expires (may be null)
+// one wave that polls *flag (bounded, pace_await in t2s_handoff.h) until it has reached `val`; the launches behind it on `stream` start
+// then.  err: a word that is raised if the wait expires (may be null)
 hipError_t t2s_launch_pace_wait(const unsigned* flag, unsigned val, unsigned long long* err, hipStream_t stream);
 hipError_t t2s_launch_pace_signal(unsigned* flag, unsigned val, hipStream_t stream);
 
@@ -114,7 +115,7 @@ struct AttArgs {
     float* wcum_save;          // optional [B][T]: cumulative weights after this step (training)
     int tile_major;            // att_energy_mfma_kernel: block -> (tile, item) in launch order instead of item-per-XCD (always 0 now; kept so that the kernel stays as measured)
     // one-launch form of energies + softmax + context (t2s_launch_att_energy with xbuf set; t2s_att_energy_ctx_ok says whether the
-    // shape is covered): [B][T] 8-byte granules + 1 error word, zero before step 0; tag = step + 1 (never 0)
+    // shape is covered): [B][T] granules of t2s_handoff.h + 1 error word, zero before step 0; tag = step + 1
     unsigned long long* xbuf;
     unsigned tag;
 };

@@ -13,6 +13,7 @@
 #include "t2s_common.h"
 #include "t2s_kernels.h"
 #include "tacotron_ops.h"
+#include "t2s_handoff.h"
 
 #include <stdlib.h>
 
@@ -776,14 +777,12 @@ __global__ __launch_bounds__(256) void att_softmax_ctx_kernel(const AttArgs a) {
 // time on two LDS reads per MAC of the convolution (profiles/r03_taco_step_kernel_counters_before.json).
 #define ATT_MQ 32
 // FUSE (teacher-forced chain at 9+ items, AttArgs::xbuf): softmax, cumulative weights and context in the SAME launch.  The n_tiles
-// workgroups of a batch element (all on one XCD, above) exchange their 32 energies through tagged 8-byte granules (one sc1 store per
-// value, the consumer lane polls its own granule: the encoder recurrence's hand-off, lstm_seq_split_kernel), every workgroup then
-// has the whole row, redoes the softmax (T exps), writes the weights / cumulative weights of ITS positions and - the first
-// enc_dim / 64 of them - one 64-channel chunk of the context.  The softmax + context launch (7 us at B = 32, T = 256, of which ~5
+// workgroups of a batch element (all on one XCD, above) exchange their 32 energies through tagged 8-byte granules (t2s_handoff.h),
+// every workgroup then has the whole row, redoes the softmax (T exps), writes the weights / cumulative weights of ITS positions and
+// - the first enc_dim / 64 of them - one 64-channel chunk of the context.  The softmax + context launch (7 us at B = 32, T = 256, of which ~5
 // are the launch itself) leaves the serial chain for one hand-off.  In-place update of w / w_cum is safe: a workgroup writes only
 // after it has every partner's energies, which a partner publishes after its own reads of the window (its halo included).
-// xbuf: [B][T] granules + 1 error word, zero before step 0 of a sequence; tag = step + 1.  Waits are bounded.
-#define ATT_FUSE_SPIN_MAX (1 << 22)
+// xbuf: [B][T] granules + 1 error word, zero before step 0 of a sequence; tag = step + 1.
 template <bool FUSE>
 __global__ __launch_bounds__(512, 2) void att_energy_mfma_kernel(const AttArgs a) {
     constexpr int AD = 128;
@@ -927,8 +926,7 @@ __global__ __launch_bounds__(512, 2) void att_energy_mfma_kernel(const AttArgs a
             const float e = ((s_e[0][tid] + s_e[1][tid]) + (s_e[2][tid] + s_e[3][tid])) + ((s_e[4][tid] + s_e[5][tid]) + (s_e[6][tid] + s_e[7][tid]));
             if (t < T) {
                 const float em = t < len ? e : -INFINITY;
-                const unsigned long long g = ((unsigned long long)a.tag << 32) | (unsigned long long)__float_as_uint(em);
-                __hip_atomic_store(xrow + t, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                handoff_publish(xrow + t, a.tag, em);
                 s_w[t] = em;
             }
         }
@@ -948,18 +946,13 @@ __global__ __launch_bounds__(512, 2) void att_energy_mfma_kernel(const AttArgs a
         bool ok = true;
         for (int t = tid; t < T; t += 512) {
             if (t >= t0 && t < t0 + ATT_MQ) continue;        // own tile: already in s_w
-            bool got = false;
-            for (int it = 0; it < ATT_FUSE_SPIN_MAX; ++it) {
-                const unsigned long long g = __hip_atomic_load(xrow + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((unsigned)(g >> 32) == a.tag) { s_w[t] = __uint_as_float((unsigned)g); got = true; break; }
-                __builtin_amdgcn_s_sleep(1);
-            }
+            const bool got = handoff_await(xrow + t, a.tag, s_w[t]);
             ok = ok && got;
         }
         if (!ok) s_fail = 1;
         __syncthreads();
         if (s_fail) {
-            if (tid == 0) __hip_atomic_store(a.xbuf + (size_t)a.B * T, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) handoff_raise(a.xbuf + (size_t)a.B * T);
             return;
         }
         // softmax over the row (reference tacotron.py:159-160), every workgroup of the element for itself
@@ -1973,31 +1966,14 @@ hipError_t t2s_launch_lstm_seq(const float* gx, const float* whhT_f, const float
 // The same recurrence with W_hh RESIDENT: the matrix of one direction (1 MB) does not fit one CU, a quarter of it (256 KB = 64
 // registers on each of 1024 threads) does.  Four workgroups share one (batch element, direction): workgroup q owns hidden units
 // 64 q .. 64 q + 63 (their four gate rows each), keeps W_hh^T[k][those 256 rows] in registers for the whole sequence and per step
-// exchanges its 64 new h values with the other three through 8-byte {value, tag} granules (MI355X_MICROARCH.md handoff-1to1 /
-// "R2's granule": one sc1 store per value, the consumer lane polls its own granule with an sc1 load until the tag is this launch's
-// step number - no flag, no fence, nothing streamed).  A step is then one hand-off (~1 us) + 64 FMAs per thread instead of 1 MB
-// through one CU (12.7 us per step at B = 32).
-//   * xbuf: [2 B groups][2 step parities][256 units] granules, caller-owned, zero before its first use; tags carry `epoch` (the
-//     caller's launch counter) so that nothing a previous launch left can match.  Slot parity: a workgroup overwrites slot s & 1 at
-//     step s + 2, after it has seen every partner's step s + 1, which they publish after reading step s.
+// exchanges its 64 new h values with the other three through 8-byte {value, tag} granules (t2s_handoff.h: nothing streamed).  A step
+// is then one hand-off (~1 us) + 64 FMAs per thread instead of 1 MB through one CU (12.7 us per step at B = 32).
+//   * xbuf: the split BiLSTM exchange buffer of t2s_handoff.h, caller-owned, zero before its first use; tags carry `epoch` (the
+//     caller's launch counter).
 //   * block number -> (group, quarter): id = 32 G + 8 m + x is quarter m of group 8 G + x - the four workgroups of a group are
 //     within 32 consecutive blocks (they become resident together; a group whose partners are not resident yet spins, complete
 //     groups in front of it always finish) and share an XCD under round-robin placement (speed only).
-//   * every wait is bounded (LSEQ_SPIN_MAX polls, seconds): on expiry the workgroup raises xbuf's error word and leaves the loop.
-#define LSEQ_SPIN_MAX (1 << 22)
-static __device__ __forceinline__ void lseq_publish(unsigned long long* slot, float v, unsigned tag) {
-    const unsigned long long g = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v);
-    __hip_atomic_store(slot, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);         // global_store_dwordx2 sc1
-}
-// polls until the granule carries `tag`; false on expiry
-static __device__ __forceinline__ bool lseq_await(const unsigned long long* slot, unsigned tag, float& v) {
-    for (int it = 0; it < LSEQ_SPIN_MAX; ++it) {
-        const unsigned long long g = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // global_load_dwordx2 sc1
-        if ((unsigned)(g >> 32) == tag) { v = __uint_as_float((unsigned)g); return true; }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return false;
-}
+//   * every wait is bounded: on expiry the workgroup raises xbuf's error word and leaves the loop.
 
 __global__ __launch_bounds__(1024) void lstm_seq_split_kernel(const float* __restrict__ gx, const float* __restrict__ whhT_f,
                                                               const float* __restrict__ whhT_r, const int* __restrict__ lengths,
@@ -2023,7 +1999,6 @@ __global__ __launch_bounds__(1024) void lstm_seq_split_kernel(const float* __res
     if (tid == 0) s_fail = 0;
     float c = 0.f;
     unsigned long long* xg = xbuf + (size_t)group * 2 * H;
-    const unsigned tag0 = epoch << 12;
     // the partner unit this thread fetches each step (threads 64 .. 255: the 192 units of the other three quarters)
     const int pu = tid >= 64 && tid < 256 ? ((tid - 64) < 64 * q ? (tid - 64) : tid) : 0;
     __syncthreads();
@@ -2050,7 +2025,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_split_kernel(const float* __res
             const float gi = s_g[tid], gf = s_g[64 + tid], gg = s_g[128 + tid], go = s_g[192 + tid];
             c = sigmoid_acc(gf) * c + sigmoid_acc(gi) * tanhf(gg);
             const float h = sigmoid_acc(go) * tanhf(c);
-            lseq_publish(xg + (size_t)(s & 1) * H + u, h, tag0 + (unsigned)s + 1u);
+            handoff_publish(xg + (size_t)(s & 1) * H + u, split_lstm_tag(epoch, s), h);
             s_h[u] = h;
             if (gates_save) {      // training: post-activation gates and cell state per step, for the BPTT kernel
                 const size_t gb = (((size_t)b * T + t) * 2 + dir) * 4 * H + u;
@@ -2063,13 +2038,13 @@ __global__ __launch_bounds__(1024) void lstm_seq_split_kernel(const float* __res
             out[((size_t)b * T_out + t) * (2 * H) + dir * H + u] = h;
         } else if (tid < 256) {
             float v = 0.f;
-            const bool ok = s + 1 < len ? lseq_await(xg + (size_t)(s & 1) * H + pu, tag0 + (unsigned)s + 1u, v) : true;
+            const bool ok = s + 1 < len ? handoff_await(xg + (size_t)(s & 1) * H + pu, split_lstm_tag(epoch, s), v) : true;
             if (!ok) s_fail = 1;
             s_h[pu] = v;                                     // (the last step's h of the partners is not needed)
         }
         __syncthreads();
         if (s_fail) {
-            if (tid == 0) __hip_atomic_store(xbuf + (size_t)2 * B * 2 * H, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) handoff_raise(xbuf + split_lstm_err_word(B));
             break;
         }
     }
@@ -2081,9 +2056,9 @@ __global__ __launch_bounds__(1024) void lstm_seq_split_kernel(const float* __res
 hipError_t t2s_launch_lstm_seq_split(const float* gx, const float* whhT_f, const float* whhT_r, const int* lengths, float* out,
                                      int B, int T, int T_out, float* gates_save, float* c_save, unsigned long long* xbuf,
                                      unsigned epoch, hipStream_t stream) {
-    if (T >= 4095) return hipErrorInvalidValue;              // (12 tag bits for the step)
+    if (T >= SPLIT_LSTM_T_LIMIT) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lstm_seq_split_kernel, dim3(((2 * B + 7) / 8) * 32), dim3(1024), 0, stream, gx, whhT_f, whhT_r, lengths, out,
-                       B, T, T_out, gates_save, c_save, xbuf, epoch & 0xFFFFFu);
+                       B, T, T_out, gates_save, c_save, xbuf, epoch & SPLIT_LSTM_EPOCH_MASK);
     return hipGetLastError();
 }
 
@@ -2092,15 +2067,10 @@ hipError_t t2s_launch_lstm_seq_split(const float* gx, const float* whhT_f, const
 // ~7 us gap on it; a word stored by the first thread of a chain launch costs nothing there).  One wave polls, bounded.
 __global__ void pace_wait_kernel(const unsigned* flag, unsigned val, unsigned long long* err) {
     if (threadIdx.x != 0) return;
-    for (int it = 0; it < (1 << 22); ++it) {
-        const unsigned v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((int)(v - val) >= 0) return;
-        __builtin_amdgcn_s_sleep(2);
-    }
-    if (err) __hip_atomic_store(err, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!pace_await(flag, val) && err) handoff_raise(err);
 }
 __global__ void pace_signal_kernel(unsigned* flag, unsigned val) {
-    if (threadIdx.x == 0) __hip_atomic_store(flag, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) pace_signal(flag, val);
 }
 hipError_t t2s_launch_pace_wait(const unsigned* flag, unsigned val, unsigned long long* err, hipStream_t stream) {
     hipLaunchKernelGGL(pace_wait_kernel, dim3(1), dim3(64), 0, stream, flag, val, err);

@@ -338,7 +338,7 @@ class _Bwd:
                    dc_d=_p(dc_d), dc_a=_p(dc_a), dw_c=_p(dw_c), dwc_c=_p(dwc_c), d_pmem=_p(d_pmem),
                    d_memory=_p(d_memory), dD_part=_p(dD_p), dK_part=_p(dK_p), dv_part=_p(dv_p), dw_buf=_p(dw_buf),
                    df_buf=_p(df_buf), dq_part=_p(dq_part), dctx_all=_p(dctx_all))
-        self.eng.__dict__["_last_bptt_xbuf"] = None
+        att_xbuf = None
         if dctx_all is not None:                   # the forward's contexts: hc_all[t][b] = [h_dec | ctx]
             bp.ctx_all, bp.s_ctx_step, bp.s_ctx_item = _p(sv["hc_all"], D), B * (D + E), D + E
             bp.dw_c2, bp.dwc_c2 = _p(dw_c2), _p(dwc_c2)
@@ -348,7 +348,7 @@ class _Bwd:
                 att_xbuf = self.zeros(2 * (B * nch * ad + 3))       # (+ the error word and two unused words: ABI v4 size)
                 bp.att_xbuf = _p(att_xbuf)
                 self.keep.append(att_xbuf)
-                self.eng.__dict__["_last_bptt_xbuf"] = (att_xbuf, B * nch * ad)     # (check_lstm_xbuf reads its error words)
+        self.eng._watch_xbuf("BPTT att_xbuf", att_xbuf, B * nch * ad)
         _lib.call("t2s_taco_bptt_steps", ctypes.byref(bp), T, 0, st)        # the whole reversed loop, enqueued from C++
         if dctx_all is not None:
             # d_memory[b] = sum_t w[t][b][:] (x) d_ctx[t][b][:]: one contraction over the decoder steps per batch element

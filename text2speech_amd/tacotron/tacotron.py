@@ -23,6 +23,9 @@ from .. import _lib
 from .modules import ConvNorm, LinearNorm, Postnet, Prenet, get_mask_from_lengths, OwnedModule
 
 BN_EPS = 1e-5
+# the split BiLSTM kernels' tag rule (csrc/t2s_handoff.h): T below this limit, the launch counter masked to 20 bits
+SPLIT_LSTM_T_LIMIT = 4095
+SPLIT_LSTM_EPOCH_MASK = 0xFFFFF
 
 
 class LocationLayer(nn.Module):
@@ -360,6 +363,8 @@ class _TacoEngine:
         self.m = model
         self.prep = None
         self.prep_key = None
+        self.lstm_xbufs = {}    # (direction of use, B, device) -> [split BiLSTM exchange buffer, epoch of its last launch]
+        self.xbuf_errs = {}     # exchange buffer name -> (its int64 view, index of its error word): read by check_lstm_xbuf()
 
     # ------------------------------------------------------------------ weight preparation
     def _pack_conv_bn(self, seq, dev, halo):
@@ -547,7 +552,7 @@ class _TacoEngine:
             gsave = pool_take(self.pool, leases, "enc_gsave", (B, T, 2, 4 * H), torch.float32, dev)
             csave = pool_take(self.pool, leases, "enc_csave", (B, T, 2, H), torch.float32, dev)
             save.update(enc_gates=gsave, enc_c=csave)
-        xb = self._lstm_xbuf("fwd", B, dev) if H == 256 and T < 4095 else None
+        xb = self._lstm_xbuf("fwd", B, T, H, dev)
         if xb is not None:      # W_hh resident, four workgroups per (element, direction) exchanging h per step (t2s_taco_encoder_lstm_split)
             _lib.call("t2s_taco_encoder_lstm_split", _lib.ptr(gx), _lib.ptr(P["whhT"][0][0]), _lib.ptr(P["whhT"][1][0]),
                       _lib.ptr(len32), _lib.ptr(memory), B, T, H, T_out, _lib.ptr(gsave), _lib.ptr(csave), _lib.ptr(xb[0]), xb[1], st)
@@ -558,44 +563,36 @@ class _TacoEngine:
             save.update(enc_ids=ids64, enc_gx=gx, enc_Xh=Xh, enc_Xl=Xl, enc_T=T, enc_Lp=Lp, enc_len32=len32, memory=memory)
         return memory, len32
 
-    def _lstm_xbuf(self, which, B, dev):
-        """Exchange buffer of the split BiLSTM recurrence (t2s_taco_encoder_lstm_split / _bwd_split) and this launch's epoch.  One
-        buffer per direction of use (forward / backward: the two may be in flight on different streams), engine-owned, zeroed once;
-        `check_lstm_xbuf()` reads the error words."""
-        bufs = self.__dict__.setdefault("_xbufs", {})
+    def _lstm_xbuf(self, which, B, T, H, dev):
+        """Exchange buffer of the split BiLSTM recurrence (t2s_taco_encoder_lstm_split / _bwd_split) and this launch's epoch, or
+        None where the split kernels do not cover the shape.  One buffer per direction of use (forward / backward: the two may be
+        in flight on different streams), engine-owned, zeroed once."""
+        if H != 256 or T >= SPLIT_LSTM_T_LIMIT:
+            return None
         key = (which, int(B), str(dev))
-        ent = bufs.get(key)
+        ent = self.lstm_xbufs.get(key)
         if ent is None:
             n = int(_lib.load().t2s_taco_lstm_xbuf_bytes(int(B)))
-            ent = bufs[key] = [torch.zeros(n // 8, dtype=torch.int64, device=dev), 0]
-        ent[1] = (ent[1] + 1) & 0xFFFFF
+            ent = self.lstm_xbufs[key] = [torch.zeros(n // 8, dtype=torch.int64, device=dev), 0]
+            self._watch_xbuf("split BiLSTM %s B=%d %s" % key, ent[0], n // 8 - 1)
+        ent[1] = (ent[1] + 1) & SPLIT_LSTM_EPOCH_MASK
         if ent[1] == 0:         # (wrapped: tags of 2^20 launches ago could match again - start over from a clean buffer)
             ent[0].zero_()
             ent[1] = 1
         return ent[0], ent[1]
 
+    def _watch_xbuf(self, name, buf, word):
+        """From now on check_lstm_xbuf() reads 8-byte word `word` of exchange buffer `buf` under `name` (buf None: nothing)."""
+        self.xbuf_errs.pop(name, None)
+        if buf is not None:
+            self.xbuf_errs[name] = (buf.view(torch.int64), word)
+
     def check_lstm_xbuf(self):
-        """Synchronises; raises if a bounded wait of the split BiLSTM kernels ever expired on one of this engine's buffers, or one
-        of the last teacher-forced decode or of the last backward's attention exchange."""
-        for key, (buf, _) in self.__dict__.get("_xbufs", {}).items():
-            if int(buf[-1].item()) != 0:
-                raise _lib.T2SError("split BiLSTM recurrence %s: a hand-off wait expired (results of that launch are invalid)" % (key,))
-        # ... and of the last teacher-forced decode's exchange buffers (t2s_taco_decoder::att_xbuf / pace_flag: their last / second
-        # 8-byte word is raised by a bounded wait that expired)
-        S = self.__dict__.get("_last_decoder_S")
-        if S is not None:
-            for name, words in (("att_xbuf", (-2, -1)), ("pace_flag", (2, 3))):
-                t = S.get(name)
-                if t is not None and any(float(t.view(-1)[w].item()) != 0.0 for w in words):
-                    raise _lib.T2SError("teacher-forced decode: a bounded wait on %s expired (results of that call are invalid)" % name)
-        # ... and of the last backward's attention exchange buffer (t2s_taco_bptt::att_xbuf: 8-byte granule E = B * ceil(T_in / 32)
-        # * att_dim is raised by a bounded wait of the folded attention cell that expired)
-        last = self.__dict__.get("_last_bptt_xbuf")
-        if last is not None:
-            buf, e = last
-            if int(buf.view(torch.int64)[e].item()) != 0:
-                raise _lib.T2SError("decoder BPTT: a bounded wait of the folded attention cell's exchange expired (gradients of that "
-                                    "step are invalid)")
+        """Synchronises; raises if a bounded hand-off wait expired on one of the exchange buffers this engine watches: its split
+        BiLSTM buffers, the last teacher-forced decode's and the last backward's (a kernel raises the buffer's error word)."""
+        for name, (words, e) in self.xbuf_errs.items():
+            if int(words[e].item()) != 0:
+                raise _lib.T2SError("%s: a bounded hand-off wait expired (results of the launch that used it are invalid)" % name)
 
     def _gemv(self, W, x, rows, items, K, y, act=0, mask=None, smask=0, mask_scale=1.0, bias=None, sy_item=None,
               sx=None):
@@ -898,7 +895,8 @@ class _TacoEngine:
             d.att_drop_scale = 1.0 / (1.0 - dec.p_attention_dropout)
             d.dec_drop_scale = 1.0 / (1.0 - dec.p_decoder_dropout)
         _lib.call("t2s_taco_decode_steps", ctypes.byref(d), 0, T_out, _lib.current_stream())
-        self.__dict__["_last_decoder_S"] = {k: S.get(k) for k in ("att_xbuf", "pace_flag")}     # (check_lstm_xbuf reads their error words)
+        self._watch_xbuf("decoder att_xbuf", S.get("att_xbuf"), B * memory.size(1))     # (error words: its last 8 bytes ...
+        self._watch_xbuf("decoder pace_flag", S.get("pace_flag"), 1)                    # ... and the second 8 of pace_flag)
         # hoisted projection + gate over all steps (reference tacotron.py:387-392)
         proj = torch.empty(T_out * B, n_mel + 1, dtype=torch.float32, device=dev)
         self._gemv(P["w_proj"], hc_all, n_mel + 1, T_out * B, D + E, proj, bias=P["b_proj"])
