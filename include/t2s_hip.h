@@ -228,6 +228,12 @@ int t2s_f32_to_planes(const float* x, int B, int C, int L, int Lp, int halo, voi
  * convolution saved for its backward pass: its weight gradient sees the masked mel (the training path re-derives that
  * convolution's saved input planes from the masked tensor, text2speech_amd/tacotron/tacotron.py). */
 int t2s_taco_parse_output(float* mel, float* mel_post, float* gate, const int* lengths, int B, int n_mel, int T, void* stream);
+/* Batched inference of texts of different lengths (ABI v4, compatible addition): planes [B][ceil(C/32)][Lp][32] (hi, lo, 16-byte
+ * aligned) get zeros in rows halo + t for lengths[b] <= t < T; the halo rows are left alone.  After the embedding and after each
+ * convolution a following convolution then reads zeros past every entry's end, as it reads its halo when the entry runs alone. */
+int t2s_zero_plane_rows(void* X_hi, void* X_lo, const int* lengths, int B, int C, int T, int Lp, int halo, void* stream);
+/* x[b][t][:] = 0 for lengths[b] <= t < N; x: [B][N][row] f32 (the alignments of a batch past each entry's output length) */
+int t2s_zero_rows_f32(float* x, const int* lengths, int B, int N, int row, void* stream);
 /* eval BatchNorm folded into the preceding conv: scale = gamma/sqrt(var+eps), bias' = (bias-mean)*scale+beta */
 int t2s_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, const float* conv_bias,
                 float eps, int C, float* scale, float* bias_out, void* stream);

@@ -79,6 +79,20 @@ int t2s_taco_parse_output(float* mel, float* mel_post, float* gate, const int* l
     return T2S_OK;
 }
 
+int t2s_zero_plane_rows(void* X_hi, void* X_lo, const int* lengths, int B, int C, int T, int Lp, int halo, void* stream) {
+    if (!X_hi || !X_lo || !lengths || B <= 0 || C <= 0 || T <= 0 || halo < 0 || B > 65535 || C > (1 << 20) || Lp < t2s_plane_rows(T, halo))
+        return T2S_EINVAL;
+    if (!al16(X_hi) || !al16(X_lo)) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_zero_plane_rows((u16*)X_hi, (u16*)X_lo, lengths, B, (C + 31) / 32, T, Lp, halo, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_zero_rows_f32(float* x, const int* lengths, int B, int N, int row, void* stream) {
+    if (!x || !lengths || B <= 0 || N <= 0 || row <= 0 || B > 65535 || (long)N * row > (1L << 36)) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_zero_rows_f32(x, lengths, B, N, row, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 int t2s_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, const float* conv_bias,
                 float eps, int C, float* scale, float* bias_out, void* stream) {
     if (!gamma || !beta || !mean || !var || !scale || !bias_out || C <= 0) return T2S_EINVAL;

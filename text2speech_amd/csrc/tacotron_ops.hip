@@ -2163,6 +2163,39 @@ hipError_t t2s_launch_parse_output(float* mel, float* mel_post, float* gate, con
     return hipGetLastError();
 }
 
+// Batched inference of ragged texts (Tacotron.inference_batch): the rows t of an entry with lengths[b] <= t < T become zero in both
+// planes, so the next convolution reads zeros past the entry's end, as the halo of the entry's solo run.  Halo rows are not touched.
+// Four threads per 32-channel row (16 bytes each), 64 rows per block; grid (row blocks, channel chunks, B).
+__global__ __launch_bounds__(256) void zero_plane_rows_kernel(u16* X_hi, u16* X_lo, const int* lengths, int T, int Lp, int halo) {
+    const int t = blockIdx.x * 64 + (threadIdx.x >> 2);
+    const int c = blockIdx.y, b = blockIdx.z;
+    if (t >= T || t < lengths[b]) return;
+    const size_t idx = (((size_t)b * gridDim.y + c) * Lp + halo + t) * 32 + (threadIdx.x & 3) * 8;
+    *(uint4*)(X_hi + idx) = make_uint4(0, 0, 0, 0);
+    *(uint4*)(X_lo + idx) = make_uint4(0, 0, 0, 0);
+}
+hipError_t t2s_launch_zero_plane_rows(u16* X_hi, u16* X_lo, const int* lengths, int B, int nch, int T, int Lp, int halo,
+                                      hipStream_t stream) {
+    hipLaunchKernelGGL(zero_plane_rows_kernel, dim3((T + 63) / 64, nch, B), dim3(256), 0, stream, X_hi, X_lo, lengths, T, Lp, halo);
+    return hipGetLastError();
+}
+
+// x[b][t][:] = 0 for lengths[b] <= t < N, x: [B][N][row] f32 (the alignments past each entry's output length)
+__global__ __launch_bounds__(256) void zero_rows_f32_kernel(float* x, const int* lengths, int N, int row) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    const long n = (long)N * row;
+    if (i >= n) return;
+    const long t0 = (long)max(lengths[b], 0) * row;
+    if (i < t0) return;
+    x[(size_t)b * n + i] = 0.f;
+}
+hipError_t t2s_launch_zero_rows_f32(float* x, const int* lengths, int B, int N, int row, hipStream_t stream) {
+    const long n = (long)N * row;
+    hipLaunchKernelGGL(zero_rows_f32_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, stream, x, lengths, N, row);
+    return hipGetLastError();
+}
+
 // eval-mode BatchNorm folded into the preceding conv: scale[o] = gamma/sqrt(var+eps),
 // bias'[o] = (bias[o] - mean[o]) * scale[o] + beta[o]      (tacotron.py:183-184, modules.py:105-129)
 __global__ void bn_fold_kernel(const float* gamma, const float* beta, const float* mean, const float* var,

@@ -497,11 +497,21 @@ class _TacoEngine:
                   layer["Cout"], layer.get("taps", 1), 1, act, L, Lp, halo, layer["Mpad"], _lib.current_stream())
         return Oh, Ol
 
-    def encode(self, ids, lengths, train_masks=None, seed=0, save=None, embedded=None, max_len=None):
+    def _zero_pad(self, Xh, Xl, len32, C, T, Lp, halo):
+        """Planes rows t >= len32[b] of entry b -> 0 (one launch; nothing when len32 is None)."""
+        if len32 is not None:
+            _lib.call("t2s_zero_plane_rows", _lib.ptr(Xh), _lib.ptr(Xl), _lib.ptr(len32), Xh.size(0), C, T, Lp, halo,
+                      _lib.current_stream())
+
+    def encode(self, ids, lengths, train_masks=None, seed=0, save=None, embedded=None, max_len=None, zero_pad=False):
         """Embedding + Encoder.forward / .inference (reference tacotron.py:40,192-220).  In training mode the
         convolutions use batch statistics and dropout(0.5) (masks from ``train_masks['enc']`` or drawn here).
-        ``embedded`` [B, E, T] f32: start from embedded inputs instead of ids (Encoder.forward's own argument)."""
+        ``embedded`` [B, E, T] f32: start from embedded inputs instead of ids (Encoder.forward's own argument).
+        ``zero_pad`` (eval mode, with ``lengths``): each entry's rows past its length are zeroed after the embedding and after
+        every convolution, so that each entry computes what it computes alone (inference_batch).  Encoder.forward does not: its
+        convolutions read the padding, as the reference's do."""
         m, P = self.m, self.prep
+        assert not zero_pad or (lengths is not None and not m.training), "zero_pad: eval mode, with lengths"
         E = m.embedding.embedding_dim
         halo = 2
         st = _lib.current_stream()
@@ -522,6 +532,7 @@ class _TacoEngine:
             Xh, Xl = self._planes((B, -(-E // 32), Lp, 32), dev, leases, "enc_x", (T,))
             _lib.call("t2s_embed_planes", _lib.ptr(ids64), _lib.ptr(P["emb"]), B, T, E, m.embedding.num_embeddings, Lp, halo,
                       _lib.ptr(Xh), _lib.ptr(Xl), st)
+        len32 = None if lengths is None else lengths.to(device=dev, dtype=torch.int32).contiguous()
         if m.training:
             given = None if train_masks is None else train_masks.get("enc")
             for i, (seq, layer) in enumerate(zip(m.encoder.convolutions, P["enc_convs_plain"])):
@@ -530,19 +541,21 @@ class _TacoEngine:
                                              save=None if save is None else save.setdefault("enc_convs", []),
                                              leases=leases, tag="enc_conv%d" % i)
         else:
+            pad32 = len32 if zero_pad else None
+            self._zero_pad(Xh, Xl, pad32, E, T, Lp, halo)
             for layer in P["enc_convs"]:
                 Xh, Xl = self._conv(layer, Xh, Xl, B, T, Lp, halo, 1)
+                self._zero_pad(Xh, Xl, pad32, layer["Cout"], T, Lp, halo)
         H = P["H"]
         gx = torch.empty(B, T, 8 * H, dtype=torch.float32, device=dev)
         self._conv(P["lstm_in"], Xh, Xl, B, T, Lp, halo, 0, out_planes=False, out_f32=gx, f32_cl=1)
         if lengths is not None:
-            len32 = lengths.to(device=dev, dtype=torch.int32).contiguous()
             # the longest entry: given by the caller (the batch tuple's max_len, reference tacotron.py:81-83 / parse_batch) or read
             # back from the device - a host synchronisation that keeps the host from enqueueing this step while the previous one
             # still runs
             T_out = int(max_len) if max_len is not None else int(lengths.max().item())
         else:
-            len32, T_out = None, T
+            T_out = T
         memory = torch.empty(B, T_out, 2 * H, dtype=torch.float32, device=dev)
         gsave = csave = None
         if save is not None:
@@ -657,9 +670,11 @@ class _TacoEngine:
             S[name] = t
         return d, S
 
-    def postnet(self, mel, train_masks=None, seed=0, save=None):
+    def postnet(self, mel, train_masks=None, seed=0, save=None, lengths=None):
         """Postnet.forward (reference modules.py:131-137): 5 x conv+BN, tanh on the first four; in training mode
-        batch statistics and dropout(0.5) after every layer."""
+        batch statistics and dropout(0.5) after every layer.  ``lengths`` (eval mode: int32 [B] on the device): each entry's
+        frames from its length on are zeroed in the input and in the outputs of the first four layers, so that each entry computes
+        what it computes alone (inference_batch); the last layer's output there is not."""
         P = self.prep
         m = self.m
         B, C, T = mel.shape
@@ -672,6 +687,7 @@ class _TacoEngine:
         _lib.call("t2s_f32_to_planes", _lib.ptr(mel), B, C, T, Lp, halo, _lib.ptr(Xh), _lib.ptr(Xl), _lib.current_stream())
         n = len(m.postnet.convolutions)
         out = torch.empty(B, C, T, dtype=torch.float32, device=dev)
+        assert lengths is None or not m.training, "postnet lengths: eval mode"
         if m.training:
             given = None if train_masks is None else train_masks.get("post")
             for i, (seq, layer) in enumerate(zip(m.postnet.convolutions, P["post_convs_plain"])):
@@ -683,9 +699,11 @@ class _TacoEngine:
                 else:
                     self._conv_bn_train(seq, layer, Xh, Xl, B, T, Lp, halo, 0, mk, want_planes=False, out_f32=out, save=sv)
             return out
+        self._zero_pad(Xh, Xl, lengths, C, T, Lp, halo)
         for i, layer in enumerate(P["post_convs"]):
             if i < n - 1:
                 Xh, Xl = self._conv(layer, Xh, Xl, B, T, Lp, halo, 2)
+                self._zero_pad(Xh, Xl, lengths, layer["Cout"], T, Lp, halo)
             else:
                 self._conv(layer, Xh, Xl, B, T, Lp, halo, 0, out_planes=False, out_f32=out)
         return out
@@ -776,10 +794,32 @@ class _TacoEngine:
         mel_post = mel + self.postnet(mel, train_masks, seed)
         return [mel, mel_post, gate, align]
 
-    def decode_free(self, memory, prenet_masks=None, seed=None, chunk=64, train_masks=None):
+    def inference_batch(self, ids, lengths, prenet_masks=None, seed=None, chunk=64):
+        """Tacotron.inference_batch (eval mode): ``ids`` [B, T] padded, ``lengths`` int64 [B] on the host, 1 <= lengths <= T.
+        Entry b computes what ``inference(ids[b:b+1, :lengths[b]])`` computes: the encoder and postnet zero its rows past its
+        length before every convolution (their solo halo), the attention reads its first lengths[b] positions.  Returns
+        ([mel, mel_post, gate, align] padded to the longest output, output lengths int64 [B] on the device); past each output
+        length mel / mel_post are 0, the gate 1e3 (Tacotron.parse_output) and the alignment rows 0."""
+        if seed is None:
+            seed = self.fresh_seed()
+        dev = ids.device
+        self.prepare(dev)
+        memory, len32 = self.encode(ids, lengths, seed=seed, max_len=int(lengths.max()), zero_pad=True)
+        mel, gate, align, olen = self.decode_free(memory, prenet_masks, seed, chunk, lengths=len32)
+        olen32 = olen.to(torch.int32)
+        mel_post = mel + self.postnet(mel, seed=seed, lengths=olen32)
+        B, n_mel, N = mel.shape
+        st = _lib.current_stream()
+        _lib.call("t2s_taco_parse_output", _lib.ptr(mel), _lib.ptr(mel_post), _lib.ptr(gate), _lib.ptr(olen32), B, n_mel, N, st)
+        _lib.call("t2s_zero_rows_f32", _lib.ptr(align), _lib.ptr(olen32), B, N, align.size(2), st)
+        return [mel, mel_post, gate, align], olen
+
+    def decode_free(self, memory, prenet_masks=None, seed=None, chunk=64, train_masks=None, lengths=None):
         """Decoder.inference (reference tacotron.py:431-466): autoregressive decode of encoder outputs ``memory`` [B, T_in, E]
         until every entry's gate passes the threshold or max_decoder_steps.  Returns (mel [B, n_mel, T], gate [B, T, 1],
-        alignments [B, T, T_in])."""
+        alignments [B, T, T_in]).  ``lengths`` (int32 [B] on the device): the attention of entry b sees its first lengths[b]
+        positions only, and a fourth result is returned, each entry's output length (int64 [B] on the device: its stop step + 1,
+        or max_decoder_steps); frames past it are not masked here."""
         if seed is None:
             seed = self.fresh_seed()
         m = self.m
@@ -797,7 +837,7 @@ class _TacoEngine:
             tm = train_masks or {}
             extra["att_drop"] = self._drop(tm.get("att"), (T_cap, B, dec.attention_rnn_dim), 1 - dec.p_attention_dropout, dev, seed + 301)
             extra["dec_drop"] = self._drop(tm.get("dec"), (T_cap, B, dec.decoder_rnn_dim), 1 - dec.p_decoder_dropout, dev, seed + 302)
-        d, S = self._decoder_struct(memory, None, T_cap, False, extra)
+        d, S = self._decoder_struct(memory, lengths, T_cap, False, extra)
         if m.training:
             d.att_drop_scale = 1.0 / (1.0 - dec.p_attention_dropout)
             d.dec_drop_scale = 1.0 / (1.0 - dec.p_decoder_dropout)
@@ -821,7 +861,10 @@ class _TacoEngine:
         mel = mel_gate[:, :n_mel, :n_done].contiguous()
         gate = mel_gate[:, n_mel, :n_done].unsqueeze(-1).contiguous()          # [B, T, 1] as the reference returns
         align = S["align_out"][:, :n_done].contiguous()
-        return mel, gate, align
+        if lengths is None:
+            return mel, gate, align
+        olen = torch.where(sv >= 0, sv + 1, torch.full_like(sv, T_cap)).to(device=dev, dtype=torch.int64)
+        return mel, gate, align, olen
 
     def forward(self, text, text_lengths, mels, output_lengths, prenet_masks=None, seed=None, train_masks=None, save=None,
                 max_len=None):
@@ -1023,6 +1066,37 @@ class Tacotron(nn.Module):
         with torch.no_grad():
             out = self._eng().inference(inputs, prenet_masks, train_masks=train_masks)
         return self._as_module_dtype(self.parse_output(out))
+
+    def inference_batch(self, inputs, input_lengths, speaker_id=None, prenet_masks=None):
+        """Autoregressive decode of a batch of texts of different lengths, in eval mode: ``inputs`` [B, T] padded ids,
+        ``input_lengths`` [B] integers (host or device), 1 <= length <= T; ``prenet_masks`` [n, B, 2, prenet_dim] as for
+        ``inference`` (entry b uses [:, b]).  Returns (mel [B, n_mel, N], mel_post [B, n_mel, N], gate [B, N, 1],
+        alignments [B, N, max(input_lengths)], output_lengths int64 [B] on the device), N = max(output_lengths).
+
+        Entry b's first output_lengths[b] frames are what ``inference(inputs[b:b+1, :input_lengths[b]])`` returns: the same stop
+        step, the same values up to float rounding.  An entry's output length is its stop step + 1, or max_decoder_steps if it
+        never stopped (with the usual warning).  Past it mel and mel_post are 0, the gate 1e3 (as ``parse_output`` fills them)
+        and the alignment rows 0; alignment columns past the entry's input length are 0.  To get there the encoder and postnet
+        convolutions see zeros past each entry's length, as a solo run sees its halo - unlike the teacher-forced ``forward``,
+        whose convolutions read the padding, as the reference's do.  ``.train()`` mode is refused: batch-statistics BatchNorm
+        and live dropout would couple the entries."""
+        self._check(inputs)
+        if self.training:
+            raise _lib.T2SError("inference_batch runs in eval mode only (call .eval())")
+        if inputs.dim() != 2:
+            raise _lib.T2SError("inference_batch: inputs must be [B, T] ids, got %s" % (tuple(inputs.shape),))
+        B, T = inputs.shape
+        lengths = torch.as_tensor(input_lengths)
+        if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+            raise _lib.T2SError("inference_batch: input_lengths must be integers, got %s" % lengths.dtype)
+        lengths = lengths.detach().to("cpu", torch.int64)           # (one read-back when they live on the device)
+        if lengths.dim() != 1 or lengths.numel() != B:
+            raise _lib.T2SError("inference_batch: input_lengths has shape %s, inputs hold %d texts" % (tuple(lengths.shape), B))
+        if B == 0 or int(lengths.min()) < 1 or int(lengths.max()) > T:
+            raise _lib.T2SError("inference_batch: input_lengths must lie in [1, %d], got %s" % (T, lengths.tolist()))
+        with torch.no_grad():
+            out, output_lengths = self._eng().inference_batch(inputs, lengths, prenet_masks)
+        return self._as_module_dtype(out) + [output_lengths]
 
     def _as_module_dtype(self, outputs):
         """After ``model.half()`` (reference inference.py:61) the reference's outputs are half tensors; the kernels here
