@@ -162,6 +162,30 @@ int t2s_wg_in_cond_gate_fold(const void* A_hi, const void* A_lo, const float* bi
                              const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
                              float* fold_acc, int fold_init, int B, int C, int n_cond, int taps, int dilation, int L,
                              int Lp, int halo, int Mpad, void* stream);
+/* ---- WN.start folded into the first gate GEMM of a flow (no-grad forward / infer) ----
+ * x0 = W_start a + b_start has C channels but only n_half + 1 independent ones, so in_layers[0](x0) (reference glow.py:156,159) is
+ * a `taps`-tap convolution of the n_half audio channels and a constant-one channel (1 inside the utterance, 0 in the zero padding:
+ * exact at the edges): ncol = taps * (n_half + 1) <= 32 logical columns, column tap * (n_half + 1) + j = z[c_off + j][t + tap - taps/2]
+ * (j = n_half: the ones-channel).  Both factors are carried to f32 accuracy by FOUR column sets of ncol columns: with
+ * x = h + l + r (h, l the split pair, r what it leaves) the weight planes hold (h, l) | split(r) | (h, l) | (l, 0) and the window planes
+ * (h, l) | (h, l) | split(r) | (l, 0).  win_chunks = 2 (two sets per 32-column chunk, 2 ncol <= 32) or 4 (one set per chunk); the
+ * convolution half of that GEMM is win_chunks K-steps instead of taps * C / 32.
+ *  t2s_wg_start_window: t2s_wg_start, and next to the X planes the window planes W_hi/W_lo [B][win_chunks][Lp][32] (zero-initialised
+ *    by the caller; rows outside [0, L) and unused columns stay zero); C >= 32 * win_chunks.
+ *  t2s_wg_startfold_weights: K-chunks 0 .. win_chunks-1 of A_hi/A_lo [win_chunks + ceil(n_cond/32)][Mpad][32] = the composed weights
+ *    (g_in / |v_in|) v_in[:, :, tap] . [w_start | b_start] in the same column sets, rows in T2S_PERM_GATE order, accumulated in f32.
+ *    v_in [2C][C][taps] and g_in [2C] (NULL: plain weight) are in_layers[0]'s; w_start [C][n_half] is t2s_weightnorm_small's output.
+ *    The conditioning weights go behind them with t2s_pack_conv_weight(_table) at koff = 32 * win_chunks.
+ *  t2s_wg_in_win_gate_fold: t2s_wg_in_cond_gate_fold for that layer, the window planes in place of X (no taps, no dilation). */
+int t2s_wg_start_window(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                        int L, int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                        void* stream);
+int t2s_wg_startfold_weights(const float* v_in, const float* g_in, const float* w_start, const float* b_start, int C, int n_half,
+                             int taps, int Mpad, int win_chunks, void* A_hi, void* A_lo, void* stream);
+int t2s_wg_in_win_gate_fold(const void* A_hi, const void* A_lo, const float* bias, const void* W_hi, const void* W_lo,
+                            const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
+                            float* fold_acc, int fold_init, int B, int C, int n_cond, int win_chunks, int L, int Lp, int halo,
+                            int Mpad, void* stream);
 /* residual half only: x += W_res acts + b  (rows [0, C) of the packed res_skip weights; 128-row tiles) */
 /* Composed conditioning for the inverse flow (weights packed once).  The ConvTranspose upsampler is linear and only ksize / stride
  * hops overlap, so cond_layers[i](upsample(mel)) at plane row t = P f + phi (P = stride / n_group) is (W_cond,i U_phi) applied to the

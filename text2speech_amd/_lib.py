@@ -40,6 +40,9 @@ SIGNATURES = {
                         c_int, c_int, c_vp],
     "t2s_wg_endfold_weights": [c_vp, c_int, c_int, c_vp],
     "t2s_wg_in_cond_gate_fold": [c_vp] * 11 + [c_int] * 10 + [c_vp],
+    "t2s_wg_start_window": [c_vp, c_vp, c_vp] + [c_int] * 8 + [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
+    "t2s_wg_startfold_weights": [c_vp] * 4 + [c_int] * 5 + [c_vp, c_vp, c_vp],
+    "t2s_wg_in_win_gate_fold": [c_vp] * 11 + [c_int] * 9 + [c_vp],
     "t2s_wg_gate_fold_slots": [c_int, c_int, c_int],
     "t2s_wg_gate_tile_rows": [c_int, c_int, c_int],
     "t2s_wg_upsample_basis": [c_vp, c_vp] + [c_int] * 6 + [c_vp, c_vp, c_vp],

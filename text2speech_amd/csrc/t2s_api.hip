@@ -146,6 +146,33 @@ int t2s_wg_start(const float* z, const float* w, const float* bias, int B, int n
 
 static int check_planes(const void* a, const void* b) { return a && b && aligned16(a) && aligned16(b); }
 
+// window chunks of the folded WN.start: 2 (two column sets per chunk) or 4 (one), each set taps * (n_half + 1) columns wide
+static bool win_chunks_ok(int taps, int n_half, int win_chunks) {
+    if (taps <= 0 || !(taps & 1) || n_half <= 0 || (win_chunks != 2 && win_chunks != 4)) return false;
+    return (4 / win_chunks) * taps * (n_half + 1) <= 32;
+}
+
+int t2s_wg_start_window(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                        int L, int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                        void* stream) {
+    if (!z || !w || !bias || !check_planes(X_hi, X_lo) || !check_planes(W_hi, W_lo)) return T2S_EINVAL;
+    if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
+    if (!win_chunks_ok(taps, n_half, win_chunks) || cdiv(C, 32) < win_chunks || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
+                                   (hipStream_t)stream, taps, win_chunks, (u16*)W_hi, (u16*)W_lo));
+    return T2S_OK;
+}
+
+int t2s_wg_startfold_weights(const float* v_in, const float* g_in, const float* w_start, const float* b_start, int C, int n_half,
+                             int taps, int Mpad, int win_chunks, void* A_hi, void* A_lo, void* stream) {
+    if (!v_in || !w_start || !b_start || !check_planes(A_hi, A_lo)) return T2S_EINVAL;
+    if (C <= 0 || !win_chunks_ok(taps, n_half, win_chunks)) return T2S_EINVAL;
+    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || (size_t)C * (n_half + 1) * sizeof(float) > 60 * 1024) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_startfold_weights(v_in, g_in, w_start, b_start, C, n_half, taps, Mpad, win_chunks, (u16*)A_hi, (u16*)A_lo,
+                                               (hipStream_t)stream));
+    return T2S_OK;
+}
+
 int t2s_wg_in_cond_gate(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
                         const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, int B, int C, int n_cond,
                         int taps, int dilation, int L, int Lp, int halo, int Mpad, void* stream) {
@@ -238,6 +265,35 @@ int t2s_wg_in_cond_gate_fold(const void* A_hi, const void* A_lo, const float* bi
     a.nk_x = taps * a.xc; a.nk = a.nk_x + a.sc;
     a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
     const int rows = gate_tile_rows(B, C, L);          // fold_acc holds t2s_wg_gate_fold_slots(B, C, L) slots
+    a.n_mtiles = cdiv(C, rows / 2); a.n_ttiles = cdiv(L, 256);
+    a.C = C;
+    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE, (hipStream_t)stream, rows));
+    return T2S_OK;
+}
+
+int t2s_wg_in_win_gate_fold(const void* A_hi, const void* A_lo, const float* bias, const void* W_hi, const void* W_lo,
+                            const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
+                            float* fold_acc, int fold_init, int B, int C, int n_cond, int win_chunks, int L, int Lp, int halo,
+                            int Mpad, void* stream) {
+    if (!check_planes(A_hi, A_lo) || !check_planes(W_hi, W_lo) || !check_planes(S_hi, S_lo) || !check_planes(acts_hi, acts_lo) ||
+        !bias)
+        return T2S_EINVAL;
+    if (!fold_A || !fold_acc || !aligned16(fold_A) || C % 16) return T2S_EINVAL;
+    if (B <= 0 || L <= 0 || C <= 0 || n_cond <= 0 || halo < 0 || Lp != t2s_plane_rows(L, halo)) return T2S_EINVAL;
+    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || !aligned16(bias) || (win_chunks != 2 && win_chunks != 4)) return T2S_EINVAL;
+    ConvGemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
+    a.X_hi = (const u16*)W_hi; a.X_lo = (const u16*)W_lo;
+    a.S_hi = (const u16*)S_hi; a.S_lo = (const u16*)S_lo;
+    a.bias = bias; a.O_hi = (u16*)acts_hi; a.O_lo = (u16*)acts_lo;
+    a.fold_A = (const u16*)fold_A; a.fold_acc = fold_acc; a.fold_init = fold_init;
+    // the window planes' columns already hold the taps: a 1-tap "convolution" over win_chunks chunks, then the conditioning
+    a.xc = win_chunks; a.sc = cdiv(n_cond, 32); a.oc = cdiv(C, 32);
+    a.taps = 1; a.dil = 1;
+    a.nk_x = win_chunks; a.nk = win_chunks + a.sc;
+    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
+    const int rows = gate_tile_rows(B, C, L);
     a.n_mtiles = cdiv(C, rows / 2); a.n_ttiles = cdiv(L, 256);
     a.C = C;
     T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE, (hipStream_t)stream, rows));

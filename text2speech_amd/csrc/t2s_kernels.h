@@ -132,8 +132,12 @@ hipError_t t2s_launch_small_logdet_batch(const SmallMatJob* jobs, int n_jobs, fl
 hipError_t t2s_launch_small_logdet_batch_host(const SmallMatJob* host_jobs, int n_jobs, float scale, hipStream_t stream);
 hipError_t t2s_launch_small_logdet_inv(const float* W, int n, float scale, float* logdet_out, float* inv_out,
                                        hipStream_t stream);
+// taps / W_hi / W_lo: optional window planes of the folded first gate GEMM (waveglow_ops.hip, startfold_weights_kernel)
 hipError_t t2s_launch_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off,
-                            int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream);
+                            int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream,
+                            int taps = 0, int nwc = 0, u16* W_hi = nullptr, u16* W_lo = nullptr);
+hipError_t t2s_launch_startfold_weights(const float* v, const float* g, const float* w_start, const float* b_start, int C,
+                                        int n_half, int taps, int Mpad, int nwc, u16* A_hi, u16* A_lo, hipStream_t stream);
 struct EndFoldJob {        // one WN layer: fold_w[c][j] = sum_o W_end[j][o] * scale[o] * v_skip[o][c]
     const float* w_end;    // [nj][C]
     const float* v_skip;   // [C][C] skip rows of res_skip_layers[i].weight_v (or weight)

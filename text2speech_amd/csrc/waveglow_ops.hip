@@ -759,10 +759,32 @@ hipError_t t2s_launch_small_logdet_inv(const float* W, int n, float scale, float
 // (reference glow.py:122-124,156).  One thread = 8 channels of START_TT time steps (64 apart): its 8 x n_half weights and 8 biases
 // are fetched once and stay in registers, each time step is n_half loads and one 16-B store per plane (one time step per thread
 // spent 40 loads on 2 stores and ran at 1.5 TB/s of plane writes).
+// With W_hi / W_lo the workgroups of the first nwc channel chunks also write the window planes [B][nwc][Lp][32] the folded first
+// gate GEMM reads in place of x (startfold_weights_kernel below has the four column sets): logical column tap * (nh + 1) + j of
+// row t is z[c_off + j][t + tap - taps / 2] for j < nh and 1 for j = nh, both 0 where t + tap - taps / 2 is outside [0, L).
 #define START_TT 8
+// Column set s of the folded WN.start (startfold_weights_kernel): with x = h + l + r (h, l the split-bf16 pair, r what it leaves),
+//   set:            0        1          2          3
+//   weight  (A):  (h, l)   split(r)   (h, l)     (l, 0)
+//   window  (B):  (h, l)   (h, l)     split(r)   (l, 0)
+// the three MFMA products per set (hi.hi + hi.lo + lo.hi) add up to W.a with both factors carried to f32 accuracy: set 0 is the
+// usual split product, 1 and 2 add the residual of either factor, 3 the lo.lo term.
+static __device__ __forceinline__ void start_fold_term(float x, int set, bool is_weight, u16& hi, u16& lo) {
+    u16 h, l;
+    split_bf16(x, h, l);
+    hi = h;
+    lo = l;
+    if (set == (is_weight ? 1 : 2)) {
+        split_bf16(x - join_bf16(h, l), hi, lo);
+    } else if (set == 3) {
+        hi = l;
+        lo = 0;
+    }
+}
 __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                     const float* __restrict__ bias, int G, int c_off, int nh, int C,
-                                                    int L, int Lp, int halo, u16* X_hi, u16* X_lo) {
+                                                    int L, int Lp, int halo, u16* X_hi, u16* X_lo, int taps, int nwc,
+                                                    u16* W_hi, u16* W_lo) {
     const int tid = threadIdx.x;
     const int q = tid & 3;
     const int tbase = blockIdx.x * (64 * START_TT) + (tid >> 2);
@@ -804,12 +826,38 @@ __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z,
         *(uint4*)(X_hi + (row0 + t) * 32 + q * 8) = ph;
         *(uint4*)(X_lo + (row0 + t) * 32 + q * 8) = pl;
     }
+    if (W_hi == nullptr || chunk >= nwc) return;
+    const int nw = nh + 1, ncol = taps * nw, spc = 4 / nwc;          // spc column sets of ncol columns per window chunk
+    const size_t wrow0 = ((size_t)b * nwc + chunk) * Lp + halo;
+    for (int it = 0; it < START_TT; ++it) {
+        const int t = tbase + it * 64;
+        if (t >= L) break;
+        u16 hi[8], lo[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int col = q * 8 + e;
+            const int sidx = col / ncol, c = col - sidx * ncol;
+            const int tap = c / nw, j = c - tap * nw;
+            const int tt = t + tap - (taps >> 1);
+            float v = 0.f;
+            if (sidx < spc && tt >= 0 && tt < L) v = j < nh ? z[((size_t)b * G + c_off + j) * L + tt] : 1.0f;
+            start_fold_term(v, chunk * spc + sidx, false, hi[e], lo[e]);
+        }
+        uint4 ph, pl;
+        ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
+        ph.z = hi[4] | ((uint32_t)hi[5] << 16); ph.w = hi[6] | ((uint32_t)hi[7] << 16);
+        pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
+        pl.z = lo[4] | ((uint32_t)lo[5] << 16); pl.w = lo[6] | ((uint32_t)lo[7] << 16);
+        *(uint4*)(W_hi + (wrow0 + t) * 32 + q * 8) = ph;
+        *(uint4*)(W_lo + (wrow0 + t) * 32 + q * 8) = pl;
+    }
 }
 hipError_t t2s_launch_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off,
-                            int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream) {
+                            int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream,
+                            int taps, int nwc, u16* W_hi, u16* W_lo) {
     dim3 grid((L + 64 * START_TT - 1) / (64 * START_TT), (C + 31) / 32, B);
     hipLaunchKernelGGL(start_kernel, grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L, Lp, halo,
-                       X_hi, X_lo);
+                       X_hi, X_lo, taps, nwc, W_hi, W_lo);
     return hipGetLastError();
 }
 
@@ -933,6 +981,66 @@ __global__ __launch_bounds__(256) void endfold_weights_kernel(const EndFoldJob* 
 hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C, hipStream_t stream) {
     hipLaunchKernelGGL(endfold_weights_kernel, dim3(n_jobs, (C + 255) / 256), dim3(256), (size_t)8 * C * sizeof(float),
                        stream, jobs, C);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// WN.start folded into the first gate GEMM of a flow (no-grad forward / infer).  x0 = W_start a + b_start has C channels but
+// only n_half + 1 independent ones, so in_layers[0](x0) (reference glow.py:156,159) is a convolution of the n_half audio
+// channels and a constant-one channel (1 inside the utterance, 0 in the zero padding - which makes the edges exact):
+//   in0(x0)[m][t] = sum_tap sum_j (W_in0[tap] W_start)[m][j] a[j][t + tap - taps/2] + sum_tap (W_in0[tap] b_start)[m] 1[t + tap - taps/2]
+// This kernel writes that composed weight, 2C x ncol = taps * (n_half + 1) <= 32 columns accumulated in f32, as the first nwc
+// K-chunks of a gate A operand (PERM_GATE rows, [K-chunk][Mpad][32]); start_kernel writes the matching window planes.  Split-bf16
+// rounds each factor to 16 bits, and here the 15 products are much larger than their sum, so the chunks hold FOUR column sets
+// (start_fold_term above: nwc = 2 chunks of two sets when 2 ncol <= 32, else 4 chunks of one) that carry both factors to f32
+// accuracy.  The K of the convolution half of that launch drops from taps * C to nwc 32-wide steps.
+// A workgroup = 8 output rows x 32 columns; a row's 32 lanes first reduce its weight-norm scale g / |v|.
+__global__ __launch_bounds__(256) void startfold_weights_kernel(const float* __restrict__ v, const float* __restrict__ g,
+                                                                const float* __restrict__ w_start,
+                                                                const float* __restrict__ b_start, int C, int nh, int Kt,
+                                                                int Mpad, int nwc, u16* A_hi, u16* A_lo) {
+    extern __shared__ float s_wb[];              // [C][nh + 1]: W_start | b_start
+    const int tid = threadIdx.x, r = tid >> 5, col = tid & 31;
+    const int nw = nh + 1, n = C * Kt, O = 2 * C;
+    for (int i = tid; i < C * nw; i += 256) {
+        const int c = i / nw, j = i - c * nw;
+        s_wb[i] = j < nh ? w_start[c * nh + j] : b_start[c];
+    }
+    const int o = blockIdx.x * 8 + r;
+    const bool row_ok = o < O;
+    const float* vrow = v + (size_t)(row_ok ? o : 0) * n;
+    float scale = 1.0f;
+    if (g) {
+        float ss = 0.f;
+        for (int i = col; i < n; i += 32) ss += vrow[i] * vrow[i];
+        ss = sum16(ss);
+        ss += __shfl_xor(ss, 16, 64);
+        scale = g[row_ok ? o : 0] / sqrtf(ss);
+    }
+    __syncthreads();
+    if (!row_ok) return;
+    const int ncol = Kt * nw, spc = 4 / nwc;
+    const int sidx = col / ncol, lc = col - sidx * ncol;
+    float acc = 0.f;
+    if (sidx < spc) {
+        const int tap = lc / nw, j = lc - tap * nw;
+#pragma unroll 8
+        for (int c = 0; c < C; ++c) acc += vrow[c * Kt + tap] * s_wb[c * nw + j];
+    }
+    const int gate = o >= C;
+    const int ch = gate ? o - C : o;
+    const int p = (ch >> 7) * 256 + ((ch >> 6) & 1) * 128 + (((ch >> 4) & 3) * 2 + gate) * 16 + (ch & 15);
+    for (int wc = 0; wc < nwc; ++wc) {
+        u16 h, l;
+        start_fold_term(acc * scale, wc * spc + sidx, true, h, l);
+        A_hi[((size_t)wc * Mpad + p) * 32 + col] = h;
+        A_lo[((size_t)wc * Mpad + p) * 32 + col] = l;
+    }
+}
+hipError_t t2s_launch_startfold_weights(const float* v, const float* g, const float* w_start, const float* b_start, int C,
+                                        int n_half, int taps, int Mpad, int nwc, u16* A_hi, u16* A_lo, hipStream_t stream) {
+    hipLaunchKernelGGL(startfold_weights_kernel, dim3((2 * C + 7) / 8), dim3(256), (size_t)C * (n_half + 1) * sizeof(float),
+                       stream, v, g, w_start, b_start, C, n_half, taps, Mpad, nwc, A_hi, A_lo);
     return hipGetLastError();
 }
 

@@ -208,17 +208,33 @@ class _Engine:
         halo = -(-((2 ** (nl - 1)) * (ks // 2)) // 32) * 32
         g = dict(C=C, nl=nl, ks=ks, n_cond=n_cond, Cpad=-(-C // 32) * 32, Spad=-(-n_cond // 32) * 32,
                  halo=halo, Mpad1=-(-C // 128) * 256)
+        # folded WN.start: logical window columns of the widest flow, and the window chunks that hold their four column sets
+        g["ncol0"] = ks * (m.n_group // 2 + 1)
+        g["nwc"] = 2 if 2 * g["ncol0"] <= 32 else 4
         g["nk1"] = ks * g["Cpad"] // 32 + g["Spad"] // 32
         g["nk2"] = g["Cpad"] // 32
         return g
 
+    def start_fold_on(self):
+        """True when the no-grad forward / infer takes layer 0 of every flow through WN.start folded into its gate GEMM (DESIGN.md
+        section 5): the taps of the n_half audio channels and of the ones-channel must fit 32 columns, and C must have as many
+        32-channel chunks as the window has (geom()["nwc"]: 2 or 4).  T2S_START_FOLD=0
+        selects the unfolded layer 0 (A/B runs, the comparison test); the opt-in composed-conditioning path keeps it too."""
+        g = self.geom()
+        if not self.use_fold or os.environ.get("T2S_START_FOLD", "1") == "0" or g["C"] % 16 or self.compose_geom() is not None:
+            return False
+        return g["ncol0"] <= 32 and g["Cpad"] // 32 >= g["nwc"]
+
     # ------------------------------------------------------------------ weights
-    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False):
+    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False, start_fold=False):
         """res_pair8: pack the residual rows of every res/skip convolution in the 8-consecutive-channels order the folded no-grad
-        path's residual GEMM wants (t2s_wg_res_only(pair8 = 1)); the training path keeps the identity order."""
+        path's residual GEMM wants (t2s_wg_res_only(pair8 = 1)); the training path keeps the identity order.
+        start_fold: layer 0 of every flow gets the operand of the folded WN.start (A0h / A0l: the composed block, then the
+        conditioning weights) and its in_layers[0] planes are NOT packed (A1h / A1l of layer 0 are stale then)."""
         m = self.m
         res_pair8 = bool(res_pair8) and self.geom()["C"] % 32 == 0
-        key = tuple(p._version for p in m.parameters()) + (str(device), res_pair8)
+        start_fold = bool(start_fold)
+        key = tuple(p._version for p in m.parameters()) + (str(device), res_pair8, start_fold)
         if not force and self.packed is not None and self.packed_key == key:
             return self.packed
         g = self.geom()
@@ -245,14 +261,18 @@ class _Engine:
                         fold_A=torch.zeros(-(-C // 128) * 8192, dtype=torch.bfloat16, device=device)))
                 flows.append(dict(layers=layers, n_half=n_half, bes=torch.zeros(nl, 8, dtype=torch.float32, device=device),
                                   w_start=torch.empty(C, n_half, dtype=torch.float32, device=device),
+                                  A0h=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
+                                  A0l=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
                                   w_inv=None))
             self.packed = dict(flows=flows, device=device)
         # One table-driven launch packs all 3 * n_layers * n_flows convolutions (weight-norm + split + permute).
         srcs = []       # f32 source tensors, in job order; their data_ptrs key the cached job table
-        specs = []
+        specs = []      # one list of jobs per flow
+        in0 = []        # (v, g) of every flow's in_layers[0]: what the folded WN.start is composed from
         for k in range(m.n_flows):
             wn = m.WN[k]
             fl = self.packed["flows"][k]
+            specs.append([])
             for i in range(nl):
                 ly = fl["layers"][i]
                 v, gg = _vg(wn.in_layers[i])
@@ -262,30 +282,38 @@ class _Engine:
                      _f32c(vc), None if gc is None else _f32c(gc),
                      _f32c(vr), None if gr is None else _f32c(gr), _f32c(wn.res_skip_layers[i].bias)]
                 srcs += t
+                if i == 0:
+                    in0.append((t[0], t[1]))
                 # (v, g, bias, bias2, A_hi, A_lo, bias_out, O, Cin, Kt, perm, C_gate, Mpad, koff, Cin_pad)
-                specs.append((t[0], t[1], t[2], t[3], ly["A1h"], ly["A1l"], ly["b1"], 2 * C, C, ks, 1, C, g["Mpad1"], 0, g["Cpad"],
-                              ly["s_in"]))
-                specs.append((t[4], t[5], None, None, ly["A1h"], ly["A1l"], None, 2 * C, g["n_cond"], 1, 1, C, g["Mpad1"],
-                              ks * g["Cpad"], g["Spad"], ly["s_cond"]))
+                if i == 0 and start_fold:
+                    # no in_layers[0] planes (t2s_wg_startfold_weights writes the first nwc K-chunks below); the conditioning weights
+                    # follow them and their job carries the layer's bias
+                    specs[k].append((t[4], t[5], t[2], t[3], fl["A0h"], fl["A0l"], ly["b1"], 2 * C, g["n_cond"], 1, 1, C,
+                                     g["Mpad1"], 32 * g["nwc"], g["Spad"], ly["s_cond"]))
+                else:
+                    specs[k].append((t[0], t[1], t[2], t[3], ly["A1h"], ly["A1l"], ly["b1"], 2 * C, C, ks, 1, C, g["Mpad1"], 0,
+                                     g["Cpad"], ly["s_in"]))
+                    specs[k].append((t[4], t[5], None, None, ly["A1h"], ly["A1l"], None, 2 * C, g["n_cond"], 1, 1, C, g["Mpad1"],
+                                     ks * g["Cpad"], g["Spad"], ly["s_cond"]))
                 # residual rows (the first C of 2C; the last layer has none) optionally in the PERM_PAIR8 order
                 p8 = res_pair8 and i < nl - 1
-                specs.append((t[6], t[7], t[8], None, ly["A2h"], ly["A2l"], ly["b2"], t[6].size(0), C, 1, 2 if p8 else 0,
-                              C if p8 else 0, ly["Mpad2"], 0, g["Cpad"], ly["s_rs"]))
-        ptr_key = tuple(0 if t is None else t.data_ptr() for t in srcs) + (res_pair8,)
-        jpf = 3 * nl                                   # jobs per flow: (in, cond, res_skip) x layers
+                specs[k].append((t[6], t[7], t[8], None, ly["A2h"], ly["A2l"], ly["b2"], t[6].size(0), C, 1, 2 if p8 else 0,
+                                 C if p8 else 0, ly["Mpad2"], 0, g["Cpad"], ly["s_rs"]))
+        ptr_key = tuple(0 if t is None else t.data_ptr() for t in srcs) + (res_pair8, start_fold)
         if self.packed.get("job_key") != ptr_key:
-            rows, flow_rows, row_start = [], [], 0
+            rows, flow_rows, flow_jobs = [], [], []
             dp = lambda t: 0 if t is None else t.data_ptr()
-            for n, (v, gg, b1, b2, Ah, Al, bo, O, Cin, Kt, perm, Cg, Mpad, koff, Cin_pad, so) in enumerate(specs):
-                if n % jpf == 0 and n:                  # row_start restarts per flow: every flow's jobs are a table of their own
-                    flow_rows.append(row_start)
-                    row_start = 0
-                rows.append([dp(v), dp(gg), dp(b1), dp(b2), dp(Ah), dp(Al), dp(bo), row_start,
-                             O, Cin, Kt, perm, Cg, Mpad, koff, Cin_pad, 0, 0, dp(so)])
-                row_start += -(-O // 16)          # the table kernel packs 16 rows per workgroup
-            flow_rows.append(row_start)
+            for fspecs in specs:                        # every flow's jobs are a table of their own: row_start restarts per flow
+                row_start = 0
+                flow_jobs.append((len(rows), len(fspecs)))
+                for (v, gg, b1, b2, Ah, Al, bo, O, Cin, Kt, perm, Cg, Mpad, koff, Cin_pad, so) in fspecs:
+                    rows.append([dp(v), dp(gg), dp(b1), dp(b2), dp(Ah), dp(Al), dp(bo), row_start,
+                                 O, Cin, Kt, perm, Cg, Mpad, koff, Cin_pad, 0, 0, dp(so)])
+                    row_start += -(-O // 16)          # the table kernel packs 16 rows per workgroup
+                flow_rows.append(row_start)
             self.packed["jobs"] = torch.tensor(rows, dtype=torch.int64).to(device)
             self.packed["flow_rows"] = flow_rows
+            self.packed["flow_jobs"] = flow_jobs        # (first job, job count) per flow
             self.packed["job_key"] = ptr_key
         # WN.end folded into the skip path: (W_end . W_skip_i)^T per layer, from the scales the pack just wrote
         fsrc = []
@@ -307,7 +335,8 @@ class _Engine:
             self.packed["fold_jobs"] = torch.tensor(rows, dtype=torch.int64).to(device)
             self.packed["fold_key"] = fkey
         # One table-driven launch per flow packs its 3 * n_layers convolutions (weight-norm + split + permute), one more
-        # builds its folded WN.end matrices, a third its `start` weights.  With `flow_events` (the no-grad forward) the per-flow
+        # builds its folded WN.end matrices, a third its `start` weights - and with start_fold a fourth composes those with
+        # in_layers[0] into the first nwc K-chunks of the layer-0 operand.  With `flow_events` (the no-grad forward) the per-flow
         # work is enqueued on the caller's current stream - a side stream there - and an event per flow lets the main stream
         # start flow k as soon as ITS weights are packed: the pack is HBM-bound (2.1 GB per forward), the GEMMs are not.
         jobs_ptr, fold_ptr = self.packed["jobs"].data_ptr(), self.packed["fold_jobs"].data_ptr()
@@ -315,12 +344,18 @@ class _Engine:
         for k in range(m.n_flows):
             wn = m.WN[k]
             fl = self.packed["flows"][k]
-            _lib.call("t2s_pack_conv_weight_table", _lib.c_vp(jobs_ptr + k * jpf * 19 * 8), jpf, self.packed["flow_rows"][k], st)
+            j0, nj = self.packed["flow_jobs"][k]
+            _lib.call("t2s_pack_conv_weight_table", _lib.c_vp(jobs_ptr + j0 * 19 * 8), nj, self.packed["flow_rows"][k], st)
             _lib.call("t2s_wg_endfold_weights", _lib.c_vp(fold_ptr + k * nl * 8 * 8), nl, C, st)
             v, gg = _vg(wn.start)
             v, gg = _f32c(v), (None if gg is None else _f32c(gg))
             starts += [v, gg]
             _lib.call("t2s_weightnorm_small", _lib.ptr(v), _lib.ptr(gg), C, fl["n_half"], _lib.ptr(fl["w_start"]), st)
+            if start_fold:
+                b_start = _f32c(wn.start.bias)
+                starts.append(b_start)
+                _lib.call("t2s_wg_startfold_weights", _lib.ptr(in0[k][0]), _lib.ptr(in0[k][1]), _lib.ptr(fl["w_start"]),
+                          _lib.ptr(b_start), C, fl["n_half"], ks, g["Mpad1"], g["nwc"], _lib.ptr(fl["A0h"]), _lib.ptr(fl["A0l"]), st)
             fl["w_inv"] = None
             if flow_events is not None:
                 ev = torch.cuda.Event()
@@ -329,6 +364,7 @@ class _Engine:
         keep = srcs + [t for tup in fsrc for t in tup[:3]] + starts
         self.packed_key = key
         self.packed["res_pair8"] = res_pair8
+        self.packed["start_fold"] = start_fold
         self._keep = keep
         return self.packed
 
@@ -394,6 +430,7 @@ class _Engine:
                      Xh=torch.zeros(B, xc, Lp, 32, **bf), Xl=torch.zeros(B, xc, Lp, 32, **bf),
                      Ah=torch.zeros(B, xc, Lp, 32, **bf), Al=torch.zeros(B, xc, Lp, 32, **bf),
                      Sh=torch.zeros(B, sc, Lp, 32, **bf), Sl=torch.zeros(B, sc, Lp, 32, **bf),
+                     Wh=torch.zeros(B, g["nwc"], Lp, 32, **bf), Wl=torch.zeros(B, g["nwc"], Lp, 32, **bf),      # folded WN.start: window
                      skip=torch.zeros(B, xc, Lp, 32, dtype=torch.float32, device=device),
                      fold_acc=torch.zeros(_lib.load().t2s_wg_gate_fold_slots(B, g["C"], L), B, 8, L, dtype=torch.float32,
                                           device=device))
@@ -427,16 +464,32 @@ class _Engine:
         wn = m.WN[k]
         b_start = _f32c(wn.start.bias)
         self._keep_wn = [b_start]
-        _lib.call("t2s_wg_start", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
-                  C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), st)
+        # layer 0 through the folded WN.start: the X planes are still written (the residual stream needs x0), the gate GEMM reads
+        # the window planes instead
+        sf = bool(self.packed.get("start_fold")) and self.use_fold and ph is None
+        if sf:
+            _lib.call("t2s_wg_start_window", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
+                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), ks, g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), st)
+        else:
+            _lib.call("t2s_wg_start", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
+                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), st)
         for i in range(nl):
             ly = fl["layers"][i]
-            timed = self.gemm_events is not None and self._gemm_launch_no % self.gemm_event_stride == 0
-            self._gemm_launch_no += 1
+            # bench.py divides the sampled launch time into the FLOPs of a full-K layer: the short folded layer 0 is neither
+            # counted nor timed
+            full_k = not (sf and i == 0)
+            timed = full_k and self.gemm_events is not None and self._gemm_launch_no % self.gemm_event_stride == 0
+            if full_k:
+                self._gemm_launch_no += 1
             if timed:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            if ph is not None:
+            if not full_k:
+                _lib.call("t2s_wg_in_win_gate_fold", _lib.ptr(fl["A0h"]), _lib.ptr(fl["A0l"]), _lib.ptr(ly["b1"]),
+                          _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
+                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
+                          1, B, C, g["n_cond"], g["nwc"], L, w["Lp"], g["halo"], g["Mpad1"], st)
+            elif ph is not None:
                 Mh, Ml, Fp, P, K2 = ph
                 _lib.call("t2s_wg_in_melwin_gate_fold", _lib.ptr(ly["A1h"]), _lib.ptr(ly["A1l"]), _lib.ptr(ly["Ach"]),
                           _lib.ptr(ly["Acl"]), _lib.ptr(ly["b1c"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(Mh), _lib.ptr(Ml),
@@ -477,7 +530,7 @@ class _Engine:
         g = self.geom()
         if n_in != n_half or spect.size(1) != g["n_cond"] or spect.size(2) != L:
             raise ValueError("WN[%d] takes audio [B, %d, L] and spect [B, %d, L]" % (k, n_half, g["n_cond"]))
-        self.pack_weights(dev, force=False, res_pair8=self.use_fold)
+        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on())
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         spect32 = _f32c(spect)
@@ -565,7 +618,7 @@ class _Engine:
         pack_events = []
         pack_s.wait_stream(main)
         with torch.cuda.stream(pack_s):
-            self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=self.use_fold)
+            self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=self.use_fold, start_fold=self.start_fold_on())
         main.wait_event(ev_inputs)
         st = _lib.current_stream()
         for k in range(m.n_flows):
@@ -592,7 +645,7 @@ class _Engine:
         # reference glow.py:254-255: drop the last (kernel - stride) upsampled samples
         T = (frames - 1) * up.stride[0] + up.kernel_size[0] - (up.kernel_size[0] - up.stride[0])
         L = T // G
-        self.pack_weights(dev, force=False, res_pair8=self.use_fold)
+        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on())
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         # Weights are packed once here, so the conditioning path can be composed with the upsampler (K = 640 -> 320 in the gate
