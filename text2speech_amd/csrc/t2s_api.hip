@@ -1,28 +1,20 @@
 // extern "C" boundary: argument validation + launch.  No torch types, no allocation, no sync.
 #include "../../include/t2s_hip.h"
 #include "t2s_kernels.h"
+#include "t2s_api_common.h"
+#include "conv_gemm_args.h"
 
 #include <stdlib.h>
 #include <string.h>
 
 static thread_local char g_hip_err[256] = "";
 
-extern "C" int t2s_internal_fail_hip(int e);
-static int fail_hip(hipError_t e) { return t2s_internal_fail_hip((int)e); }
 extern "C" int t2s_internal_fail_hip(int ei) {
     hipError_t e = (hipError_t)ei;
     strncpy(g_hip_err, hipGetErrorString(e), sizeof(g_hip_err) - 1);
     g_hip_err[sizeof(g_hip_err) - 1] = 0;
     return T2S_EHIP;
 }
-#define T2S_CHECK_HIP(expr)                   \
-    do {                                      \
-        hipError_t _e = (expr);               \
-        if (_e != hipSuccess) return fail_hip(_e); \
-    } while (0)
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 extern "C" {
 
@@ -91,7 +83,7 @@ int t2s_wg_upsample_squeeze(const float* mel, const float* W, const float* bias,
                             void* stream) {
     if (!mel || !W || !bias || !S_hi || !S_lo) return T2S_EINVAL;
     if (B <= 0 || n_mel <= 0 || frames <= 0 || L <= 0 || n_group <= 0 || stride <= 0 || ksize % stride) return T2S_EINVAL;
-    if (!aligned16(W) || !aligned16(S_hi) || !aligned16(S_lo)) return T2S_EINVAL;
+    if (!al16(W) || !al16(S_hi) || !al16(S_lo)) return T2S_EINVAL;
     if (Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
     // every squeezed sample must exist in the transposed-conv output (reference glow.py:216 assert)
     if ((long)L * n_group > (long)(frames - 1) * stride + ksize) return T2S_EINVAL;
@@ -138,13 +130,11 @@ int t2s_wg_start(const float* z, const float* w, const float* bias, int B, int n
                  int L, int Lp, int halo, void* X_hi, void* X_lo, void* stream) {
     if (!z || !w || !bias || !X_hi || !X_lo) return T2S_EINVAL;
     if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
-    if (!aligned16(X_hi) || !aligned16(X_lo) || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
+    if (!al16(X_hi) || !al16(X_lo) || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
                                    (hipStream_t)stream));
     return T2S_OK;
 }
-
-static int check_planes(const void* a, const void* b) { return a && b && aligned16(a) && aligned16(b); }
 
 // window chunks of the folded WN.start: 2 (two column sets per chunk) or 4 (one), each set taps * (n_half + 1) columns wide
 static bool win_chunks_ok(int taps, int n_half, int win_chunks) {
@@ -155,7 +145,7 @@ static bool win_chunks_ok(int taps, int n_half, int win_chunks) {
 int t2s_wg_start_window(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
                         int L, int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
                         void* stream) {
-    if (!z || !w || !bias || !check_planes(X_hi, X_lo) || !check_planes(W_hi, W_lo)) return T2S_EINVAL;
+    if (!z || !w || !bias || !planes_ok(X_hi, X_lo) || !planes_ok(W_hi, W_lo)) return T2S_EINVAL;
     if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
     if (!win_chunks_ok(taps, n_half, win_chunks) || cdiv(C, 32) < win_chunks || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
@@ -165,7 +155,7 @@ int t2s_wg_start_window(const float* z, const float* w, const float* bias, int B
 
 int t2s_wg_startfold_weights(const float* v_in, const float* g_in, const float* w_start, const float* b_start, int C, int n_half,
                              int taps, int Mpad, int win_chunks, void* A_hi, void* A_lo, void* stream) {
-    if (!v_in || !w_start || !b_start || !check_planes(A_hi, A_lo)) return T2S_EINVAL;
+    if (!v_in || !w_start || !b_start || !planes_ok(A_hi, A_lo)) return T2S_EINVAL;
     if (C <= 0 || !win_chunks_ok(taps, n_half, win_chunks)) return T2S_EINVAL;
     if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || (size_t)C * (n_half + 1) * sizeof(float) > 60 * 1024) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_startfold_weights(v_in, g_in, w_start, b_start, C, n_half, taps, Mpad, win_chunks, (u16*)A_hi, (u16*)A_lo,
@@ -176,46 +166,29 @@ int t2s_wg_startfold_weights(const float* v_in, const float* g_in, const float* 
 int t2s_wg_in_cond_gate(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
                         const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, int B, int C, int n_cond,
                         int taps, int dilation, int L, int Lp, int halo, int Mpad, void* stream) {
-    if (!check_planes(A_hi, A_lo) || !check_planes(X_hi, X_lo) || !check_planes(acts_hi, acts_lo) || !bias) return T2S_EINVAL;
-    if (n_cond > 0 && !check_planes(S_hi, S_lo)) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || taps <= 0 || !(taps & 1) || dilation <= 0) return T2S_EINVAL;
-    if ((taps / 2) * dilation > halo || Lp != t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || !aligned16(bias)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.S_hi = (const u16*)S_hi; a.S_lo = (const u16*)S_lo;
-    a.bias = bias; a.O_hi = (u16*)acts_hi; a.O_lo = (u16*)acts_lo;
-    a.xc = cdiv(C, 32); a.sc = cdiv(n_cond, 32); a.oc = cdiv(C, 32);
-    a.taps = taps; a.dil = dilation;
-    a.nk_x = taps * a.xc; a.nk = a.nk_x + a.sc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_mtiles = cdiv(C, 128); a.n_ttiles = cdiv(L, 256);
-    a.C = C;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE, (hipStream_t)stream));
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias)) return T2S_EINVAL;
+    if ((n_cond > 0 && !planes_ok(S_hi, S_lo)) || !gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(C, 32), taps, dilation, S_hi, S_lo, cdiv(n_cond, 32));
+    g.output(acts_hi, acts_lo, cdiv(C, 32));
+    g.a.C = C;
+    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, 256, stream));
     return T2S_OK;
 }
 
 int t2s_wg_res_skip(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                     void* X_hi, void* X_lo, float* skip, int B, int C, int n_res, int skip_init, int L, int Lp,
                     int halo, int Mpad, void* stream) {
-    if (!check_planes(A_hi, A_lo) || !check_planes(acts_hi, acts_lo) || !bias || !skip || !aligned16(skip)) return T2S_EINVAL;
-    if (n_res > 0 && !check_planes(X_hi, X_lo)) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || (n_res != 0 && n_res != C)) return T2S_EINVAL;
-    if (Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < n_res + C || !aligned16(bias)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)acts_hi; a.X_lo = (const u16*)acts_lo;
-    a.bias = bias; a.O_hi = (u16*)X_hi; a.O_lo = (u16*)X_lo; a.skip = skip;
-    a.xc = cdiv(C, 32); a.sc = 0; a.oc = cdiv(C, 32);
-    a.taps = 1; a.dil = 1;
-    a.nk_x = a.xc; a.nk = a.xc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_mtiles = cdiv(n_res + C, 256); a.n_ttiles = cdiv(L, 256);
-    a.C = C; a.n_res = n_res; a.skip_init = skip_init;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream));
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias) || !skip || !al16(skip)) return T2S_EINVAL;
+    if (n_res > 0 && !planes_ok(X_hi, X_lo)) return T2S_EINVAL;
+    if (C <= 0 || C % 4 || (n_res != 0 && n_res != C) || !geometry_ok(B, L, Lp, halo, Mpad, n_res + C)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(acts_hi, acts_lo, cdiv(C, 32), 1, 1);
+    g.output(X_hi, X_lo, cdiv(C, 32));
+    g.a.skip = skip; g.a.C = C; g.a.n_res = n_res; g.a.skip_init = skip_init;
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, n_res + C, 256, stream));
     return T2S_OK;
 }
 
@@ -224,13 +197,6 @@ int t2s_wg_endfold_weights(const t2s_endfold_job* jobs, int n_jobs, int C, void*
     static_assert(sizeof(t2s_endfold_job) == sizeof(EndFoldJob), "t2s_endfold_job layout");
     T2S_CHECK_HIP(t2s_launch_endfold_weights((const EndFoldJob*)jobs, n_jobs, C, (hipStream_t)stream));
     return T2S_OK;
-}
-
-// Gate GEMM tile height for a shape: 256-row tiles (the ping-pong kernel) unless they leave at least half of the chip's 256 CUs
-// without a workgroup - short utterances at B = 1 - where 128-row tiles give twice the workgroups at half the work each.
-static int gate_tile_rows(int B, int C, int L) {
-    const long wg256 = (long)cdiv(C, 128) * cdiv(L, 256) * B;
-    return (wg256 <= 128 && C % 64 == 0) ? 128 : 256;
 }
 
 int t2s_wg_gate_tile_rows(int B, int C, int L) {
@@ -247,27 +213,16 @@ int t2s_wg_in_cond_gate_fold(const void* A_hi, const void* A_lo, const float* bi
                              const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
                              float* fold_acc, int fold_init, int B, int C, int n_cond, int taps, int dilation, int L,
                              int Lp, int halo, int Mpad, void* stream) {
-    if (!check_planes(A_hi, A_lo) || !check_planes(X_hi, X_lo) || !check_planes(acts_hi, acts_lo) || !bias) return T2S_EINVAL;
-    if (!fold_A || !fold_acc || !aligned16(fold_A) || C % 16) return T2S_EINVAL;
-    if (n_cond > 0 && !check_planes(S_hi, S_lo)) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || taps <= 0 || !(taps & 1) || dilation <= 0) return T2S_EINVAL;
-    if ((taps / 2) * dilation > halo || Lp != t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || !aligned16(bias)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.S_hi = (const u16*)S_hi; a.S_lo = (const u16*)S_lo;
-    a.bias = bias; a.O_hi = (u16*)acts_hi; a.O_lo = (u16*)acts_lo;
-    a.fold_A = (const u16*)fold_A; a.fold_acc = fold_acc; a.fold_init = fold_init;
-    a.xc = cdiv(C, 32); a.sc = cdiv(n_cond, 32); a.oc = cdiv(C, 32);
-    a.taps = taps; a.dil = dilation;
-    a.nk_x = taps * a.xc; a.nk = a.nk_x + a.sc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    const int rows = gate_tile_rows(B, C, L);          // fold_acc holds t2s_wg_gate_fold_slots(B, C, L) slots
-    a.n_mtiles = cdiv(C, rows / 2); a.n_ttiles = cdiv(L, 256);
-    a.C = C;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE, (hipStream_t)stream, rows));
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias)) return T2S_EINVAL;
+    if ((n_cond > 0 && !planes_ok(S_hi, S_lo)) || !fold_ok(fold_A, fold_acc, C)) return T2S_EINVAL;
+    if (!gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(C, 32), taps, dilation, S_hi, S_lo, cdiv(n_cond, 32));
+    g.output(acts_hi, acts_lo, cdiv(C, 32));
+    g.fold(fold_A, fold_acc, fold_init);
+    g.a.C = C;
+    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, gate_tile_rows(B, C, L), stream));
     return T2S_OK;
 }
 
@@ -275,34 +230,25 @@ int t2s_wg_in_win_gate_fold(const void* A_hi, const void* A_lo, const float* bia
                             const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
                             float* fold_acc, int fold_init, int B, int C, int n_cond, int win_chunks, int L, int Lp, int halo,
                             int Mpad, void* stream) {
-    if (!check_planes(A_hi, A_lo) || !check_planes(W_hi, W_lo) || !check_planes(S_hi, S_lo) || !check_planes(acts_hi, acts_lo) ||
-        !bias)
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(W_hi, W_lo) || !planes_ok(S_hi, S_lo) || !planes_ok(acts_hi, acts_lo) || !bias ||
+        !al16(bias))
         return T2S_EINVAL;
-    if (!fold_A || !fold_acc || !aligned16(fold_A) || C % 16) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || n_cond <= 0 || halo < 0 || Lp != t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || !aligned16(bias) || (win_chunks != 2 && win_chunks != 4)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)W_hi; a.X_lo = (const u16*)W_lo;
-    a.S_hi = (const u16*)S_hi; a.S_lo = (const u16*)S_lo;
-    a.bias = bias; a.O_hi = (u16*)acts_hi; a.O_lo = (u16*)acts_lo;
-    a.fold_A = (const u16*)fold_A; a.fold_acc = fold_acc; a.fold_init = fold_init;
+    if (!fold_ok(fold_A, fold_acc, C) || C <= 0 || n_cond <= 0 || halo < 0 || (win_chunks != 2 && win_chunks != 4)) return T2S_EINVAL;
+    if (!geometry_ok(B, L, Lp, halo, Mpad, cdiv(C, 128) * 256)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
     // the window planes' columns already hold the taps: a 1-tap "convolution" over win_chunks chunks, then the conditioning
-    a.xc = win_chunks; a.sc = cdiv(n_cond, 32); a.oc = cdiv(C, 32);
-    a.taps = 1; a.dil = 1;
-    a.nk_x = win_chunks; a.nk = win_chunks + a.sc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    const int rows = gate_tile_rows(B, C, L);
-    a.n_mtiles = cdiv(C, rows / 2); a.n_ttiles = cdiv(L, 256);
-    a.C = C;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE, (hipStream_t)stream, rows));
+    g.k_side(W_hi, W_lo, win_chunks, 1, 1, S_hi, S_lo, cdiv(n_cond, 32));
+    g.output(acts_hi, acts_lo, cdiv(C, 32));
+    g.fold(fold_A, fold_acc, fold_init);
+    g.a.C = C;
+    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, gate_tile_rows(B, C, L), stream));
     return T2S_OK;
 }
 
 int t2s_wg_upsample_basis(const float* W, const float* bias, int n_mel, int ksize, int stride, int n_group, int Lp, int halo,
                           void* U_hi, void* U_lo, void* stream) {
-    if (!W || !bias || !check_planes(U_hi, U_lo)) return T2S_EINVAL;
+    if (!W || !bias || !planes_ok(U_hi, U_lo)) return T2S_EINVAL;
     if (n_mel <= 0 || n_group <= 0 || stride <= 0 || ksize <= 0 || ksize % stride || stride % n_group) return T2S_EINVAL;
     const int ncols = (stride / n_group) * (ksize / stride) * n_mel + 1;
     if (halo < 0 || Lp != t2s_plane_rows(ncols, halo)) return T2S_EINVAL;
@@ -313,7 +259,7 @@ int t2s_wg_upsample_basis(const float* W, const float* bias, int n_mel, int ksiz
 
 int t2s_wg_compose_cond(const float* tmp, const float* bias_in, int rows, int Mpad, int P, int K2, long ld, void* A2_hi,
                         void* A2_lo, float* bias_out, void* stream) {
-    if (!tmp || !bias_in || !bias_out || !check_planes(A2_hi, A2_lo)) return T2S_EINVAL;
+    if (!tmp || !bias_in || !bias_out || !planes_ok(A2_hi, A2_lo)) return T2S_EINVAL;
     if (rows <= 0 || Mpad % 256 || rows > Mpad || P <= 0 || K2 <= 0 || K2 % 32 || ld < (long)P * K2 + 1) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_compose_pack(tmp, bias_in, rows, Mpad, P, K2, (int)ld, (u16*)A2_hi, (u16*)A2_lo, bias_out,
                                           (hipStream_t)stream));
@@ -321,7 +267,7 @@ int t2s_wg_compose_cond(const float* tmp, const float* bias_in, int rows, int Mp
 }
 
 int t2s_wg_melwin_planes(const float* mel, int B, int n_mel, int frames, int nlag, int Fp, void* M_hi, void* M_lo, void* stream) {
-    if (!mel || !check_planes(M_hi, M_lo)) return T2S_EINVAL;
+    if (!mel || !planes_ok(M_hi, M_lo)) return T2S_EINVAL;
     if (B <= 0 || n_mel <= 0 || frames <= 0 || nlag <= 0 || Fp < frames) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_melwin_planes(mel, B, n_mel, frames, nlag, Fp, (u16*)M_hi, (u16*)M_lo, (hipStream_t)stream));
     return T2S_OK;
@@ -331,57 +277,40 @@ int t2s_wg_in_melwin_gate_fold(const void* A_hi, const void* A_lo, const void* A
                                const void* X_hi, const void* X_lo, const void* M_hi, const void* M_lo, void* acts_hi,
                                void* acts_lo, const void* fold_A, float* fold_acc, int fold_init, int B, int C, int K2,
                                int taps, int dilation, int L, int Lp, int halo, int Mpad, int P, int Fp, void* stream) {
-    if (!check_planes(A_hi, A_lo) || !check_planes(A2_hi, A2_lo) || !check_planes(X_hi, X_lo) || !check_planes(M_hi, M_lo) ||
-        !check_planes(acts_hi, acts_lo) || !bias)
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(A2_hi, A2_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(M_hi, M_lo) ||
+        !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias))
         return T2S_EINVAL;
-    if (!fold_A || !fold_acc || !aligned16(fold_A) || C % 16) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || taps <= 0 || !(taps & 1) || dilation <= 0 || K2 <= 0 || K2 % 32) return T2S_EINVAL;
-    if ((taps / 2) * dilation > halo || Lp != t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || !aligned16(bias) || P <= 0) return T2S_EINVAL;
+    if (!fold_ok(fold_A, fold_acc, C) || !gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad)) return T2S_EINVAL;
+    if (K2 <= 0 || K2 % 32 || P <= 0) return T2S_EINVAL;
     const int F = cdiv(L, P);
-    if (Fp < F) return T2S_EINVAL;
     // the phase tiles are 256 rows high: fold_acc must have been sized (t2s_wg_gate_fold_slots) for that tile height
-    if (gate_tile_rows(B, C, L) != 256) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.A2_hi = (const u16*)A2_hi; a.A2_lo = (const u16*)A2_lo;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.S_hi = (const u16*)M_hi; a.S_lo = (const u16*)M_lo;
-    a.bias = bias; a.O_hi = (u16*)acts_hi; a.O_lo = (u16*)acts_lo;
-    a.fold_A = (const u16*)fold_A; a.fold_acc = fold_acc; a.fold_init = fold_init;
-    a.xc = cdiv(C, 32); a.sc = K2 / 32; a.oc = cdiv(C, 32);
-    a.taps = taps; a.dil = dilation;
-    a.nk_x = taps * a.xc; a.nk = a.nk_x + a.sc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_mtiles = cdiv(C, 128); a.n_ttiles = 0;
-    a.C = C;
-    a.ph_P = P; a.ph_Fp = Fp;
-    a.ph_FT = F <= 64 ? 64 : (F <= 128 ? 128 : 256);
-    a.ph_bper = 256 / a.ph_FT;
-    a.ph_nft = cdiv(F, a.ph_FT);
-    T2S_CHECK_HIP(t2s_launch_gate_gemm_pp(a, (hipStream_t)stream));
+    if (Fp < F || gate_tile_rows(B, C, L) != 256) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(C, 32), taps, dilation, M_hi, M_lo, K2 / 32);
+    g.output(acts_hi, acts_lo, cdiv(C, 32));
+    g.fold(fold_A, fold_acc, fold_init);
+    g.a.A2_hi = (const u16*)A2_hi; g.a.A2_lo = (const u16*)A2_lo;
+    g.a.C = C;
+    g.a.n_ttiles = 0;      // a phase tile's 256 columns are (batch entry, frame) pairs, ph_nft tiles per batch entry
+    g.a.ph_P = P; g.a.ph_Fp = Fp;
+    g.a.ph_FT = F <= 64 ? 64 : (F <= 128 ? 128 : 256);
+    g.a.ph_bper = 256 / g.a.ph_FT;
+    g.a.ph_nft = cdiv(F, g.a.ph_FT);
+    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, 256, stream));
     return T2S_OK;
 }
 
 int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                     void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, void* stream) {
-    if (!check_planes(A_hi, A_lo) || !check_planes(acts_hi, acts_lo) || !check_planes(X_hi, X_lo) || !bias) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < C || !aligned16(bias))
-        return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)acts_hi; a.X_lo = (const u16*)acts_lo;
-    a.bias = bias; a.O_hi = (u16*)X_hi; a.O_lo = (u16*)X_lo;
-    a.xc = cdiv(C, 32); a.sc = 0; a.oc = cdiv(C, 32);
-    a.taps = 1; a.dil = 1; a.nk_x = a.xc; a.nk = a.xc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_mtiles = cdiv(C, 128); a.n_ttiles = cdiv(L, 256);
-    a.C = 0; a.n_res = C;
-    if (pair8 && C % 32) return T2S_EINVAL;
-    a.pair8 = pair8 ? 1 : 0;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream, 128));
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !bias || !al16(bias)) return T2S_EINVAL;
+    if (C <= 0 || C % 4 || (pair8 && C % 32) || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(acts_hi, acts_lo, cdiv(C, 32), 1, 1);
+    g.output(X_hi, X_lo, cdiv(C, 32));
+    g.a.C = 0; g.a.n_res = C; g.a.pair8 = pair8 ? 1 : 0;
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, 128, stream));
     return T2S_OK;
 }
 
@@ -408,26 +337,17 @@ int t2s_wg_end_affine(const float* skip, const float* w_end, const float* b_end,
 int t2s_conv_bias_act(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
                       void* O_hi, void* O_lo, float* out_f32, int f32_channel_last, int B, int Cin, int Cout, int taps,
                       int dilation, int act, int L, int Lp, int halo, int Mpad, void* stream) {
-    if (!check_planes(A_hi, A_lo) || !check_planes(X_hi, X_lo) || !bias || !aligned16(bias)) return T2S_EINVAL;
-    if ((O_hi || O_lo) && !check_planes(O_hi, O_lo)) return T2S_EINVAL;
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !bias || !al16(bias)) return T2S_EINVAL;
+    if ((O_hi || O_lo) && !planes_ok(O_hi, O_lo)) return T2S_EINVAL;
     if (!O_hi && !out_f32) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || Cin <= 0 || Cout <= 0 || Cout % 4 || taps <= 0 || !(taps & 1) || dilation <= 0) return T2S_EINVAL;
-    if ((taps / 2) * dilation > halo || Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < Cout) return T2S_EINVAL;
+    if (Cin <= 0 || Cout <= 0 || Cout % 4 || !taps_ok(taps, dilation, halo) || !geometry_ok(B, L, Lp, halo, Mpad, Cout)) return T2S_EINVAL;
     if (act < T2S_ACT_NONE || act > T2S_ACT_TANH) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.bias = bias; a.O_hi = (u16*)O_hi; a.O_lo = (u16*)O_lo; a.out_f32 = out_f32;
-    a.xc = cdiv(Cin, 32); a.sc = 0; a.oc = cdiv(Cout, 32);
-    a.taps = taps; a.dil = dilation;
-    a.nk_x = taps * a.xc; a.nk = a.nk_x;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    // a grid of at most 64 workgroups is latency-bound per K-step: 128-row tiles with three LDS stages (conv_gemm.hip)
-    const int rows = (long)cdiv(Cout, 256) * cdiv(L, 256) * B <= 64 ? 128 : 256;
-    a.n_mtiles = cdiv(Cout, rows); a.n_ttiles = cdiv(L, 256);
-    a.C = Cout; a.act = act; a.f32_cl = f32_channel_last;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_BIAS_ACT, (hipStream_t)stream, rows));
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(Cin, 32), taps, dilation);
+    g.output(O_hi, O_lo, cdiv(Cout, 32));
+    g.a.out_f32 = out_f32; g.a.C = Cout; g.a.act = act; g.a.f32_cl = f32_channel_last;
+    T2S_CHECK_HIP(g.launch(EPI_BIAS_ACT, Cout, bias_act_tile_rows(B, Cout, L), stream));
     return T2S_OK;
 }
 

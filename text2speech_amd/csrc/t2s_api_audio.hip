@@ -1,17 +1,12 @@
 // extern "C" boundary of the audio front-end / back-end (STFT, mel, inverse STFT, denoiser glue).
 #include "../../include/t2s_hip.h"
 #include "t2s_kernels.h"
+#include "t2s_api_common.h"
 #include "audio_ops.h"
 #include "tacotron_ops.h"
 
 #include <string.h>
 
-extern "C" int t2s_internal_fail_hip(int e);
-#define T2S_CHECK_HIP(expr)                                          \
-    do {                                                             \
-        hipError_t _e = (expr);                                      \
-        if (_e != hipSuccess) return t2s_internal_fail_hip((int)_e); \
-    } while (0)
 
 // y[item][row] = sum_k W[row][k] x[item * sx + k]  per batch element, through the GEMV / matrix-core dispatcher
 static hipError_t frames_gemm(const float* W, int rows, int K, const float* x, long sx, int items, float* y, long sy_item,

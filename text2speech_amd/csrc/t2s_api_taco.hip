@@ -1,21 +1,13 @@
 // extern "C" boundary of the Tacotron-2 kernels: validation, argument blocks, and the decode-step driver.
 #include "../../include/t2s_hip.h"
 #include "t2s_kernels.h"
+#include "t2s_api_common.h"
 #include "tacotron_ops.h"
 #include "t2s_handoff.h"
 
 #include <stdlib.h>
 #include <string.h>
 
-extern "C" int t2s_internal_fail_hip(int e);   // defined in t2s_api.hip (records the HIP error text)
-
-#define T2S_CHECK_HIP(expr)                                        \
-    do {                                                           \
-        hipError_t _e = (expr);                                    \
-        if (_e != hipSuccess) return t2s_internal_fail_hip((int)_e); \
-    } while (0)
-
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // one fused attention launch per step (one workgroup per batch element) up to this batch; beyond it the three-kernel form
 constexpr int ATT_FUSED_MAX_B = 8;

@@ -1,6 +1,7 @@
 // extern "C" boundary of the Tacotron-2 backward kernels.
 #include "../../include/t2s_hip.h"
 #include "t2s_kernels.h"
+#include "t2s_api_common.h"
 #include "taco_bwd_ops.h"
 #include "tacotron_ops.h"
 #include "t2s_handoff.h"
@@ -9,12 +10,6 @@
 
 #include <mutex>
 
-extern "C" int t2s_internal_fail_hip(int e);
-#define T2S_CHECK_HIP(expr)                                          \
-    do {                                                             \
-        hipError_t _e = (expr);                                      \
-        if (_e != hipSuccess) return t2s_internal_fail_hip((int)_e); \
-    } while (0)
 
 // The one piece of library-owned state (documented in include/t2s_hip.h): the BPTT driver overlaps two dependent
 // chains on two streams.  The caller hands over ONE stream, so the helper and its events belong to the library:

@@ -2,31 +2,14 @@
 #include "../../include/t2s_hip.h"
 #include "t2s_kernels.h"
 #include "train_ops.h"
+#include "t2s_api_common.h"
+#include "conv_gemm_args.h"
 
 #include <math.h>
 #include <string.h>
 
-extern "C" int t2s_internal_fail_hip(int e);
-
-#define T2S_CHECK_HIP(expr)                                          \
-    do {                                                             \
-        hipError_t _e = (expr);                                      \
-        if (_e != hipSuccess) return t2s_internal_fail_hip((int)_e); \
-    } while (0)
-
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-// The accumulate / gate-backward GEMMs of the training backward: 256-row tiles on the ping-pong schedule (csrc/gate_gemm_pp.hip)
-// once they give at least ~100 workgroups - M = 512 at 8 x 16000 is 128, half the chip, and the rest is taken by the
-// weight-gradient stream that runs beside them - else the lockstep kernels on 128-row tiles (twice the workgroups).
-static bool bwd_pp256(const ConvGemmArgs& a, int rows) {
-    return t2s_pp_shape_ok(a) && (long)cdiv(rows, 256) * a.n_ttiles * a.B >= 100;
-}
-
-static int planes_ok(const void* a, const void* b) { return a && b && al16(a) && al16(b); }
-
 // Can the backward GEMM with `rows` output rows over B x L columns take PERM_PAIR8-packed operands (16-byte epilogue pieces)?  Only
-// the 256-row ping-pong kernels have that epilogue: the grid rule of bwd_pp256 above, whole 32-row groups.
+// the 256-row ping-pong kernels have that epilogue: the grid rule of bwd_pp256 (conv_gemm_args.h), whole 32-row groups.
 extern "C" int t2s_wg_bwd_pair8_ok(int B, int rows, int L) {
     if (B <= 0 || rows <= 0 || L <= 0 || rows % 32) return 0;
     return (long)cdiv(rows, 256) * cdiv(L, 256) * B >= 100 ? 1 : 0;
@@ -48,127 +31,84 @@ int t2s_wg_in_cond_gate_train(const void* A_hi, const void* A_lo, const float* b
                               const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, void* T_hi, void* T_lo,
                               void* G_hi, void* G_lo, int B, int C, int n_cond, int taps, int dilation, int L, int Lp,
                               int halo, int Mpad, void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !bias) return T2S_EINVAL;
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias)) return T2S_EINVAL;
     if (!planes_ok(G_hi, G_lo) || ((T_hi || T_lo) && !planes_ok(T_hi, T_lo))) return T2S_EINVAL;      // tanh planes are optional
-    if (n_cond > 0 && !planes_ok(S_hi, S_lo)) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || taps <= 0 || !(taps & 1) || dilation <= 0) return T2S_EINVAL;
-    if ((taps / 2) * dilation > halo || Lp != t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || !al16(bias)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.S_hi = (const u16*)S_hi; a.S_lo = (const u16*)S_lo;
-    a.bias = bias; a.O_hi = (u16*)acts_hi; a.O_lo = (u16*)acts_lo;
-    a.T_hi = (u16*)T_hi; a.T_lo = (u16*)T_lo; a.G_hi = (u16*)G_hi; a.G_lo = (u16*)G_lo;
-    a.xc = cdiv(C, 32); a.sc = cdiv(n_cond, 32); a.oc = cdiv(C, 32); a.tc = a.oc;
-    a.taps = taps; a.dil = dilation;
-    a.nk_x = taps * a.xc; a.nk = a.nk_x + a.sc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_mtiles = cdiv(C, 128); a.n_ttiles = cdiv(L, 256);
-    a.C = C;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE, (hipStream_t)stream));
+    if ((n_cond > 0 && !planes_ok(S_hi, S_lo)) || !gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(C, 32), taps, dilation, S_hi, S_lo, cdiv(n_cond, 32));
+    g.output(acts_hi, acts_lo, cdiv(C, 32));
+    g.a.T_hi = (u16*)T_hi; g.a.T_lo = (u16*)T_lo; g.a.G_hi = (u16*)G_hi; g.a.G_lo = (u16*)G_lo; g.a.tc = g.a.oc;
+    g.a.C = C;
+    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, 256, stream));
     return T2S_OK;
 }
-
-// gate GEMM tile height: the library's own decision (csrc/t2s_api.hip)
-extern "C" int t2s_wg_gate_tile_rows(int B, int C, int L);
 
 int t2s_wg_in_cond_gate_fold_train(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
                                    const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, void* G_hi, void* G_lo,
                                    int act_bchunks, const void* fold_A, float* fold_acc, int fold_init, int B, int C, int n_cond,
                                    int taps, int dilation, int L, int Lp, int halo, int Mpad, void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(G_hi, G_lo) || !bias)
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(G_hi, G_lo) || !bias ||
+        !al16(bias))
         return T2S_EINVAL;
-    if (!fold_A || !fold_acc || !al16(fold_A) || C % 16) return T2S_EINVAL;
-    if (n_cond > 0 && !planes_ok(S_hi, S_lo)) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || taps <= 0 || !(taps & 1) || dilation <= 0) return T2S_EINVAL;
-    if ((taps / 2) * dilation > halo || Lp != t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    if (Mpad % 256 || Mpad < cdiv(C, 128) * 256 || !al16(bias)) return T2S_EINVAL;
-    if (act_bchunks != 0 && act_bchunks < cdiv(C, 32)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.S_hi = (const u16*)S_hi; a.S_lo = (const u16*)S_lo;
-    a.bias = bias; a.O_hi = (u16*)acts_hi; a.O_lo = (u16*)acts_lo;
-    a.G_hi = (u16*)G_hi; a.G_lo = (u16*)G_lo;
-    a.fold_A = (const u16*)fold_A; a.fold_acc = fold_acc; a.fold_init = fold_init;
-    a.xc = cdiv(C, 32); a.sc = cdiv(n_cond, 32);
-    a.oc = act_bchunks ? act_bchunks : cdiv(C, 32); a.tc = a.oc;      // oc = batch stride of the acts / sigmoid planes
-    a.taps = taps; a.dil = dilation;
-    a.nk_x = taps * a.xc; a.nk = a.nk_x + a.sc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    const int rows = t2s_wg_gate_tile_rows(B, C, L);          // fold_acc holds t2s_wg_gate_fold_slots(B, C, L) slots
-    a.n_mtiles = cdiv(C, rows / 2); a.n_ttiles = cdiv(L, 256);
-    a.C = C;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE, (hipStream_t)stream, rows));
+    if ((n_cond > 0 && !planes_ok(S_hi, S_lo)) || !fold_ok(fold_A, fold_acc, C)) return T2S_EINVAL;
+    if (!gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad) || (act_bchunks != 0 && act_bchunks < cdiv(C, 32))) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(C, 32), taps, dilation, S_hi, S_lo, cdiv(n_cond, 32));
+    g.output(acts_hi, acts_lo, act_bchunks ? act_bchunks : cdiv(C, 32));      // oc = batch stride of the acts / sigmoid planes
+    g.fold(fold_A, fold_acc, fold_init);
+    g.a.G_hi = (u16*)G_hi; g.a.G_lo = (u16*)G_lo; g.a.tc = g.a.oc;
+    g.a.C = C;
+    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, gate_tile_rows(B, C, L), stream));
     return T2S_OK;
 }
 
 int t2s_wg_res_only_train(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                           int act_bchunks, const void* R_hi, const void* R_lo, void* X_hi, void* X_lo, int B, int C, int L, int Lp,
                           int halo, int Mpad, int pair8, void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(R_hi, R_lo) || !bias)
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(R_hi, R_lo) || !bias ||
+        !al16(bias))
         return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < C || !al16(bias)) return T2S_EINVAL;
-    if ((act_bchunks != 0 && act_bchunks < cdiv(C, 32)) || (pair8 && C % 32)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)acts_hi; a.X_lo = (const u16*)acts_lo; a.xbs = act_bchunks;
-    a.bias = bias; a.O_hi = (u16*)X_hi; a.O_lo = (u16*)X_lo;
-    a.R_hi = (const u16*)R_hi; a.R_lo = (const u16*)R_lo;
-    a.xc = cdiv(C, 32); a.sc = 0; a.oc = cdiv(C, 32);
-    a.taps = 1; a.dil = 1; a.nk_x = a.xc; a.nk = a.xc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_mtiles = cdiv(C, 128); a.n_ttiles = cdiv(L, 256);
-    a.C = 0; a.n_res = C;
-    a.pair8 = pair8 ? 1 : 0;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream, 128));
+    if (C <= 0 || C % 4 || (pair8 && C % 32) || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
+    if (act_bchunks != 0 && act_bchunks < cdiv(C, 32)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(acts_hi, acts_lo, cdiv(C, 32), 1, 1, nullptr, nullptr, 0, act_bchunks);
+    g.output(X_hi, X_lo, cdiv(C, 32));
+    g.a.R_hi = (const u16*)R_hi; g.a.R_lo = (const u16*)R_lo;
+    g.a.C = 0; g.a.n_res = C; g.a.pair8 = pair8 ? 1 : 0;
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, 128, stream));
     return T2S_OK;
 }
 
 int t2s_wg_skip_sum(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                     int n_k_chunks, int act_bchunks, float* skip, int B, int C, int L, int Lp, int halo, int Mpad, void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !skip || !al16(skip) || !al16(bias)) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || n_k_chunks <= 0 || Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < C) return T2S_EINVAL;
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias) || !skip || !al16(skip)) return T2S_EINVAL;
+    if (C <= 0 || C % 4 || n_k_chunks <= 0 || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
     if (act_bchunks != 0 && act_bchunks < n_k_chunks) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)acts_hi; a.X_lo = (const u16*)acts_lo; a.xbs = act_bchunks;
-    a.bias = bias; a.skip = skip;
-    a.xc = n_k_chunks; a.sc = 0; a.oc = cdiv(C, 32);
-    a.taps = 1; a.dil = 1; a.nk_x = a.xc; a.nk = a.xc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_ttiles = cdiv(L, 256);
-    a.C = C; a.n_res = 0; a.skip_init = 1;
-    const int mt_rows = cdiv(C, 256) * a.n_ttiles * B < 200 ? 128 : 256;
-    a.n_mtiles = cdiv(C, mt_rows);
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream, mt_rows));
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(acts_hi, acts_lo, n_k_chunks, 1, 1, nullptr, nullptr, 0, act_bchunks);
+    g.output(nullptr, nullptr, cdiv(C, 32));
+    g.a.skip = skip; g.a.C = C; g.a.n_res = 0; g.a.skip_init = 1;
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, lockstep_tile_rows(B, C, L), stream));
     return T2S_OK;
 }
 
 int t2s_wg_res_skip_train(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi,
                           const void* acts_lo, const void* R_hi, const void* R_lo, void* X_hi, void* X_lo, float* skip,
                           int B, int C, int n_res, int skip_init, int L, int Lp, int halo, int Mpad, void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !skip || !al16(skip)) return T2S_EINVAL;
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias) || !skip || !al16(skip)) return T2S_EINVAL;
     if (n_res > 0 && (!planes_ok(X_hi, X_lo) || !planes_ok(R_hi, R_lo))) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 4 || (n_res != 0 && n_res != C)) return T2S_EINVAL;
-    if (Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < n_res + C || !al16(bias)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)acts_hi; a.X_lo = (const u16*)acts_lo;
-    a.bias = bias; a.O_hi = (u16*)X_hi; a.O_lo = (u16*)X_lo; a.skip = skip;
-    a.R_hi = (const u16*)R_hi; a.R_lo = (const u16*)R_lo;
-    a.xc = cdiv(C, 32); a.sc = 0; a.oc = cdiv(C, 32);
-    a.taps = 1; a.dil = 1; a.nk_x = a.xc; a.nk = a.xc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_mtiles = cdiv(n_res + C, 256); a.n_ttiles = cdiv(L, 256);
-    a.C = C; a.n_res = n_res; a.skip_init = skip_init;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream));
+    if (C <= 0 || C % 4 || (n_res != 0 && n_res != C) || !geometry_ok(B, L, Lp, halo, Mpad, n_res + C)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(acts_hi, acts_lo, cdiv(C, 32), 1, 1);
+    g.output(X_hi, X_lo, cdiv(C, 32));
+    g.a.R_hi = (const u16*)R_hi; g.a.R_lo = (const u16*)R_lo;
+    g.a.skip = skip; g.a.C = C; g.a.n_res = n_res; g.a.skip_init = skip_init;
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, n_res + C, 256, stream));
     return T2S_OK;
 }
 
@@ -180,37 +120,20 @@ int t2s_wg_bwd_gate_dgrad(const void* A_hi, const void* A_lo, const float* zero_
         !planes_ok(DP_hi, DP_lo) || !zero_bias)
         return T2S_EINVAL;
     if (DX_hi && !planes_ok(DX_hi, DX_lo)) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || C % 32 || Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < C) return T2S_EINVAL;
+    if (C <= 0 || C % 32 || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
     if ((dp_bchunks != 0 && dp_bchunks < 2 * (C / 32)) || (tg_bchunks != 0 && tg_bchunks < C / 32)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
     const int cc = C / 32;
-    if (DX_hi) {   // K = [d_x channels | d_skip channels]
-        a.X_hi = (const u16*)DX_hi; a.X_lo = (const u16*)DX_lo; a.xc = cc;
-        a.S_hi = (const u16*)DS_hi; a.S_lo = (const u16*)DS_lo; a.sc = cc;
-    } else {       // last layer: only skip rows exist
-        a.X_hi = (const u16*)DS_hi; a.X_lo = (const u16*)DS_lo; a.xc = cc; a.sc = 0;
-    }
-    a.bias = zero_bias; a.O_hi = (u16*)DP_hi; a.O_lo = (u16*)DP_lo;
-    a.T_hi = (u16*)T_hi; a.T_lo = (u16*)T_lo; a.G_hi = (u16*)G_hi; a.G_lo = (u16*)G_lo;
-    a.oc = dp_bchunks ? dp_bchunks : 2 * cc;                 // oc = batch stride of the output planes (a slice of a wider set)
-    a.tc = tg_bchunks ? tg_bchunks : cc;                     // the same for the saved gate output / sigmoid planes
-    a.taps = 1; a.dil = 1; a.nk_x = a.xc; a.nk = a.xc + a.sc;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_ttiles = cdiv(L, 256);
-    a.C = C;
-    a.pair8 = pair8 ? 1 : 0;
-    if (bwd_pp256(a, C)) {
-        a.n_mtiles = cdiv(C, 256);
-        T2S_CHECK_HIP(t2s_launch_bwd_gemm_pp(a, EPI_GATE_BWD, (hipStream_t)stream));
-        return T2S_OK;
-    }
-    if (pair8) return T2S_EINVAL;        // PERM_PAIR8 operands need the 256-row ping-pong kernel (t2s_wg_bwd_pair8_ok)
-    // 128-row tiles when 256-row tiles would leave half the CUs without a workgroup (C = 512: 2 x 64 tiles)
-    const int mt_rows = cdiv(C, 256) * a.n_ttiles * B < 200 ? 128 : 256;
-    a.n_mtiles = cdiv(C, mt_rows);
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_GATE_BWD, (hipStream_t)stream, mt_rows));
+    ConvGemm g(A_hi, A_lo, zero_bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    if (DX_hi) g.k_side(DX_hi, DX_lo, cc, 1, 1, DS_hi, DS_lo, cc);      // K = [d_x channels | d_skip channels]
+    else g.k_side(DS_hi, DS_lo, cc, 1, 1);                              // last layer: only skip rows exist
+    g.output(DP_hi, DP_lo, dp_bchunks ? dp_bchunks : 2 * cc);           // oc = batch stride of the output planes (a slice of a wider set)
+    g.a.T_hi = (u16*)T_hi; g.a.T_lo = (u16*)T_lo; g.a.G_hi = (u16*)G_hi; g.a.G_lo = (u16*)G_lo;
+    g.a.tc = tg_bchunks ? tg_bchunks : cc;                              // the same for the saved gate output / sigmoid planes
+    g.a.C = C; g.a.pair8 = pair8 ? 1 : 0;
+    const bool pp = bwd_pp256(g.a, C);
+    if (pair8 && !pp) return T2S_EINVAL;        // PERM_PAIR8 operands need the 256-row ping-pong kernel (t2s_wg_bwd_pair8_ok)
+    T2S_CHECK_HIP(g.launch(EPI_GATE_BWD, C, pp ? 256 : lockstep_tile_rows(B, C, L), stream, pp));
     return T2S_OK;
 }
 
@@ -218,76 +141,59 @@ int t2s_conv_accumulate(const void* A_hi, const void* A_lo, const float* zero_bi
                         int x_bchunks, void* O_hi, void* O_lo, int B, int Cin, int Cout, int taps, int dilation, int init, int L, int Lp,
                         int halo, int Mpad, int pair8, void* stream) {
     if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(O_hi, O_lo) || !zero_bias) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || Cin <= 0 || Cout <= 0 || Cout % 4 || taps <= 0 || !(taps & 1) || dilation <= 0) return T2S_EINVAL;
-    if ((taps / 2) * dilation > halo || Lp != t2s_plane_rows(L, halo) || Mpad % 256 || Mpad < Cout) return T2S_EINVAL;
-    if (x_bchunks != 0 && x_bchunks < cdiv(Cin, 32)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.bias = zero_bias; a.O_hi = (u16*)O_hi; a.O_lo = (u16*)O_lo;
-    a.xc = cdiv(Cin, 32); a.sc = 0; a.oc = cdiv(Cout, 32); a.xbs = x_bchunks;
-    a.taps = taps; a.dil = dilation; a.nk_x = taps * a.xc; a.nk = a.nk_x;
-    a.Mpad = Mpad; a.Lp = Lp; a.halo = halo; a.L = L; a.B = B;
-    a.n_ttiles = cdiv(L, 256);
-    a.C = 0; a.n_res = Cout; a.res_init = init;      // every row takes the residual branch
-    if (pair8 && Cout % 32) return T2S_EINVAL;
-    a.pair8 = pair8 ? 1 : 0;
-    if (bwd_pp256(a, Cout)) {
-        a.n_mtiles = cdiv(Cout, 256);
-        T2S_CHECK_HIP(t2s_launch_bwd_gemm_pp(a, EPI_RESSKIP, (hipStream_t)stream));
-        return T2S_OK;
-    }
-    if (pair8) return T2S_EINVAL;        // PERM_PAIR8 operands need the 256-row ping-pong kernel (t2s_wg_bwd_pair8_ok)
-    // 128-row tiles when 256-row tiles would leave most CUs without a workgroup
-    const int mt_rows = (cdiv(Cout, 256) * a.n_ttiles * B <= 128 || Cout % 256 == 0) && cdiv(Cout, 256) * a.n_ttiles * B < 200 ? 128 : 256;
-    a.n_mtiles = cdiv(Cout, mt_rows);
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_RESSKIP, (hipStream_t)stream, mt_rows));
+    if (Cin <= 0 || Cout <= 0 || Cout % 4 || !taps_ok(taps, dilation, halo) || !geometry_ok(B, L, Lp, halo, Mpad, Cout)) return T2S_EINVAL;
+    if ((x_bchunks != 0 && x_bchunks < cdiv(Cin, 32)) || (pair8 && Cout % 32)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, zero_bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(Cin, 32), taps, dilation, nullptr, nullptr, 0, x_bchunks);
+    g.output(O_hi, O_lo, cdiv(Cout, 32));
+    g.a.C = 0; g.a.n_res = Cout; g.a.res_init = init;      // every row takes the residual branch
+    g.a.pair8 = pair8 ? 1 : 0;
+    const bool pp = bwd_pp256(g.a, Cout);
+    if (pair8 && !pp) return T2S_EINVAL;        // PERM_PAIR8 operands need the 256-row ping-pong kernel (t2s_wg_bwd_pair8_ok)
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, Cout, pp ? 256 : accumulate_tile_rows(B, Cout, L), stream, pp));
     return T2S_OK;
+}
+
+// The two weight-gradient GEMMs: M x N outputs over K = B x time chunks [k0, k1) of time-major planes, one f32 slab per K split.
+static bool wgrad_shape_ok(const void* A_hi, const void* A_lo, const void* X_hi, const void* X_lo, const float* zero_bias, float* out,
+                           int B, int M, int N, int Mpad, int Npad, int n_tchunks, int k0, int k1) {
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !zero_bias || !out) return false;
+    return M > 0 && M % 4 == 0 && geometry_ok(B, N, Npad, 0, Mpad, M) && n_tchunks > 0 && k0 >= 0 && k1 <= n_tchunks && k0 < k1;
+}
+// `slabs` grid batch entries, each a K range of kchunk steps
+static void wgrad_fill(ConvGemm& g, const void* X_hi, const void* X_lo, float* out, int slabs, int M, int N, int Mpad, int Npad,
+                       int n_tchunks, int k0, int k1, int kchunk) {
+    g.geometry(slabs, N, Npad, 0, Mpad);
+    g.k_side(X_hi, X_lo, n_tchunks, 1, 1);
+    g.output(nullptr, nullptr, cdiv(M, 32));
+    g.a.a_bstride = (long)n_tchunks * Mpad * 32;
+    g.a.out_f32 = out; g.a.C = M; g.a.act = ACT_NONE;
+    g.a.k0 = k0; g.a.kend = k1; g.a.kchunk = kchunk;
 }
 
 int t2s_wgrad_gemm(const void* A_hi, const void* A_lo, const void* X_hi, const void* X_lo, const float* zero_bias,
                    float* out, int B, int M, int N, int Mpad, int Npad, int n_tchunks, int k0, int k1, int ksplit,
                    void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !zero_bias || !out) return T2S_EINVAL;
-    if (B <= 0 || M <= 0 || N <= 0 || M % 4 || Mpad % 256 || Mpad < M || Npad != cdiv(N, 256) * 256 || n_tchunks <= 0)
-        return T2S_EINVAL;
-    if (k0 < 0 || k1 > n_tchunks || k0 >= k1 || ksplit < 1 || ksplit > 16) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo; a.a_bstride = (long)n_tchunks * Mpad * 32;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.bias = zero_bias; a.out_f32 = out;
-    a.xc = n_tchunks; a.sc = 0; a.oc = cdiv(M, 32);
-    a.taps = 1; a.dil = 1; a.nk_x = n_tchunks; a.nk = n_tchunks;
-    a.Mpad = Mpad; a.Lp = Npad; a.halo = 0; a.L = N; a.B = B * ksplit;
-    a.ksplit = ksplit; a.k0 = k0; a.kend = k1; a.kchunk = cdiv(k1 - k0, ksplit);
-    a.n_mtiles = cdiv(M, 256); a.n_ttiles = cdiv(N, 256);
-    a.C = M; a.act = ACT_NONE;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_BIAS_ACT, (hipStream_t)stream));
+    if (!wgrad_shape_ok(A_hi, A_lo, X_hi, X_lo, zero_bias, out, B, M, N, Mpad, Npad, n_tchunks, k0, k1)) return T2S_EINVAL;
+    if (ksplit < 1 || ksplit > 16) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, zero_bias);
+    wgrad_fill(g, X_hi, X_lo, out, B * ksplit, M, N, Mpad, Npad, n_tchunks, k0, k1, cdiv(k1 - k0, ksplit));
+    g.a.ksplit = ksplit;
+    T2S_CHECK_HIP(g.launch(EPI_BIAS_ACT, M, 256, stream));
     return T2S_OK;
 }
 
 int t2s_wgrad_gemm_flat(const void* A_hi, const void* A_lo, const void* X_hi, const void* X_lo, const float* zero_bias,
                         float* out, int B, int M, int N, int Mpad, int Npad, int n_tchunks, int k0, int k1, int nsplit,
                         void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !zero_bias || !out) return T2S_EINVAL;
-    if (B <= 0 || M <= 0 || N <= 0 || M % 4 || Mpad % 256 || Mpad < M || Npad != cdiv(N, 256) * 256 || n_tchunks <= 0)
-        return T2S_EINVAL;
-    if (k0 < 0 || k1 > n_tchunks || k0 >= k1 || nsplit < 1 || nsplit > B * (k1 - k0)) return T2S_EINVAL;
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A_hi = (const u16*)A_hi; a.A_lo = (const u16*)A_lo; a.a_bstride = (long)n_tchunks * Mpad * 32;
-    a.X_hi = (const u16*)X_hi; a.X_lo = (const u16*)X_lo;
-    a.bias = zero_bias; a.out_f32 = out;
-    a.xc = n_tchunks; a.sc = 0; a.oc = cdiv(M, 32);
-    a.taps = 1; a.dil = 1; a.nk_x = n_tchunks; a.nk = n_tchunks;
-    a.Mpad = Mpad; a.Lp = Npad; a.halo = 0; a.L = N; a.B = nsplit;
-    a.ksplit = 1; a.k0 = k0; a.kend = k1; a.kflat = B; a.kchunk = cdiv(B * (k1 - k0), nsplit);
-    if ((long)a.kchunk * (nsplit - 1) >= (long)B * (k1 - k0)) return T2S_EINVAL;      // every slab must own >= 1 K-step
-    a.n_mtiles = cdiv(M, 256); a.n_ttiles = cdiv(N, 256);
-    a.C = M; a.act = ACT_NONE;
-    T2S_CHECK_HIP(t2s_launch_conv_gemm(a, EPI_BIAS_ACT, (hipStream_t)stream));
+    if (!wgrad_shape_ok(A_hi, A_lo, X_hi, X_lo, zero_bias, out, B, M, N, Mpad, Npad, n_tchunks, k0, k1)) return T2S_EINVAL;
+    if (nsplit < 1 || nsplit > B * (k1 - k0)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, zero_bias);
+    wgrad_fill(g, X_hi, X_lo, out, nsplit, M, N, Mpad, Npad, n_tchunks, k0, k1, cdiv(B * (k1 - k0), nsplit));
+    g.a.ksplit = 1; g.a.kflat = B;
+    if ((long)g.a.kchunk * (nsplit - 1) >= (long)B * (k1 - k0)) return T2S_EINVAL;      // every slab must own >= 1 K-step
+    T2S_CHECK_HIP(g.launch(EPI_BIAS_ACT, M, 256, stream));
     return T2S_OK;
 }
 
