@@ -211,6 +211,24 @@ int t2s_wg_in_melwin_gate_fold(const void* A_hi, const void* A_lo, const void* A
  * 16 m + 4 q + e holds channel 8 q + 4 m + e), which lets the epilogue touch x in 16-byte pieces; C % 32 == 0 */
 int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                     void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, void* stream);
+/* t2s_wg_res_only(pair8 = 1) for the first layer of a flow when nothing wrote x0 = WN.start's output to the X planes: the epilogue
+ * rebuilds x0[c][t] = b_start[c] + sum_j w_start[c][j] * z[b][c_off + j][t] (t2s_wg_start's operation order, rounded to the (hi, lo)
+ * pair as the planes would hold it) and stores x0 + W_res acts + b; the X planes are only written.  n_half <= 4, C % 32 == 0. */
+int t2s_wg_res_only_start(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                          const float* z, const float* w_start, const float* b_start, int n_group, int c_off, int n_half,
+                          void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, void* stream);
+/* One flow boundary of the no-grad forward in one launch, column by column of z_in [B][n_group][L]:
+ *  - fold_acc != NULL: the forward coupling of the flow before, t2s_wg_end_fold_affine(reverse = 0) with (c_off_prev, n_half_prev
+ *    <= 4); log_s (may be NULL) is that flow's;
+ *  - W != NULL: this flow's 1x1 convolution on channels [c_off, c_off + n_rem), as t2s_wg_convinv;
+ *  - all n_group <= 16 channels go to z_out (a second buffer: z_in stays as it was);
+ *  - the window planes W_hi / W_lo of the folded WN.start over channels [c_off, c_off + n_half) of the finished columns, as
+ *    t2s_wg_start_window writes them (taps <= 33, n_half <= 4 as in t2s_wg_res_only_start).  No X planes: t2s_wg_res_only_start rebuilds x0.
+ * fold_acc == NULL and W == NULL: only the window planes, from z_in (z_out may be NULL). */
+int t2s_wg_flow_boundary(const float* z_in, float* z_out, const float* fold_acc, int nslots, const float* bes, int n_layers,
+                         const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off, int n_rem,
+                         int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                         void* stream);
 /* WN.end output from the folded accumulators + affine coupling (forward or reverse) */
 int t2s_wg_end_fold_affine(const float* fold_acc, int nslots, const float* bes, int n_layers, const float* b_end,
                            float* z, float* log_s, float* wn_out, int B, int n_group, int c_off, int n_half, int L, int reverse,

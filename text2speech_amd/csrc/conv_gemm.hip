@@ -50,7 +50,9 @@ static __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 // (A is indexed tap*xc + c as packed, no repack); the conditioning part keeps the one-tile-per-step scheme.
 // NS = LDS stages of the plain main loop: 2, or 3 where the stage is small enough (128-row tiles: 3 x 48 KB) - those GEMMs have
 // K-steps of ~0.7 us of MFMA against a ~1.7 us fill turnaround, so the fill must be issued two steps ahead.
-template <int EPI, int MT, bool SH = false, int NS = 2>
+// X0 = RESSKIP on 128-row tiles with PERM_PAIR8 rows, first layer of a flow: the residual values are WN.start's output, rebuilt in
+// the epilogue from the n_half <= 4 audio channels of the lane's columns (a.x0_*) instead of read back from the X planes.
+template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false>
 __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     constexpr int WN = 4;                            // waves along N (time): 8 waves of 128 x 64, two per SIMD
     constexpr int NTH = 128 * WN;                    // threads per workgroup
@@ -164,9 +166,36 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     // MFMA and fill: every CU reading, then writing, its 128 x 256 tile of x at the same moment (33 + 33 MB in one burst).  With the
     // read half moved under the loop only the write burst is left.  64 VGPRs; 256-row tiles have no room for it.
     constexpr bool PREX = EPI == EPI_RESSKIP && MT == 128;
-    u16x4 pre_h[PREX ? MW : 1][PREX ? NWT : 1], pre_l[PREX ? MW : 1][PREX ? NWT : 1];
+    constexpr bool PRER = PREX && !X0;               // the residual values come from the planes
+    static_assert(!X0 || PREX, "X0 is a variant of the 128-row RESSKIP kernel");
+    u16x4 pre_h[PRER ? MW : 1][PRER ? NWT : 1], pre_l[PRER ? MW : 1][PRER ? NWT : 1];
     typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
-    if constexpr (PREX) {
+    // X0: what WN.start needs for this lane's NWT columns and 8 consecutive channels per m-tile pair - the audio values, 8 x n_half
+    // weights and 8 biases - requested here like the residual values of the ordinary launch (which this variant does not hold)
+    float x0a[X0 ? NWT : 1][4], x0w[X0 ? MW / 2 : 1][8][4], x0c[X0 ? MW / 2 : 1][8];
+    if constexpr (X0) {
+        const int tcol_p = lane & 15, rq_p = (lane >> 4) * 4;
+#pragma unroll
+        for (int n = 0; n < NWT; ++n) {
+            const int t = t0 + wc * (NWT * 16) + n * 16 + tcol_p;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                x0a[n][j] = j < a.x0_nh ? a.x0_z[((size_t)b * a.x0_G + a.x0_coff + j) * a.L + (t < a.L ? t : 0)] : 0.f;
+        }
+#pragma unroll
+        for (int m = 0; m < MW; m += 2) {
+            const int prow = mt * MT + wr * (MT / 2) + m * 16 + rq_p;
+            const int ch = (prow & ~31) + 2 * rq_p;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const bool ok = ch + e < a.n_res;
+                x0c[m / 2][e] = ok ? a.x0_b[ch + e] : 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x0w[m / 2][e][j] = (ok && j < a.x0_nh) ? a.x0_w[(ch + e) * a.x0_nh + j] : 0.f;
+            }
+        }
+    }
+    if constexpr (PRER) {
         const int tcol_p = lane & 15, rq_p = (lane >> 4) * 4;
         if (a.pair8) {
             // residual rows packed with PERM_PAIR8: the two m-tiles of a 32-channel group give this lane 8 consecutive channels of a
@@ -496,7 +525,7 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                 }
             }
         }
-    } else if (EPI == EPI_RESSKIP && PREX && a.pair8) {
+    } else if (EPI == EPI_RESSKIP && PREX && (X0 || a.pair8)) {
         // t2s_wg_res_only with PERM_PAIR8 rows (residual rows only, values prefetched in front of the K loop): per m-tile pair and
         // column one 16-byte store per plane
       if constexpr (PREX) {
@@ -512,13 +541,33 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                 const int t = t0 + wc * (NWT * 16) + n * 16 + tcol;
                 if (t >= a.L) continue;
                 u16x8_t hi, lo;
+                float r[8];            // the residual values: channels ch .. ch + 7 of column t
+                if constexpr (X0) {
+                    // start_kernel's operation order, then its rounding to the (hi, lo) pair: the value the X planes would hold
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        float v = x0c[m / 2][e];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (j < a.x0_nh) v += x0w[m / 2][e][j] * x0a[n][j];
+                        u16 h, l;
+                        split_bf16(v, h, l);
+                        r[e] = join_bf16(h, l);
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        r[e] = join_bf16(pre_h[m][n][e], pre_l[m][n][e]);
+                        r[4 + e] = join_bf16(pre_h[m + 1][n][e], pre_l[m + 1][n][e]);
+                    }
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     u16 h, l;
-                    split_bf16(join_bf16(pre_h[m][n][e], pre_l[m][n][e]) + (acc[m][n][e] + b0[e]), h, l);
+                    split_bf16(r[e] + (acc[m][n][e] + b0[e]), h, l);
                     hi[e] = h;
                     lo[e] = l;
-                    split_bf16(join_bf16(pre_h[m + 1][n][e], pre_l[m + 1][n][e]) + (acc[m + 1][n][e] + b1[e]), h, l);
+                    split_bf16(r[4 + e] + (acc[m + 1][n][e] + b1[e]), h, l);
                     hi[4 + e] = h;
                     lo[4 + e] = l;
                 }
@@ -552,7 +601,7 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                     ol[mi][n] = (u16x4){0, 0, 0, 0};
                     sv[mi][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
                     if (is_res) {
-                        if constexpr (PREX) {
+                        if constexpr (PRER) {
                             oh[mi][n] = pre_h[m0 + mi][n];
                             ol[mi][n] = pre_l[m0 + mi][n];
                         } else if (!a.res_init) {
@@ -684,20 +733,21 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     }
 }
 
-template <int EPI, int MT, bool SH = false, int NS = 2>
+template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false>
 static hipError_t launch_one(const ConvGemmArgs& a, hipStream_t stream) {
     const int nwg = a.n_mtiles * a.n_ttiles * a.B;
     constexpr size_t lds = SH ? 2 * (2 * MT * 64) + 4 * 320 * 64 : NS * (2 * MT * 64 + 2 * B_PLANE_BYTES);
     static std::atomic<unsigned long long> attr_mask{0};        // per instantiation; bit d = raised on device d
-    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, SH, NS>, (int)lds, attr_mask);
+    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, SH, NS, X0>, (int)lds, attr_mask);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, SH, NS>), dim3(nwg), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, SH, NS, X0>), dim3(nwg), dim3(512), lds, stream, a);
     return hipGetLastError();
 }
 
 // a.n_mtiles must have been computed for the same tile height `mt_rows` (256 or 128)
 hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows) {
     if (mt_rows == 128) {
+        if (epi == EPI_RESSKIP && a.x0_z) return launch_one<EPI_RESSKIP, 128, false, 2, true>(a, stream);
         if (epi == EPI_RESSKIP) return launch_one<EPI_RESSKIP, 128>(a, stream);
         if (epi == EPI_GATE_BWD) return launch_one<EPI_GATE_BWD, 128>(a, stream);
         if (epi == EPI_GATE && a.ksplit <= 1 && a.k0 == 0 && a.kflat == 0) return launch_one<EPI_GATE, 128>(a, stream);

@@ -314,6 +314,47 @@ int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const
     return T2S_OK;
 }
 
+int t2s_wg_res_only_start(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                          const float* z, const float* w_start, const float* b_start, int n_group, int c_off, int n_half,
+                          void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, void* stream) {
+    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !bias || !al16(bias)) return T2S_EINVAL;
+    if (!z || !w_start || !b_start || n_half <= 0 || n_half > 4 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
+    if (C <= 0 || C % 32 || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(acts_hi, acts_lo, cdiv(C, 32), 1, 1);
+    g.output(X_hi, X_lo, cdiv(C, 32));
+    g.a.C = 0; g.a.n_res = C; g.a.pair8 = 1;
+    g.a.x0_z = z; g.a.x0_w = w_start; g.a.x0_b = b_start; g.a.x0_G = n_group; g.a.x0_coff = c_off; g.a.x0_nh = n_half;
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, 128, stream));
+    return T2S_OK;
+}
+
+int t2s_wg_flow_boundary(const float* z_in, float* z_out, const float* fold_acc, int nslots, const float* bes, int n_layers,
+                         const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off, int n_rem,
+                         int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                         void* stream) {
+    if (!z_in || !planes_ok(W_hi, W_lo) || z_out == z_in || ((fold_acc || W) && !z_out)) return T2S_EINVAL;
+    if (B <= 0 || L <= 0 || n_group <= 0 || n_group > 16 || halo < 0 || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
+    // n_half <= 4 like its partner t2s_wg_res_only_start and the folded WN.end (8 rows = b ; log_s of 4 channels)
+    if (n_half <= 0 || n_half > 4 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
+    if (!win_chunks_ok(taps, n_half, win_chunks) || taps > t2s_flow_boundary_max_taps()) return T2S_EINVAL;
+    if (W && (n_rem < n_half || n_rem > 16 || c_off + n_rem > n_group)) return T2S_EINVAL;
+    if (fold_acc) {
+        if (!bes || !b_end || nslots <= 0 || n_layers <= 0) return T2S_EINVAL;
+        if (n_half_prev <= 0 || n_half_prev > 4 || c_off_prev < 0 || c_off_prev + 2 * n_half_prev > n_group) return T2S_EINVAL;
+    }
+    FlowBoundaryArgs a;
+    memset(&a, 0, sizeof(a));
+    a.z_in = z_in; a.z_out = z_out; a.fold_acc = fold_acc; a.bes = bes; a.b_end = b_end; a.log_s = fold_acc ? log_s : nullptr;
+    a.W = W; a.W_hi = (u16*)W_hi; a.W_lo = (u16*)W_lo;
+    a.nslots = nslots; a.n_layers = n_layers; a.c_off_prev = c_off_prev; a.nh_prev = n_half_prev;
+    a.c_off = c_off; a.n_rem = n_rem; a.nh = n_half;
+    a.G = n_group; a.L = L; a.Lp = Lp; a.halo = halo; a.taps = taps; a.nwc = win_chunks;
+    T2S_CHECK_HIP(t2s_launch_flow_boundary(a, B, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 int t2s_wg_end_fold_affine(const float* fold_acc, int nslots, const float* bes, int n_layers, const float* b_end,
                            float* z, float* log_s, float* wn_out, int B, int n_group, int c_off, int n_half, int L, int reverse,
                            void* stream) {

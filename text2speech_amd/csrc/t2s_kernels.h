@@ -60,6 +60,12 @@ struct ConvGemmArgs {
     int ph_bper;           // batch entries per tile = 256 / ph_FT
     int ph_nft;            // frame tiles per batch entry
     int ph_Fp;             // rows of the mel-window planes S[B][sc][ph_Fp][32]
+    // RESSKIP, 128-row tiles, PERM_PAIR8 rows, first layer of a flow (t2s_wg_res_only_start): the residual values are not read
+    // from the X planes but rebuilt, x0[c][t] = x0_b[c] + sum_j x0_w[c][j] * x0_z[b][x0_coff + j][t]  (WN.start)
+    const float* x0_z;     // [B][x0_G][L]
+    const float* x0_w;     // [C][x0_nh]
+    const float* x0_b;     // [C]
+    int x0_G, x0_coff, x0_nh;      // x0_nh <= 4
 };
 
 hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows = 256);
@@ -151,6 +157,24 @@ hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C,
 hipError_t t2s_launch_end_fold_affine(const float* fold_acc, int nslots, const float* bes, int n_layers,
                                       const float* b_end, float* z, float* log_s, float* wn_out, int B, int n_group, int c_off,
                                       int n_half, int L, int reverse, hipStream_t stream);
+// one flow boundary of the no-grad forward (waveglow_ops.hip, flow_boundary_kernel): the coupling of the flow before (fold_acc,
+// optional), this flow's 1x1 convolution (W, optional), the column copy to z_out and the window planes of the folded WN.start
+struct FlowBoundaryArgs {
+    const float* z_in;      // [B][G][L]
+    float* z_out;           // [B][G][L], not z_in (may be null in the window-only form)
+    const float* fold_acc;  // [nslots][B][8][L] of the flow before, or null
+    const float* bes;       // [n_layers][8]
+    const float* b_end;     // [2 nh_prev]
+    float* log_s;           // [B][nh_prev][L] of the flow before, or null
+    const float* W;         // [n_rem][n_rem], or null
+    u16* W_hi;              // window planes [B][nwc][Lp][32]
+    u16* W_lo;
+    int nslots, n_layers, c_off_prev, nh_prev;
+    int c_off, n_rem, nh;
+    int G, L, Lp, halo, taps, nwc;
+};
+hipError_t t2s_launch_flow_boundary(const FlowBoundaryArgs& a, int B, hipStream_t stream);
+int t2s_flow_boundary_max_taps();
 hipError_t t2s_launch_end_affine(const float* skip, const float* w_end, const float* b_end, float* z, float* log_s,
                                  float* wn_out, int B, int n_group, int c_off, int n_half, int C, int L, int Lp, int halo,
                                  int reverse, hipStream_t stream);

@@ -1074,3 +1074,98 @@ hipError_t t2s_launch_end_fold_affine(const float* fold_acc, int nslots, const f
                        n_layers, b_end, z, log_s, wn_out, B, n_group, c_off, n_half, L, reverse);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// The boundary between two flows of the no-grad forward in ONE launch (it was end_fold_affine_kernel -> convinv_kernel ->
+// start_kernel, three dependent launches over the same columns).  A workgroup owns FB_TC columns of one batch entry and, per column:
+//   (1) the affine coupling of the flow before (fold_acc given): end_fold_affine_kernel's forward direction, sums in its order;
+//   (2) this flow's 1x1 convolution (W given) on channels [c_off, c_off + n_rem): convinv_kernel's accumulation order;
+//   (3) all G channels of the finished column -> z_out, a second buffer: the window of row t reads the finished columns
+//       t + tap - taps / 2, which belong to the neighbouring workgroup at the edges of the range, so the input stays intact;
+//   (4) the window planes of the folded WN.start exactly as start_kernel defines them - and no X planes: the layer-0 residual GEMM
+//       rebuilds x0 from z_out (conv_gemm.hip, the X0 variant).
+// The taps - 1 edge columns are recomputed from the neighbours' ranges with the same arithmetic (so they carry the same bits) and the
+// 16-byte pieces of the window rows are spread over all 256 threads: the grid is over columns only.
+// fold_acc == NULL and W == NULL: window-only writer (z_out may be NULL then).
+#define FB_TC 64            // columns per workgroup: 8 x 2000 columns give 256 workgroups
+#define FB_EDGE 32          // most edge columns (taps - 1) a workgroup takes from its neighbours' ranges
+__global__ __launch_bounds__(256) void flow_boundary_kernel(const FlowBoundaryArgs a) {
+    __shared__ float zs[16][FB_TC + FB_EDGE];       // the columns after (1)
+    __shared__ float zo[16][FB_TC + FB_EDGE];       // rows [0, n_rem): channels [c_off, c_off + n_rem) after (2)
+    __shared__ float ws[16 * 16];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int G = a.G, L = a.L;
+    const int hw = a.taps >> 1, tce = FB_TC + 2 * hw;
+    const int t0 = blockIdx.x * FB_TC, te0 = t0 - hw;       // first own column, first staged column
+    if (a.W && tid < a.n_rem * a.n_rem) ws[tid] = a.W[tid];
+    for (int idx = tid; idx < G * tce; idx += 256) {
+        const int g = idx / tce, lc = idx - g * tce, t = te0 + lc;
+        zs[g][lc] = (t >= 0 && t < L) ? a.z_in[((size_t)b * G + g) * L + t] : 0.f;
+    }
+    __syncthreads();
+    if (a.fold_acc) {
+        const int nh = a.nh_prev, B = gridDim.y;
+        for (int idx = tid; idx < nh * tce; idx += 256) {
+            const int i = idx / tce, lc = idx - i * tce, t = te0 + lc;
+            if (t < 0 || t >= L) continue;
+            float bb = a.b_end[i], ls = a.b_end[nh + i];
+            for (int l = 0; l < a.n_layers; ++l) { bb += a.bes[l * 8 + i]; ls += a.bes[l * 8 + nh + i]; }
+            for (int s = 0; s < a.nslots; ++s) {
+                bb += a.fold_acc[(((size_t)s * B + b) * 8 + i) * L + t];
+                ls += a.fold_acc[(((size_t)s * B + b) * 8 + nh + i) * L + t];
+            }
+            const int g = a.c_off_prev + nh + i;
+            const float a1 = zs[g][lc];
+            zs[g][lc] = expf(ls) * a1 + bb;
+            if (a.log_s && lc >= hw && lc < hw + FB_TC) a.log_s[((size_t)b * nh + i) * L + t] = ls;
+        }
+        __syncthreads();
+    }
+    if (a.W) {
+        const int n = a.n_rem;
+        for (int idx = tid; idx < n * tce; idx += 256) {
+            const int i = idx / tce, lc = idx - i * tce;
+            float s = 0.f;
+            for (int j = 0; j < n; ++j) s += ws[i * n + j] * zs[a.c_off + j][lc];
+            zo[i][lc] = s;
+        }
+        __syncthreads();
+    }
+    const int c_lo = a.W ? a.c_off : G, c_hi = a.W ? a.c_off + a.n_rem : G;       // channels that live in zo
+    auto col = [&](int g, int lc) { return (g >= c_lo && g < c_hi) ? zo[g - c_lo][lc] : zs[g][lc]; };
+    if (a.z_out) {
+        for (int idx = tid; idx < G * FB_TC; idx += 256) {
+            const int g = idx / FB_TC, r = idx - g * FB_TC, t = t0 + r;
+            if (t < L) a.z_out[((size_t)b * G + g) * L + t] = col(g, r + hw);
+        }
+    }
+    const int nh = a.nh, nw = nh + 1, ncol = a.taps * nw, nwc = a.nwc, spc = 4 / nwc;
+    for (int idx = tid; idx < FB_TC * nwc * 4; idx += 256) {
+        const int q = idx & 3, rc = idx >> 2, chunk = rc % nwc, r = rc / nwc, t = t0 + r;
+        if (t >= L) continue;
+        u16 hi[8], lo[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int cc = q * 8 + e;
+            const int sidx = cc / ncol, c = cc - sidx * ncol;
+            const int tap = c / nw, j = c - tap * nw;
+            const int tt = t + tap - hw;
+            float v = 0.f;
+            if (sidx < spc && tt >= 0 && tt < L) v = j < nh ? col(a.c_off + j, r + tap) : 1.0f;
+            start_fold_term(v, chunk * spc + sidx, false, hi[e], lo[e]);
+        }
+        uint4 ph, pl;
+        ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
+        ph.z = hi[4] | ((uint32_t)hi[5] << 16); ph.w = hi[6] | ((uint32_t)hi[7] << 16);
+        pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
+        pl.z = lo[4] | ((uint32_t)lo[5] << 16); pl.w = lo[6] | ((uint32_t)lo[7] << 16);
+        const size_t o = (((size_t)b * nwc + chunk) * a.Lp + a.halo + t) * 32 + q * 8;
+        *(uint4*)(a.W_hi + o) = ph;
+        *(uint4*)(a.W_lo + o) = pl;
+    }
+}
+int t2s_flow_boundary_max_taps() { return FB_EDGE + 1; }
+hipError_t t2s_launch_flow_boundary(const FlowBoundaryArgs& a, int B, hipStream_t stream) {
+    hipLaunchKernelGGL(flow_boundary_kernel, dim3((a.L + FB_TC - 1) / FB_TC, B), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}

@@ -225,8 +225,19 @@ class _Engine:
             return False
         return g["ncol0"] <= 32 and g["Cpad"] // 32 >= g["nwc"]
 
+    def flow_boundary_on(self):
+        """True when the folded path also takes the flow boundaries in one launch each (t2s_wg_flow_boundary: coupling of the flow
+        before, 1x1 convolution, window planes) and lets the layer-0 residual GEMM rebuild x0 instead of reading X planes nobody wrote
+        (t2s_wg_res_only_start).  Needs the residual rows in the PAIR8 order (C % 32 == 0) and a layer that has a
+        residual half (n_layers >= 2); both kernels hold n_half <= 4 audio channels, as the folded WN.end does.  The callers decide
+        once per call and hand the answer to pack_weights() (which records it) and _wn().  T2S_FLOW_BOUNDARY=0 selects the three-kernel
+        boundary with the X-plane round trip (A/B runs, the comparison test)."""
+        g = self.geom()
+        return (self.start_fold_on() and os.environ.get("T2S_FLOW_BOUNDARY", "1") != "0" and g["C"] % 32 == 0 and g["nl"] >= 2
+                and self.m.n_group // 2 <= 4)
+
     # ------------------------------------------------------------------ weights
-    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False, start_fold=False):
+    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False, start_fold=False, flow_boundary=False):
         """res_pair8: pack the residual rows of every res/skip convolution in the 8-consecutive-channels order the folded no-grad
         path's residual GEMM wants (t2s_wg_res_only(pair8 = 1)); the training path keeps the identity order.
         start_fold: layer 0 of every flow gets the operand of the folded WN.start (A0h / A0l: the composed block, then the
@@ -235,7 +246,11 @@ class _Engine:
         res_pair8 = bool(res_pair8) and self.geom()["C"] % 32 == 0
         start_fold = bool(start_fold)
         key = tuple(p._version for p in m.parameters()) + (str(device), res_pair8, start_fold)
+        # which boundary the caller takes (flow_boundary_on()) changes nothing in the packed weights: recorded next to them, as
+        # start_fold is, for whoever asks which path ran
+        flow_boundary = bool(flow_boundary) and start_fold and res_pair8
         if not force and self.packed is not None and self.packed_key == key:
+            self.packed["flow_boundary"] = flow_boundary
             return self.packed
         g = self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
@@ -365,6 +380,7 @@ class _Engine:
         self.packed_key = key
         self.packed["res_pair8"] = res_pair8
         self.packed["start_fold"] = start_fold
+        self.packed["flow_boundary"] = flow_boundary
         self._keep = keep
         return self.packed
 
@@ -432,6 +448,7 @@ class _Engine:
                      Sh=torch.zeros(B, sc, Lp, 32, **bf), Sl=torch.zeros(B, sc, Lp, 32, **bf),
                      Wh=torch.zeros(B, g["nwc"], Lp, 32, **bf), Wl=torch.zeros(B, g["nwc"], Lp, 32, **bf),      # folded WN.start: window
                      skip=torch.zeros(B, xc, Lp, 32, dtype=torch.float32, device=device),
+                     z2=torch.empty(B, self.m.n_group, L, dtype=torch.float32, device=device),        # one-launch flow boundaries: the other z
                      fold_acc=torch.zeros(_lib.load().t2s_wg_gate_fold_slots(B, g["C"], L), B, 8, L, dtype=torch.float32,
                                           device=device))
             self.ws = {key: w}      # keep one shape resident
@@ -454,9 +471,32 @@ class _Engine:
                   _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), _lib.current_stream())
         self._keep_up = (mel32, W, bias)
 
-    def _wn(self, k, z, B, L, w, c_off, n_half, ph=None):
+    def _boundary(self, k, z_in, z_out, B, L, w, prev=None, W=None):
+        """t2s_wg_flow_boundary in front of flow k: prev = (flow index, log_s) applies that flow's coupling, W this flow's 1x1
+        convolution, both to z_in -> z_out; always writes flow k's window planes.  prev = W = None: the window planes only."""
+        m, g = self.m, self.geom()
+        c_off, n_rem, n_half = self._flow_geom(k)
+        fold_acc = bes = b_end = log_s = None
+        nslots = c_off_p = nh_p = 0
+        if prev is not None:
+            kp, log_s = prev
+            c_off_p, _, nh_p = self._flow_geom(kp)
+            fold_acc, nslots = w["fold_acc"], w["fold_acc"].size(0)
+            bes = self.packed["flows"][kp]["bes"]
+            b_end = _f32c(m.WN[kp].end.bias)
+            self._keep_boundary.append(b_end)
+        # Stream order makes the reuse of fold_acc and of the window planes safe: this launch reads the sums of the flow before
+        # ahead of flow k's layer-0 gate GEMM, which re-initialises them, and writes the window planes behind the last launch (the
+        # layer-0 gate GEMM of the flow before) that read them.
+        _lib.call("t2s_wg_flow_boundary", _lib.ptr(z_in), _lib.ptr(z_out), _lib.ptr(fold_acc), nslots, _lib.ptr(bes), g["nl"],
+                  _lib.ptr(b_end), _lib.ptr(log_s), c_off_p, nh_p, _lib.ptr(W), c_off, n_rem, n_half, B, m.n_group, L, w["Lp"],
+                  g["halo"], g["ks"], g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), _lib.current_stream())
+
+    def _wn(self, k, z, B, L, w, c_off, n_half, ph=None, fb=False, window_done=False):
         """start -> n_layers x (in+cond+gate, res/skip); leaves the skip sum in w['skip'].  ph = (M_hi, M_lo, Fp, P, K2):
-        conditioning through the composed weights and the mel-window planes (inverse flow)."""
+        conditioning through the composed weights and the mel-window planes (inverse flow).  fb: the caller's
+        flow_boundary_on() - nobody writes x0 to the X planes, the layer-0 residual GEMM rebuilds it from z; window_done: the caller's t2s_wg_flow_boundary already wrote this flow's
+        window planes from z."""
         m, g = self.m, self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
         fl = self.packed["flows"][k]
@@ -467,7 +507,13 @@ class _Engine:
         # layer 0 through the folded WN.start: the X planes are still written (the residual stream needs x0), the gate GEMM reads
         # the window planes instead
         sf = bool(self.packed.get("start_fold")) and self.use_fold and ph is None
-        if sf:
+        # ... and with the one-launch boundary nobody writes them: the layer-0 residual GEMM rebuilds x0 from z
+        fb = bool(fb) and sf
+        if fb:
+            if not window_done:
+                self._keep_boundary = []
+                self._boundary(k, z, None, B, L, w)
+        elif sf:
             _lib.call("t2s_wg_start_window", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
                       C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), ks, g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), st)
         else:
@@ -510,7 +556,12 @@ class _Engine:
                 self.gemm_events.append((e0, e1))
             n_res = C if i < nl - 1 else 0
             if self.use_fold:
-                if n_res:       # the last layer has no residual half, and its skip half lives in the fold
+                if n_res and fb and i == 0:
+                    _lib.call("t2s_wg_res_only_start", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
+                              _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start),
+                              m.n_group, c_off, n_half, _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"],
+                              ly["Mpad2"], st)
+                elif n_res:     # the last layer has no residual half, and its skip half lives in the fold
                     _lib.call("t2s_wg_res_only", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
                               _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
                               g["halo"], ly["Mpad2"], 1 if self.packed.get("res_pair8") else 0, st)
@@ -530,14 +581,15 @@ class _Engine:
         g = self.geom()
         if n_in != n_half or spect.size(1) != g["n_cond"] or spect.size(2) != L:
             raise ValueError("WN[%d] takes audio [B, %d, L] and spect [B, %d, L]" % (k, n_half, g["n_cond"]))
-        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on())
+        fb = self.flow_boundary_on()
+        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on(), flow_boundary=fb)
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         spect32 = _f32c(spect)
         _lib.call("t2s_f32_to_planes", _lib.ptr(spect32), B, g["n_cond"], L, w["Lp"], g["halo"], _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), st)
         z = torch.zeros(B, m.n_group, L, dtype=torch.float32, device=dev)
         z[:, c_off:c_off + n_half] = audio.detach().to(torch.float32)
-        self._wn(k, z, B, L, w, c_off, n_half)
+        self._wn(k, z, B, L, w, c_off, n_half, fb=fb)
         wn_out = torch.empty(B, 2 * n_half, L, dtype=torch.float32, device=dev)
         if self.use_fold:
             w2 = dict(w)
@@ -588,6 +640,13 @@ class _Engine:
         self.side_stream = side
         audio32 = _f32c(audio)
         z = torch.empty(B, G, L, dtype=torch.float32, device=dev)
+        # one-launch flow boundaries read one [B, G, L] buffer and write the other: the squeezed audio goes into the one that makes
+        # the caller's own tensor (never the workspace's) the last one written
+        fb = self.flow_boundary_on()
+        if fb:
+            bufs = [z, w["z2"]] if m.n_flows % 2 == 0 else [w["z2"], z]
+            z = bufs[0]
+            self._keep_boundary = []
         log_s_list, log_det_list = [], []
         log_det = torch.empty(m.n_flows, dtype=torch.float32, device=dev)
         Ws = [_f32c(m.convinv[k].conv.weight) for k in range(m.n_flows)]
@@ -618,17 +677,27 @@ class _Engine:
         pack_events = []
         pack_s.wait_stream(main)
         with torch.cuda.stream(pack_s):
-            self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=self.use_fold, start_fold=self.start_fold_on())
+            self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=self.use_fold, start_fold=self.start_fold_on(),
+                              flow_boundary=fb)
         main.wait_event(ev_inputs)
         st = _lib.current_stream()
         for k in range(m.n_flows):
             main.wait_event(pack_events[k])
             c_off, n_rem, n_half = self._flow_geom(k)
             Wk = Ws[k]
-            _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(Wk), B, G, c_off, n_rem, L, st)
-            self._wn(k, z, B, L, w, c_off, n_half)
             log_s = torch.empty(B, n_half, L, dtype=torch.float32, device=dev)
-            self._end(k, z, log_s, B, L, w, c_off, n_half, reverse=False)
+            if fb:
+                # boundary(k): coupling of flow k - 1 (none in front of flow 0), this flow's 1x1 convolution, the window planes
+                z_out = bufs[(k + 1) % 2]
+                self._boundary(k, z, z_out, B, L, w, prev=(k - 1, log_s_list[k - 1]) if k else None, W=Wk)
+                z = z_out
+                self._wn(k, z, B, L, w, c_off, n_half, fb=True, window_done=True)
+                if k == m.n_flows - 1:          # the last coupling has no boundary behind it: in place on the current buffer
+                    self._end(k, z, log_s, B, L, w, c_off, n_half, reverse=False)
+            else:
+                _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(Wk), B, G, c_off, n_rem, L, st)
+                self._wn(k, z, B, L, w, c_off, n_half)
+                self._end(k, z, log_s, B, L, w, c_off, n_half, reverse=False)
             log_s_list.append(log_s)
             log_det_list.append(log_det[k])
         main.wait_stream(side)               # log_det
@@ -645,7 +714,8 @@ class _Engine:
         # reference glow.py:254-255: drop the last (kernel - stride) upsampled samples
         T = (frames - 1) * up.stride[0] + up.kernel_size[0] - (up.kernel_size[0] - up.stride[0])
         L = T // G
-        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on())
+        fb = self.flow_boundary_on()
+        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on(), flow_boundary=fb)
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         # Weights are packed once here, so the conditioning path can be composed with the upsampler (K = 640 -> 320 in the gate
@@ -693,7 +763,7 @@ class _Engine:
                 fl["w_inv"] = torch.empty(n_rem, n_rem, dtype=torch.float32, device=dev)
                 _lib.call("t2s_small_logdet_inv", _lib.ptr(Wk), n_rem, 1.0, None, _lib.ptr(fl["w_inv"]), st)
                 fl["_Wk"] = Wk
-            self._wn(k, z, B, L, w, c_off, n_half, ph=ph)
+            self._wn(k, z, B, L, w, c_off, n_half, ph=ph, fb=fb)
             self._end(k, z, None, B, L, w, c_off, n_half, reverse=True)
             _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(fl["w_inv"]), B, G, c_off, n_rem, L, st)
         audio = torch.empty(B, L * G, dtype=torch.float32, device=dev)
