@@ -502,7 +502,8 @@ int t2s_wgrad_gemm_flat(const void* A_hi, const void* A_lo, const void* X_hi, co
  * kernel, whose epilogue stores 16-byte pieces; any other ldp the round-2 lockstep kernel.
  * Every K-block is a WHOLE block of 32 plane rows starting at row 32 k (+ the shift folded into the pointer): the caller makes
  * sure rows [32 k0 - max shift, 32 k1 + max shift) exist in every plane (halo % 32 == 0 does, text2speech_amd/glow.py geom()).
- * bias_cols != 0 (ping-pong kernel only, ldp >= N + 4): columns N .. N+3 of every slab also receive four partial sums of the
+ * bias_cols != 0 (ping-pong kernel only, ldp >= N + 4, N % 256 == 0 - whole N tiles: in a ragged last tile columns N .. N+3 are
+ * scratch columns of the tile's own epilogue - else T2S_EINVAL): columns N .. N+3 of every slab also receive four partial sums of the
  * M-side operand's rows over the slab's K range - the bias gradient of a convolution, db[m] = sum_t d_out[m][t], without an
  * all-ones column in the N-side table (t2s_wn_backward adds them: n_bias_cols = 4).
  * Both tables live in device memory ([n_tiles * 8] entries).  Replaces 7 t2s_plane_transpose launches per WN layer. */

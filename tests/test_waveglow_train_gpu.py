@@ -19,26 +19,26 @@ def _rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-def _train_once(cfg, batch, n_samples, seed):
-    """One forward+backward on the GPU and the same through the CPU oracle."""
+def _train_once(cfg, batch, n_samples, seed, loss_fn=None):
+    """One forward+backward on the GPU and the same through the CPU oracle.  loss_fn(outputs) replaces WaveGlowLoss on both sides."""
     assert torch.cuda.is_available()
     _lib.load()
     from oracle import waveglow_oracle as O
     from text2speech_amd.glow import WaveGlow, WaveGlowLoss
     sd = synth.waveglow_state(cfg)
-    mel, audio = synth.waveglow_inputs(batch, n_samples, seed=seed)
+    mel, audio = synth.waveglow_inputs(batch, n_samples, n_mel=cfg["n_mel_channels"], seed=seed)
     m = WaveGlow(**cfg)
     m.load_state_dict(sd)
     m = m.to(DEV).train()
     out = m((mel.to(DEV), audio.to(DEV)))
-    loss = WaveGlowLoss(1.0)(out)
+    loss = WaveGlowLoss(1.0)(out) if loss_fn is None else loss_fn(out)
     loss.backward()
     torch.cuda.synchronize()
     got = {n: p.grad.detach().cpu() for n, p in m.named_parameters() if p.grad is not None}
     # CPU autograd through the oracle (f32)
     sd_cpu = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     outo = O.waveglow_forward(sd_cpu, cfg, mel, audio)
-    losso = O.waveglow_loss(outo)
+    losso = O.waveglow_loss(outo) if loss_fn is None else loss_fn(outo)
     losso.backward()
     want = {k: v.grad for k, v in sd_cpu.items() if v.grad is not None}
     return dict(got=got, want=want, loss=float(loss), loss_o=float(losso), model=m, n_params=len(list(m.parameters())))
@@ -331,3 +331,91 @@ def test_backward_is_bitwise_reproducible():
         runs.append({n: p.grad.detach().clone() for n, p in m.named_parameters() if p.grad is not None})
     for n in runs[0]:
         assert torch.equal(runs[0][n], runs[1][n]) and torch.equal(runs[0][n], runs[2][n]), n
+
+
+# ---- whole steps at awkward lengths, channel counts and kernel sizes, on every path the backward can take (a short model keeps
+# the CPU oracle quick; the bars are the ones above: loss within 1e-4, a gradient for every parameter, worst tensor below 2e-3)
+
+def _short_cfg(C=64, ks=3, **over):
+    return dict(synth.WAVEGLOW_SMALL, n_flows=4, n_early_every=2, WN_config=dict(n_layers=4, n_channels=C, kernel_size=ks), **over)
+
+
+def _assert_step_vs_oracle(t):
+    assert abs(t["loss"] - t["loss_o"]) < 1e-4, (t["loss"], t["loss_o"])
+    assert len(t["got"]) == t["n_params"], "a parameter received no gradient"
+    worst = sorted(((_rel(t["got"][n], w), n) for n, w in t["want"].items()), reverse=True)
+    assert all(n in t["got"] for n in t["want"]) and worst[0][0] < 2e-3, worst[:6]
+    print("worst per-tensor gradient error %.2e (%s)" % worst[0])
+
+
+def _train_state(t):
+    """The training workspace (glow_autograd._alloc_train) of the one shape the model has run."""
+    states = [v for k, v in t["model"]._eng().ws.items() if k[0] == "train"]
+    assert len(states) == 1
+    return states[0]
+
+
+@pytest.mark.parametrize("batch,n_samples", [(1, 2005), (1, 8), (5, 777)])
+def test_odd_sizes_grads_vs_oracle(batch, n_samples):
+    """Lengths that are no multiple of 32 (L = 250, 1, 97), a tail of samples the squeeze drops, B = 1 and an odd batch."""
+    _assert_step_vs_oracle(_train_once(_short_cfg(), batch, n_samples, 41))
+
+
+def test_ragged_channel_tiles_grads_vs_oracle():
+    """C = 160: five 32-channel chunks, the last 128-row and 256-row tiles of every GEMM partly filled."""
+    _assert_step_vs_oracle(_train_once(_short_cfg(C=160), 2, 2048, 42))
+
+
+def test_kernel_size_5_grads_vs_oracle():
+    _assert_step_vs_oracle(_train_once(_short_cfg(ks=5), 2, 2048, 43))
+
+
+def test_time_major_fallback_grads_vs_oracle():
+    """n_mel_channels = 10: 80 conditioning channels are no multiple of 32, so the weight gradients take the time-major path
+    (t2s_plane_transpose, t2s_tm_ones_row, t2s_wgrad_gemm_flat) instead of t2s_wgrad_cl."""
+    t = _train_once(_short_cfg(n_mel_channels=10), 2, 2048, 44)
+    assert _train_state(t).cl_ok is False
+    _assert_step_vs_oracle(t)
+
+
+@pytest.mark.parametrize("batch,n_samples,p8_c,p8_x", [(2, 34816, 1, 0), (4, 51200, 1, 1)])
+def test_ping_pong_backward_grads_vs_oracle(batch, n_samples, p8_c, p8_x):
+    """The 256-row ping-pong backward GEMMs against the oracle: at 2 x 34816 (L = 4352) only the conditioning GEMM reaches 100
+    tiles (PERM_PAIR8 operand there, 128-row lockstep kernels with identity rows for the rest), at 4 x 51200 (L = 6400) all do."""
+    t = _train_once(_short_cfg(), batch, n_samples, 45)
+    ts = _train_state(t)
+    assert (ts.p8_c, ts.p8_x) == (p8_c, p8_x)
+    _assert_step_vs_oracle(t)
+
+
+def test_general_loss_grads_vs_oracle(monkeypatch):
+    """A loss with element-wise upstream gradients: (z a).sum() + sum_k (log_s_k b_k).sum() + sum_k c_k log_det_W_k with random
+    a, b_k, c_k (scaled by 1 / numel(z), as WaveGlowLoss is) - gz is non-null and no g_log_s is a broadcast scalar."""
+    from text2speech_amd import glow_autograd as GA
+    cfg, B, T = _short_cfg(), 2, 2048
+    L = T // cfg["n_group"]
+    N = B * cfg["n_group"] * L
+    gen = torch.Generator().manual_seed(46)
+    a = torch.randn(B, cfg["n_group"], L, generator=gen) / N
+    bs = [torch.randn(B, nh, L, generator=gen) / N for _, nh in synth.waveglow_flow_sizes(cfg)]
+    cs = [float(torch.randn(1, generator=gen)) / N for _ in bs]
+
+    def loss_fn(outputs):
+        z, log_s, log_det = outputs
+        d = z.device
+        return ((z * a.to(d)).sum() + sum((ls * b.to(d)).sum() for ls, b in zip(log_s, bs))
+                + sum(c * ld for c, ld in zip(cs, log_det)))
+
+    seen = {}
+    backward_train = GA.backward_train
+
+    def spy(eng, ts, gz, g_log_s, g_log_det):
+        seen.update(gz=gz, g_log_s=list(g_log_s))
+        return backward_train(eng, ts, gz, g_log_s, g_log_det)
+
+    monkeypatch.setattr(GA, "backward_train", spy)
+    t = _train_once(cfg, B, T, 46, loss_fn=loss_fn)
+    assert seen["gz"] is not None
+    assert len(seen["g_log_s"]) == cfg["n_flows"]
+    assert all(g is not None and any(s != 0 for s in g.stride()) for g in seen["g_log_s"])
+    _assert_step_vs_oracle(t)

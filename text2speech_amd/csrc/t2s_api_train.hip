@@ -201,7 +201,8 @@ int t2s_wgrad_cl(const t2s_wgrad_chunk* a_chunks, int n_a_chunks, const t2s_wgra
                  int B, int M, int N, int ldp, int k0, int k1, int nsplit, int bias_cols, void* stream) {
     static_assert(sizeof(t2s_wgrad_chunk) == sizeof(WgradChunk), "t2s_wgrad_chunk layout");
     if (!a_chunks || !b_chunks || !out || B <= 0 || M <= 0 || N <= 0 || k0 < 0 || k0 >= k1 || nsplit < 1) return T2S_EINVAL;
-    if (ldp < N || (ldp % 4 == 0 && !al16(out)) || (bias_cols && (ldp % 4 || ldp < N + 4))) return T2S_EINVAL;
+    // (bias_cols on whole N tiles only: t2s_launch_wgrad_cl, which holds the same three conditions, says why)
+    if (ldp < N || (ldp % 4 == 0 && !al16(out)) || (bias_cols && (ldp % 4 || ldp < N + 4 || N % 256))) return T2S_EINVAL;
     const int n_mtiles = cdiv(M, 256), n_ntiles = cdiv(N, 256);
     if (n_a_chunks != n_mtiles * 8 || n_b_chunks != n_ntiles * 8 || nsplit > B * (k1 - k0)) return T2S_EINVAL;
     WgradClArgs a;

@@ -513,7 +513,9 @@ __global__ __launch_bounds__(512) void wgrad_cl_pp_kernel(const WgradClArgs a) {
 hipError_t t2s_launch_wgrad_cl(const WgradClArgs& a, hipStream_t stream) {
     const int nwg = a.n_mtiles * a.n_ntiles * a.nslab;
     constexpr int lds = 2 * WG_STAGE;
-    if (a.bias_cols && !(a.ldp % 4 == 0 && a.ldp >= a.N + 4)) return hipErrorInvalidValue;    // only the ping-pong kernel has it
+    // bias_cols: only the ping-pong kernel has it, and only on whole N tiles - in a ragged last tile columns N .. N+3 are columns the
+    // tile's own epilogue stores scratch to (16-byte pieces up to ldp), unordered against the bias sums other waves write there
+    if (a.bias_cols && !(a.ldp % 4 == 0 && a.ldp >= a.N + 4 && a.N % 256 == 0)) return hipErrorInvalidValue;
     if (a.ldp % 4 == 0) {
         static std::atomic<unsigned long long> attr_mask_pp{0};
         const hipError_t e = t2s_raise_lds_limit((const void*)wgrad_cl_pp_kernel, lds, attr_mask_pp);

@@ -86,7 +86,7 @@ def _alloc_train(eng, B, L, dev):
     st.DP2 = [pl(nl * 2 * xc), pl(nl * 2 * xc)]
     st.dp_chunks = nl * 2 * xc
     st.DSp = pl(sc)
-    st.N2 = 3 * C + g["n_cond"] + 1
+    st.N2 = g["ks"] * C + g["n_cond"] + 1        # [x at every tap | spect | 1]
     st.N2pad = -(-st.N2 // 256) * 256
     st.N1 = C + 1
     st.N1pad = -(-st.N1 // 256) * 256
