@@ -211,7 +211,7 @@ def test_forward_small_on_vs_off_golden_oracle(monkeypatch, golden_dir, name, ba
         with torch.no_grad():
             out = m((mel.to(DEV), audio.to(DEV)))
         torch.cuda.synchronize()
-        assert bool(eng.packed["flow_boundary"]) == on and bool(eng.packed["start_fold"])
+        assert bool(eng.last_path.boundary) == on and bool(eng.packed["start_fold"])
         return out
     (z, log_s, log_det), (z0, log_s0, _) = _both(monkeypatch, run)
     with torch.no_grad():
@@ -241,7 +241,7 @@ def test_infer_small_on_vs_off_golden(monkeypatch, golden_dir):
 
     def run(on):
         a = m.infer(mel.to(DEV), sigma=0.666, noise=noise)
-        assert bool(eng.packed["flow_boundary"]) == on and bool(eng.packed["start_fold"])
+        assert bool(eng.last_path.boundary) == on and bool(eng.packed["start_fold"])
         return a
     a_on, a_off = _both(monkeypatch, run)
     d = _rel(a_on, a_off)
@@ -266,7 +266,7 @@ def test_wn_forward_on_vs_off(monkeypatch):
 
         def run(on):
             got = m.WN[k]((audio.to(DEV), spect.to(DEV)))
-            assert bool(eng.packed["flow_boundary"]) == on
+            assert bool(eng.last_path.boundary) == on
             return got
         on, off = _both(monkeypatch, run)
         d = _rel(on, off)
@@ -288,7 +288,7 @@ def test_stress_weights_vs_oracle():
     with torch.no_grad():
         z, log_s, _ = m((mel.to(DEV), audio.to(DEV)))
         torch.cuda.synchronize()
-        assert bool(eng.packed["flow_boundary"])
+        assert bool(eng.last_path.boundary)
         zo, lso, _ = O.waveglow_forward(sd, cfg, mel, audio)
     assert max(float(l.abs().max()) for l in lso) > 2.5          # the stress is real
     rz, mz = _rel(z, zo), _maxrel(z, zo)
@@ -310,7 +310,7 @@ def test_second_shorter_forward_matches_a_fresh_model():
         z1, ls1, _ = m((mel1.to(DEV), audio1.to(DEV)))
         z1c, ls1c = z1.clone(), [t.clone() for t in ls1]
         z2, ls2, _ = m((mel2.to(DEV), audio2.to(DEV)))
-        assert bool(m._eng().packed["flow_boundary"])
+        assert bool(m._eng().last_path.boundary)
         z2f, ls2f, _ = _build(cfg)((mel2.to(DEV), audio2.to(DEV)))
         z1b, _, _ = m((mel1.to(DEV), audio1.to(DEV)))           # same shape as the first call again
     torch.cuda.synchronize()

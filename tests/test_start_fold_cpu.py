@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import waveglow_oracle as O
-from text2speech_amd import planes, synth
+from text2speech_amd import _lib, planes, synth
 
 
 def _layer0_preact_oracle(sd, cfg, k, a):
@@ -58,29 +58,46 @@ def test_window_definition():
 
 def test_start_fold_switch_and_fallback(monkeypatch):
     """Host logic: on by default for the no-grad path, T2S_START_FOLD=0 and the composed-conditioning opt-in select the unfolded
-    layer 0, and a geometry whose taps do not fit a 32-wide K-step (kernel_size 7: 7 * 5 = 35 columns) falls back."""
+    layer 0, and a geometry whose taps do not fit a 32-wide K-step (kernel_size 7: 7 * 5 = 35 columns) falls back.  path() is the
+    one decision all of it comes from: the same cases on the whole record, the one-launch flow boundary included."""
     from text2speech_amd.glow import WaveGlow
     monkeypatch.delenv("T2S_START_FOLD", raising=False)
+    monkeypatch.delenv("T2S_FLOW_BOUNDARY", raising=False)
     monkeypatch.delenv("T2S_COND_COMPOSE", raising=False)
     eng = WaveGlow(**synth.WAVEGLOW_SMALL)._eng()
     assert eng.start_fold_on()
+    assert eng.path() == (True, True, None)
+    monkeypatch.setenv("T2S_FLOW_BOUNDARY", "0")
+    assert eng.path() == (True, False, None)
+    monkeypatch.delenv("T2S_FLOW_BOUNDARY")
     monkeypatch.setenv("T2S_START_FOLD", "0")
     assert not eng.start_fold_on()
+    assert eng.path() == (False, False, None)
     monkeypatch.setenv("T2S_START_FOLD", "1")
     assert eng.start_fold_on()
+    assert eng.path() == (True, True, None)
     monkeypatch.setenv("T2S_COND_COMPOSE", "1")
     assert not eng.start_fold_on()
+    assert eng.path() == (False, False, (32, 4, 320))
     monkeypatch.delenv("T2S_COND_COMPOSE")
-    eng.use_fold = False
-    assert not eng.start_fold_on()
     cfg7 = dict(synth.WAVEGLOW_SMALL, n_flows=4, WN_config=dict(n_layers=4, n_channels=64, kernel_size=7))
     assert not WaveGlow(**cfg7)._eng().start_fold_on()
+    assert WaveGlow(**cfg7)._eng().path() == (False, False, None)
     cfg5 = dict(synth.WAVEGLOW_SMALL, n_flows=4, WN_config=dict(n_layers=4, n_channels=128, kernel_size=5))
     e5 = WaveGlow(**cfg5)._eng()
     assert e5.start_fold_on() and e5.geom()["nwc"] == 4     # 5 * 5 = 25 columns: one column set per window chunk
+    assert e5.path() == (True, True, None)
     cfg5["WN_config"]["n_channels"] = 64
     assert not WaveGlow(**cfg5)._eng().start_fold_on()      # ... which needs four channel chunks of start_kernel workgroups
+    assert WaveGlow(**cfg5)._eng().path() == (False, False, None)
     assert eng.geom()["nwc"] == 2
+    # the one-launch boundary wants the residual rows in the PAIR8 order: C % 32 == 0
+    cfg48 = dict(synth.WAVEGLOW_SMALL, n_flows=4, WN_config=dict(n_layers=4, n_channels=48, kernel_size=3))
+    assert WaveGlow(**cfg48)._eng().path() == (True, False, None)
+    # every no-grad gate GEMM carries the folded WN.end (C % 16 == 0): refused here, by name, not by the first launch
+    cfg48["WN_config"]["n_channels"] = 40
+    with pytest.raises(_lib.T2SError, match="n_channels % 16"):
+        WaveGlow(**cfg48)._eng().path()
 
 
 @pytest.mark.parametrize("nwc,ncol", [(2, 15), (2, 9), (4, 25)])

@@ -12,9 +12,8 @@ eager-PyTorch fallback: without the library, or off-GPU, the calls raise.
 Reference lines are cited per method.
 """
 import ctypes
-import math
-
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F  # noqa: F401  (kept for API parity with the reference module)
@@ -181,6 +180,9 @@ def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+_Path = namedtuple("_Path", "start_fold boundary compose")      # which kernels a no-grad call takes: _Engine.path()
+
+
 class _Engine:
     """Owns the HBM-resident state of one WaveGlow: packed (hi, lo) bf16 weight
     planes and the activation workspaces, and issues the kernel sequence."""
@@ -190,7 +192,9 @@ class _Engine:
         self.packed = None
         self.packed_key = None
         self.ws = {}
-        self.use_fold = True        # no-grad forward / infer: WN.end folded into the skip path (t2s_wg_*_fold)
+        self.last_path = None       # the _Path of the latest forward / infer / WN.forward
+        self._keep = []             # the current call's temporaries whose pointers went to a kernel
+        self._streams = {}
         self.grad_sync = None       # distributed.GradSync: bucketed RCCL all-reduce issued from inside backward
         self.gemm_events = None     # bench.py: list of (start, end) torch.cuda.Event pairs around the gate GEMM
         self.gemm_event_stride = 1  # bench.py: time every n-th gate-GEMM launch (an event pair costs ~1.5 us of stream time)
@@ -215,77 +219,95 @@ class _Engine:
         g["nk2"] = g["Cpad"] // 32
         return g
 
-    def start_fold_on(self):
-        """True when the no-grad forward / infer takes layer 0 of every flow through WN.start folded into its gate GEMM (DESIGN.md
-        section 5): the taps of the n_half audio channels and of the ones-channel must fit 32 columns, and C must have as many
-        32-channel chunks as the window has (geom()["nwc"]: 2 or 4).  T2S_START_FOLD=0
-        selects the unfolded layer 0 (A/B runs, the comparison test); the opt-in composed-conditioning path keeps it too."""
+    def path(self):
+        """The kernel path of a no-grad call, decided here only: forward, infer and wn_forward take it once, keep it as last_path
+        and hand it down.
+        start_fold: layer 0 of every flow goes through WN.start folded into its gate GEMM: the taps of the n_half audio channels
+        and of the ones-channel must fit 32 columns, and C must have as many 32-channel chunks as the window has (geom()["nwc"]: 2
+        or 4).  T2S_START_FOLD=0 selects the unfolded layer 0 (A/B runs, the comparison test), as composed conditioning does.
+        boundary: the flow boundaries also take one launch each (t2s_wg_flow_boundary: coupling of the flow before, 1x1 convolution,
+        window planes) and the layer-0 residual GEMM rebuilds x0 instead of reading X planes nobody wrote (t2s_wg_res_only_start).
+        Needs the residual rows in the PAIR8 order (C % 32 == 0) and a layer that has a residual half (n_layers >= 2); both kernels
+        hold n_half <= 4 audio channels, as the folded WN.end does.  T2S_FLOW_BOUNDARY=0 selects the three-kernel boundary with the
+        X-plane round trip (A/B runs, the comparison test)."""
         g = self.geom()
-        if not self.use_fold or os.environ.get("T2S_START_FOLD", "1") == "0" or g["C"] % 16 or self.compose_geom() is not None:
-            return False
-        return g["ncol0"] <= 32 and g["Cpad"] // 32 >= g["nwc"]
+        if g["C"] % 16:         # every no-grad gate GEMM carries WN.end folded in, which the library has for such C only
+            raise _lib.T2SError("WaveGlow's forward without gradients, infer and WN.forward need n_channels %% 16 == 0, not %d" % g["C"])
+        compose = self.compose_geom()
+        start_fold = (compose is None and os.environ.get("T2S_START_FOLD", "1") != "0" and g["ncol0"] <= 32
+                      and g["Cpad"] // 32 >= g["nwc"])
+        boundary = (start_fold and os.environ.get("T2S_FLOW_BOUNDARY", "1") != "0" and g["C"] % 32 == 0 and g["nl"] >= 2
+                    and self.m.n_group // 2 <= 4)
+        return _Path(start_fold, boundary, compose)
 
-    def flow_boundary_on(self):
-        """True when the folded path also takes the flow boundaries in one launch each (t2s_wg_flow_boundary: coupling of the flow
-        before, 1x1 convolution, window planes) and lets the layer-0 residual GEMM rebuild x0 instead of reading X planes nobody wrote
-        (t2s_wg_res_only_start).  Needs the residual rows in the PAIR8 order (C % 32 == 0) and a layer that has a
-        residual half (n_layers >= 2); both kernels hold n_half <= 4 audio channels, as the folded WN.end does.  The callers decide
-        once per call and hand the answer to pack_weights() (which records it) and _wn().  T2S_FLOW_BOUNDARY=0 selects the three-kernel
-        boundary with the X-plane round trip (A/B runs, the comparison test)."""
-        g = self.geom()
-        return (self.start_fold_on() and os.environ.get("T2S_FLOW_BOUNDARY", "1") != "0" and g["C"] % 32 == 0 and g["nl"] >= 2
-                and self.m.n_group // 2 <= 4)
+    def start_fold_on(self):
+        return self.path().start_fold
+
+    def _stream(self, name, device):
+        """The engine's side stream of that name on that device, made on first use."""
+        key = (name, str(device))
+        if key not in self._streams:
+            self._streams[key] = torch.cuda.Stream(device=device)
+        return self._streams[key]
 
     # ------------------------------------------------------------------ weights
-    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False, start_fold=False, flow_boundary=False):
+    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False, start_fold=False):
         """res_pair8: pack the residual rows of every res/skip convolution in the 8-consecutive-channels order the folded no-grad
         path's residual GEMM wants (t2s_wg_res_only(pair8 = 1)); the training path keeps the identity order.
         start_fold: layer 0 of every flow gets the operand of the folded WN.start (A0h / A0l: the composed block, then the
         conditioning weights) and its in_layers[0] planes are NOT packed (A1h / A1l of layer 0 are stale then)."""
-        m = self.m
         res_pair8 = bool(res_pair8) and self.geom()["C"] % 32 == 0
-        start_fold = bool(start_fold)
-        key = tuple(p._version for p in m.parameters()) + (str(device), res_pair8, start_fold)
-        # which boundary the caller takes (flow_boundary_on()) changes nothing in the packed weights: recorded next to them, as
-        # start_fold is, for whoever asks which path ran
-        flow_boundary = bool(flow_boundary) and start_fold and res_pair8
+        key = tuple(p._version for p in self.m.parameters()) + (str(device), res_pair8, start_fold)
         if not force and self.packed is not None and self.packed_key == key:
-            self.packed["flow_boundary"] = flow_boundary
             return self.packed
-        g = self.geom()
-        C, nl, ks = g["C"], g["nl"], g["ks"]
-        st = _lib.current_stream()
         if self.packed is None or self.packed["device"] != device:
-            flows = []
-            for k in range(m.n_flows):
-                n_half = m.WN[k].start.in_channels
-                layers = []
-                for i in range(nl):
-                    rows2 = 2 * C if i < nl - 1 else C
-                    Mpad2 = _lib.padded_rows(rows2)
-                    layers.append(dict(
-                        A1h=torch.zeros(g["nk1"], g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                        A1l=torch.zeros(g["nk1"], g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                        b1=torch.zeros(g["Mpad1"], dtype=torch.float32, device=device),
-                        A2h=torch.zeros(g["nk2"], Mpad2, 32, dtype=torch.bfloat16, device=device),
-                        A2l=torch.zeros(g["nk2"], Mpad2, 32, dtype=torch.bfloat16, device=device),
-                        b2=torch.zeros(Mpad2, dtype=torch.float32, device=device), Mpad2=Mpad2,
-                        s_in=torch.empty(2 * C, dtype=torch.float32, device=device),
-                        s_cond=torch.empty(2 * C, dtype=torch.float32, device=device),
-                        s_rs=torch.empty(rows2, dtype=torch.float32, device=device),
-                        fold_A=torch.zeros(-(-C // 128) * 8192, dtype=torch.bfloat16, device=device)))
-                flows.append(dict(layers=layers, n_half=n_half, bes=torch.zeros(nl, 8, dtype=torch.float32, device=device),
-                                  w_start=torch.empty(C, n_half, dtype=torch.float32, device=device),
-                                  A0h=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                                  A0l=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                                  w_inv=None))
-            self.packed = dict(flows=flows, device=device)
-        # One table-driven launch packs all 3 * n_layers * n_flows convolutions (weight-norm + split + permute).
-        srcs = []       # f32 source tensors, in job order; their data_ptrs key the cached job table
-        specs = []      # one list of jobs per flow
-        in0 = []        # (v, g) of every flow's in_layers[0]: what the folded WN.start is composed from
+            self.packed = dict(flows=self._alloc_planes(device), device=device)
+        srcs = self._pack_jobs(res_pair8, start_fold)
+        fsrcs = self._fold_jobs()
+        starts = self._launch_pack(start_fold, flow_events)
+        self.packed_key = key
+        self.packed["res_pair8"] = res_pair8
+        self.packed["start_fold"] = start_fold
+        self.packed["keep"] = srcs + fsrcs + starts         # what the job tables point at, for as long as the pack is cached
+        return self.packed
+
+    def _alloc_planes(self, device):
+        """The per-flow plane set of pack_weights(), zeroed."""
+        m, g = self.m, self.geom()
+        C, nl = g["C"], g["nl"]
+        flows = []
         for k in range(m.n_flows):
-            wn = m.WN[k]
+            n_half = m.WN[k].start.in_channels
+            layers = []
+            for i in range(nl):
+                rows2 = 2 * C if i < nl - 1 else C
+                Mpad2 = _lib.padded_rows(rows2)
+                layers.append(dict(
+                    A1h=torch.zeros(g["nk1"], g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
+                    A1l=torch.zeros(g["nk1"], g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
+                    b1=torch.zeros(g["Mpad1"], dtype=torch.float32, device=device),
+                    A2h=torch.zeros(g["nk2"], Mpad2, 32, dtype=torch.bfloat16, device=device),
+                    A2l=torch.zeros(g["nk2"], Mpad2, 32, dtype=torch.bfloat16, device=device),
+                    b2=torch.zeros(Mpad2, dtype=torch.float32, device=device), Mpad2=Mpad2,
+                    s_in=torch.empty(2 * C, dtype=torch.float32, device=device),
+                    s_cond=torch.empty(2 * C, dtype=torch.float32, device=device),
+                    s_rs=torch.empty(rows2, dtype=torch.float32, device=device),
+                    fold_A=torch.zeros(-(-C // 128) * 8192, dtype=torch.bfloat16, device=device)))
+            flows.append(dict(layers=layers, n_half=n_half, bes=torch.zeros(nl, 8, dtype=torch.float32, device=device),
+                              w_start=torch.empty(C, n_half, dtype=torch.float32, device=device),
+                              A0h=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
+                              A0l=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
+                              w_inv=None))
+        return flows
+
+    def _pack_jobs(self, res_pair8, start_fold):
+        """The job table of t2s_pack_conv_weight_table: all 3 * n_layers * n_flows convolutions (weight-norm + split + permute),
+        rebuilt only when a source tensor moved (job_key).  Returns the f32 sources in job order."""
+        m, g = self.m, self.geom()
+        C, nl, ks = g["C"], g["nl"], g["ks"]
+        srcs = []
+        specs = []      # one list of jobs per flow
+        for k, wn in enumerate(m.WN):
             fl = self.packed["flows"][k]
             specs.append([])
             for i in range(nl):
@@ -297,8 +319,6 @@ class _Engine:
                      _f32c(vc), None if gc is None else _f32c(gc),
                      _f32c(vr), None if gr is None else _f32c(gr), _f32c(wn.res_skip_layers[i].bias)]
                 srcs += t
-                if i == 0:
-                    in0.append((t[0], t[1]))
                 # (v, g, bias, bias2, A_hi, A_lo, bias_out, O, Cin, Kt, perm, C_gate, Mpad, koff, Cin_pad)
                 if i == 0 and start_fold:
                     # no in_layers[0] planes (t2s_wg_startfold_weights writes the first nwc K-chunks below); the conditioning weights
@@ -326,14 +346,19 @@ class _Engine:
                                  O, Cin, Kt, perm, Cg, Mpad, koff, Cin_pad, 0, 0, dp(so)])
                     row_start += -(-O // 16)          # the table kernel packs 16 rows per workgroup
                 flow_rows.append(row_start)
-            self.packed["jobs"] = torch.tensor(rows, dtype=torch.int64).to(device)
+            self.packed["jobs"] = torch.tensor(rows, dtype=torch.int64).to(self.packed["device"])
             self.packed["flow_rows"] = flow_rows
             self.packed["flow_jobs"] = flow_jobs        # (first job, job count) per flow
             self.packed["job_key"] = ptr_key
-        # WN.end folded into the skip path: (W_end . W_skip_i)^T per layer, from the scales the pack just wrote
+        return srcs
+
+    def _fold_jobs(self):
+        """The job table of t2s_wg_endfold_weights - WN.end folded into the skip path: (W_end . W_skip_i)^T per layer, from the
+        scales the pack writes - rebuilt only when a source tensor moved (fold_key).  Returns the f32 sources."""
+        m, g = self.m, self.geom()
+        C, nl = g["C"], g["nl"]
         fsrc = []
-        for k in range(m.n_flows):
-            wn = m.WN[k]
+        for k, wn in enumerate(m.WN):
             fl = self.packed["flows"][k]
             w_end = _f32c(wn.end.weight)
             for i in range(nl):
@@ -347,17 +372,22 @@ class _Engine:
             for (w_end, vr, br, r0, ly, bes, i, nj) in fsrc:
                 rows.append([w_end.data_ptr(), vr.data_ptr() + 4 * r0 * C, ly["s_rs"].data_ptr() + 4 * r0,
                              br.data_ptr() + 4 * r0, ly["fold_A"].data_ptr(), bes.data_ptr() + 4 * 8 * i, nj, C])
-            self.packed["fold_jobs"] = torch.tensor(rows, dtype=torch.int64).to(device)
+            self.packed["fold_jobs"] = torch.tensor(rows, dtype=torch.int64).to(self.packed["device"])
             self.packed["fold_key"] = fkey
-        # One table-driven launch per flow packs its 3 * n_layers convolutions (weight-norm + split + permute), one more
-        # builds its folded WN.end matrices, a third its `start` weights - and with start_fold a fourth composes those with
-        # in_layers[0] into the first nwc K-chunks of the layer-0 operand.  With `flow_events` (the no-grad forward) the per-flow
-        # work is enqueued on the caller's current stream - a side stream there - and an event per flow lets the main stream
-        # start flow k as soon as ITS weights are packed: the pack is HBM-bound (2.1 GB per forward), the GEMMs are not.
+        return [t for tup in fsrc for t in tup[:3]]
+
+    def _launch_pack(self, start_fold, flow_events):
+        """One table-driven launch per flow packs its 3 * n_layers convolutions (weight-norm + split + permute), one more
+        builds its folded WN.end matrices, a third its `start` weights - and with start_fold a fourth composes those with
+        in_layers[0] into the first nwc K-chunks of the layer-0 operand.  With `flow_events` (the no-grad forward) the per-flow
+        work is enqueued on the caller's current stream - a side stream there - and an event per flow lets the main stream
+        start flow k as soon as ITS weights are packed: the pack is HBM-bound (2.1 GB per forward), the GEMMs are not."""
+        m, g = self.m, self.geom()
+        C, nl, ks = g["C"], g["nl"], g["ks"]
+        st = _lib.current_stream()
         jobs_ptr, fold_ptr = self.packed["jobs"].data_ptr(), self.packed["fold_jobs"].data_ptr()
         starts = []
-        for k in range(m.n_flows):
-            wn = m.WN[k]
+        for k, wn in enumerate(m.WN):
             fl = self.packed["flows"][k]
             j0, nj = self.packed["flow_jobs"][k]
             _lib.call("t2s_pack_conv_weight_table", _lib.c_vp(jobs_ptr + j0 * 19 * 8), nj, self.packed["flow_rows"][k], st)
@@ -367,22 +397,17 @@ class _Engine:
             starts += [v, gg]
             _lib.call("t2s_weightnorm_small", _lib.ptr(v), _lib.ptr(gg), C, fl["n_half"], _lib.ptr(fl["w_start"]), st)
             if start_fold:
-                b_start = _f32c(wn.start.bias)
-                starts.append(b_start)
-                _lib.call("t2s_wg_startfold_weights", _lib.ptr(in0[k][0]), _lib.ptr(in0[k][1]), _lib.ptr(fl["w_start"]),
+                v0, g0 = _vg(wn.in_layers[0])
+                v0, g0, b_start = _f32c(v0), (None if g0 is None else _f32c(g0)), _f32c(wn.start.bias)
+                starts += [v0, g0, b_start]
+                _lib.call("t2s_wg_startfold_weights", _lib.ptr(v0), _lib.ptr(g0), _lib.ptr(fl["w_start"]),
                           _lib.ptr(b_start), C, fl["n_half"], ks, g["Mpad1"], g["nwc"], _lib.ptr(fl["A0h"]), _lib.ptr(fl["A0l"]), st)
             fl["w_inv"] = None
             if flow_events is not None:
                 ev = torch.cuda.Event()
                 ev.record()
                 flow_events.append(ev)
-        keep = srcs + [t for tup in fsrc for t in tup[:3]] + starts
-        self.packed_key = key
-        self.packed["res_pair8"] = res_pair8
-        self.packed["start_fold"] = start_fold
-        self.packed["flow_boundary"] = flow_boundary
-        self._keep = keep
-        return self.packed
+        return starts
 
     # ------------------------------------------------------------------ composed conditioning (inverse flow)
     def compose_geom(self):
@@ -390,7 +415,7 @@ class _Engine:
         m, g = self.m, self.geom()
         up = m.upsample
         ksz, stride, G = up.kernel_size[0], up.stride[0], m.n_group
-        if os.environ.get("T2S_COND_COMPOSE") != "1" or not self.use_fold:      # opt-in: see DESIGN.md section 5 for the measurements
+        if os.environ.get("T2S_COND_COMPOSE") != "1":      # opt-in: see DESIGN.md section 5 for the measurements
             return None
         if ksz % stride or stride % G or ((ksz // stride) * up.in_channels) % 32 or g["C"] % 16:
             return None
@@ -430,7 +455,7 @@ class _Engine:
                           ncols, Lp_u, 0, g["Mpad1"], st)
                 _lib.call("t2s_wg_compose_cond", _lib.ptr(tmp), _lib.ptr(ly["b1"]), 2 * C, g["Mpad1"], P, K2, ncols,
                           _lib.ptr(ly["Ach"]), _lib.ptr(ly["Acl"]), _lib.ptr(ly["b1c"]), st)
-        self._keep_compose = (U_h, U_l, tmp, zb, W, bias)
+        self._keep += [U_h, U_l, tmp, zb, W, bias]
         self.packed["compose_key"] = self.packed_key
 
     # ------------------------------------------------------------------ workspaces
@@ -447,7 +472,6 @@ class _Engine:
                      Ah=torch.zeros(B, xc, Lp, 32, **bf), Al=torch.zeros(B, xc, Lp, 32, **bf),
                      Sh=torch.zeros(B, sc, Lp, 32, **bf), Sl=torch.zeros(B, sc, Lp, 32, **bf),
                      Wh=torch.zeros(B, g["nwc"], Lp, 32, **bf), Wl=torch.zeros(B, g["nwc"], Lp, 32, **bf),      # folded WN.start: window
-                     skip=torch.zeros(B, xc, Lp, 32, dtype=torch.float32, device=device),
                      z2=torch.empty(B, self.m.n_group, L, dtype=torch.float32, device=device),        # one-launch flow boundaries: the other z
                      fold_acc=torch.zeros(_lib.load().t2s_wg_gate_fold_slots(B, g["C"], L), B, 8, L, dtype=torch.float32,
                                           device=device))
@@ -469,7 +493,7 @@ class _Engine:
         _lib.call("t2s_wg_upsample_squeeze", _lib.ptr(mel32), _lib.ptr(W), _lib.ptr(bias), B, up.in_channels,
                   mel32.size(2), up.kernel_size[0], up.stride[0], m.n_group, L, w["Lp"], g["halo"],
                   _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), _lib.current_stream())
-        self._keep_up = (mel32, W, bias)
+        self._keep += [mel32, W, bias]
 
     def _boundary(self, k, z_in, z_out, B, L, w, prev=None, W=None):
         """t2s_wg_flow_boundary in front of flow k: prev = (flow index, log_s) applies that flow's coupling, W this flow's 1x1
@@ -484,7 +508,7 @@ class _Engine:
             fold_acc, nslots = w["fold_acc"], w["fold_acc"].size(0)
             bes = self.packed["flows"][kp]["bes"]
             b_end = _f32c(m.WN[kp].end.bias)
-            self._keep_boundary.append(b_end)
+            self._keep.append(b_end)
         # Stream order makes the reuse of fold_acc and of the window planes safe: this launch reads the sums of the flow before
         # ahead of flow k's layer-0 gate GEMM, which re-initialises them, and writes the window planes behind the last launch (the
         # layer-0 gate GEMM of the flow before) that read them.
@@ -492,38 +516,29 @@ class _Engine:
                   _lib.ptr(b_end), _lib.ptr(log_s), c_off_p, nh_p, _lib.ptr(W), c_off, n_rem, n_half, B, m.n_group, L, w["Lp"],
                   g["halo"], g["ks"], g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), _lib.current_stream())
 
-    def _wn(self, k, z, B, L, w, c_off, n_half, ph=None, fb=False, window_done=False):
-        """start -> n_layers x (in+cond+gate, res/skip); leaves the skip sum in w['skip'].  ph = (M_hi, M_lo, Fp, P, K2):
-        conditioning through the composed weights and the mel-window planes (inverse flow).  fb: the caller's
-        flow_boundary_on() - nobody writes x0 to the X planes, the layer-0 residual GEMM rebuilds it from z; window_done: the caller's t2s_wg_flow_boundary already wrote this flow's
-        window planes from z."""
+    def _wn(self, k, z, B, L, w, c_off, n_half, path, ph=None):
+        """start -> n_layers x (gate GEMM with WN.end folded in, residual GEMM) on the call's `path`; leaves WN.end's sums in
+        w['fold_acc'].  With path.boundary the caller's _boundary() has written this flow's window planes from z, and x0 is rebuilt
+        by the layer-0 residual GEMM.  ph = (M_hi, M_lo, Fp, P, K2): composed conditioning from the mel-window planes (inverse flow)."""
         m, g = self.m, self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
         fl = self.packed["flows"][k]
         st = _lib.current_stream()
-        wn = m.WN[k]
-        b_start = _f32c(wn.start.bias)
-        self._keep_wn = [b_start]
-        # layer 0 through the folded WN.start: the X planes are still written (the residual stream needs x0), the gate GEMM reads
-        # the window planes instead
-        sf = bool(self.packed.get("start_fold")) and self.use_fold and ph is None
-        # ... and with the one-launch boundary nobody writes them: the layer-0 residual GEMM rebuilds x0 from z
-        fb = bool(fb) and sf
-        if fb:
-            if not window_done:
-                self._keep_boundary = []
-                self._boundary(k, z, None, B, L, w)
-        elif sf:
-            _lib.call("t2s_wg_start_window", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
-                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), ks, g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), st)
-        else:
+        b_start = _f32c(m.WN[k].start.bias)
+        self._keep.append(b_start)
+        if not path.start_fold:
             _lib.call("t2s_wg_start", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
                       C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), st)
+        elif not path.boundary:
+            # layer 0 through the folded WN.start: the X planes are still written (the residual stream needs x0), the gate GEMM
+            # reads the window planes instead
+            _lib.call("t2s_wg_start_window", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
+                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), ks, g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), st)
         for i in range(nl):
             ly = fl["layers"][i]
             # bench.py divides the sampled launch time into the FLOPs of a full-K layer: the short folded layer 0 is neither
             # counted nor timed
-            full_k = not (sf and i == 0)
+            full_k = not (path.start_fold and i == 0)
             timed = full_k and self.gemm_events is not None and self._gemm_launch_no % self.gemm_event_stride == 0
             if full_k:
                 self._gemm_launch_no += 1
@@ -541,39 +556,29 @@ class _Engine:
                           _lib.ptr(ly["Acl"]), _lib.ptr(ly["b1c"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(Mh), _lib.ptr(Ml),
                           _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
                           1 if i == 0 else 0, B, C, K2, ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], P, Fp, st)
-            elif self.use_fold:
+            else:
                 _lib.call("t2s_wg_in_cond_gate_fold", _lib.ptr(ly["A1h"]), _lib.ptr(ly["A1l"]), _lib.ptr(ly["b1"]),
                           _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
                           _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
                           1 if i == 0 else 0, B, C, g["n_cond"], ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], st)
-            else:
-                _lib.call("t2s_wg_in_cond_gate", _lib.ptr(ly["A1h"]), _lib.ptr(ly["A1l"]), _lib.ptr(ly["b1"]),
-                          _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), B, C, g["n_cond"], ks, 2 ** i, L, w["Lp"], g["halo"],
-                          g["Mpad1"], st)
             if timed:
                 e1.record()
                 self.gemm_events.append((e0, e1))
-            n_res = C if i < nl - 1 else 0
-            if self.use_fold:
-                if n_res and fb and i == 0:
-                    _lib.call("t2s_wg_res_only_start", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
-                              _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start),
-                              m.n_group, c_off, n_half, _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"],
-                              ly["Mpad2"], st)
-                elif n_res:     # the last layer has no residual half, and its skip half lives in the fold
-                    _lib.call("t2s_wg_res_only", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
-                              _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
-                              g["halo"], ly["Mpad2"], 1 if self.packed.get("res_pair8") else 0, st)
+            if i == nl - 1:     # the last layer has no residual half, and its skip half lives in the fold
+                continue
+            if path.boundary and i == 0:
+                _lib.call("t2s_wg_res_only_start", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
+                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start),
+                          m.n_group, c_off, n_half, _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"],
+                          ly["Mpad2"], st)
             else:
-                _lib.call("t2s_wg_res_skip", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(w["skip"]),
-                          B, C, n_res, 1 if i == 0 else 0, L, w["Lp"], g["halo"], ly["Mpad2"], st)
+                _lib.call("t2s_wg_res_only", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
+                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
+                          g["halo"], ly["Mpad2"], 1 if self.packed["res_pair8"] else 0, st)
 
     def wn_forward(self, k, audio, spect):
         """WN[k].forward((audio, spect)) (reference glow.py:154-175) on the no-grad kernels: start, n_layers x (gate GEMM with
         WN.end folded in, residual GEMM), then WN.end's output (b ; log_s) without applying the coupling."""
-        m = self.m
         self._check_inputs(audio, spect)
         dev = audio.device
         B, n_in, L = audio.shape
@@ -581,45 +586,49 @@ class _Engine:
         g = self.geom()
         if n_in != n_half or spect.size(1) != g["n_cond"] or spect.size(2) != L:
             raise ValueError("WN[%d] takes audio [B, %d, L] and spect [B, %d, L]" % (k, n_half, g["n_cond"]))
-        fb = self.flow_boundary_on()
-        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on(), flow_boundary=fb)
+        path = self.last_path = self.path()
+        self._keep = []
+        self.pack_weights(dev, force=False, res_pair8=True, start_fold=path.start_fold)
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         spect32 = _f32c(spect)
         _lib.call("t2s_f32_to_planes", _lib.ptr(spect32), B, g["n_cond"], L, w["Lp"], g["halo"], _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), st)
-        z = torch.zeros(B, m.n_group, L, dtype=torch.float32, device=dev)
+        z = torch.zeros(B, self.m.n_group, L, dtype=torch.float32, device=dev)
         z[:, c_off:c_off + n_half] = audio.detach().to(torch.float32)
-        self._wn(k, z, B, L, w, c_off, n_half, fb=fb)
+        if path.boundary:
+            self._boundary(k, z, None, B, L, w)
+        self._wn(k, z, B, L, w, c_off, n_half, path)
         wn_out = torch.empty(B, 2 * n_half, L, dtype=torch.float32, device=dev)
-        if self.use_fold:
-            w2 = dict(w)
-            w2["wn_out"] = wn_out
-            self._end(k, z, None, B, L, w2, c_off, n_half, reverse=False)
-        else:
-            self._end(k, z, None, B, L, w, c_off, n_half, reverse=False, wn_out=wn_out)
-        self._keep_wnf = (spect32, z)
+        self._end_fold(k, z, None, w["fold_acc"], wn_out, B, L, c_off, n_half, reverse=False)
+        self._keep += [spect32, z]
         return wn_out.to(audio.dtype)
 
-    def _end(self, k, z, log_s, B, L, w, c_off, n_half, reverse, wn_out=None, skip=None):
-        m, g = self.m, self.geom()
-        wn = m.WN[k]
+    def _end_fold(self, k, z, log_s, fold_acc, wn_out, B, L, c_off, n_half, reverse):
+        """WN.end from the sums the gate GEMMs folded it into, and flow k's coupling on z (wn_out: also WN.end's output)."""
+        b_end = _f32c(self.m.WN[k].end.bias)
+        self._keep.append(b_end)
+        _lib.call("t2s_wg_end_fold_affine", _lib.ptr(fold_acc), fold_acc.size(0), _lib.ptr(self.packed["flows"][k]["bes"]),
+                  self.geom()["nl"], _lib.ptr(b_end), _lib.ptr(z), _lib.ptr(log_s), _lib.ptr(wn_out), B, self.m.n_group, c_off,
+                  n_half, L, 1 if reverse else 0, _lib.current_stream())
+
+    def _end_skip(self, k, z, log_s, skip, wn_out, Lp, B, L, c_off, n_half):
+        """WN.end as a convolution of the skip sum, and flow k's coupling on z: the training forward where C % 16 != 0."""
+        g, wn = self.geom(), self.m.WN[k]
         w_end, b_end = _f32c(wn.end.weight), _f32c(wn.end.bias)
-        self._keep_end = (w_end, b_end)
-        if self.use_fold and wn_out is None and skip is None:
-            fl = self.packed["flows"][k]
-            _lib.call("t2s_wg_end_fold_affine", _lib.ptr(w["fold_acc"]), w["fold_acc"].size(0), _lib.ptr(fl["bes"]),
-                      g["nl"], _lib.ptr(b_end), _lib.ptr(z), _lib.ptr(log_s), _lib.ptr(w.get("wn_out")), B, m.n_group, c_off,
-                      n_half, L, 1 if reverse else 0, _lib.current_stream())
-            return
-        _lib.call("t2s_wg_end_affine", _lib.ptr(w["skip"] if skip is None else skip), _lib.ptr(w_end), _lib.ptr(b_end),
-                  _lib.ptr(z), _lib.ptr(log_s), _lib.ptr(wn_out), B, m.n_group, c_off, n_half, g["C"], L, w["Lp"], g["halo"], 1 if reverse else 0,
-                  _lib.current_stream())
+        self._keep += [w_end, b_end]
+        _lib.call("t2s_wg_end_affine", _lib.ptr(skip), _lib.ptr(w_end), _lib.ptr(b_end), _lib.ptr(z), _lib.ptr(log_s),
+                  _lib.ptr(wn_out), B, self.m.n_group, c_off, n_half, g["C"], L, Lp, g["halo"], 0, _lib.current_stream())
 
     def _flow_geom(self, k):
         m = self.m
         c_off = m.n_early_size * (k // m.n_early_every)
         n_rem = m.n_group - c_off
         return c_off, n_rem, n_rem // 2
+
+    def logdet_jobs(self, Ws, log_det, inverses=None):
+        """Host job table of t2s_small_logdet_inv_batch(_host): per flow W_k, where log|det W_k| goes, where W_k^-1 goes or 0, n_rem."""
+        return torch.tensor([[Ws[k].data_ptr(), log_det.data_ptr() + 4 * k, 0 if inverses is None else inverses[k].data_ptr(),
+                              self._flow_geom(k)[1]] for k in range(self.m.n_flows)], dtype=torch.int64)
 
     # ------------------------------------------------------------------ forward / infer
     def forward(self, mel, audio):
@@ -632,32 +641,29 @@ class _Engine:
         up = m.upsample
         if (mel.size(2) - 1) * up.stride[0] + up.kernel_size[0] < T:
             raise AssertionError("upsampled spectrogram shorter than audio (reference glow.py:216)")
+        path = self.last_path = self.path()
+        self._keep = []
         w = self.workspace(B, L, dev)
         # The input-side work (conditioning upsampler: compute-bound; audio squeeze; 12 log-determinants) does not depend on
         # the per-forward weight pack (HBM-bound): it runs on a second HIP stream next to the pack and joins before flow 0.
         main = torch.cuda.current_stream(dev)
-        side = self.side_stream if getattr(self, "side_stream", None) is not None else torch.cuda.Stream(device=dev)
-        self.side_stream = side
+        side = self._stream("side", dev)
         audio32 = _f32c(audio)
         z = torch.empty(B, G, L, dtype=torch.float32, device=dev)
         # one-launch flow boundaries read one [B, G, L] buffer and write the other: the squeezed audio goes into the one that makes
         # the caller's own tensor (never the workspace's) the last one written
-        fb = self.flow_boundary_on()
-        if fb:
+        if path.boundary:
             bufs = [z, w["z2"]] if m.n_flows % 2 == 0 else [w["z2"], z]
             z = bufs[0]
-            self._keep_boundary = []
         log_s_list, log_det_list = [], []
         log_det = torch.empty(m.n_flows, dtype=torch.float32, device=dev)
         Ws = [_f32c(m.convinv[k].conv.weight) for k in range(m.n_flows)]
-        keep = list(Ws)
         # B*L*logdet(W_k) of all flows in one launch (reference glow.py:100)
         use_val = m.n_flows <= 16          # the table travels as a kernel argument: no per-forward host -> device copy
-        jobs = torch.tensor([[Ws[k].data_ptr(), log_det.data_ptr() + 4 * k, 0, self._flow_geom(k)[1]]
-                             for k in range(m.n_flows)], dtype=torch.int64)
+        jobs = self.logdet_jobs(Ws, log_det)
         if not use_val:
             jobs = jobs.to(dev)
-        keep.append(jobs)
+        self._keep += [audio32, jobs] + Ws
         side.wait_stream(main)               # inputs, the job table and earlier users of the workspace are ordered before
         with torch.cuda.stream(side):
             st2 = _lib.current_stream()
@@ -672,36 +678,30 @@ class _Engine:
         # The per-forward weight pack (weight_norm recompute + split + permute, HBM-bound: 1.07 GB in, 1.07 GB out) runs flow by
         # flow on a third stream; the main stream waits for flow k's event only, so all but the first flow's share of the pack
         # hides under the GEMMs of the flows before it.
-        pack_s = self.pack_stream if getattr(self, "pack_stream", None) is not None else torch.cuda.Stream(device=dev)
-        self.pack_stream = pack_s
+        pack_s = self._stream("pack", dev)
         pack_events = []
         pack_s.wait_stream(main)
         with torch.cuda.stream(pack_s):
-            self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=self.use_fold, start_fold=self.start_fold_on(),
-                              flow_boundary=fb)
+            self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=True, start_fold=path.start_fold)
         main.wait_event(ev_inputs)
         st = _lib.current_stream()
         for k in range(m.n_flows):
             main.wait_event(pack_events[k])
             c_off, n_rem, n_half = self._flow_geom(k)
-            Wk = Ws[k]
             log_s = torch.empty(B, n_half, L, dtype=torch.float32, device=dev)
-            if fb:
+            if path.boundary:
                 # boundary(k): coupling of flow k - 1 (none in front of flow 0), this flow's 1x1 convolution, the window planes
                 z_out = bufs[(k + 1) % 2]
-                self._boundary(k, z, z_out, B, L, w, prev=(k - 1, log_s_list[k - 1]) if k else None, W=Wk)
+                self._boundary(k, z, z_out, B, L, w, prev=(k - 1, log_s_list[k - 1]) if k else None, W=Ws[k])
                 z = z_out
-                self._wn(k, z, B, L, w, c_off, n_half, fb=True, window_done=True)
-                if k == m.n_flows - 1:          # the last coupling has no boundary behind it: in place on the current buffer
-                    self._end(k, z, log_s, B, L, w, c_off, n_half, reverse=False)
             else:
-                _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(Wk), B, G, c_off, n_rem, L, st)
-                self._wn(k, z, B, L, w, c_off, n_half)
-                self._end(k, z, log_s, B, L, w, c_off, n_half, reverse=False)
+                _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(Ws[k]), B, G, c_off, n_rem, L, st)
+            self._wn(k, z, B, L, w, c_off, n_half, path)
+            if not path.boundary or k == m.n_flows - 1:     # the last coupling has no boundary behind it: in place on the current buffer
+                self._end_fold(k, z, log_s, w["fold_acc"], None, B, L, c_off, n_half, reverse=False)
             log_s_list.append(log_s)
             log_det_list.append(log_det[k])
         main.wait_stream(side)               # log_det
-        self._keep_fwd = (audio32, keep)
         return z, log_s_list, log_det_list
 
     def infer(self, mel, sigma, noise):
@@ -714,19 +714,18 @@ class _Engine:
         # reference glow.py:254-255: drop the last (kernel - stride) upsampled samples
         T = (frames - 1) * up.stride[0] + up.kernel_size[0] - (up.kernel_size[0] - up.stride[0])
         L = T // G
-        fb = self.flow_boundary_on()
-        self.pack_weights(dev, force=False, res_pair8=self.use_fold, start_fold=self.start_fold_on(), flow_boundary=fb)
+        path = self.last_path = self.path()
+        self._keep = []
+        self.pack_weights(dev, force=False, res_pair8=True, start_fold=path.start_fold)
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         # Weights are packed once here, so the conditioning path can be composed with the upsampler (K = 640 -> 320 in the gate
         # GEMM, no upsampler launch) - wherever the grid is large enough for the 256-row ping-pong tiles anyway.  Opt-in
         # (T2S_COND_COMPOSE=1): with the activations in time-major planes the phase tiles read rows 2 KB apart and the gate GEMM
         # gains 3.5 % instead of 14.7 % (1000 frames: 32.5 -> 31.7 ms; 300-400 frames lose to tile padding)
-        cg = self.compose_geom()
-        C = self.geom()["C"]
-        ph = None
-        if cg is not None and _lib.load().t2s_wg_gate_tile_rows(B, C, L) == 256:      # the library's own tile-height decision
-            P, nlag, K2 = cg
+        ph = None       # (256: the library's own tile-height decision)
+        if path.compose is not None and _lib.load().t2s_wg_gate_tile_rows(B, self.geom()["C"], L) == 256:
+            P, nlag, K2 = path.compose
             self.compose_cond(dev)
             Fp = -(-frames // 256) * 256
             key = ("melwin", B, Fp, str(dev))
@@ -737,7 +736,7 @@ class _Engine:
                 self.ws[key] = mw
             mel32 = _f32c(mel)
             _lib.call("t2s_wg_melwin_planes", _lib.ptr(mel32), B, mel32.size(1), frames, nlag, Fp, _lib.ptr(mw[0]), _lib.ptr(mw[1]), st)
-            self._keep_up = (mel32,)
+            self._keep.append(mel32)
             ph = (mw[0], mw[1], Fp, P, K2)
         else:
             self._upsample(mel, B, L, w)
@@ -763,8 +762,10 @@ class _Engine:
                 fl["w_inv"] = torch.empty(n_rem, n_rem, dtype=torch.float32, device=dev)
                 _lib.call("t2s_small_logdet_inv", _lib.ptr(Wk), n_rem, 1.0, None, _lib.ptr(fl["w_inv"]), st)
                 fl["_Wk"] = Wk
-            self._wn(k, z, B, L, w, c_off, n_half, ph=ph, fb=fb)
-            self._end(k, z, None, B, L, w, c_off, n_half, reverse=True)
+            if path.boundary:
+                self._boundary(k, z, None, B, L, w)         # the window planes only
+            self._wn(k, z, B, L, w, c_off, n_half, path, ph=ph)
+            self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True)
             _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(fl["w_inv"]), B, G, c_off, n_rem, L, st)
         audio = torch.empty(B, L * G, dtype=torch.float32, device=dev)
         _lib.call("t2s_wg_audio_squeeze", _lib.ptr(audio), _lib.ptr(z), B, L * G, G, L, 1, st)
@@ -839,7 +840,6 @@ class WaveGlow(torch.nn.Module):
     def _refuse_overflow(t):
         """fp16-operand build only: a plane element beyond fp16's range (65504) became inf inside the flow and shows as a non-finite
         output - an error, not a result (the shipped bf16 planes have f32's exponent range and need no such check)."""
-        import os
         if os.environ.get("T2S_F16_GUARD", "1") == "0":     # timing runs only: the check is a device read-back per call
             return
         if not bool(torch.isfinite(t).all()):

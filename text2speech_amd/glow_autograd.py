@@ -52,7 +52,7 @@ def _alloc_train(eng, B, L, dev):
     # 128-row tiles) + what the backward needs: every layer's input x, gate output and sigmoid.  The skip sum is never formed in
     # the forward; the backward rebuilds it once per flow from the saved gate outputs (t2s_wg_skip_sum), which is why the gate
     # outputs of a flow's layers sit side by side in ONE plane set (layer i = chunks [xc i, xc (i + 1)) of every batch entry).
-    st.fold_train = C % 16 == 0 and eng.use_fold
+    st.fold_train = C % 16 == 0
     st.act_bchunks = nl * xc if st.fold_train else 0
     st.layers, st.AF, st.GF = [], [], []
     for k in range(m.n_flows):
@@ -210,12 +210,12 @@ def forward_train(eng, mel, audio):
     g = eng.geom()
     C, nl, ks = g["C"], g["nl"], g["ks"]
     ts = _alloc_train(eng, B, L, dev)
+    eng._keep = []
     # The per-step weight work (weight-norm + pack of every convolution, the folded WN.end matrices, the 12 log-determinants and
     # inverses of the 1x1 convolutions, the transposed operands of the backward) depends on the weights only: it runs on the
     # engine's pack stream, flow by flow, and the main stream waits for flow k's event only - as in the no-grad forward.
     main = torch.cuda.current_stream(dev)
-    pack_s = eng.pack_stream if getattr(eng, "pack_stream", None) is not None else torch.cuda.Stream(device=dev)
-    eng.pack_stream = pack_s
+    pack_s = eng._stream("pack", dev)
     pack_events = []
     log_det = torch.empty(m.n_flows, dtype=torch.float32, device=dev)
     Ws = [_f32c(m.convinv[k].conv.weight) for k in range(m.n_flows)]
@@ -224,8 +224,7 @@ def forward_train(eng, mel, audio):
         eng.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=ts.fold_train)
         stp = _lib.current_stream()
         if m.n_flows <= 16:         # B*L*logdet(W_k) and W_k^-1 of every flow in one launch (the table travels as a kernel argument)
-            jobs = torch.tensor([[Ws[k].data_ptr(), log_det.data_ptr() + 4 * k, ts.Winv[k].data_ptr(), eng._flow_geom(k)[1]]
-                                 for k in range(m.n_flows)], dtype=torch.int64)
+            jobs = eng.logdet_jobs(Ws, log_det, ts.Winv)
             _lib.call("t2s_small_logdet_inv_batch_host", ctypes.c_void_p(jobs.data_ptr()), m.n_flows, float(B * L), stp)
             ts.keep_jobs = jobs
         else:
@@ -301,9 +300,9 @@ def forward_train(eng, mel, audio):
         log_s = torch.empty(B, n_half, L, dtype=torch.float32, device=dev)
         ts.wn_out[k] = torch.empty(B, 2 * n_half, L, dtype=torch.float32, device=dev)
         if ts.fold_train:
-            eng._end(k, z, log_s, B, L, dict(Lp=ts.Lp, fold_acc=ts.fold_acc, wn_out=ts.wn_out[k]), c_off, n_half, reverse=False)
+            eng._end_fold(k, z, log_s, ts.fold_acc, ts.wn_out[k], B, L, c_off, n_half, reverse=False)
         else:
-            eng._end(k, z, log_s, B, L, dict(Lp=ts.Lp), c_off, n_half, reverse=False, wn_out=ts.wn_out[k], skip=ts.skip[k])
+            eng._end_skip(k, z, log_s, ts.skip[k], ts.wn_out[k], ts.Lp, B, L, c_off, n_half)
         log_s_list.append(log_s)
     main.wait_stream(pack_s)            # log-determinants, inverses, transposed operands: all in before the outputs are used
     ts.z_final = z
@@ -342,9 +341,7 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
     # chain updates DX in place; every layer has its own slice of the flow-wide d_pre planes, which the next flow reuses only
     # after the two streams have joined).  The split-K slabs belong to the side stream alone.
     main_s = torch.cuda.current_stream(dev)
-    side_s = getattr(eng, "bwd_side_stream", None)
-    if side_s is None:
-        side_s = eng.bwd_side_stream = torch.cuda.Stream(device=dev)
+    side_s = eng._stream("bwd_side", dev)
     st2 = _lib.c_vp(side_s.cuda_stream)
     side_s.wait_stream(main_s)
     cl = ts.cl_ok       # weight-gradient GEMMs straight from the channel-last planes (no time-major copies)
