@@ -401,10 +401,34 @@ typedef struct t2s_taco_decoder {
 
 /* Enqueue decoder steps [step0, step0+n_steps) (Decoder.decode, tacotron.py:355-393, plus in autoregressive mode
  * the projection and the prenet of the next step, tacotron.py:447-461) on `stream` without host synchronisation.
- * Teacher-forced with att_h_all and hc_all given (training): the decoder LSTM cells - which feed nothing but the next decoder cell
- * and the projection after the loop - are enqueued on a library-owned helper stream, 16 steps behind the
- * attention chain, reading h_att / ctx from those saves; `stream` has been made to wait for the helper when the call returns. */
+ * Which kernels a step launches is decided once per call from the struct's shapes and NULL pointers (t2s_taco_decode_plan below
+ * reports it; DESIGN.md section 5b lists the launches of every plan).  Three schedules:
+ *  - serial: attention cell, attention, decoder cell [, projection + next prenet] of each step in turn, all on `stream`;
+ *  - split (teacher-forced with att_h_all and hc_all given: training, or the no-grad forward at 9+ items): the decoder cells - which
+ *    feed nothing but the next decoder cell and the projection after the loop - are enqueued on a library-owned helper stream, 16 steps
+ *    behind the attention chain, reading h_att / ctx from those saves;
+ *  - paced (split at 9+ items with pace_flag, unless T2S_DECODE_PACED=0): the helper's cell of step s - 1 is released by the word the
+ *    attention cell of step s stores as it starts.
+ * With the helper stream in use `stream` has been made to wait for it when the call returns, error returns included. */
 int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, void* stream);
+
+/* The plan t2s_taco_decode_steps(d, step0, n_steps, .) would follow, as T2S_PLAN_* bits in *bits (may be NULL).  Host only: no
+ * pointer of `d` is dereferenced and nothing is enqueued.  Returns what t2s_taco_decode_steps returns from its validation.  The
+ * plan does not depend on the step range: decisions that look at a ping-pong buffer (att_h0 / att_h1, dec_h0 / dec_h1) hold only
+ * if they hold for both, so calls that continue a sequence follow one plan (ABI v4, compatible addition). */
+#define T2S_PLAN_SPLIT 0x001u         /* decoder cells on the helper stream (teacher-forced with att_h_all + hc_all) */
+#define T2S_PLAN_PACED 0x002u         /* ... one step behind the chain, released through pace_flag; without it: 16-step chunks */
+#define T2S_PLAN_SIG_BY_KERNEL 0x004u /* paced: the matrix-core attention cell stores the pace word; without it: a launch of its own */
+#define T2S_PLAN_FUSED_ATT 0x008u     /* one attention launch per step; without it: [query GEMV +] energies [+ softmax / context] */
+#define T2S_PLAN_Q_PARTS 0x010u       /* fused attention sums the partial queries of the attention cell's workgroups (q_part) */
+#define T2S_PLAN_Q_BIG 0x020u         /* the energies kernel sums those of the matrix-core cell (q_part): no query GEMV */
+#define T2S_PLAN_ONE 0x040u           /* the energies launch also does softmax, cumulative weights and context (att_xbuf) */
+#define T2S_PLAN_STREAM_GATES 0x080u  /* the fused attention launch streams the cells' gate partials (gate_part) */
+#define T2S_PLAN_FOLD_PRE2 0x100u     /* prenet layer 1 inside the attention cell's launch (w_pre2T), steps below mask_steps */
+#define T2S_PLAN_USE_PLOC 0x200u      /* the attention's location term comes out of the previous projection launch (ploc) */
+#define T2S_PLAN_PROJ_FUSED 0x400u    /* autoregressive: projection and the next prenet layer 0 in one launch */
+#define T2S_PLAN_UNITS_2 0x800u       /* the VALU cells take 2 hidden units per workgroup (att_gates_all given); without it: 4 */
+int t2s_taco_decode_plan(const t2s_taco_decoder* d, int step0, int n_steps, unsigned* bits);
 
 /* ABI v4.  One call of the location-sensitive attention alone (Attention.forward, tacotron.py:145-166, with the state update of
  * Decoder.decode around it, tacotron.py:371-379): query = w_query . h_att, energies from the location features of (w, w_cum) and

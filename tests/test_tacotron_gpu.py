@@ -232,11 +232,18 @@ def test_streamed_gate_partials_match_unstreamed_decode(model, B, T_in, n):
     try:
         eng.decode_stream = True
         a = model.inference(ids, None, prenet_masks=masks)
+        plan_a = eng.last_decode_plan
         eng.decode_stream = False
         b = model.inference(ids, None, prenet_masks=masks)
+        plan_b = eng.last_decode_plan
     finally:
         eng.decode_stream = True
         model.decoder.gate_threshold, model.decoder.max_decoder_steps = HP["gate_threshold"], HP["max_decoder_steps"]
+    if B <= 4:      # the two runs differ in exactly the streaming decisions ...
+        streaming = dict(stream_gates=True, fold_pre2=True, use_ploc=True)
+        assert plan_a == plan_b._replace(**streaming) and plan_b == plan_a._replace(**{k: False for k in streaming})
+    else:           # ... and beyond 4 items the library streams nothing, offered or not: one chain, run twice
+        assert plan_a == plan_b and not plan_a.stream_gates
     for name, x, y in zip(("mel", "mel_post", "gate", "align"), a, b):
         assert tuple(x.shape) == tuple(y.shape)
         assert _rel(x, y) < 2e-5 and _maxrel(x, y) < 1e-4, (name, _rel(x, y), _maxrel(x, y))

@@ -81,6 +81,7 @@ SIGNATURES = {
     "t2s_taco_attention": [c_vp] * 14 + [c_int] * 7 + [c_vp],
     "t2s_bernoulli_mask": [c_vp, ctypes.c_size_t, ctypes.c_ulonglong, ctypes.c_ulonglong, c_float, c_vp],
     "t2s_taco_decode_steps": [c_vp, c_int, c_int, c_vp],
+    "t2s_taco_decode_plan": [c_vp, c_int, c_int, c_vp],
     "t2s_taco_stop_check": [c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp],
     "t2s_rows_to_tm": [c_vp, c_long, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp],
     "t2s_rows_to_tm_batched": [c_vp, c_long, c_long, c_int, c_int, c_int, c_int, c_vp, c_vp, c_long, c_int, c_int, c_int, c_vp],

@@ -12,6 +12,7 @@ that is fresh for every call (``_TacoEngine.fresh_seed``, reproducible under ``t
 Training mode (BatchNorm batch statistics, encoder / LSTM / postnet dropout) runs here; its backward
 is ``tacotron/autograd.py``.
 """
+import collections
 import ctypes
 import sys
 from math import sqrt
@@ -182,6 +183,7 @@ class Decoder(OwnedModule):
             d, S = eng._decoder_struct(mem, len32, 2, True, extra)
             d.att_xbuf = None       # (its tags are step numbers, used once per sequence: the two step slots here repeat them)
             d.pace_flag = None
+            eng._query_plan(d, 0, 1)
             self.__dict__["_step"] = dict(d=d, S=S, n=0, len32=len32, B=B, T_in=T_in, E=E)
             self.memory, self.processed_memory, self.mask = memory, S["pmem"], mask
             self._publish_state()
@@ -249,6 +251,25 @@ class _DecoderStruct(ctypes.Structure):
            "dec_gates_all", "dec_c_all", "att_h_all", "q_all", "wcum_all", "gate_part", "w_pre2T", "ploc", "dec_in_part", "att_xbuf", "pace_flag"]
     _fields_ = ([(n, ctypes.c_int) for n in _I] + [(n, ctypes.c_void_p) for n in _P1] +
                 [(n, ctypes.c_float) for n in _F] + [(n, ctypes.c_void_p) for n in _P2])
+
+
+# T2S_PLAN_* of include/t2s_hip.h, bit 0 upwards; the last bit is `units == 2`
+_PLAN_FLAGS = ("split", "paced", "sig_by_kernel", "fused_att", "q_parts", "q_big", "one", "stream_gates", "fold_pre2", "use_ploc",
+               "proj_fused")
+
+
+class DecodePlan(collections.namedtuple("DecodePlan", _PLAN_FLAGS + ("units",))):
+    """The kernel chain ``t2s_taco_decode_steps`` follows for a decoder struct (``t2s_taco_decode_plan``)."""
+
+    @classmethod
+    def from_bits(cls, bits):
+        n = len(_PLAN_FLAGS)
+        return cls(*[bool(bits >> i & 1) for i in range(n)], units=2 if bits >> n & 1 else 4)
+
+
+# the optional pointers of t2s_taco_decoder and the plan flags that say the library uses them
+PLAN_USES = dict(q_part=("q_parts", "q_big"), att_xbuf=("one",), pace_flag=("paced",), gate_part=("stream_gates",),
+                 ploc=("use_ploc",), w_pre2T=("fold_pre2",))
 
 
 def _f32(t):
@@ -365,6 +386,9 @@ class _TacoEngine:
         self.prep_key = None
         self.lstm_xbufs = {}    # (direction of use, B, device) -> [split BiLSTM exchange buffer, epoch of its last launch]
         self.xbuf_errs = {}     # exchange buffer name -> (its int64 view, index of its error word): read by check_lstm_xbuf()
+        self.decode_stream = True       # offer the streamed-gate buffers (gate_part, ploc, w_pre2T); False: the plain chain (A/B tests)
+        self.last_decode_plan = None    # DecodePlan of the last decoder struct handed to the library ...
+        self.last_decode_offer = ()     # ... and the optional pointers (PLAN_USES) that were set in it
 
     # ------------------------------------------------------------------ weight preparation
     def _pack_conv_bn(self, seq, dev, halo):
@@ -625,16 +649,19 @@ class _TacoEngine:
         # recurrent state and scratch that must start at zero: views of one buffer cleared by one launch
         shapes = dict(att_h0=(B, A), att_h1=(B, A), att_c=(B, A), dec_h0=(B, D), dec_h1=(B, D), dec_c=(B, D),
                       att_w=(B, T_in), att_wcum=(B, T_in), ctx=(B, E), q=(B, ad), energies=(B, T_in),
-                      pre1=(B, Pd), pre2=(B, Pd), q_part=(A // 2, B, ad))
-        if B > 8 and T_in <= 512:
-            shapes["att_xbuf"] = (2 * (B * T_in + 1),)      # (8-byte granules + error word, as f32 pairs; zero = no tag matches)
-        if B > 8 and teacher:
-            shapes["pace_flag"] = (4,)                      # step counter + error word of the paced decoder cells
-        if not teacher:
-            shapes["align_out"] = (B, T_cap, T_in)          # rows past the stop step stay zero
-            if B <= 8 and A == 1024 and D == 1024 and getattr(self, "decode_stream", True):
-                shapes["gate_part"] = (3, B, 4 * A)         # streamed gate partials (ABI v4): zero = h_att(-1) . W_hh_att
-                shapes["ploc"] = (B, T_in, ad)              # location term of the next step's attention (zero: w = w_cum = 0)
+                      pre1=(B, Pd), pre2=(B, Pd))
+        # Buffers that depend on the path: name, shape, condition.  The optional ones are offered under the library's own thresholds
+        # at the default dimensions (t2s_api_taco.hip decode_plan; last_decode_plan says which of them it took).
+        stream = not teacher and B <= 4 and A == 1024 and D == 1024 and self.decode_stream
+        optional = [
+            ("q_part", (A // 2, B, ad), True),                      # partial queries of the attention cell's workgroups
+            ("att_xbuf", (2 * (B * T_in + 1),), B > 8 and T_in <= 512),     # 8-byte granules + error word, as f32 pairs; zero = no tag matches
+            ("pace_flag", (4,), B > 8 and teacher),                 # step counter + error word of the paced decoder cells
+            ("align_out", (B, T_cap, T_in), not teacher),           # (not optional: rows past the stop step stay zero)
+            ("gate_part", (3, B, 4 * A), stream),                   # streamed gate partials: zero = h_att(-1) . W_hh_att
+            ("ploc", (B, T_in, ad), stream),                        # location term of the next step's attention (zero: w = w_cum = 0)
+        ]
+        shapes.update((name, sh) for name, sh, offered in optional if offered)
         offs, tot = {}, 0
         for name, sh in shapes.items():
             n = 1
@@ -669,6 +696,14 @@ class _TacoEngine:
             setattr(d, name, None if t is None else t.data_ptr())
             S[name] = t
         return d, S
+
+    def _query_plan(self, d, step0, n_steps):
+        """The library's plan for the finished struct ``d`` -> last_decode_plan / last_decode_offer; raises what the decode call
+        would raise from its validation."""
+        bits = ctypes.c_uint(0)
+        _lib.call("t2s_taco_decode_plan", ctypes.byref(d), step0, n_steps, ctypes.byref(bits))
+        self.last_decode_offer = tuple(k for k in PLAN_USES if getattr(d, k))
+        self.last_decode_plan = DecodePlan.from_bits(bits.value)
 
     def postnet(self, mel, train_masks=None, seed=0, save=None, lengths=None):
         """Postnet.forward (reference modules.py:131-137): 5 x conv+BN, tanh on the first four; in training mode
@@ -842,6 +877,7 @@ class _TacoEngine:
             d.att_drop_scale = 1.0 / (1.0 - dec.p_attention_dropout)
             d.dec_drop_scale = 1.0 / (1.0 - dec.p_decoder_dropout)
         d.mask_steps = mk.numel() // (B * 2 * dec.prenet_dim)
+        self._query_plan(d, 0, min(chunk, T_cap))
         stop = torch.full((B,), -1, dtype=torch.int32, device=dev)
         st = _lib.current_stream()
         s0 = 0
@@ -937,6 +973,7 @@ class _TacoEngine:
         if m.training:
             d.att_drop_scale = 1.0 / (1.0 - dec.p_attention_dropout)
             d.dec_drop_scale = 1.0 / (1.0 - dec.p_decoder_dropout)
+        self._query_plan(d, 0, T_out)
         _lib.call("t2s_taco_decode_steps", ctypes.byref(d), 0, T_out, _lib.current_stream())
         self._watch_xbuf("decoder att_xbuf", S.get("att_xbuf"), B * memory.size(1))     # (error words: its last 8 bytes ...
         self._watch_xbuf("decoder pace_flag", S.get("pace_flag"), 1)                    # ... and the second 8 of pace_flag)
