@@ -629,7 +629,9 @@ typedef struct t2s_att_bwd {
     const float *ctx; long s_ctx;
     float *dw_carry_out, *dwc_carry_out;
 } t2s_att_bwd;
-/* one decoder step of the location-sensitive attention, backward (tacotron.py:124-166,379) */
+/* one decoder step of the location-sensitive attention, backward (tacotron.py:124-166,379).  T2S_EINVAL, nothing enqueued:
+ * att_dim > 128, loc_f > 32, loc_ks even or > 63, enc_dim % 4 != 0 or > 1024, a NULL required pointer, or the one-launch fields
+ * with a shape or a d_memory that form does not take (t2s_taco_bptt_steps asks the same of its dimensions) */
 int t2s_taco_att_bwd(const t2s_att_bwd* a, void* stream);
 
 /* Reversed decoder loop (BPTT through tacotron.py:355-393,418-427): steps t_hi-1 ... t_lo, newest first.  All buffers are the

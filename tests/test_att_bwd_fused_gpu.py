@@ -1,7 +1,8 @@
 """The one-launch attention backward (att_bwd_fused_kernel: sdot from the saved context, carries scattered into three slots per
 position) against the three-launch form of the same step, through the C ABI (t2s_taco_att_bwd), on random inputs: several row
 lengths (whole and partial 32-position chunks), both location-kernel sizes, ragged lengths, garbage in the carry slots that do
-not exist for a position.  Reference: tacotron/tacotron.py:124-166,379 (the forward both differentiate)."""
+not exist for a position.  Reference: tacotron/tacotron.py:124-166,379 (the forward both differentiate).
+Both forms against float64 autograd of that forward: tests/test_tacotron_bwd_kernels_gpu.py (section 1)."""
 import ctypes
 
 import pytest

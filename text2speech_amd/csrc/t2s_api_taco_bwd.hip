@@ -102,7 +102,8 @@ int t2s_relu_drop_bwd(const float* dy, const float* y, float scale, size_t n, fl
 int t2s_taco_att_bwd(const t2s_att_bwd* p, void* stream) {
     if (!p || !p->w_cur || !p->q || !p->pmem || !p->memory || !p->w_loc_conv || !p->w_loc_dense || !p->w_v ||
         !p->dw_carry || !p->dwc_carry || !p->d_q || !p->d_pmem || (!p->d_memory && !p->dctx_out) || !p->dD_part || !p->dK_part ||
-        !p->dv_part || !p->dw_buf || !p->df_buf || !p->dq_part || p->B <= 0 || p->T <= 0)
+        !p->dv_part || !p->dw_buf || !p->df_buf || !p->dq_part || p->B <= 0 || p->T <= 0 ||
+        !t2s_att_bwd_shape_ok(p->att_dim, p->enc_dim, p->loc_f, p->loc_ks))
         return T2S_EINVAL;
     static_assert(sizeof(t2s_att_bwd) == sizeof(AttBwdArgs), "t2s_att_bwd layout");
     AttBwdArgs a;
@@ -130,7 +131,8 @@ int t2s_taco_bptt_steps(const t2s_taco_bptt* p, int t_hi, int t_lo, void* stream
         !p->dec_gates_all || !p->dec_c_all || !p->att_gates_all || !p->att_c_all || !p->q_all || !p->wcum_all || !p->align ||
         !p->pmem || !p->memory || !p->d_hc || !p->out_d || !p->out_a || !p->dg_d || !p->dg_a || !p->dq_all ||
         !p->dc_d || !p->dc_a || !p->dw_c || !p->dwc_c || !p->d_pmem || !p->d_memory || !p->dD_part || !p->dK_part ||
-        !p->dv_part || !p->dw_buf || !p->df_buf || !p->dq_part)
+        !p->dv_part || !p->dw_buf || !p->df_buf || !p->dq_part || P < 0 || A <= 0 || D <= 0 ||
+        !t2s_att_bwd_shape_ok(ad, E, p->loc_filters, p->loc_kernel))      // (refused before anything is enqueued)
         return T2S_EINVAL;
     // Two chains, two streams.  The decoder-cell chain of step t (pointwise backward, then [W_ih | W_hh]^T dgates) needs only
     // the decoder-cell chain of step t+1: h_dec feeds the next decoder cell and the projection, never the attention.  The

@@ -78,6 +78,8 @@ hipError_t t2s_launch_rows_to_tm_batched(const float* x, long ld, long x_bstride
                                          hipStream_t stream);
 hipError_t t2s_launch_lstm_cell_bwd(const LstmBwdArgs& a, hipStream_t stream);
 hipError_t t2s_launch_relu_drop_bwd(const float* dy, const float* y, float scale, size_t n, float* dz, hipStream_t stream);
+// the dimensions every attention-backward kernel covers (both forms): what the launchers and the C ABI wrappers refuse otherwise
+bool t2s_att_bwd_shape_ok(int att_dim, int enc_dim, int loc_f, int loc_ks);
 hipError_t t2s_launch_att_bwd(const AttBwdArgs& a, hipStream_t stream);
 // the same in two parts: (d_w, energies) and (location-conv backward: carries for step t-1, kernel gradient, d_q fold)
 hipError_t t2s_launch_att_bwd_front(const AttBwdArgs& a, hipStream_t stream);

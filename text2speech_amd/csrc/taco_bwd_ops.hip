@@ -306,6 +306,11 @@ __global__ __launch_bounds__(512) void att_bwd_energy_kernel(const AttBwdArgs a)
         const int ai = i >> 5, f = i & 31;
         s_d[i] = (f < F && ai < AD) ? a.w_loc_dense[ai * F + f] : 0.f;
     }
+    // fewer than 32 filters: the products below run over all 32 feature columns against zero weights, so the columns the
+    // convolution does not write must hold zeros (0 x whatever the LDS held before is not 0 for a NaN or an infinity)
+    if (F < 32)
+        for (int i = tid; i < ATTB_CH * 32; i += 512)
+            if ((i & 31) >= F) s_f[i >> 5][i & 31] = 0.f;
     // this thread's slice of the parameter-gradient slot, fetched early (it is read-modify-write at the very end):
     // dD^T [f][a]: a = tid % 128, f = (tid / 128) * 8 + i
     const int ga = tid & 127, gf0 = (tid >> 7) * 8;
@@ -1248,9 +1253,12 @@ __global__ __launch_bounds__(512) void att_bwd_fused_kernel(const AttBwdArgs a, 
     }
 }
 
+bool t2s_att_bwd_shape_ok(int att_dim, int enc_dim, int loc_f, int loc_ks) {
+    return att_dim > 0 && att_dim <= 128 && enc_dim > 0 && enc_dim <= 1024 && !(enc_dim & 3) && loc_f > 0 && loc_f <= 32 &&
+           loc_ks > 0 && loc_ks <= 63 && (loc_ks & 1);
+}
 static bool att_bwd_ok(const AttBwdArgs& a) {
-    return !(a.enc_dim > 1024 || (a.enc_dim & 3) || a.att_dim > 128 || a.loc_f > 32 || a.loc_ks > 63 || !(a.loc_ks & 1) ||
-             !a.dw_buf || !a.df_buf || !a.dq_part);
+    return t2s_att_bwd_shape_ok(a.att_dim, a.enc_dim, a.loc_f, a.loc_ks) && a.dw_buf && a.df_buf && a.dq_part;
 }
 hipError_t t2s_launch_att_bwd_front(const AttBwdArgs& a, hipStream_t stream) {
     if (!att_bwd_ok(a)) return hipErrorInvalidValue;

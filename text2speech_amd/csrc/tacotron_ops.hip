@@ -618,6 +618,11 @@ __global__ __launch_bounds__(256) void att_energy_kernel(const AttArgs a) {
         const float* src = c ? a.w_cum : a.w_prev;
         s_cat[c][j] = (t >= 0 && t < a.T) ? src[(size_t)b * a.T + t] : 0.f;
     }
+    // fewer than 32 filters: the energies below multiply all 32 feature columns (by zero weights past F), so the columns the
+    // convolution does not write must hold zeros (0 x whatever the LDS held before is not 0 for a NaN or an infinity)
+    if (F < 32)
+        for (int i = tid; i < ATT_TQ * 32; i += 256)
+            if ((i & 31) >= F) s_f[i >> 5][i & 31] = 0.f;
     __syncthreads();
     for (int i = tid; i < ATT_TQ * F; i += 256) {
         const int tq = i / F, f = i - tq * F;
@@ -1225,6 +1230,9 @@ __global__ __launch_bounds__(1024) void att_fused_kernel(const AttArgs a) {
             for (int j = 0; j < KS; ++j) acc += s_k[(f * 2 + c) * KS + j] * s_cat[c][t + j];
         s_f[t * 33 + f] = acc;
     }
+    if (F < 32)             // (the energies multiply all 32 feature columns, by zero weights past F: those columns must hold zeros)
+        for (int i = tid; i < T * 32; i += 1024)
+            if ((i & 31) >= F) s_f[(i >> 5) * 33 + (i & 31)] = 0.f;
     __syncthreads();
     PROBE_MID(2)
     // ---- energies: attention_dim on lanes (2 per lane), one wave per time step ----
