@@ -250,7 +250,9 @@ int t2s_conv_bias_act(const void* A_hi, const void* A_lo, const float* bias, con
 /* y[item][row] = act(bias1[row] + bias2[row] + [W1[row] | W2[row]] . [x1 | x2 | x3](item)) * mask * mask_scale
  * One wave per output row (weights in registers), loop over items.  Replaces the small Linear layers:
  * query_layer (tacotron.py:137), linear_projection / gate_layer (:387-392), Prenet (modules.py:19-22),
- * memory_layer (tacotron.py:306).  K = n1+n2+n3 = k1+k2 <= 2560, every n a multiple of 4. */
+ * memory_layer (tacotron.py:306).  K = n1+n2+n3 = k1+k2 <= 4096; every n, k, ld and item stride a multiple of 4; W and x
+ * 16-byte aligned; act 0..2.  Anything else: T2S_EINVAL, nothing enqueued.  More than 8 items with every n and k1 a multiple of
+ * 16 run on the f32 matrix cores (same results up to summation order). */
 int t2s_gemv(const float* W1, int ld1, int k1, const float* W2, int ld2, int k2, const float* x1, int n1, long sx1,
              const float* x2, int n2, long sx2, const float* x3, int n3, long sx3, const float* bias1,
              const float* bias2, float* y, long sy_item, long sy_row, int rows, int items, int act,

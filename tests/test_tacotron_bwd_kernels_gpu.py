@@ -36,6 +36,7 @@ import torch.nn.functional as F
 
 import wg_bwd_util as U
 from text2speech_amd import _lib
+from taco_ref_util import LEN as _LEN, att_step as _att_step, lstm as _lstm
 from text2speech_amd.tacotron.autograd import _AttBwd, _Bptt, _BnBwd, _p
 from wg_bwd_util import DEV, F32_MAX, F32_NORM, Guarded, check, dev
 
@@ -91,22 +92,6 @@ def _added(o, name, t, shape=None):
 def _print_floors(ref64, ref32, tag):
     for k, v in ref64.items():
         print("FLOOR  %-60s norm-rel %.3e  max-rel %.3e" % ("%s %s" % (tag, k), U.rel(ref32[k], v), U.maxrel(ref32[k], v)))
-
-
-# ------------------------------------------------------------------------------------ the attention step, in any floating type
-def _att_step(q, pmem, memory, w_prev, wc_prev, K, D, v, lengths):
-    """tacotron.py:124-166,379: f = conv1d([w_prev; wc_prev], K); e = v . tanh(q + D f + pmem), -inf from `length` on;
-    w = softmax(e); ctx = w . memory; wc = wc_prev + w."""
-    T = pmem.size(1)
-    f = F.conv1d(torch.stack([w_prev, wc_prev], 1), K, padding=K.size(2) // 2)              # [B, F, T]
-    e = torch.tanh(q[:, None, :] + f.transpose(1, 2) @ D.t() + pmem) @ v
-    e = e.masked_fill(torch.arange(T)[None, :] >= lengths[:, None], float("-inf"))
-    w = torch.softmax(e, 1)
-    return w, torch.einsum("bt,bte->be", w, memory), wc_prev + w
-
-
-_LEN = {1: lambda T: [T], 2: lambda T: [T, max(1, T - 7)], 3: lambda T: [T, max(1, T - 7), 1],
-        9: lambda T: [T, max(1, T - 7), max(1, T // 2), T, max(1, T - 15), 1, max(1, T - 2), max(1, T // 3), T]}
 
 
 # ================================================================================ 1. t2s_taco_att_bwd against float64 autograd
@@ -310,14 +295,6 @@ def test_att_bwd_one_launch(lib, T, KS):
 # ======================================================================== 2. t2s_taco_bptt_steps on a small float64 decoder loop
 _BPTT = {}
 _BP = dict(P=32, E=64, A=128, D=128, T_in=40, T_out=18, T_cap=20, p_att=0.1, p_dec=0.1)
-
-
-def _lstm(x_full, W, bias, c_prev):
-    z = x_full @ W.t() + bias
-    i, f, g, o = z.chunk(4, 1)
-    i, f, g, o = torch.sigmoid(i), torch.sigmoid(f), torch.tanh(g), torch.sigmoid(o)
-    c = f * c_prev + i * g
-    return z, torch.cat([i, f, g, o], 1), c, o * torch.tanh(c)
 
 
 def _bptt_case(ad, F_, KS, B, masks):
