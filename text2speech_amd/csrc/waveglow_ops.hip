@@ -932,54 +932,137 @@ hipError_t t2s_launch_end_affine(const float* skip, const float* w_end, const fl
 // and W_end W_skip,i is only [2*n_half x C].  So the skip half of every res_skip GEMM (9 % of the FLOPs)
 // and the f32 skip accumulator (2 x 33 MB of traffic per layer) disappear; the gate GEMM's epilogue
 // applies the 8-row product to the gate outputs it already holds in registers.
-__global__ __launch_bounds__(256) void endfold_weights_kernel(const EndFoldJob* __restrict__ jobs, int C) {
-    extern __shared__ float s_ws[];              // [8][C]: W_end[j][o] * scale[o]
-    __shared__ float red[4];
-    const EndFoldJob j = jobs[blockIdx.x];
-    const int tid = threadIdx.x;
+//
+// Per layer F = (W_end . diag(scale)) . V_skip is an [8 x C] by [C x C] product whose cost is the one read of V_skip (C*C floats).
+// One workgroup = (layer, block of 32 columns c), so a flow's launch is n_layers * C / 32 short-lived workgroups.  Thread =
+// (o slice s = tid / 8, column quad cq = tid % 8): slice s takes rows o = s, s + 32, ..., a wave request is 8 rows of 128
+// contiguous bytes, and 8 independent 16-byte loads per thread are in flight under the arithmetic of the 8 before.  The 32
+// slices are summed through LDS in slice order (no atomics: the same inputs give the same bits), by the thread that stores
+// the element, in fold_A order.
+#define EF_OROWS 8            // rows o per thread and chunk of 32 * EF_OROWS rows
+#define EF_PART (8 * 33)      // floats per slice of the partial sums [32][8][33] (33: rows r on different banks)
+typedef const float __attribute__((address_space(1))) * ef_gptr;      // the job's pointers come from memory: say they are global
+typedef float ef_f4 __attribute__((ext_vector_type(4)));
+// Row and columns are clamped into the matrix, so every load is unconditional: a row o >= C meets a zero weight, a column
+// c >= C is never stored.
+template <bool VEC>
+static __device__ __forceinline__ float4 endfold_load4(ef_gptr v, int o, int c0, int C) {
+    ef_gptr p = v + (size_t)min(o, C - 1) * C;
+    if (VEC) {                                   // C % 4 == 0: the quad is wholly inside the row
+        const ef_f4 t = *(const ef_f4 __attribute__((address_space(1))) *)(p + min(c0, C - 4));
+        return make_float4(t.x, t.y, t.z, t.w);
+    }
+    return make_float4(p[min(c0, C - 1)], p[min(c0 + 1, C - 1)], p[min(c0 + 2, C - 1)], p[min(c0 + 3, C - 1)]);
+}
+template <bool VEC>
+static __device__ __forceinline__ void endfold_block(const EndFoldJob& j, int C, int Cp, float* s_ef, float* s_bes) {
+    const int tid = threadIdx.x, s = tid >> 3, cq = tid & 7;
     const int nj = (int)j.nj;
-    for (int i = tid; i < 8 * C; i += 256) {
-        const int r = i / C, o = i - r * C;
-        s_ws[i] = (r < nj) ? j.w_end[(size_t)r * C + o] * (j.scale ? j.scale[o] : 1.f) : 0.f;
+    const int c0 = blockIdx.y * 32 + cq * 4;
+    ef_gptr v = (ef_gptr)j.v_skip;
+    float4 x[EF_OROWS], xn[EF_OROWS];
+#pragma unroll
+    for (int e = 0; e < EF_OROWS; ++e) x[e] = endfold_load4<VEC>(v, s + 32 * e, c0, C);      // in flight under the staging
+    // W_end * scale into LDS: thread = rows o = tid, tid + 256 of all 8 rows r, its 2 * (8 + 2) loads in flight together.  The
+    // workgroups of column block 0 also sum bes[r] = W_end[r] . b_skip from the same registers.
+    ef_gptr w_end = (ef_gptr)j.w_end, scale = (ef_gptr)j.scale, b_skip = (ef_gptr)j.b_skip;
+    const bool with_bes = blockIdx.y == 0;
+    float bsum[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) bsum[r] = 0.f;
+    for (int ob = 0; ob < Cp; ob += 512) {
+        float sc[2], bk[2], wv[2][8];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int o = ob + u * 256 + tid;
+            const bool ok = o < C;
+            sc[u] = (ok && scale) ? scale[o] : 1.f;
+            bk[u] = (ok && with_bes) ? b_skip[o] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) wv[u][r] = (ok && r < nj) ? w_end[(size_t)r * C + o] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int o = ob + u * 256 + tid;
+            if (o < Cp) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    s_ef[r * Cp + o] = wv[u][r] * sc[u];
+                    bsum[r] += wv[u][r] * bk[u];
+                }
+            }
+        }
+    }
+    if (with_bes) {                              // fixed order: wave sums, then the four waves
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const float t = wave_sum(bsum[r]);
+            if ((tid & 63) == 0) s_bes[(tid >> 6) * 8 + r] = t;
+        }
     }
     __syncthreads();
-    const int c = blockIdx.y * 256 + tid;
-    if (c < C) {
-        float acc[8];
+    if (with_bes && tid < 8) j.bes[tid] = s_bes[tid] + s_bes[8 + tid] + s_bes[16 + tid] + s_bes[24 + tid];
+    float acc[8][4];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) acc[r] = 0.f;
-        for (int o = 0; o < C; ++o) {
-            const float v = j.v_skip[(size_t)o * C + c];
+    for (int r = 0; r < 8; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.f;
+    for (int o0 = 0; o0 < C; o0 += 32 * EF_OROWS) {
+        const int o1 = o0 + 32 * EF_OROWS;
+        if (o1 < C) {
 #pragma unroll
-            for (int r = 0; r < 8; ++r) acc[r] += s_ws[r * C + o] * v;
+            for (int e = 0; e < EF_OROWS; ++e) xn[e] = endfold_load4<VEC>(v, o1 + s + 32 * e, c0, C);
         }
-        // scatter into the A-fragment layout the gate epilogue reads: lane = q*16 + row j, element e = half*4 + reg
-        const int mt = c >> 7, wr = (c >> 6) & 1, pair = (c >> 5) & 1, half = (c >> 4) & 1, q = (c >> 2) & 3, reg = c & 3;
-        u16* base = j.fold_A + ((size_t)((mt * 2 + wr) * 2 + pair) * 2 * 64) * 8;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            u16 h, l;
-            split_bf16(acc[r], h, l);
-            const int lane = q * 16 + r;
-            base[(size_t)lane * 8 + half * 4 + reg] = h;
-            base[(size_t)(64 + lane) * 8 + half * 4 + reg] = l;
+        for (int e = 0; e < EF_OROWS; ++e) {
+            const float* w = s_ef + o0 + s + 32 * e;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                acc[r][0] += w[r * Cp] * x[e].x;
+                acc[r][1] += w[r * Cp] * x[e].y;
+                acc[r][2] += w[r * Cp] * x[e].z;
+                acc[r][3] += w[r * Cp] * x[e].w;
+            }
         }
+#pragma unroll
+        for (int e = 0; e < EF_OROWS; ++e) x[e] = xn[e];
     }
-    if (blockIdx.y == 0) {
-        for (int r = 0; r < 8; ++r) {
-            float s = 0.f;
-            if (r < nj)
-                for (int o = tid; o < C; o += 256) s += j.w_end[(size_t)r * C + o] * j.b_skip[o];
-            s = wave_sum(s);
-            __syncthreads();
-            if ((tid & 63) == 0) red[tid >> 6] = s;
-            __syncthreads();
-            if (tid == 0) j.bes[r] = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();                             // every read of W_end * scale is done: the buffer becomes the partial sums
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        float* p = s_ef + s * EF_PART + r * 33 + cq * 4;
+        p[0] = acc[r][0]; p[1] = acc[r][1]; p[2] = acc[r][2]; p[3] = acc[r][3];
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(256) void endfold_weights_kernel(const EndFoldJob* __restrict__ jobs, int C) {
+    extern __shared__ float s_ef[];              // [8][Cp]: W_end[j][o] * scale[o], zero for o >= C; then the partial sums [32][EF_PART]
+    __shared__ float s_bes[4 * 8];               // bes per wave
+    const EndFoldJob j = jobs[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int Cp = (C + 32 * EF_OROWS - 1) & ~(32 * EF_OROWS - 1);      // whole chunks of rows
+    if (!(C & 3) && !((uintptr_t)j.v_skip & 15)) endfold_block<true>(j, C, Cp, s_ef, s_bes);
+    else endfold_block<false>(j, C, Cp, s_ef, s_bes);
+    {
+        // thread -> one element of the A-fragment layout the gate epilogue reads: lane = q*16 + row r, element e = half*4 + reg of
+        // column c = block*32 + half*16 + q*4 + reg; a wave stores 64 consecutive bf16 per plane
+        const int q = tid >> 6, r = (tid >> 3) & 7, e = tid & 7;
+        const int cl = (e >> 2) * 16 + q * 4 + (e & 3);
+        float sum = 0.f;
+#pragma unroll 8
+        for (int sl = 0; sl < 32; ++sl) sum += s_ef[sl * EF_PART + r * 33 + cl];
+        if (blockIdx.y * 32 + cl < C) {
+            u16* base = j.fold_A + (size_t)blockIdx.y * 2 * 64 * 8;      // block = c >> 5 = (mt*2 + wr)*2 + pair
+            u16 h, l;
+            split_bf16(sum, h, l);
+            const int lane = q * 16 + r;
+            base[(size_t)lane * 8 + e] = h;
+            base[(size_t)(64 + lane) * 8 + e] = l;
         }
     }
 }
 hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C, hipStream_t stream) {
-    hipLaunchKernelGGL(endfold_weights_kernel, dim3(n_jobs, (C + 255) / 256), dim3(256), (size_t)8 * C * sizeof(float),
+    const int Cp = (C + 32 * EF_OROWS - 1) & ~(32 * EF_OROWS - 1);
+    const int lds_floats = 8 * Cp > 32 * EF_PART ? 8 * Cp : 32 * EF_PART;
+    hipLaunchKernelGGL(endfold_weights_kernel, dim3(n_jobs, (C + 31) / 32), dim3(256), (size_t)lds_floats * sizeof(float),
                        stream, jobs, C);
     return hipGetLastError();
 }
@@ -994,53 +1077,96 @@ hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C,
 // rounds each factor to 16 bits, and here the 15 products are much larger than their sum, so the chunks hold FOUR column sets
 // (start_fold_term above: nwc = 2 chunks of two sets when 2 ncol <= 32, else 4 chunks of one) that carry both factors to f32
 // accuracy.  The K of the convolution half of that launch drops from taps * C to nwc 32-wide steps.
-// A workgroup = 8 output rows x 32 columns; a row's 32 lanes first reduce its weight-norm scale g / |v|.
+// A wave = one output row, a workgroup = up to 4 of them, so the launch is 2C / 4 short-lived workgroups.  The wave reads its row
+// of v once with coalesced 16-byte loads into LDS, summing the squares for the weight-norm scale g / |v| on the way; the dot
+// products then come from the staged copy: lane = (half of the C range, column), the two halves are added by one shuffle (a fixed
+// order: the same inputs give the same bits).  Half 0 stores the hi plane, half 1 the lo plane.
 __global__ __launch_bounds__(256) void startfold_weights_kernel(const float* __restrict__ v, const float* __restrict__ g,
                                                                 const float* __restrict__ w_start,
                                                                 const float* __restrict__ b_start, int C, int nh, int Kt,
                                                                 int Mpad, int nwc, u16* A_hi, u16* A_lo) {
-    extern __shared__ float s_wb[];              // [C][nh + 1]: W_start | b_start
-    const int tid = threadIdx.x, r = tid >> 5, col = tid & 31;
+    extern __shared__ float s_sf[];              // [C][nh + 1]: W_start | b_start (padded to 16 bytes), then a row [C * Kt] per wave
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nwaves = blockDim.x >> 6;
     const int nw = nh + 1, n = C * Kt, O = 2 * C;
-    for (int i = tid; i < C * nw; i += 256) {
-        const int c = i / nw, j = i - c * nw;
-        s_wb[i] = j < nh ? w_start[c * nh + j] : b_start[c];
-    }
-    const int o = blockIdx.x * 8 + r;
+    float* xs = s_sf + ((C * nw + 3) & ~3) + (size_t)wave * ((n + 3) & ~3);
+    const int o = blockIdx.x * nwaves + wave;
     const bool row_ok = o < O;
     const float* vrow = v + (size_t)(row_ok ? o : 0) * n;
-    float scale = 1.0f;
-    if (g) {
-        float ss = 0.f;
-        for (int i = col; i < n; i += 32) ss += vrow[i] * vrow[i];
-        ss = sum16(ss);
-        ss += __shfl_xor(ss, 16, 64);
-        scale = g[row_ok ? o : 0] / sqrtf(ss);
+    float ss = 0.f;
+    const bool vec = !(n & 3) && !((uintptr_t)v & 15);
+    const int bd = blockDim.x, nws = C * nh;
+    if (!vec) {
+        for (int i = lane; i < n; i += 64) {
+            const float x = vrow[i];
+            xs[i] = x;
+            ss += x * x;
+        }
     }
+    // One pass at WaveGlow's shapes: 8 row loads of 16 bytes, 8 of W_start and 2 of b_start per thread, all in flight together.
+    for (int b = 0;; ++b) {
+        const int v0 = b * 2048 + lane * 4, w0 = b * 8 * bd + tid, b0 = b * 2 * bd + tid;
+        if ((!vec || b * 2048 >= n) && b * 8 * bd >= nws && b * 2 * bd >= C) break;
+        float4 xr[8];
+        float wr[8], br[2];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            xr[k] = (vec && v0 + k * 256 < n) ? *(const float4*)(vrow + v0 + k * 256) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wr[k] = w0 + k * bd < nws ? w_start[w0 + k * bd] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) br[k] = b0 + k * bd < C ? b_start[b0 + k * bd] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (vec && v0 + k * 256 < n) {
+                *(float4*)(xs + v0 + k * 256) = xr[k];
+                ss += xr[k].x * xr[k].x + xr[k].y * xr[k].y + xr[k].z * xr[k].z + xr[k].w * xr[k].w;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = w0 + k * bd;
+            if (i < nws) {
+                const int c = i / nh;
+                s_sf[c * nw + (i - c * nh)] = wr[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (b0 + k * bd < C) s_sf[(b0 + k * bd) * nw + nh] = br[k];
+    }
+    ss = wave_sum(ss);
+    const float scale = g ? g[row_ok ? o : 0] / sqrtf(ss) : 1.0f;
     __syncthreads();
     if (!row_ok) return;
+    const int half = lane >> 5, col = lane & 31;
     const int ncol = Kt * nw, spc = 4 / nwc;
     const int sidx = col / ncol, lc = col - sidx * ncol;
     float acc = 0.f;
     if (sidx < spc) {
         const int tap = lc / nw, j = lc - tap * nw;
+        const int ch = (C + 1) >> 1, c1 = half ? C : ch;
 #pragma unroll 8
-        for (int c = 0; c < C; ++c) acc += vrow[c * Kt + tap] * s_wb[c * nw + j];
+        for (int c = half ? ch : 0; c < c1; ++c) acc += xs[c * Kt + tap] * s_sf[c * nw + j];
     }
+    acc += __shfl_xor(acc, 32, 64);
     const int gate = o >= C;
     const int ch = gate ? o - C : o;
     const int p = (ch >> 7) * 256 + ((ch >> 6) & 1) * 128 + (((ch >> 4) & 3) * 2 + gate) * 16 + (ch & 15);
+    u16* A = half ? A_lo : A_hi;
     for (int wc = 0; wc < nwc; ++wc) {
         u16 h, l;
         start_fold_term(acc * scale, wc * spc + sidx, true, h, l);
-        A_hi[((size_t)wc * Mpad + p) * 32 + col] = h;
-        A_lo[((size_t)wc * Mpad + p) * 32 + col] = l;
+        A[((size_t)wc * Mpad + p) * 32 + col] = half ? l : h;
     }
 }
 hipError_t t2s_launch_startfold_weights(const float* v, const float* g, const float* w_start, const float* b_start, int C,
                                         int n_half, int taps, int Mpad, int nwc, u16* A_hi, u16* A_lo, hipStream_t stream) {
-    hipLaunchKernelGGL(startfold_weights_kernel, dim3((2 * C + 7) / 8), dim3(256), (size_t)C * (n_half + 1) * sizeof(float),
-                       stream, v, g, w_start, b_start, C, n_half, taps, Mpad, nwc, A_hi, A_lo);
+    // rows (waves) per workgroup: 4 where their staged copies fit in 64 KB of LDS next to [W_start | b_start]
+    const size_t wb = (size_t)((C * (n_half + 1) + 3) & ~3), row = (size_t)((C * taps + 3) & ~3);
+    int rows = 4;
+    while (rows > 1 && (wb + rows * row) * sizeof(float) > 65536) rows >>= 1;
+    hipLaunchKernelGGL(startfold_weights_kernel, dim3((2 * C + rows - 1) / rows), dim3(64 * rows),
+                       (wb + rows * row) * sizeof(float), stream, v, g, w_start, b_start, C, n_half, taps, Mpad, nwc, A_hi, A_lo);
     return hipGetLastError();
 }
 

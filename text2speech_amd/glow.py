@@ -677,7 +677,8 @@ class _Engine:
                 _lib.call("t2s_small_logdet_inv_batch", _lib.ptr(jobs), m.n_flows, float(B * L), st2)
         # The per-forward weight pack (weight_norm recompute + split + permute, HBM-bound: 1.07 GB in, 1.07 GB out) runs flow by
         # flow on a third stream; the main stream waits for flow k's event only, so all but the first flow's share of the pack
-        # hides under the GEMMs of the flows before it.
+        # runs beside the GEMMs of the flows before it.  It is not free there: without these launches the 16.36 ms step at
+        # 8 x 16000 is 0.98 ms shorter (profiles/weight_prep_ceiling.txt).
         pack_s = self._stream("pack", dev)
         pack_events = []
         pack_s.wait_stream(main)
