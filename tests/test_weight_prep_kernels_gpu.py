@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import wg_bwd_util as U
+from wg_fwd_util import _endfold_decode, _gate_row
 from text2speech_amd import _lib, planes
 
 pytestmark = pytest.mark.gpu
@@ -58,19 +59,6 @@ def _endfold_run(C, jobs):
     _lib.call("t2s_wg_endfold_weights", _lib.ptr(table), len(jobs), C, _lib.current_stream())
     torch.cuda.synchronize()
     return table
-
-
-def _endfold_decode(fold, C):
-    """fold_A -> (float64 [16, 128 ceil(C / 128)] by lane row and column, hi + lo): element (c, r) is at block c >> 5, plane hi / lo,
-    lane ((c >> 2) & 3) * 16 + r, element ((c >> 4) & 1) * 4 + (c & 3)"""
-    a = fold.double().cpu().view(-1, 2, 64, 8)
-    c = torch.arange(a.size(0) * 32)
-    out = torch.zeros(16, c.numel(), dtype=torch.float64)
-    for r in range(16):
-        lane = ((c >> 2) & 3) * 16 + r
-        e = ((c >> 4) & 1) * 4 + (c & 3)
-        out[r] = a[c >> 5, 0, lane, e] + a[c >> 5, 1, lane, e]
-    return out
 
 
 ENDFOLD_CASES = [(32, [(8, True)]), (32, [(4, True), (6, False), (8, True)]),
@@ -120,13 +108,6 @@ def test_endfold_weights_same_bits_every_launch():
 
 
 # ---------------------------------------------------------------------------------------------- startfold
-def _gate_row(o, C):
-    """packed row of output channel o of a 2C-row gate convolution (T2S_PERM_GATE)"""
-    gate = (o >= C).long()
-    ch = o - gate * C
-    return (ch >> 7) * 256 + ((ch >> 6) & 1) * 128 + (((ch >> 4) & 3) * 2 + gate) * 16 + (ch & 15)
-
-
 def _startfold_inputs(C, nh, taps, with_g, seed):
     gen = torch.Generator().manual_seed(seed)
     return dict(v=U.dev(torch.randn(2 * C, C, taps, generator=gen)),
