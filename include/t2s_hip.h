@@ -229,6 +229,31 @@ int t2s_wg_flow_boundary(const float* z_in, float* z_out, const float* fold_acc,
                          const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off, int n_rem,
                          int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks, void* W_hi, void* W_lo,
                          void* stream);
+/* ---- Batched inference of mels of different lengths (ABI v4, compatible addition) ----
+ * Within one column the inverse flow is pointwise; an entry of a padded batch reads past its own end only through the taps of the gate
+ * GEMM on the X planes and through the taps the window planes hold.  So the writers of those planes take `lengths` ([B] int32 in
+ * device memory, in columns; an entry's length is clamped to [0, L]) and the gate GEMMs stay as they are.  Each entry point below takes
+ * its partner's arguments and checks plus `lengths` (NULL: T2S_EINVAL); for t < lengths[b] it stores what the partner stores.
+ *  t2s_wg_start_ragged: t2s_wg_start_window, or t2s_wg_start when W_hi == W_lo == NULL (taps and win_chunks are not read then).  X rows
+ *    lengths[b] <= t < L are stored as zeros, hi and lo (stored: the planes may hold a longer call's rows); a window tap at column
+ *    tt >= lengths[b] counts as outside, for the audio columns and the ones-column.
+ *  t2s_wg_res_only_ragged, t2s_wg_res_only_start_ragged: X rows lengths[b] <= t < L are stored as zeros, hi and lo.
+ *  t2s_wg_flow_boundary_ragged: the window planes as t2s_wg_start_ragged writes them; coupling, convolution and z_out are per column
+ *    and cover all L columns as in the partner. */
+int t2s_wg_start_ragged(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                        int L, int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                        const int* lengths, void* stream);
+int t2s_wg_res_only_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                           void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, const int* lengths,
+                           void* stream);
+int t2s_wg_res_only_start_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                                 const float* z, const float* w_start, const float* b_start, int n_group, int c_off, int n_half,
+                                 void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, const int* lengths,
+                                 void* stream);
+int t2s_wg_flow_boundary_ragged(const float* z_in, float* z_out, const float* fold_acc, int nslots, const float* bes, int n_layers,
+                                const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off,
+                                int n_rem, int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks,
+                                void* W_hi, void* W_lo, const int* lengths, void* stream);
 /* WN.end output from the folded accumulators + affine coupling (forward or reverse) */
 int t2s_wg_end_fold_affine(const float* fold_acc, int nslots, const float* bes, int n_layers, const float* b_end,
                            float* z, float* log_s, float* wn_out, int B, int n_group, int c_off, int n_half, int L, int reverse,

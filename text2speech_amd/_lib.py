@@ -52,6 +52,10 @@ SIGNATURES = {
     "t2s_wg_res_only": [c_vp] * 7 + [c_int] * 7 + [c_vp],
     "t2s_wg_res_only_start": [c_vp] * 8 + [c_int] * 3 + [c_vp, c_vp] + [c_int] * 6 + [c_vp],
     "t2s_wg_flow_boundary": [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp] + [c_int] * 10 + [c_vp, c_vp, c_vp],
+    "t2s_wg_start_ragged": [c_vp, c_vp, c_vp] + [c_int] * 8 + [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
+    "t2s_wg_res_only_ragged": [c_vp] * 7 + [c_int] * 7 + [c_vp, c_vp],
+    "t2s_wg_res_only_start_ragged": [c_vp] * 8 + [c_int] * 3 + [c_vp, c_vp] + [c_int] * 6 + [c_vp, c_vp],
+    "t2s_wg_flow_boundary_ragged": [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp] + [c_int] * 10 + [c_vp, c_vp, c_vp, c_vp],
     "t2s_wg_end_fold_affine": [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     "t2s_wg_end_affine": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                           c_int, c_vp],

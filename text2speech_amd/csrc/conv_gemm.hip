@@ -52,7 +52,11 @@ static __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 // K-steps of ~0.7 us of MFMA against a ~1.7 us fill turnaround, so the fill must be issued two steps ahead.
 // X0 = RESSKIP on 128-row tiles with PERM_PAIR8 rows, first layer of a flow: the residual values are WN.start's output, rebuilt in
 // the epilogue from the n_half <= 4 audio channels of the lane's columns (a.x0_*) instead of read back from the X planes.
-template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false>
+// RAG = the 128-row RESSKIP kernels for a batch of entries of different lengths (a.lengths): columns lengths[b] <= t < L of the
+// residual rows are stored as zeros, hi and lo - stored, not skipped: the planes may hold an earlier, longer call's rows - so that
+// the dilated taps of the next gate GEMM read past an entry's end what they read past L when it runs alone.  Columns t < lengths[b]
+// take the arithmetic of the RAG = false kernel in its order.
+template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false, bool RAG = false>
 __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     constexpr int WN = 4;                            // waves along N (time): 8 waves of 128 x 64, two per SIMD
     constexpr int NTH = 128 * WN;                    // threads per workgroup
@@ -168,6 +172,9 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     constexpr bool PREX = EPI == EPI_RESSKIP && MT == 128;
     constexpr bool PRER = PREX && !X0;               // the residual values come from the planes
     static_assert(!X0 || PREX, "X0 is a variant of the 128-row RESSKIP kernel");
+    static_assert(!RAG || PREX, "RAG is a variant of the 128-row RESSKIP kernels");
+    int len_b = 0;                                   // RAG: this batch entry's columns
+    if constexpr (RAG) len_b = min(max(a.lengths[b], 0), a.L);
     u16x4 pre_h[PRER ? MW : 1][PRER ? NWT : 1], pre_l[PRER ? MW : 1][PRER ? NWT : 1];
     typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
     // X0: what WN.start needs for this lane's NWT columns and 8 consecutive channels per m-tile pair - the audio values, 8 x n_half
@@ -541,6 +548,14 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                 const int t = t0 + wc * (NWT * 16) + n * 16 + tcol;
                 if (t >= a.L) continue;
                 u16x8_t hi, lo;
+                if constexpr (RAG) {
+                    if (t >= len_b) {
+                        hi = lo = (u16x8_t){0, 0, 0, 0, 0, 0, 0, 0};
+                        *(u16x8_t*)(a.O_hi + base + (size_t)t * 32) = hi;
+                        *(u16x8_t*)(a.O_lo + base + (size_t)t * 32) = lo;
+                        continue;
+                    }
+                }
                 float r[8];            // the residual values: channels ch .. ch + 7 of column t
                 if constexpr (X0) {
                     // start_kernel's operation order, then its rounding to the (hi, lo) pair: the value the X planes would hold
@@ -626,6 +641,14 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                         const int t = t0 + wc * (NWT * 16) + n * 16 + tcol;
                         if (t >= a.L) continue;
                         u16x4 hi, lo;
+                        if constexpr (RAG) {
+                            if (t >= len_b) {
+                                hi = lo = (u16x4){0, 0, 0, 0};
+                                *(u16x4*)(xhi + (size_t)t * 32) = hi;
+                                *(u16x4*)(xlo + (size_t)t * 32) = lo;
+                                continue;
+                            }
+                        }
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const float v = join_bf16(oh[mi][n][e], ol[mi][n][e]) + (acc[m][n][e] + bv[mi][e]);
@@ -733,20 +756,23 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     }
 }
 
-template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false>
+template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false, bool RAG = false>
 static hipError_t launch_one(const ConvGemmArgs& a, hipStream_t stream) {
     const int nwg = a.n_mtiles * a.n_ttiles * a.B;
     constexpr size_t lds = SH ? 2 * (2 * MT * 64) + 4 * 320 * 64 : NS * (2 * MT * 64 + 2 * B_PLANE_BYTES);
     static std::atomic<unsigned long long> attr_mask{0};        // per instantiation; bit d = raised on device d
-    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, SH, NS, X0>, (int)lds, attr_mask);
+    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, SH, NS, X0, RAG>, (int)lds, attr_mask);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, SH, NS, X0>), dim3(nwg), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, SH, NS, X0, RAG>), dim3(nwg), dim3(512), lds, stream, a);
     return hipGetLastError();
 }
 
 // a.n_mtiles must have been computed for the same tile height `mt_rows` (256 or 128)
 hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows) {
+    if (a.lengths && (mt_rows != 128 || epi != EPI_RESSKIP)) return hipErrorInvalidValue;     // the ragged form exists for these only
     if (mt_rows == 128) {
+        if (epi == EPI_RESSKIP && a.lengths && a.x0_z) return launch_one<EPI_RESSKIP, 128, false, 2, true, true>(a, stream);
+        if (epi == EPI_RESSKIP && a.lengths) return launch_one<EPI_RESSKIP, 128, false, 2, false, true>(a, stream);
         if (epi == EPI_RESSKIP && a.x0_z) return launch_one<EPI_RESSKIP, 128, false, 2, true>(a, stream);
         if (epi == EPI_RESSKIP) return launch_one<EPI_RESSKIP, 128>(a, stream);
         if (epi == EPI_GATE_BWD) return launch_one<EPI_GATE_BWD, 128>(a, stream);

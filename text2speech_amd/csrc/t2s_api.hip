@@ -142,14 +142,36 @@ static bool win_chunks_ok(int taps, int n_half, int win_chunks) {
     return (4 / win_chunks) * taps * (n_half + 1) <= 32;
 }
 
-int t2s_wg_start_window(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
-                        int L, int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
-                        void* stream) {
+// t2s_wg_start_window and, with `lengths`, the window form of t2s_wg_start_ragged
+static int start_window(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C, int L,
+                        int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                        const int* lengths, void* stream) {
     if (!z || !w || !bias || !planes_ok(X_hi, X_lo) || !planes_ok(W_hi, W_lo)) return T2S_EINVAL;
     if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
     if (!win_chunks_ok(taps, n_half, win_chunks) || cdiv(C, 32) < win_chunks || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
-                                   (hipStream_t)stream, taps, win_chunks, (u16*)W_hi, (u16*)W_lo));
+                                   (hipStream_t)stream, taps, win_chunks, (u16*)W_hi, (u16*)W_lo, lengths));
+    return T2S_OK;
+}
+
+int t2s_wg_start_window(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                        int L, int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                        void* stream) {
+    return start_window(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, X_hi, X_lo, taps, win_chunks, W_hi, W_lo, nullptr, stream);
+}
+
+int t2s_wg_start_ragged(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                        int L, int Lp, int halo, void* X_hi, void* X_lo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                        const int* lengths, void* stream) {
+    if (!lengths) return T2S_EINVAL;
+    if (W_hi || W_lo)
+        return start_window(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, X_hi, X_lo, taps, win_chunks, W_hi, W_lo, lengths, stream);
+    // no window planes: t2s_wg_start's checks (taps and win_chunks are not read)
+    if (!z || !w || !bias || !X_hi || !X_lo) return T2S_EINVAL;
+    if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
+    if (!al16(X_hi) || !al16(X_lo) || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
+                                   (hipStream_t)stream, 0, 0, nullptr, nullptr, lengths));
     return T2S_OK;
 }
 
@@ -301,8 +323,10 @@ int t2s_wg_in_melwin_gate_fold(const void* A_hi, const void* A_lo, const void* A
     return T2S_OK;
 }
 
-int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
-                    void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, void* stream) {
+// t2s_wg_res_only and, with `lengths`, t2s_wg_res_only_ragged
+static int res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                    void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, const int* lengths,
+                    void* stream) {
     if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !bias || !al16(bias)) return T2S_EINVAL;
     if (C <= 0 || C % 4 || (pair8 && C % 32) || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
     ConvGemm g(A_hi, A_lo, bias);
@@ -310,13 +334,27 @@ int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const
     g.k_side(acts_hi, acts_lo, cdiv(C, 32), 1, 1);
     g.output(X_hi, X_lo, cdiv(C, 32));
     g.a.C = 0; g.a.n_res = C; g.a.pair8 = pair8 ? 1 : 0;
+    g.a.lengths = lengths;
     T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, 128, stream));
     return T2S_OK;
 }
 
-int t2s_wg_res_only_start(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                    void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, void* stream) {
+    return res_only(A_hi, A_lo, bias, acts_hi, acts_lo, X_hi, X_lo, B, C, L, Lp, halo, Mpad, pair8, nullptr, stream);
+}
+
+int t2s_wg_res_only_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                           void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, const int* lengths,
+                           void* stream) {
+    if (!lengths) return T2S_EINVAL;
+    return res_only(A_hi, A_lo, bias, acts_hi, acts_lo, X_hi, X_lo, B, C, L, Lp, halo, Mpad, pair8, lengths, stream);
+}
+
+// t2s_wg_res_only_start and, with `lengths`, t2s_wg_res_only_start_ragged
+static int res_only_start(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                           const float* z, const float* w_start, const float* b_start, int n_group, int c_off, int n_half,
-                          void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, void* stream) {
+                          void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, const int* lengths, void* stream) {
     if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !bias || !al16(bias)) return T2S_EINVAL;
     if (!z || !w_start || !b_start || n_half <= 0 || n_half > 4 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
     if (C <= 0 || C % 32 || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
@@ -326,14 +364,32 @@ int t2s_wg_res_only_start(const void* A_hi, const void* A_lo, const float* bias,
     g.output(X_hi, X_lo, cdiv(C, 32));
     g.a.C = 0; g.a.n_res = C; g.a.pair8 = 1;
     g.a.x0_z = z; g.a.x0_w = w_start; g.a.x0_b = b_start; g.a.x0_G = n_group; g.a.x0_coff = c_off; g.a.x0_nh = n_half;
+    g.a.lengths = lengths;
     T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, 128, stream));
     return T2S_OK;
 }
 
-int t2s_wg_flow_boundary(const float* z_in, float* z_out, const float* fold_acc, int nslots, const float* bes, int n_layers,
+int t2s_wg_res_only_start(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                          const float* z, const float* w_start, const float* b_start, int n_group, int c_off, int n_half,
+                          void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, void* stream) {
+    return res_only_start(A_hi, A_lo, bias, acts_hi, acts_lo, z, w_start, b_start, n_group, c_off, n_half, X_hi, X_lo, B, C, L, Lp,
+                          halo, Mpad, nullptr, stream);
+}
+
+int t2s_wg_res_only_start_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                                 const float* z, const float* w_start, const float* b_start, int n_group, int c_off, int n_half,
+                                 void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, const int* lengths,
+                                 void* stream) {
+    if (!lengths) return T2S_EINVAL;
+    return res_only_start(A_hi, A_lo, bias, acts_hi, acts_lo, z, w_start, b_start, n_group, c_off, n_half, X_hi, X_lo, B, C, L, Lp,
+                          halo, Mpad, lengths, stream);
+}
+
+// t2s_wg_flow_boundary and, with `lengths`, t2s_wg_flow_boundary_ragged
+static int flow_boundary(const float* z_in, float* z_out, const float* fold_acc, int nslots, const float* bes, int n_layers,
                          const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off, int n_rem,
                          int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks, void* W_hi, void* W_lo,
-                         void* stream) {
+                         const int* lengths, void* stream) {
     if (!z_in || !planes_ok(W_hi, W_lo) || z_out == z_in || ((fold_acc || W) && !z_out)) return T2S_EINVAL;
     if (B <= 0 || L <= 0 || n_group <= 0 || n_group > 16 || halo < 0 || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
     // n_half <= 4 like its partner t2s_wg_res_only_start and the folded WN.end (8 rows = b ; log_s of 4 channels)
@@ -351,8 +407,26 @@ int t2s_wg_flow_boundary(const float* z_in, float* z_out, const float* fold_acc,
     a.nslots = nslots; a.n_layers = n_layers; a.c_off_prev = c_off_prev; a.nh_prev = n_half_prev;
     a.c_off = c_off; a.n_rem = n_rem; a.nh = n_half;
     a.G = n_group; a.L = L; a.Lp = Lp; a.halo = halo; a.taps = taps; a.nwc = win_chunks;
+    a.lengths = lengths;
     T2S_CHECK_HIP(t2s_launch_flow_boundary(a, B, (hipStream_t)stream));
     return T2S_OK;
+}
+
+int t2s_wg_flow_boundary(const float* z_in, float* z_out, const float* fold_acc, int nslots, const float* bes, int n_layers,
+                         const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off, int n_rem,
+                         int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks, void* W_hi, void* W_lo,
+                         void* stream) {
+    return flow_boundary(z_in, z_out, fold_acc, nslots, bes, n_layers, b_end, log_s, c_off_prev, n_half_prev, W, c_off, n_rem, n_half,
+                         B, n_group, L, Lp, halo, taps, win_chunks, W_hi, W_lo, nullptr, stream);
+}
+
+int t2s_wg_flow_boundary_ragged(const float* z_in, float* z_out, const float* fold_acc, int nslots, const float* bes, int n_layers,
+                                const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off,
+                                int n_rem, int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks,
+                                void* W_hi, void* W_lo, const int* lengths, void* stream) {
+    if (!lengths) return T2S_EINVAL;
+    return flow_boundary(z_in, z_out, fold_acc, nslots, bes, n_layers, b_end, log_s, c_off_prev, n_half_prev, W, c_off, n_rem, n_half,
+                         B, n_group, L, Lp, halo, taps, win_chunks, W_hi, W_lo, lengths, stream);
 }
 
 int t2s_wg_end_fold_affine(const float* fold_acc, int nslots, const float* bes, int n_layers, const float* b_end,

@@ -66,6 +66,9 @@ struct ConvGemmArgs {
     const float* x0_w;     // [C][x0_nh]
     const float* x0_b;     // [C]
     int x0_G, x0_coff, x0_nh;      // x0_nh <= 4
+    // RESSKIP, 128-row tiles, the ragged variants (t2s_wg_res_only_ragged / _start_ragged): columns lengths[b] <= t < L of batch entry b
+    // get zeros (hi and lo) in place of the residual update; null everywhere else.  Last, so that no other field moves.
+    const int* lengths;    // [B] int32, device
 };
 
 hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows = 256);
@@ -139,9 +142,10 @@ hipError_t t2s_launch_small_logdet_batch_host(const SmallMatJob* host_jobs, int 
 hipError_t t2s_launch_small_logdet_inv(const float* W, int n, float scale, float* logdet_out, float* inv_out,
                                        hipStream_t stream);
 // taps / W_hi / W_lo: optional window planes of the folded first gate GEMM (waveglow_ops.hip, startfold_weights_kernel)
+// lengths ([B] int32, device; optional): the ragged variant - batch entry b ends at column lengths[b] <= L
 hipError_t t2s_launch_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off,
                             int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream,
-                            int taps = 0, int nwc = 0, u16* W_hi = nullptr, u16* W_lo = nullptr);
+                            int taps = 0, int nwc = 0, u16* W_hi = nullptr, u16* W_lo = nullptr, const int* lengths = nullptr);
 hipError_t t2s_launch_startfold_weights(const float* v, const float* g, const float* w_start, const float* b_start, int C,
                                         int n_half, int taps, int Mpad, int nwc, u16* A_hi, u16* A_lo, hipStream_t stream);
 struct EndFoldJob {        // one WN layer: fold_w[c][j] = sum_o W_end[j][o] * scale[o] * v_skip[o][c]
@@ -172,6 +176,7 @@ struct FlowBoundaryArgs {
     int nslots, n_layers, c_off_prev, nh_prev;
     int c_off, n_rem, nh;
     int G, L, Lp, halo, taps, nwc;
+    const int* lengths;     // [B] int32 (device) or null: the ragged variant - the window of entry b reads zeros from column lengths[b] on
 };
 hipError_t t2s_launch_flow_boundary(const FlowBoundaryArgs& a, int B, hipStream_t stream);
 int t2s_flow_boundary_max_taps();

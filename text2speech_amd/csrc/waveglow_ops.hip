@@ -762,6 +762,9 @@ hipError_t t2s_launch_small_logdet_inv(const float* W, int n, float scale, float
 // With W_hi / W_lo the workgroups of the first nwc channel chunks also write the window planes [B][nwc][Lp][32] the folded first
 // gate GEMM reads in place of x (startfold_weights_kernel below has the four column sets): logical column tap * (nh + 1) + j of
 // row t is z[c_off + j][t + tap - taps / 2] for j < nh and 1 for j = nh, both 0 where t + tap - taps / 2 is outside [0, L).
+// RAG (a batch of entries of different lengths, lengths[b] <= L columns): the X rows lengths[b] <= t < L are stored as zeros - the
+// planes may hold a longer call's rows - and a window tap counts as outside from lengths[b] on, the ones-column included: entry b's
+// planes then hold at every row t < lengths[b], and show to every dilated tap from there, what they hold when it runs alone.
 #define START_TT 8
 // Column set s of the folded WN.start (startfold_weights_kernel): with x = h + l + r (h, l the split-bf16 pair, r what it leaves),
 //   set:            0        1          2          3
@@ -781,16 +784,19 @@ static __device__ __forceinline__ void start_fold_term(float x, int set, bool is
         lo = 0;
     }
 }
+template <bool RAG>
 __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                     const float* __restrict__ bias, int G, int c_off, int nh, int C,
                                                     int L, int Lp, int halo, u16* X_hi, u16* X_lo, int taps, int nwc,
-                                                    u16* W_hi, u16* W_lo) {
+                                                    u16* W_hi, u16* W_lo, const int* __restrict__ lengths) {
     const int tid = threadIdx.x;
     const int q = tid & 3;
     const int tbase = blockIdx.x * (64 * START_TT) + (tid >> 2);
     const int chunk = blockIdx.y;
     const int b = blockIdx.z;
     const int c8 = chunk * 32 + q * 8;
+    int lim = L;                // first column that counts as outside the entry
+    if constexpr (RAG) lim = min(max(lengths[b], 0), L);
     // static trip counts with guards (nh <= 8): weights stay in registers
     float wv[8][8], bv[8];
 #pragma unroll
@@ -806,6 +812,13 @@ __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z,
     for (int it = 0; it < START_TT; ++it) {
         const int t = tbase + it * 64;
         if (t >= L) break;
+        if constexpr (RAG) {
+            if (t >= lim) {
+                *(uint4*)(X_hi + (row0 + t) * 32 + q * 8) = make_uint4(0, 0, 0, 0);
+                *(uint4*)(X_lo + (row0 + t) * 32 + q * 8) = make_uint4(0, 0, 0, 0);
+                continue;
+            }
+        }
         float a0[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) a0[j] = j < nh ? z[((size_t)b * G + c_off + j) * L + t] : 0.f;
@@ -840,7 +853,7 @@ __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z,
             const int tap = c / nw, j = c - tap * nw;
             const int tt = t + tap - (taps >> 1);
             float v = 0.f;
-            if (sidx < spc && tt >= 0 && tt < L) v = j < nh ? z[((size_t)b * G + c_off + j) * L + tt] : 1.0f;
+            if (sidx < spc && tt >= 0 && tt < lim) v = j < nh ? z[((size_t)b * G + c_off + j) * L + tt] : 1.0f;
             start_fold_term(v, chunk * spc + sidx, false, hi[e], lo[e]);
         }
         uint4 ph, pl;
@@ -854,10 +867,14 @@ __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z,
 }
 hipError_t t2s_launch_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off,
                             int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream,
-                            int taps, int nwc, u16* W_hi, u16* W_lo) {
+                            int taps, int nwc, u16* W_hi, u16* W_lo, const int* lengths) {
     dim3 grid((L + 64 * START_TT - 1) / (64 * START_TT), (C + 31) / 32, B);
-    hipLaunchKernelGGL(start_kernel, grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L, Lp, halo,
-                       X_hi, X_lo, taps, nwc, W_hi, W_lo);
+    if (lengths)
+        hipLaunchKernelGGL(start_kernel<true>, grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L, Lp, halo,
+                           X_hi, X_lo, taps, nwc, W_hi, W_lo, lengths);
+    else
+        hipLaunchKernelGGL(start_kernel<false>, grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L, Lp, halo,
+                           X_hi, X_lo, taps, nwc, W_hi, W_lo, lengths);
     return hipGetLastError();
 }
 
@@ -1213,8 +1230,10 @@ hipError_t t2s_launch_end_fold_affine(const float* fold_acc, int nslots, const f
 // The taps - 1 edge columns are recomputed from the neighbours' ranges with the same arithmetic (so they carry the same bits) and the
 // 16-byte pieces of the window rows are spread over all 256 threads: the grid is over columns only.
 // fold_acc == NULL and W == NULL: window-only writer (z_out may be NULL then).
+// RAG (a.lengths): a window tap counts as outside from column lengths[b] on, as in start_kernel; (1) - (3) are per column and stay.
 #define FB_TC 64            // columns per workgroup: 8 x 2000 columns give 256 workgroups
 #define FB_EDGE 32          // most edge columns (taps - 1) a workgroup takes from its neighbours' ranges
+template <bool RAG>
 __global__ __launch_bounds__(256) void flow_boundary_kernel(const FlowBoundaryArgs a) {
     __shared__ float zs[16][FB_TC + FB_EDGE];       // the columns after (1)
     __shared__ float zo[16][FB_TC + FB_EDGE];       // rows [0, n_rem): channels [c_off, c_off + n_rem) after (2)
@@ -1266,6 +1285,8 @@ __global__ __launch_bounds__(256) void flow_boundary_kernel(const FlowBoundaryAr
         }
     }
     const int nh = a.nh, nw = nh + 1, ncol = a.taps * nw, nwc = a.nwc, spc = 4 / nwc;
+    int lim = L;                // first column that counts as outside the entry
+    if constexpr (RAG) lim = min(max(a.lengths[b], 0), L);
     for (int idx = tid; idx < FB_TC * nwc * 4; idx += 256) {
         const int q = idx & 3, rc = idx >> 2, chunk = rc % nwc, r = rc / nwc, t = t0 + r;
         if (t >= L) continue;
@@ -1277,7 +1298,7 @@ __global__ __launch_bounds__(256) void flow_boundary_kernel(const FlowBoundaryAr
             const int tap = c / nw, j = c - tap * nw;
             const int tt = t + tap - hw;
             float v = 0.f;
-            if (sidx < spc && tt >= 0 && tt < L) v = j < nh ? col(a.c_off + j, r + tap) : 1.0f;
+            if (sidx < spc && tt >= 0 && tt < lim) v = j < nh ? col(a.c_off + j, r + tap) : 1.0f;
             start_fold_term(v, chunk * spc + sidx, false, hi[e], lo[e]);
         }
         uint4 ph, pl;
@@ -1292,6 +1313,8 @@ __global__ __launch_bounds__(256) void flow_boundary_kernel(const FlowBoundaryAr
 }
 int t2s_flow_boundary_max_taps() { return FB_EDGE + 1; }
 hipError_t t2s_launch_flow_boundary(const FlowBoundaryArgs& a, int B, hipStream_t stream) {
-    hipLaunchKernelGGL(flow_boundary_kernel, dim3((a.L + FB_TC - 1) / FB_TC, B), dim3(256), 0, stream, a);
+    const dim3 grid((a.L + FB_TC - 1) / FB_TC, B);
+    if (a.lengths) hipLaunchKernelGGL(flow_boundary_kernel<true>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(flow_boundary_kernel<false>, grid, dim3(256), 0, stream, a);
     return hipGetLastError();
 }

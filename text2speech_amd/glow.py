@@ -219,9 +219,9 @@ class _Engine:
         g["nk2"] = g["Cpad"] // 32
         return g
 
-    def path(self):
+    def path(self, compose=True):
         """The kernel path of a no-grad call, decided here only: forward, infer and wn_forward take it once, keep it as last_path
-        and hand it down.
+        and hand it down.  compose = False (infer_batch): the path as if T2S_COND_COMPOSE were not set.
         start_fold: layer 0 of every flow goes through WN.start folded into its gate GEMM: the taps of the n_half audio channels
         and of the ones-channel must fit 32 columns, and C must have as many 32-channel chunks as the window has (geom()["nwc"]: 2
         or 4).  T2S_START_FOLD=0 selects the unfolded layer 0 (A/B runs, the comparison test), as composed conditioning does.
@@ -233,7 +233,7 @@ class _Engine:
         g = self.geom()
         if g["C"] % 16:         # every no-grad gate GEMM carries WN.end folded in, which the library has for such C only
             raise _lib.T2SError("WaveGlow's forward without gradients, infer and WN.forward need n_channels %% 16 == 0, not %d" % g["C"])
-        compose = self.compose_geom()
+        compose = self.compose_geom() if compose else None
         start_fold = (compose is None and os.environ.get("T2S_START_FOLD", "1") != "0" and g["ncol0"] <= 32
                       and g["Cpad"] // 32 >= g["nwc"])
         boundary = (start_fold and os.environ.get("T2S_FLOW_BOUNDARY", "1") != "0" and g["C"] % 32 == 0 and g["nl"] >= 2
@@ -495,9 +495,10 @@ class _Engine:
                   _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), _lib.current_stream())
         self._keep += [mel32, W, bias]
 
-    def _boundary(self, k, z_in, z_out, B, L, w, prev=None, W=None):
+    def _boundary(self, k, z_in, z_out, B, L, w, prev=None, W=None, lens=None):
         """t2s_wg_flow_boundary in front of flow k: prev = (flow index, log_s) applies that flow's coupling, W this flow's 1x1
-        convolution, both to z_in -> z_out; always writes flow k's window planes.  prev = W = None: the window planes only."""
+        convolution, both to z_in -> z_out; always writes flow k's window planes.  prev = W = None: the window planes only.
+        lens (int32 [B] on the device, columns; infer_batch only): the _ragged entry point."""
         m, g = self.m, self.geom()
         c_off, n_rem, n_half = self._flow_geom(k)
         fold_acc = bes = b_end = log_s = None
@@ -512,21 +513,33 @@ class _Engine:
         # Stream order makes the reuse of fold_acc and of the window planes safe: this launch reads the sums of the flow before
         # ahead of flow k's layer-0 gate GEMM, which re-initialises them, and writes the window planes behind the last launch (the
         # layer-0 gate GEMM of the flow before) that read them.
-        _lib.call("t2s_wg_flow_boundary", _lib.ptr(z_in), _lib.ptr(z_out), _lib.ptr(fold_acc), nslots, _lib.ptr(bes), g["nl"],
-                  _lib.ptr(b_end), _lib.ptr(log_s), c_off_p, nh_p, _lib.ptr(W), c_off, n_rem, n_half, B, m.n_group, L, w["Lp"],
-                  g["halo"], g["ks"], g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), _lib.current_stream())
+        args = (_lib.ptr(z_in), _lib.ptr(z_out), _lib.ptr(fold_acc), nslots, _lib.ptr(bes), g["nl"],
+                _lib.ptr(b_end), _lib.ptr(log_s), c_off_p, nh_p, _lib.ptr(W), c_off, n_rem, n_half, B, m.n_group, L, w["Lp"],
+                g["halo"], g["ks"], g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]))
+        if lens is None:
+            _lib.call("t2s_wg_flow_boundary", *args, _lib.current_stream())
+        else:
+            _lib.call("t2s_wg_flow_boundary_ragged", *args, _lib.ptr(lens), _lib.current_stream())
 
-    def _wn(self, k, z, B, L, w, c_off, n_half, path, ph=None):
+    def _wn(self, k, z, B, L, w, c_off, n_half, path, ph=None, lens=None):
         """start -> n_layers x (gate GEMM with WN.end folded in, residual GEMM) on the call's `path`; leaves WN.end's sums in
         w['fold_acc'].  With path.boundary the caller's _boundary() has written this flow's window planes from z, and x0 is rebuilt
-        by the layer-0 residual GEMM.  ph = (M_hi, M_lo, Fp, P, K2): composed conditioning from the mel-window planes (inverse flow)."""
+        by the layer-0 residual GEMM.  ph = (M_hi, M_lo, Fp, P, K2): composed conditioning from the mel-window planes (inverse flow).
+        lens (int32 [B] on the device, columns; infer_batch only): every writer of the X and window planes is the _ragged entry
+        point in place of its partner; the gate GEMMs are the same launches."""
         m, g = self.m, self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
         fl = self.packed["flows"][k]
         st = _lib.current_stream()
         b_start = _f32c(m.WN[k].start.bias)
         self._keep.append(b_start)
-        if not path.start_fold:
+        if lens is not None and not path.boundary:
+            win = (ks, g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"])) if path.start_fold else (0, 0, None, None)
+            _lib.call("t2s_wg_start_ragged", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
+                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), *win, _lib.ptr(lens), st)
+        elif lens is not None:
+            pass            # _boundary(lens=...) wrote the window planes
+        elif not path.start_fold:
             _lib.call("t2s_wg_start", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
                       C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), st)
         elif not path.boundary:
@@ -566,7 +579,17 @@ class _Engine:
                 self.gemm_events.append((e0, e1))
             if i == nl - 1:     # the last layer has no residual half, and its skip half lives in the fold
                 continue
-            if path.boundary and i == 0:
+            pair8 = 1 if self.packed["res_pair8"] else 0
+            if lens is not None and path.boundary and i == 0:
+                _lib.call("t2s_wg_res_only_start_ragged", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
+                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start),
+                          m.n_group, c_off, n_half, _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"],
+                          ly["Mpad2"], _lib.ptr(lens), st)
+            elif lens is not None:
+                _lib.call("t2s_wg_res_only_ragged", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
+                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
+                          g["halo"], ly["Mpad2"], pair8, _lib.ptr(lens), st)
+            elif path.boundary and i == 0:
                 _lib.call("t2s_wg_res_only_start", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
                           _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start),
                           m.n_group, c_off, n_half, _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"],
@@ -574,7 +597,7 @@ class _Engine:
             else:
                 _lib.call("t2s_wg_res_only", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
                           _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
-                          g["halo"], ly["Mpad2"], 1 if self.packed["res_pair8"] else 0, st)
+                          g["halo"], ly["Mpad2"], pair8, st)
 
     def wn_forward(self, k, audio, spect):
         """WN[k].forward((audio, spect)) (reference glow.py:154-175) on the no-grad kernels: start, n_layers x (gate GEMM with
@@ -706,6 +729,25 @@ class _Engine:
         return z, log_s_list, log_det_list
 
     def infer(self, mel, sigma, noise):
+        return self._infer(mel, sigma, noise, None)
+
+    def infer_batch(self, mel, lengths, sigma, noise):
+        """infer() on a padded batch whose entry b is lengths[b] frames long (host int64 [B], validated by the caller): the same
+        launches with every writer of the X and window planes replaced by its _ragged partner, which shows each entry zeros past
+        its own end as its solo run shows it past L, and one more that zeroes the audio tails.  Always the
+        plain conditioning path.  Returns (audio [B, stride * frames], audio lengths int64 [B] on the device)."""
+        m = self.m
+        self._check_inputs(mel)
+        stride = m.upsample.stride[0]
+        # columns per entry, once per call: the only host -> device copy, and the array every _ragged launch reads
+        lens = (lengths * (stride // m.n_group)).to(torch.int32).to(mel.device)
+        audio = self._infer(mel, sigma, noise, lens)
+        B, T = audio.shape
+        _lib.call("t2s_zero_rows_f32", _lib.ptr(audio), _lib.ptr(lens), B, T // m.n_group, m.n_group, _lib.current_stream())
+        self._keep.append(lens)
+        return audio, (lengths * stride).to(mel.device)
+
+    def _infer(self, mel, sigma, noise, lens):
         m = self.m
         self._check_inputs(mel)
         dev = mel.device
@@ -715,7 +757,7 @@ class _Engine:
         # reference glow.py:254-255: drop the last (kernel - stride) upsampled samples
         T = (frames - 1) * up.stride[0] + up.kernel_size[0] - (up.kernel_size[0] - up.stride[0])
         L = T // G
-        path = self.last_path = self.path()
+        path = self.last_path = self.path(compose=lens is None)      # infer_batch: never the composed conditioning
         self._keep = []
         self.pack_weights(dev, force=False, res_pair8=True, start_fold=path.start_fold)
         w = self.workspace(B, L, dev)
@@ -764,8 +806,8 @@ class _Engine:
                 _lib.call("t2s_small_logdet_inv", _lib.ptr(Wk), n_rem, 1.0, None, _lib.ptr(fl["w_inv"]), st)
                 fl["_Wk"] = Wk
             if path.boundary:
-                self._boundary(k, z, None, B, L, w)         # the window planes only
-            self._wn(k, z, B, L, w, c_off, n_half, path, ph=ph)
+                self._boundary(k, z, None, B, L, w, lens=lens)         # the window planes only
+            self._wn(k, z, B, L, w, c_off, n_half, path, ph=ph, lens=lens)
             self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True)
             _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(fl["w_inv"]), B, G, c_off, n_rem, L, st)
         audio = torch.empty(B, L * G, dtype=torch.float32, device=dev)
@@ -856,6 +898,48 @@ class WaveGlow(torch.nn.Module):
         if _lib.operand_format() == 1:
             self._refuse_overflow(out)
         return out.to(spect.dtype) if spect.dtype in (torch.float16, torch.bfloat16) else out
+
+    def infer_batch(self, spect, lengths, sigma=1.0, noise=None):
+        """Vocode a batch of mels of different lengths: ``spect`` [B, n_mel, F] padded, ``lengths`` [B] integers (host or device,
+        e.g. ``Tacotron.inference_batch``'s ``output_lengths`` as returned), 1 <= lengths[b] <= F.  ``noise`` = (final
+        [B, n_remaining, Lmax], [early draws]) padded to Lmax = F * stride / n_group columns, entry b using its first
+        lengths[b] * stride / n_group; None: drawn on the device at the padded shape.
+
+        Returns (audio [B, stride * F], audio_lengths int64 [B] on the device): ``audio[b, :stride * lengths[b]]`` is what
+        ``infer(spect[b:b+1, :, :lengths[b]], sigma, noise sliced to entry b's columns)`` returns, up to float rounding, and the
+        rest of the row is 0.  What the padding of ``spect`` and of ``noise`` holds does not reach a valid sample.  Always the plain
+        conditioning path (``T2S_COND_COMPOSE`` is not read)."""
+        T2SError = _lib.T2SError
+        if not spect.is_cuda:
+            raise T2SError("WaveGlow (MI355X build) needs CUDA/HIP tensors; got a %s tensor - there is no CPU fallback" % spect.device)
+        if spect.dim() != 3:
+            raise T2SError("infer_batch: spect must be [B, n_mel, F], got %s" % (tuple(spect.shape),))
+        B, _, F_ = spect.shape
+        lens = torch.as_tensor(lengths)
+        if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+            raise T2SError("infer_batch: lengths must be integers, got %s" % lens.dtype)
+        lens = lens.detach().to("cpu", torch.int64)           # (one read-back when they live on the device)
+        if lens.dim() != 1 or lens.numel() != B:
+            raise T2SError("infer_batch: lengths has shape %s, spect holds %d mels" % (tuple(lens.shape), B))
+        if B == 0 or int(lens.min()) < 1 or int(lens.max()) > F_:
+            raise T2SError("infer_batch: lengths must lie in [1, %d], got %s" % (F_, lens.tolist()))
+        stride, G = self.upsample.stride[0], self.n_group
+        if stride % G:
+            raise T2SError("infer_batch needs the upsampler's stride (%d) to be a multiple of n_group (%d)" % (stride, G))
+        if noise is not None:
+            Lmax = F_ * stride // G
+            early = [k for k in range(self.n_flows) if k % self.n_early_every == 0 and k > 0]
+            ok = isinstance(noise, (tuple, list)) and len(noise) == 2 and torch.is_tensor(noise[0]) \
+                and tuple(noise[0].shape) == (B, self.n_remaining_channels, Lmax) and len(noise[1]) == len(early) \
+                and all(torch.is_tensor(t) and tuple(t.shape) == (B, self.n_early_size, Lmax) for t in noise[1])
+            if not ok:
+                raise T2SError("infer_batch: noise must be (final [%d, %d, %d], %d early draws of [%d, %d, %d])"
+                               % (B, self.n_remaining_channels, Lmax, len(early), B, self.n_early_size, Lmax))
+        with torch.no_grad():
+            out, out_lens = self._eng().infer_batch(spect, lens, float(sigma), noise)
+        if _lib.operand_format() == 1:
+            self._refuse_overflow(out)         # (the tails are zeros by now: the valid samples decide)
+        return (out.to(spect.dtype) if spect.dtype in (torch.float16, torch.bfloat16) else out), out_lens
 
     @staticmethod
     def remove_weightnorm(model):
