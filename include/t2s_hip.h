@@ -457,6 +457,31 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, voi
 #define T2S_PLAN_UNITS_2 0x800u       /* the VALU cells take 2 hidden units per workgroup (att_gates_all given); without it: 4 */
 int t2s_taco_decode_plan(const t2s_taco_decoder* d, int step0, int n_steps, unsigned* bits);
 
+/* ABI v4, compatible addition.  attention_rnn.weight_ih / _hh and decoder_rnn.weight_ih / _hh as IEEE binary16 (what a .half() model
+ * holds): device pointers, 8-byte aligned, shapes and row-major layout those of the f32 members of t2s_taco_decoder with the same
+ * names (every row length a multiple of 4). */
+typedef struct t2s_taco_w16 {
+    const void *att_w_ih, *att_w_hh, *dec_w_ih, *dec_w_hh;
+} t2s_taco_w16;
+
+/* t2s_taco_decode_steps with the four LSTM matrices streamed from `w` - half the bytes per step - and widened to f32 in registers.
+ * Autoregressive decode of up to 8 items: the two VALU cells, the folded-prenet attention cell and the gate-stream role of the fused
+ * attention launch read `w`; everything else (biases, state, inputs, the other weights, `w_pre2T`) stays f32 and comes from `d`, whose
+ * four f32 matrix pointers are validated as by t2s_taco_decode_steps and not read.  The plan is chosen as for `d` alone, and a slot
+ * of 4 halves sits at the k of the f32 form's float4, so sums run in the same order: the outputs EQUAL those of
+ * t2s_taco_decode_steps on the widened matrices bit for bit (fp16 subnormals widen exactly).
+ * No fallback: T2S_EINVAL, with nothing enqueued, for what the fp16 kernels do not cover - teacher_forced, B > 8, any training save
+ * pointer (att_gates_all, att_c_all, dec_gates_all, dec_c_all, att_h_all, q_all, wcum_all) - and for `w` NULL, a NULL member, a
+ * member that is not 8-byte aligned, or a matrix row length that is not a multiple of 4. */
+int t2s_taco_decode_steps_w16(const t2s_taco_decoder* d, const t2s_taco_w16* w, int step0, int n_steps, void* stream);
+
+/* Host only, like t2s_taco_decode_plan: returns what t2s_taco_decode_steps_w16(d, w, step0, n_steps, .) returns from its validation;
+ * *bits (may be NULL) is exactly what t2s_taco_decode_plan gives for `d`; *lstm_weight_bytes (may be NULL) is the number of bytes of
+ * the four LSTM matrices that one decoder step reads (2 bytes per element).  With w == NULL (where the steps call refuses) it
+ * accepts every struct t2s_taco_decode_plan accepts and reports the f32 figure of t2s_taco_decode_steps, 4 bytes per element. */
+int t2s_taco_decode_plan_w16(const t2s_taco_decoder* d, const t2s_taco_w16* w, int step0, int n_steps, unsigned* bits,
+                             long long* lstm_weight_bytes);
+
 /* ABI v4.  One call of the location-sensitive attention alone (Attention.forward, tacotron.py:145-166, with the state update of
  * Decoder.decode around it, tacotron.py:371-379): query = w_query . h_att, energies from the location features of (w, w_cum) and
  * the processed memory, masked softmax over T, context.  IN PLACE: w [B][T] holds the previous weights on entry and the new ones on

@@ -86,6 +86,8 @@ SIGNATURES = {
     "t2s_bernoulli_mask": [c_vp, ctypes.c_size_t, ctypes.c_ulonglong, ctypes.c_ulonglong, c_float, c_vp],
     "t2s_taco_decode_steps": [c_vp, c_int, c_int, c_vp],
     "t2s_taco_decode_plan": [c_vp, c_int, c_int, c_vp],
+    "t2s_taco_decode_steps_w16": [c_vp, c_vp, c_int, c_int, c_vp],
+    "t2s_taco_decode_plan_w16": [c_vp, c_vp, c_int, c_int, c_vp, c_vp],
     "t2s_taco_stop_check": [c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp],
     "t2s_rows_to_tm": [c_vp, c_long, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp],
     "t2s_rows_to_tm_batched": [c_vp, c_long, c_long, c_int, c_int, c_int, c_int, c_vp, c_vp, c_long, c_int, c_int, c_int, c_vp],
@@ -138,6 +140,11 @@ _RESTYPE = {"t2s_error_string": ctypes.c_char_p, "t2s_last_hip_error": ctypes.c_
 
 class T2SError(RuntimeError):
     pass
+
+
+class TacoW16(ctypes.Structure):
+    """Mirror of ``t2s_taco_w16`` (include/t2s_hip.h): the decoder's four LSTM matrices as IEEE binary16."""
+    _fields_ = [(n, c_vp) for n in ("att_w_ih", "att_w_hh", "dec_w_ih", "dec_w_hh")]
 
 
 _lib = None

@@ -181,7 +181,12 @@ struct DecodePlan {
     bool use_ploc;       // with stream_gates: the location term comes out of the previous step's projection launch (ploc)
     bool proj_fused;     // projection and the next step's prenet layer 0 are one row block: one launch
     int units;           // hidden units per workgroup of lstm_cell_kernel: 2 with the training saves, else 4
+    // not a decision of decode_plan: set by t2s_taco_decode_steps_w16 after it.  The cells and the gate-stream role then read the four
+    // LSTM matrices from here as binary16 (the argument blocks carry them in their float pointers, tacotron_ops.h); NULL: f32 from `d`
+    const t2s_taco_w16* w16;
 };
+// element `off` of a binary16 matrix, as the cells' argument blocks carry it
+static const float* w16_at(const void* w, size_t off) { return (const float*)((const uint16_t*)w + off); }
 
 static float* att_h_in(const t2s_taco_decoder& d, int s) { return (s & 1) ? d.att_h1 : d.att_h0; }
 static float* att_h_out(const t2s_taco_decoder& d, int s) { return (s & 1) ? d.att_h0 : d.att_h1; }
@@ -215,6 +220,7 @@ static void fill_att_cell(const t2s_taco_decoder& d, const DecodePlan& p, int s,
         ca.x1 = nullptr; ca.w_p2 = d.w_pre2T; ca.p1 = d.pre1;
         ca.p2_mask = d.prenet_masks + (size_t)s * B * 2 * P + P; ca.s_p2_mask = 2 * P; ca.p2_scale = 2.0f;
     }
+    if (p.w16) { ca.W_ih = w16_at(p.w16->att_w_ih, 0); ca.W_hh = w16_at(p.w16->att_w_hh, 0); }
 }
 
 // 2.-4. attention: query, location-sensitive energies, softmax, context, cumulative weights
@@ -243,7 +249,7 @@ static void fill_att_args(const t2s_taco_decoder& d, const DecodePlan& p, int s,
 
 // the role beside the fused attention launch of step s: W_hh_dec . h_dec(s-1) and W_ih_dec[:, :A] . h_att(s) for this step's
 // decoder cell, W_hh_att . h_att(s) for the next step's attention cell
-static void fill_gate_stream(const t2s_taco_decoder& d, int s, GateStreamArgs& gs) {
+static void fill_gate_stream(const t2s_taco_decoder& d, const DecodePlan& p, int s, GateStreamArgs& gs) {
     const int A = d.att_rnn_dim, D = d.dec_rnn_dim;
     const size_t GP = gate_block(d);
     memset(&gs, 0, sizeof(gs));
@@ -251,6 +257,7 @@ static void fill_gate_stream(const t2s_taco_decoder& d, int s, GateStreamArgs& g
     gs.W1 = d.dec_w_ih; gs.ld1 = A + d.enc_dim; gs.out1 = d.gate_part + GP;
     gs.W2 = d.att_w_hh; gs.ld2 = A; gs.out2 = d.gate_part + 2 * GP; gs.x12 = att_h_out(d, s);
     gs.rows = 4 * A; gs.H = A; gs.B = d.B;
+    if (p.w16) { gs.W0 = w16_at(p.w16->dec_w_hh, 0); gs.W1 = w16_at(p.w16->dec_w_ih, 0); gs.W2 = w16_at(p.w16->att_w_hh, 0); }
 }
 
 // the query of the three-launch attention, W_query . h_att
@@ -326,7 +333,7 @@ static int decode_plan(const t2s_taco_decoder* d_, int step0, int n_steps, Decod
         p.stream_gates = true;
         for (int s = 0; s < 2 && p.stream_gates; ++s) {
             GateStreamArgs gs;
-            fill_gate_stream(d, s, gs);
+            fill_gate_stream(d, p, s, gs);
             p.stream_gates = t2s_att_fused_stream_ok(aa, gs);
         }
     }
@@ -349,7 +356,7 @@ static int run_att_cell(const t2s_taco_decoder& d, const DecodePlan& p, int s, h
     LstmCellArgs ca;
     fill_att_cell(d, p, s, ca);
     if (p.paced && !p.sig_by_kernel) T2S_CHECK_HIP(t2s_launch_pace_signal(ca.sig_ptr, ca.sig_val, stream));
-    T2S_CHECK_HIP(t2s_launch_lstm_cell(ca, stream));
+    T2S_CHECK_HIP(t2s_launch_lstm_cell(ca, stream, p.w16 != nullptr));
     return T2S_OK;
 }
 
@@ -359,8 +366,8 @@ static int run_attention(const t2s_taco_decoder& d, const DecodePlan& p, int s, 
     fill_att_args(d, p, s, aa);
     if (p.fused_att) {
         GateStreamArgs gs;
-        if (p.stream_gates) fill_gate_stream(d, s, gs);
-        T2S_CHECK_HIP(t2s_launch_att_fused(aa, stream, p.stream_gates ? &gs : nullptr));
+        if (p.stream_gates) fill_gate_stream(d, p, s, gs);
+        T2S_CHECK_HIP(t2s_launch_att_fused(aa, stream, p.stream_gates ? &gs : nullptr, p.stream_gates && p.w16));
         return T2S_OK;
     }
     if (!p.q_big) {
@@ -394,7 +401,8 @@ static int run_dec_cell(const t2s_taco_decoder& d, const DecodePlan& p, int s, h
     if (d.dec_drop) { cd.drop_mask = d.dec_drop + (size_t)s * B * D; cd.drop_scale = d.dec_drop_scale; }
     if (d.teacher_forced) { cd.h_copy = d.hc_all + (size_t)s * B * (D + E); cd.s_copy = D + E; }
     if (d.dec_gates_all) { cd.gates_out = d.dec_gates_all + (size_t)s * B * 4 * D; cd.c_out = d.dec_c_all + (size_t)s * B * D; }
-    T2S_CHECK_HIP(t2s_launch_lstm_cell(cd, stream));
+    if (p.w16) { cd.W_ih = w16_at(p.w16->dec_w_ih, p.stream_gates ? A : 0); cd.W_hh = w16_at(p.w16->dec_w_hh, 0); }
+    T2S_CHECK_HIP(t2s_launch_lstm_cell(cd, stream, p.w16 != nullptr));
     return T2S_OK;
 }
 
@@ -484,23 +492,55 @@ int t2s_taco_attention(const float* h_att, const float* memory, const float* pme
     return T2S_OK;
 }
 
+}  // extern "C"
+
+static unsigned plan_bits(const DecodePlan& p) {
+    return (p.split ? T2S_PLAN_SPLIT : 0) | (p.paced ? T2S_PLAN_PACED : 0) | (p.sig_by_kernel ? T2S_PLAN_SIG_BY_KERNEL : 0) |
+            (p.fused_att ? T2S_PLAN_FUSED_ATT : 0) | (p.q_parts ? T2S_PLAN_Q_PARTS : 0) | (p.q_big ? T2S_PLAN_Q_BIG : 0) |
+            (p.one ? T2S_PLAN_ONE : 0) | (p.stream_gates ? T2S_PLAN_STREAM_GATES : 0) | (p.fold_pre2 ? T2S_PLAN_FOLD_PRE2 : 0) |
+            (p.use_ploc ? T2S_PLAN_USE_PLOC : 0) | (p.proj_fused ? T2S_PLAN_PROJ_FUSED : 0) | (p.units == 2 ? T2S_PLAN_UNITS_2 : 0);
+}
+
+extern "C" {
+
 int t2s_taco_decode_plan(const t2s_taco_decoder* d, int step0, int n_steps, unsigned* bits) {
     DecodePlan p;
     const int rc = decode_plan(d, step0, n_steps, p);
     if (rc != T2S_OK || !bits) return rc;
-    *bits = (p.split ? T2S_PLAN_SPLIT : 0) | (p.paced ? T2S_PLAN_PACED : 0) | (p.sig_by_kernel ? T2S_PLAN_SIG_BY_KERNEL : 0) |
-            (p.fused_att ? T2S_PLAN_FUSED_ATT : 0) | (p.q_parts ? T2S_PLAN_Q_PARTS : 0) | (p.q_big ? T2S_PLAN_Q_BIG : 0) |
-            (p.one ? T2S_PLAN_ONE : 0) | (p.stream_gates ? T2S_PLAN_STREAM_GATES : 0) | (p.fold_pre2 ? T2S_PLAN_FOLD_PRE2 : 0) |
-            (p.use_ploc ? T2S_PLAN_USE_PLOC : 0) | (p.proj_fused ? T2S_PLAN_PROJ_FUSED : 0) | (p.units == 2 ? T2S_PLAN_UNITS_2 : 0);
+    *bits = plan_bits(p);
+    return T2S_OK;
+}
+
+}  // extern "C"
+
+// elements of attention_rnn.weight_ih / _hh and decoder_rnn.weight_ih / _hh: what the cells (and the gate-stream role) of one step read
+static long long lstm_weight_elems(const t2s_taco_decoder& d) {
+    const long long P = d.prenet_dim, E = d.enc_dim, A = d.att_rnn_dim, D = d.dec_rnn_dim;
+    return 4 * A * (P + E + A) + 4 * D * (A + E + D);
+}
+
+// The plan of `d` (the same decisions as for the f32 matrices: only the weight reads differ) with the four LSTM matrices taken from
+// `w`.  Refused, never run on the f32 matrices instead: what the fp16 kernels do not cover - teacher forcing, the matrix-core cells of
+// 9+ items, the training saves - and matrices whose 4-element slots are not 8-byte loads.
+static int decode_plan_w16(const t2s_taco_decoder* d_, const t2s_taco_w16* w, int step0, int n_steps, DecodePlan& p) {
+    T2S_TRY(decode_plan(d_, step0, n_steps, p));
+    const t2s_taco_decoder& d = *d_;
+    if (!w || d.teacher_forced || d.B > 8) return T2S_EINVAL;
+    if (d.att_gates_all || d.att_c_all || d.dec_gates_all || d.dec_c_all || d.att_h_all || d.q_all || d.wcum_all) return T2S_EINVAL;
+    const void* m[] = {w->att_w_ih, w->att_w_hh, w->dec_w_ih, w->dec_w_hh};
+    for (const void* q : m)
+        if (!q || ((uintptr_t)q & 7)) return T2S_EINVAL;
+    if (((d.prenet_dim + d.enc_dim) | d.att_rnn_dim | (d.att_rnn_dim + d.enc_dim) | d.dec_rnn_dim) & 3) return T2S_EINVAL;
+    p.w16 = w;
     return T2S_OK;
 }
 
 // Enqueues steps [step0, step0 + n_steps) in one of three schedules: serial (every launch of a step on `stream`); split (teacher
 // forced with the saves: the attention chain of 16 steps on `stream`, one event, their decoder cells on the helper stream); paced
 // (split at 9+ items with pace_flag: the helper's cell of step s - 1 waits for the word the attention cell of step s stores).
-int t2s_taco_decode_steps(const t2s_taco_decoder* d_, int step0, int n_steps, void* stream_) {
+static int decode_steps(const t2s_taco_decoder* d_, const t2s_taco_w16* w16, int step0, int n_steps, void* stream_) {
     DecodePlan p;
-    const int rc = decode_plan(d_, step0, n_steps, p);
+    const int rc = w16 ? decode_plan_w16(d_, w16, step0, n_steps, p) : decode_plan(d_, step0, n_steps, p);
     if (rc != T2S_OK) return rc;
     const t2s_taco_decoder& d = *d_;
     hipStream_t stream = (hipStream_t)stream_;
@@ -550,6 +590,27 @@ int t2s_taco_decode_steps(const t2s_taco_decoder* d_, int step0, int n_steps, vo
             if (!d.teacher_forced) T2S_TRY(run_projection(d, p, s, stream));
         }
     }
+    return T2S_OK;
+}
+
+extern "C" {
+
+int t2s_taco_decode_steps(const t2s_taco_decoder* d, int step0, int n_steps, void* stream) {
+    return decode_steps(d, nullptr, step0, n_steps, stream);
+}
+
+int t2s_taco_decode_steps_w16(const t2s_taco_decoder* d, const t2s_taco_w16* w, int step0, int n_steps, void* stream) {
+    if (!w) return T2S_EINVAL;          // (no fallback to the f32 matrices of `d`: that is t2s_taco_decode_steps)
+    return decode_steps(d, w, step0, n_steps, stream);
+}
+
+int t2s_taco_decode_plan_w16(const t2s_taco_decoder* d, const t2s_taco_w16* w, int step0, int n_steps, unsigned* bits,
+                             long long* lstm_weight_bytes) {
+    DecodePlan p;
+    const int rc = w ? decode_plan_w16(d, w, step0, n_steps, p) : decode_plan(d, step0, n_steps, p);
+    if (rc != T2S_OK) return rc;
+    if (bits) *bits = plan_bits(p);
+    if (lstm_weight_bytes) *lstm_weight_bytes = lstm_weight_elems(*d) * (w ? 2 : 4);
     return T2S_OK;
 }
 

@@ -138,11 +138,13 @@ bool t2s_sbgemm_plain_ok(const GemvArgs& a);
 hipError_t t2s_launch_sbgemm_plain(const GemvArgs& a, hipStream_t stream);
 bool t2s_sbgemm_lstm_ok(const LstmCellArgs& a);
 hipError_t t2s_launch_sbgemm_lstm(const LstmCellArgs& a, hipStream_t stream);
-hipError_t t2s_launch_lstm_cell(const LstmCellArgs& a, hipStream_t stream);
+// w16: W_ih / W_hh hold IEEE binary16 data of the same shape (8-byte aligned, ld_ih counted in elements); up to 8 items, no saves
+hipError_t t2s_launch_lstm_cell(const LstmCellArgs& a, hipStream_t stream, bool w16 = false);
 hipError_t t2s_launch_att_energy(const AttArgs& a, hipStream_t stream);
 hipError_t t2s_launch_att_softmax_ctx(const AttArgs& a, hipStream_t stream);
-hipError_t t2s_launch_att_fused(const AttArgs& a, hipStream_t stream, const GateStreamArgs* gs = nullptr);
-bool t2s_att_fused_stream_ok(const AttArgs& a, const GateStreamArgs& g);
+// w16: gs->W0 / W1 / W2 hold IEEE binary16 data of the same shape (8-byte aligned)
+hipError_t t2s_launch_att_fused(const AttArgs& a, hipStream_t stream, const GateStreamArgs* gs = nullptr, bool w16 = false);
+bool t2s_att_fused_stream_ok(const AttArgs& a, const GateStreamArgs& g, bool w16 = false);
 hipError_t t2s_launch_lstm_seq_split(const float* gx, const float* whhT_f, const float* whhT_r, const int* lengths, float* out,
                                      int B, int T, int T_out, float* gates_save, float* c_save, unsigned long long* xbuf,
                                      unsigned epoch, hipStream_t stream);

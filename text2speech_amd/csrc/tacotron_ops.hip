@@ -312,9 +312,22 @@ hipError_t t2s_launch_gemv_with_loc(const GemvArgs& a, const LocPreArgs& lp_in, 
 // (profiles/r04_cache_policy_ab.txt; all-plain: 31.4 / 31.3; the unstreamed chain prefers nt in the cells: 37.5-37.7 vs 38.3-38.7).
 #define T2S_CLOAD(p) (*(p))
 
-template <int NVW, int UNITS, bool SAVE, bool STREAMED = false>
+// fp16 weight form (W16; t2s_taco_decode_steps_w16): the pointers named W_* in the argument block then hold IEEE binary16 data of the
+// same shape.  A 4-element slot is ONE 8-byte load at the same k as the float4 of the f32 form and is widened in registers
+// (v_cvt_f32_f16: exact, fp16 subnormals included) before the first product, so lane-to-k mapping, FMA order, wave_sum and the
+// epilogues are those of the f32 form and the result equals the f32 form's on the widened copy of the weights bit for bit.
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+template <bool W16> struct WSlot { typedef float elem; typedef f32x4 vec; };
+template <> struct WSlot<true> { typedef _Float16 elem; typedef h16x4 vec; };
+static __device__ __forceinline__ f32x4 widen(const f32x4 v) { return v; }
+static __device__ __forceinline__ f32x4 widen(const h16x4 v) { return (f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
+
+template <int NVW, int UNITS, bool SAVE, bool STREAMED = false, bool W16 = false>
 __global__ __launch_bounds__(UNITS * 256) void lstm_cell_kernel(const LstmCellArgs a) {
     PROBE_BEGIN(200 + NVW)
+    typedef typename WSlot<W16>::elem WT;
+    typedef typename WSlot<W16>::vec WV;
+    const WT* const W_ih = (const WT*)a.W_ih, *const W_hh = (const WT*)a.W_hh;
     __shared__ float s_part[UNITS][4][4][64];        // [unit][kq][gate][item]
     __shared__ float s_h[UNITS][64];                 // new h of this workgroup's units (for the partial attention query)
     const int lane = threadIdx.x & 63;
@@ -346,7 +359,7 @@ __global__ __launch_bounds__(UNITS * 256) void lstm_cell_kernel(const LstmCellAr
             g_pb[g] = pb[i];
         }
     }
-    f32x4 w[4][NVW];
+    WV wr[4][NVW];
     const float* xp[NVW];
     long xs[NVW];
     bool valid[NVW];
@@ -360,12 +373,12 @@ __global__ __launch_bounds__(UNITS * 256) void lstm_cell_kernel(const LstmCellAr
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const size_t row = (size_t)g * a.H + u;
-            const float* wp = kc < K1 ? a.W_ih + row * ldi + kc : a.W_hh + row * a.H + (kc - K1);
-            w[g][j] = STREAMED ? T2S_CLOAD((const f32x4*)wp) : T2S_WLOAD((const f32x4*)wp);
+            const WT* wp = kc < K1 ? W_ih + row * ldi + kc : W_hh + row * a.H + (kc - K1);
+            wr[g][j] = STREAMED ? T2S_CLOAD((const WV*)wp) : T2S_WLOAD((const WV*)wp);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-            if (!valid[j]) w[g][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (!valid[j]) wr[g][j] = (WV){0, 0, 0, 0};
         if (!valid[j]) { xp[j] = a.c; xs[j] = 0; }          // (a readable dummy: x1 is NULL in the folded-prenet form)
         else if (k < a.n1) { xp[j] = a.x1 + k; xs[j] = a.sx1; }
         else if (k < K1) { xp[j] = a.x2 + (k - a.n1); xs[j] = a.sx2; }
@@ -385,12 +398,24 @@ __global__ __launch_bounds__(UNITS * 256) void lstm_cell_kernel(const LstmCellAr
             f32x4 xv[NVW];
 #pragma unroll
             for (int j = 0; j < NVW; ++j) xv[j] = *(const f32x4*)(xp[j] + (size_t)it * xs[j]);
+            if constexpr (W16) {
+                // The slots stay packed (2 registers each) across items and are widened where they are used.  The empty statement
+                // makes them a value of this iteration: hoisted out of the item loop, the conversions bring the f32 form's register
+                // count back, and with it the full-row cell's spill (NVW = 3 at the 128-register cap of a 1024-thread workgroup).
+#pragma unroll
+                for (int j = 0; j < NVW; ++j) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(wr[g][j]));
+                }
+            }
 #pragma unroll
             for (int j = 0; j < NVW; ++j) {
                 const f32x4 x = valid[j] ? xv[j] : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    acc[g] += w[g][j][0] * x[0] + w[g][j][1] * x[1] + w[g][j][2] * x[2] + w[g][j][3] * x[3];
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 w = widen(wr[g][j]);
+                    acc[g] += w[0] * x[0] + w[1] * x[1] + w[2] * x[2] + w[3] * x[3];
+                }
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -453,8 +478,11 @@ __global__ __launch_bounds__(UNITS * 256) void lstm_cell_kernel(const LstmCellAr
 // (lane l accumulates outputs 4l .. 4l+3); a wave ballots its 64-entry segment of pre1 and walks the set bits with scalar
 // code.  ~64 KB per workgroup out of L2 instead of the dense 256 KB (a CU draws 64 B/clk: 1.9 us for the dense form, measured
 // 10.0 us per launch against 6.4 for the plain cell).  Exact: skipped terms are products with 0.0f.
+template <bool W16 = false>
 __global__ __launch_bounds__(768) void lstm_cell_p2_kernel(const LstmCellArgs a) {
     PROBE_BEGIN(210)
+    typedef typename WSlot<W16>::elem WT;
+    typedef typename WSlot<W16>::vec WV;
     __shared__ float s_part[4][3][4][8];             // [unit][kq][gate][item]
     __shared__ float s_h[4][8];
     __shared__ float s_bsum[4][4];
@@ -466,9 +494,9 @@ __global__ __launch_bounds__(768) void lstm_cell_p2_kernel(const LstmCellArgs a)
     const int u = blockIdx.x * 4 + ul;
     const int ldi = a.ld_ih > 0 ? a.ld_ih : 768;
     // LSTM rows (HBM, non-temporal: read once per step by this wave)
-    f32x4 w[4];
+    WV wr[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) w[g] = T2S_CLOAD((const f32x4*)(a.W_ih + ((size_t)g * a.H + u) * ldi + kq * 256 + 4 * lane));
+    for (int g = 0; g < 4; ++g) wr[g] = T2S_CLOAD((const WV*)((const WT*)a.W_ih + ((size_t)g * a.H + u) * ldi + kq * 256 + 4 * lane));
     // prenet: this wave's 64-entry segment of pre1 (three waves share a segment and take its entries k = sub, sub + 3, ...)
     const int seg = wave & 3, sub = wave >> 2;
     float p1 = a.p1[seg * 64 + lane];
@@ -531,6 +559,9 @@ __global__ __launch_bounds__(768) void lstm_cell_p2_kernel(const LstmCellArgs a)
         for (int i = 0; i < 4; ++i) s_wq[i][tid] = wq[i];
     }
     // ---- gate pre-activations: slot 0 = pre2 (LDS), slots 1, 2 = the context ----
+    f32x4 w[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) w[g] = widen(wr[g]);
     for (int b = 0; b < a.B; ++b) {
         const f32x4 x = kq == 0 ? *(const f32x4*)(s_p2 + b * 256 + 4 * lane)
                                 : *(const f32x4*)(a.x2 + (size_t)b * a.sx2 + (kq - 1) * 256 + 4 * lane);
@@ -568,8 +599,12 @@ __global__ __launch_bounds__(768) void lstm_cell_p2_kernel(const LstmCellArgs a)
     PROBE_END()
 }
 
-hipError_t t2s_launch_lstm_cell(const LstmCellArgs& a, hipStream_t stream) {
-    if (t2s_sbgemm_lstm_ok(a)) return t2s_launch_sbgemm_lstm(a, stream);        // 9+ items: f32 matrix cores
+hipError_t t2s_launch_lstm_cell(const LstmCellArgs& a, hipStream_t stream, bool w16) {
+    // fp16 weights: the VALU inference forms only (up to 8 items, no training saves), 8-byte slots
+    if (w16 && (a.B > 8 || a.gates_out || a.c_out || (((uintptr_t)a.W_ih | (uintptr_t)a.W_hh) & 7) || (a.ld_ih & 3) ||
+                ((a.n1 + a.n2) & 3)))
+        return hipErrorInvalidValue;
+    if (!w16 && t2s_sbgemm_lstm_ok(a)) return t2s_launch_sbgemm_lstm(a, stream);        // 9+ items: f32 matrix cores
     const int K = a.n1 + a.n2 + (a.h_in ? a.H : 0);
     const int nv4 = (K + 255) / 256;
     const int nvw = (nv4 + 3) / 4;
@@ -582,18 +617,29 @@ hipError_t t2s_launch_lstm_cell(const LstmCellArgs& a, hipStream_t stream) {
         else if (a.pre_a) hipLaunchKernelGGL((lstm_cell_kernel<N, 4, false, true>), dim3(a.H / 4), dim3(1024), 0, stream, a); \
         else hipLaunchKernelGGL((lstm_cell_kernel<N, 4, false>), dim3(a.H / 4), dim3(1024), 0, stream, a);          \
     } while (0)
+#define LL16(N)                                                                                                   \
+    do {                                                                                                          \
+        if (a.pre_a) hipLaunchKernelGGL((lstm_cell_kernel<N, 4, false, true, true>), dim3(a.H / 4), dim3(1024), 0, stream, a); \
+        else hipLaunchKernelGGL((lstm_cell_kernel<N, 4, false, false, true>), dim3(a.H / 4), dim3(1024), 0, stream, a); \
+    } while (0)
     if (a.w_p2) {           // folded prenet layer 1 (lstm_cell_p2_kernel): K = 256 (pre2) + 512 (context), W_hh . h streamed earlier
         if (a.gates_out || a.c_out || a.n1 != 256 || a.n2 != 512 || a.h_in || !a.pre_a || a.pre_b || a.B > 8 || !a.p1 ||
             !a.p2_mask || !a.x2 || (a.sx2 & 3))
             return hipErrorInvalidValue;
-        hipLaunchKernelGGL(lstm_cell_p2_kernel, dim3(a.H / 4), dim3(768), 0, stream, a);
+        if (w16) hipLaunchKernelGGL(lstm_cell_p2_kernel<true>, dim3(a.H / 4), dim3(768), 0, stream, a);
+        else hipLaunchKernelGGL(lstm_cell_p2_kernel<false>, dim3(a.H / 4), dim3(768), 0, stream, a);
         return hipGetLastError();
     }
-    if (nvw <= 1) LL(1);
+    if (nvw > 3) return hipErrorInvalidValue;
+    if (w16) {
+        if (nvw <= 1) LL16(1);
+        else if (nvw <= 2) LL16(2);
+        else LL16(3);
+    } else if (nvw <= 1) LL(1);
     else if (nvw <= 2) LL(2);
-    else if (nvw <= 3) LL(3);
-    else return hipErrorInvalidValue;
+    else LL(3);
 #undef LL
+#undef LL16
     return hipGetLastError();
 }
 
@@ -1363,12 +1409,15 @@ static __device__ __forceinline__ float row16_ror(float v, int n) {
 // workgroups and 12288 units a strided loop left 48 waves a second pass: 15.6 us per launch instead of ~11).  Non-temporal
 // weight loads: each row is read once per step by one wave.  The two input vectors (h_dec(t-1), h_att(t)) are staged in LDS
 // once per workgroup.  Requires 3 NW <= n_units <= 4 NW (checked on the host).
+template <bool W16>
 static __device__ __forceinline__ void gate_stream_role(const GateStreamArgs& g, int role_block, int role_blocks, float* s_x) {
+    typedef typename WSlot<W16>::elem WT;
+    typedef typename WSlot<W16>::vec WV;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int NW = role_blocks * 16, gw = role_block * 16 + wave;
     const int n_units = 3 * g.rows;
     const bool four = gw + 3 * NW < n_units;                    // wave-uniform
-    f32x4 w[4][4];
+    WV wr[4][4];
     float* ob[4];
     int rr[4];
     bool first[4];
@@ -1376,15 +1425,15 @@ static __device__ __forceinline__ void gate_stream_role(const GateStreamArgs& g,
     for (int j = 0; j < 4; ++j) {
         const int un = (j < 3 || four) ? gw + j * NW : gw;      // (j = 3 without a fourth unit: a row this wave reads anyway)
         const int blk = un / g.rows, r = un - blk * g.rows;
-        const float* W = blk == 0 ? g.W0 : (blk == 1 ? g.W1 : g.W2);
+        const WT* W = (const WT*)(blk == 0 ? g.W0 : (blk == 1 ? g.W1 : g.W2));
         const int ld = blk == 0 ? g.ld0 : (blk == 1 ? g.ld1 : g.ld2);
         first[j] = blk == 0;
         ob[j] = blk == 0 ? g.out0 : (blk == 1 ? g.out1 : g.out2);
         rr[j] = r;
-        const float* wp = W + (size_t)r * ld + 4 * lane;
+        const WT* wp = W + (size_t)r * ld + 4 * lane;
         if (j < 3 || four) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) w[j][v] = T2S_WLOAD((const f32x4*)(wp + 256 * v));
+            for (int v = 0; v < 4; ++v) wr[j][v] = T2S_WLOAD((const WV*)(wp + 256 * v));
         }
     }
     // input vectors -> LDS: [b][2][H] (h_dec, h_att), 2 * B * H floats <= 64 KB
@@ -1402,8 +1451,8 @@ static __device__ __forceinline__ void gate_stream_role(const GateStreamArgs& g,
             float acc = 0.f;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                const f32x4 x = *(const f32x4*)(xs + 4 * lane + 256 * v);
-                acc += w[j][v][0] * x[0] + w[j][v][1] * x[1] + w[j][v][2] * x[2] + w[j][v][3] * x[3];
+                const f32x4 x = *(const f32x4*)(xs + 4 * lane + 256 * v), w = widen(wr[j][v]);
+                acc += w[0] * x[0] + w[1] * x[1] + w[2] * x[2] + w[3] * x[3];
             }
             acc = wave_sum(acc);
             if (lane == 0) ob[j][(size_t)b * g.rows + rr[j]] = acc;
@@ -1412,12 +1461,12 @@ static __device__ __forceinline__ void gate_stream_role(const GateStreamArgs& g,
 }
 
 // PLOC: the location term of this step was computed one launch earlier (AttArgs::ploc): no matrix-core stage here.
-template <bool STREAM, bool PLOC = false>
+template <bool STREAM, bool PLOC = false, bool W16 = false>
 __global__ __launch_bounds__(1024) void att_fused_mfma_kernel(const AttArgs a, const GateStreamArgs gs) {
     if constexpr (STREAM) {
         if ((int)blockIdx.x >= a.B) {           // whole workgroups take this branch: no barrier of the attention role is skipped
             extern __shared__ __attribute__((aligned(16))) float s_role[];
-            gate_stream_role(gs, (int)blockIdx.x - a.B, (int)gridDim.x - a.B, s_role);
+            gate_stream_role<W16>(gs, (int)blockIdx.x - a.B, (int)gridDim.x - a.B, s_role);
             return;
         }
     }
@@ -1781,21 +1830,25 @@ static int gate_stream_blocks(int B, int n_units) {
 }
 
 // the gate-stream role rides on the matrix-core form of the fused attention launch only; three [4H][H] blocks, H = 1024
-bool t2s_att_fused_stream_ok(const AttArgs& a, const GateStreamArgs& g) {
+// (w16: W0 / W1 / W2 hold binary16 data, read in 8-byte slots)
+bool t2s_att_fused_stream_ok(const AttArgs& a, const GateStreamArgs& g, bool w16) {
     if (!att_fused_mfma_form(a) || a.B > 8 || a.T > ATT_FUSED_MAXT) return false;
     if (gate_stream_blocks(a.B, 3 * g.rows) == 0) return false;
     if (g.H != 1024 || g.rows != 4 * g.H || g.B != a.B) return false;
-    const void* ptrs[] = {g.W0, g.W1, g.W2, g.x0, g.x12, g.out0, g.out1, g.out2};
+    const void* wptrs[] = {g.W0, g.W1, g.W2};
+    for (const void* p : wptrs)
+        if (!p || ((uintptr_t)p & (w16 ? 7 : 15))) return false;
+    const void* ptrs[] = {g.x0, g.x12, g.out0, g.out1, g.out2};
     for (const void* p : ptrs)
         if (!p || ((uintptr_t)p & 15)) return false;
     if (g.ld0 < g.H || g.ld1 < g.H || g.ld2 < g.H || ((g.ld0 | g.ld1 | g.ld2) & 3)) return false;
     return true;
 }
 
-hipError_t t2s_launch_att_fused(const AttArgs& a, hipStream_t stream, const GateStreamArgs* gs) {
+hipError_t t2s_launch_att_fused(const AttArgs& a, hipStream_t stream, const GateStreamArgs* gs, bool w16) {
     if (a.T > ATT_FUSED_MAXT || a.enc_dim > 512 || a.att_dim > 128 || a.loc_f > 32 || a.loc_ks > 63 || a.att_rnn > 1024)
         return hipErrorInvalidValue;
-    if (gs && !t2s_att_fused_stream_ok(a, *gs)) return hipErrorInvalidValue;
+    if (gs && !t2s_att_fused_stream_ok(a, *gs, w16)) return hipErrorInvalidValue;
     if (att_fused_mfma_form(a)) {
         const int Tp = (a.T + 15) & ~15, KP = (2 * a.loc_ks + 3) & ~3;
         const size_t nF = (size_t)Tp * 36 > 4096 ? (size_t)Tp * 36 : 4096;      // (FS = 36 floats per feature row in the kernel)
@@ -1810,6 +1863,16 @@ hipError_t t2s_launch_att_fused(const AttArgs& a, hipStream_t stream, const Gate
             if (blocks == 0) return hipErrorInvalidValue;
             const size_t lds1 = lds > 84 * 1024 ? lds : 84 * 1024;      // more than half a CU's LDS: never two workgroups on one CU
             const GateStreamArgs& g2 = *gs;
+            if (w16) {      // the same launch with the role's weight rows in fp16; the attention workgroups read no LSTM weights
+                if (a.ploc && (!a.q_part || (a.n_part & 31) || a.n_part > 256)) return hipErrorInvalidValue;
+                static std::atomic<unsigned long long> attr_mask5{0}, attr_mask6{0};
+                const hipError_t e5 = a.ploc ? t2s_raise_lds_limit((const void*)att_fused_mfma_kernel<true, true, true>, 120 * 1024, attr_mask6)
+                                             : t2s_raise_lds_limit((const void*)att_fused_mfma_kernel<true, false, true>, 120 * 1024, attr_mask5);
+                if (e5 != hipSuccess) return e5;
+                if (a.ploc) hipLaunchKernelGGL((att_fused_mfma_kernel<true, true, true>), dim3(a.B + blocks), dim3(1024), lds1, stream, a, g2);
+                else hipLaunchKernelGGL((att_fused_mfma_kernel<true, false, true>), dim3(a.B + blocks), dim3(1024), lds1, stream, a, g2);
+                return hipGetLastError();
+            }
             if (a.ploc) {
                 if (!a.q_part || (a.n_part & 31) || a.n_part > 256) return hipErrorInvalidValue;
                 static std::atomic<unsigned long long> attr_mask4{0};

@@ -389,6 +389,12 @@ class _TacoEngine:
         self.decode_stream = True       # offer the streamed-gate buffers (gate_part, ploc, w_pre2T); False: the plain chain (A/B tests)
         self.last_decode_plan = None    # DecodePlan of the last decoder struct handed to the library ...
         self.last_decode_offer = ()     # ... and the optional pointers (PLAN_USES) that were set in it
+        # a .half() model's autoregressive decode at up to 8 items streams the four LSTM matrices as the fp16 the parameters hold
+        # (t2s_taco_decode_steps_w16: bit-identical to the widened f32 copies, half the bytes).  None: automatic; False: the f32 copies
+        # (A/B tests); True: required - an error where the library or the model cannot
+        self.decode_w16 = None
+        self.last_decode_w16 = False    # whether the last decode_free went through t2s_taco_decode_steps_w16 ...
+        self.last_decode_lstm_bytes = None      # ... and the bytes of LSTM weights one of its steps read (t2s_taco_decode_plan_w16)
 
     # ------------------------------------------------------------------ weight preparation
     def _pack_conv_bn(self, seq, dev, halo):
@@ -414,6 +420,9 @@ class _TacoEngine:
     def prepare(self, dev):
         m = self.m
         key = tuple(p._version for p in m.parameters()) + (str(dev), m.training)
+        lstm_w = [m.decoder.attention_rnn.weight_ih, m.decoder.attention_rnn.weight_hh, m.decoder.decoder_rnn.weight_ih,
+                  m.decoder.decoder_rnn.weight_hh]
+        key += tuple(t.dtype for t in lstm_w)
         if not m.training:       # BatchNorm running statistics are folded into the eval-mode weights
             key += tuple(b._version for b in m.buffers())
         if self.prep is not None and self.prep_key == key:
@@ -463,6 +472,11 @@ class _TacoEngine:
                         ("w_pre1", dec.prenet.layers[0].linear_layer.weight),
                         ("w_pre2", dec.prenet.layers[1].linear_layer.weight)]:
             P[name] = _f32(t)
+        # a .half() model: references to the four LSTM parameters themselves (no copy) for the fp16-weight decode; the f32 copies above
+        # stay, every other path reads them
+        P["w16"] = None
+        if all(t.dtype == torch.float16 and t.is_contiguous() and t.device == P["att_w_ih"].device for t in lstm_w):
+            P["w16"] = tuple(t.detach() for t in lstm_w)
         n_mel = dec.n_mel_channels * dec.n_frames_per_step
         Pd = dec.prenet_dim
         DE = dec.linear_projection.linear_layer.in_features
@@ -697,13 +711,41 @@ class _TacoEngine:
             S[name] = t
         return d, S
 
-    def _query_plan(self, d, step0, n_steps):
+    def _query_plan(self, d, step0, n_steps, w16=None):
         """The library's plan for the finished struct ``d`` -> last_decode_plan / last_decode_offer; raises what the decode call
-        would raise from its validation."""
+        would raise from its validation.  ``w16`` (a ``_lib.TacoW16``): the plan of ``t2s_taco_decode_steps_w16`` - the same bits -
+        and its LSTM bytes per step -> last_decode_lstm_bytes."""
         bits = ctypes.c_uint(0)
-        _lib.call("t2s_taco_decode_plan", ctypes.byref(d), step0, n_steps, ctypes.byref(bits))
+        if w16 is None:
+            _lib.call("t2s_taco_decode_plan", ctypes.byref(d), step0, n_steps, ctypes.byref(bits))
+        else:
+            nbytes = ctypes.c_longlong(0)
+            _lib.call("t2s_taco_decode_plan_w16", ctypes.byref(d), ctypes.byref(w16), step0, n_steps, ctypes.byref(bits),
+                      ctypes.byref(nbytes))
+            self.last_decode_lstm_bytes = int(nbytes.value)
         self.last_decode_offer = tuple(k for k in PLAN_USES if getattr(d, k))
         self.last_decode_plan = DecodePlan.from_bits(bits.value)
+
+    def _decode_w16(self, d, step0, n_steps):
+        """The ``_lib.TacoW16`` of a .half() model where decode_free streams fp16 LSTM weights (see ``decode_w16``), else None; also
+        fills last_decode_lstm_bytes with the f32 figure in that case."""
+        refs = self.prep["w16"]
+        lib = _lib.load()
+        have = hasattr(lib, "t2s_taco_decode_plan_w16") and hasattr(lib, "t2s_taco_decode_steps_w16")     # (an older diagnostic build)
+        want = self.decode_w16 is not False and refs is not None and d.B <= 8 and have
+        if self.decode_w16 is True and not want:
+            raise _lib.T2SError("decode_w16 = True needs a .half() model, at most 8 items and a library with t2s_taco_decode_steps_w16")
+        self.last_decode_lstm_bytes = None
+        if not want:
+            if have:
+                nbytes = ctypes.c_longlong(0)
+                _lib.call("t2s_taco_decode_plan_w16", ctypes.byref(d), None, step0, n_steps, None, ctypes.byref(nbytes))
+                self.last_decode_lstm_bytes = int(nbytes.value)
+            return None
+        w16 = _lib.TacoW16()
+        for name, t in zip(("att_w_ih", "att_w_hh", "dec_w_ih", "dec_w_hh"), refs):
+            setattr(w16, name, t.data_ptr())
+        return w16
 
     def postnet(self, mel, train_masks=None, seed=0, save=None, lengths=None):
         """Postnet.forward (reference modules.py:131-137): 5 x conv+BN, tanh on the first four; in training mode
@@ -877,14 +919,19 @@ class _TacoEngine:
             d.att_drop_scale = 1.0 / (1.0 - dec.p_attention_dropout)
             d.dec_drop_scale = 1.0 / (1.0 - dec.p_decoder_dropout)
         d.mask_steps = mk.numel() // (B * 2 * dec.prenet_dim)
-        self._query_plan(d, 0, min(chunk, T_cap))
+        w16 = self._decode_w16(d, 0, min(chunk, T_cap))
+        self._query_plan(d, 0, min(chunk, T_cap), w16)
+        self.last_decode_w16 = w16 is not None
         stop = torch.full((B,), -1, dtype=torch.int32, device=dev)
         st = _lib.current_stream()
         s0 = 0
         n_done = T_cap
         while s0 < T_cap:
             n = min(chunk, T_cap - s0)
-            _lib.call("t2s_taco_decode_steps", ctypes.byref(d), s0, n, st)
+            if w16 is None:
+                _lib.call("t2s_taco_decode_steps", ctypes.byref(d), s0, n, st)
+            else:
+                _lib.call("t2s_taco_decode_steps_w16", ctypes.byref(d), ctypes.byref(w16), s0, n, st)
             _lib.call("t2s_taco_stop_check", _lib.ptr(mel_gate), B, n_mel, T_cap, s0, n, float(dec.gate_threshold),
                       _lib.ptr(stop), st)
             s0 += n
