@@ -217,6 +217,34 @@ int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const
 int t2s_wg_res_only_start(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                           const float* z, const float* w_start, const float* b_start, int n_group, int c_off, int n_half,
                           void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, void* stream);
+/* ---- ABI v4, fp16 vocoder planes: WaveGlow.infer for a model whose WN parameters are fp16 (.half()) ----
+ * The effective weight of an in / cond / res_skip convolution of such a model, rounded to fp16, IS the GEMM's A operand: one plane,
+ * no lo.  Activation planes (X, acts, conditioning) are split-fp16 hi + lo, and each MAC is A.B_hi + A.B_lo accumulated in f32 -
+ * two v_mfma_f32_16x16x32_f16 where the split-bf16 entry points spend three.  Biases, the fold sums, WN.start / WN.end, the 1x1
+ * convolutions and the coupling stay f32.  Every entry point takes its partner's argument list and checks; the A-operand lo
+ * pointer is never read and may be NULL.  An fp16 plane overflows at |x| > 65504 (the caller checks its result for non-finite
+ * values).  The plain chain only: no window planes (folded WN.start), no flow-boundary launch, no composed conditioning, no ragged
+ * batch - their composed weights are not exact in fp16 and have no one-plane form.
+ *  t2s_pack_conv_weight_table_h16: the same job table; A_hi receives fp16 (round to nearest even) of the f32 effective weight in the
+ *    same permuted layout, A_lo is not touched, bias_out / scale_out as before.
+ *  t2s_wg_endfold_weights_h16: fold_A as fp16 hi / lo fragments (a composed matrix: it keeps both planes and three products); bes f32.
+ *  t2s_wg_upsample_squeeze_h16, t2s_wg_start_h16: fp16 hi / lo conditioning and X planes; halo and channel-padding rules unchanged.
+ *  t2s_wg_in_cond_gate_fold_h16: both tile heights; t2s_wg_gate_tile_rows / t2s_wg_gate_fold_slots decide as for the partner.
+ *  t2s_wg_res_only_h16: both pair8 row orders.
+ * t2s_wg_end_fold_affine, t2s_wg_convinv, t2s_wg_audio_squeeze and t2s_weightnorm_small are f32 and serve both formats. */
+int t2s_pack_conv_weight_table_h16(const t2s_pack_job* jobs, int n_jobs, long total_groups, void* stream);
+int t2s_wg_endfold_weights_h16(const t2s_endfold_job* jobs, int n_jobs, int C, void* stream);
+int t2s_wg_upsample_squeeze_h16(const float* mel, const float* W, const float* bias, int B, int n_mel, int frames,
+                                int ksize, int stride, int n_group, int L, int Lp, int halo, void* S_hi, void* S_lo,
+                                void* stream);
+int t2s_wg_start_h16(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                     int L, int Lp, int halo, void* X_hi, void* X_lo, void* stream);
+int t2s_wg_in_cond_gate_fold_h16(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
+                                 const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
+                                 float* fold_acc, int fold_init, int B, int C, int n_cond, int taps, int dilation, int L,
+                                 int Lp, int halo, int Mpad, void* stream);
+int t2s_wg_res_only_h16(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                        void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, void* stream);
 /* One flow boundary of the no-grad forward in one launch, column by column of z_in [B][n_group][L]:
  *  - fold_acc != NULL: the forward coupling of the flow before, t2s_wg_end_fold_affine(reverse = 0) with (c_off_prev, n_half_prev
  *    <= 4); log_s (may be NULL) is that flow's;

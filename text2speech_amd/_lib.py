@@ -134,6 +134,11 @@ SIGNATURES = {
                               c_vp],
     "t2s_adam_table": [c_vp, c_int, c_long, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_vp],
 }
+# fp16 vocoder planes (WaveGlow.infer for .half() models): every _h16 entry point takes its partner's argument list
+for _n in ("t2s_pack_conv_weight_table", "t2s_wg_endfold_weights", "t2s_wg_upsample_squeeze", "t2s_wg_start",
+           "t2s_wg_in_cond_gate_fold", "t2s_wg_res_only"):
+    SIGNATURES[_n + "_h16"] = list(SIGNATURES[_n])
+del _n
 _RESTYPE = {"t2s_error_string": ctypes.c_char_p, "t2s_last_hip_error": ctypes.c_char_p,
             "t2s_small_wgrad_scratch": ctypes.c_long, "t2s_taco_lstm_xbuf_bytes": ctypes.c_long}
 

@@ -56,8 +56,12 @@ static __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 // residual rows are stored as zeros, hi and lo - stored, not skipped: the planes may hold an earlier, longer call's rows - so that
 // the dilated taps of the next gate GEMM read past an entry's end what they read past L when it runs alone.  Columns t < lengths[b]
 // take the arithmetic of the RAG = false kernel in its order.
-template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false, bool RAG = false>
+// FMT = the operand format of the planes (t2s_common.h), A1 = the A operand is ONE plane (weights exact in the format; a.A_lo is never
+// read): two products per MAC, A.B_hi + A.B_lo, and half the A-side DMA instructions per stage, which DMA_PER_ISSUE counts.  The
+// LDS layout stays as it is (the A_lo part of a stage is not filled).
+template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false, bool RAG = false, class FMT = T2sFmt, bool A1 = false>
 __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
+    typedef typename FMT::frag8 fragT;
     constexpr int WN = 4;                            // waves along N (time): 8 waves of 128 x 64, two per SIMD
     constexpr int NTH = 128 * WN;                    // threads per workgroup
     constexpr int NWT = 16 / WN;                     // 16-column MFMA tiles per wave
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
 #pragma unroll
         for (int j = 0; j < A_PLANE / CALL_BYTES; ++j) {
             glds16(ah + j * CALL_BYTES, dst + j * CALL_BYTES);
-            glds16(al + j * CALL_BYTES, dst + A_PLANE + j * CALL_BYTES);
+            if constexpr (!A1) glds16(al + j * CALL_BYTES, dst + A_PLANE + j * CALL_BYTES);
         }
 #pragma unroll
         for (int j = 0; j < B_PLANE_BYTES / CALL_BYTES; ++j) {
@@ -275,10 +279,10 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     }
 
   if constexpr (!SH) {
-    constexpr int DMA_PER_ISSUE = 2 * (A_PLANE / CALL_BYTES) + 2 * (B_PLANE_BYTES / CALL_BYTES);
+    constexpr int DMA_PER_ISSUE = (A1 ? 1 : 2) * (A_PLANE / CALL_BYTES) + 2 * (B_PLANE_BYTES / CALL_BYTES);
     const int nk = nk_split;
     const char *nbh = nullptr, *nbl = nullptr;       // B sources of the next stage to issue, computed one step ahead
-    bf16x8 bh[NWT], bl[NWT];
+    fragT bh[NWT], bl[NWT];
     if (nk > 0) {
         b_source(0, nbh, nbl);
         issue(0, 0, nbh, nbl);
@@ -303,27 +307,29 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
         // fragments of m-tile m+1 are fetched while m's 12 MFMAs issue.
         const bool issued = ks + NS - 1 < nk;
         if (issued) issue(ks + NS - 1, nxt, nbh, nbl);
-        bf16x8 ah = *(const bf16x8*)(sb + a_frag);
-        bf16x8 al = *(const bf16x8*)(sb + a_frag + A_PLANE);
+        fragT ah = *(const fragT*)(sb + a_frag);
+        fragT al = {};
+        if constexpr (!A1) al = *(const fragT*)(sb + a_frag + A_PLANE);
 #pragma unroll
         for (int n = 0; n < NWT; ++n) {
-            bh[n] = *(const bf16x8*)(sb + b_frag + n * 1024);
-            bl[n] = *(const bf16x8*)(sb + b_frag + B_PLANE_BYTES + n * 1024);
+            bh[n] = *(const fragT*)(sb + b_frag + n * 1024);
+            bl[n] = *(const fragT*)(sb + b_frag + B_PLANE_BYTES + n * 1024);
         }
         if (ks + NS < nk) b_source(ks + NS, nbh, nbl);
 #pragma unroll
         for (int m = 0; m < MW; ++m) {
-            bf16x8 ah_n = ah, al_n = al;
+            fragT ah_n = ah, al_n = al;
             if (m + 1 < MW) {
-                ah_n = *(const bf16x8*)(sb + a_frag + (m + 1) * 1024);
-                al_n = *(const bf16x8*)(sb + a_frag + A_PLANE + (m + 1) * 1024);
+                ah_n = *(const fragT*)(sb + a_frag + (m + 1) * 1024);
+                if constexpr (!A1) al_n = *(const fragT*)(sb + a_frag + A_PLANE + (m + 1) * 1024);
             }
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(al, bh[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n)
+                if constexpr (!A1) acc[m][n] = FMT::mfma(al, bh[n], acc[m][n]);
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bl[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n) acc[m][n] = FMT::mfma(ah, bl[n], acc[m][n]);
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bh[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n) acc[m][n] = FMT::mfma(ah, bh[n], acc[m][n]);
             ah = ah_n;
             al = al_n;
         }
@@ -352,7 +358,7 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
 #pragma unroll
         for (int j = 0; j < A_PLANE / CALL_BYTES; ++j) {
             glds16(ah + j * CALL_BYTES, dst + j * CALL_BYTES);
-            glds16(al + j * CALL_BYTES, dst + A_PLANE + j * CALL_BYTES);
+            if constexpr (!A1) glds16(al + j * CALL_BYTES, dst + A_PLANE + j * CALL_BYTES);
         }
     };
     auto issue_bunit = [&](int c, int u, int buf) {       // one 16-row unit of block c's extended tile (both planes)
@@ -373,27 +379,29 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
         }
     };
     auto compute = [&](const char* sa, const char* sbx, int boff) {
-        bf16x8 bh[NWT], bl[NWT];
-        bf16x8 ah = *(const bf16x8*)(sa + a_frag);
-        bf16x8 al = *(const bf16x8*)(sa + a_frag + A_PLANE);
+        fragT bh[NWT], bl[NWT];
+        fragT ah = *(const fragT*)(sa + a_frag);
+        fragT al = {};
+        if constexpr (!A1) al = *(const fragT*)(sa + a_frag + A_PLANE);
 #pragma unroll
         for (int n = 0; n < NWT; ++n) {
-            bh[n] = *(const bf16x8*)(sbx + boff + n * 1024);
-            bl[n] = *(const bf16x8*)(sbx + BX_PLANE + boff + n * 1024);
+            bh[n] = *(const fragT*)(sbx + boff + n * 1024);
+            bl[n] = *(const fragT*)(sbx + BX_PLANE + boff + n * 1024);
         }
 #pragma unroll
         for (int m = 0; m < MW; ++m) {
-            bf16x8 ah_n = ah, al_n = al;
+            fragT ah_n = ah, al_n = al;
             if (m + 1 < MW) {
-                ah_n = *(const bf16x8*)(sa + a_frag + (m + 1) * 1024);
-                al_n = *(const bf16x8*)(sa + a_frag + A_PLANE + (m + 1) * 1024);
+                ah_n = *(const fragT*)(sa + a_frag + (m + 1) * 1024);
+                if constexpr (!A1) al_n = *(const fragT*)(sa + a_frag + A_PLANE + (m + 1) * 1024);
             }
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(al, bh[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n)
+                if constexpr (!A1) acc[m][n] = FMT::mfma(al, bh[n], acc[m][n]);
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bl[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n) acc[m][n] = FMT::mfma(ah, bl[n], acc[m][n]);
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) acc[m][n] = T2S_MFMA32(ah, bh[n], acc[m][n], 0, 0, 0);
+            for (int n = 0; n < NWT; ++n) acc[m][n] = FMT::mfma(ah, bh[n], acc[m][n]);
             ah = ah_n;
             al = al_n;
         }
@@ -474,13 +482,13 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                             const float tv = fast_tanh(acc[2 * mp][n][e] + bt[e]);
                             const float gv = fast_sigmoid(acc[2 * mp + 1][n][e] + bs[e]);
                             u16 h, l;
-                            split_bf16(tv * gv, h, l);
+                            split_fmt<FMT>(tv * gv, h, l);
                             hi[e] = h;
                             lo[e] = l;
-                            split_bf16(tv, h, l);
+                            split_fmt<FMT>(tv, h, l);
                             thi[e] = h;
                             tlo[e] = l;
-                            split_bf16(gv, h, l);
+                            split_fmt<FMT>(gv, h, l);
                             ghi[e] = h;
                             glo[e] = l;
                         }
@@ -502,8 +510,8 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
             }
             if (a.fold_A) {
                 const u16* fa = a.fold_A + ((size_t)(mt * (MT / 64) + wr * (MT / 128) + pair) * 2 * 64 + lane) * 8;
-                const bf16x8 wh = *(const bf16x8*)fa;
-                const bf16x8 wl = *(const bf16x8*)(fa + 64 * 8);
+                const fragT wh = *(const fragT*)fa;
+                const fragT wl = *(const fragT*)(fa + 64 * 8);
 #pragma unroll
                 for (int n = 0; n < NWT; ++n) {
                     typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
@@ -511,11 +519,11 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                                        hv[1][n][0], hv[1][n][1], hv[1][n][2], hv[1][n][3]};
                     const u16x8 bl8 = {lv[0][n][0], lv[0][n][1], lv[0][n][2], lv[0][n][3],
                                        lv[1][n][0], lv[1][n][1], lv[1][n][2], lv[1][n][3]};
-                    const bf16x8 bh = __builtin_bit_cast(bf16x8, bh8);
-                    const bf16x8 bl = __builtin_bit_cast(bf16x8, bl8);
-                    facc[n] = T2S_MFMA32(wl, bh, facc[n], 0, 0, 0);
-                    facc[n] = T2S_MFMA32(wh, bl, facc[n], 0, 0, 0);
-                    facc[n] = T2S_MFMA32(wh, bh, facc[n], 0, 0, 0);
+                    const fragT bh = __builtin_bit_cast(fragT, bh8);
+                    const fragT bl = __builtin_bit_cast(fragT, bl8);
+                    facc[n] = FMT::mfma(wl, bh, facc[n]);         // fold_A is a composed matrix: hi + lo, three products
+                    facc[n] = FMT::mfma(wh, bl, facc[n]);
+                    facc[n] = FMT::mfma(wh, bh, facc[n]);
                 }
             }
         }
@@ -566,23 +574,23 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                         for (int j = 0; j < 4; ++j)
                             if (j < a.x0_nh) v += x0w[m / 2][e][j] * x0a[n][j];
                         u16 h, l;
-                        split_bf16(v, h, l);
-                        r[e] = join_bf16(h, l);
+                        split_fmt<FMT>(v, h, l);
+                        r[e] = join_fmt<FMT>(h, l);
                     }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        r[e] = join_bf16(pre_h[m][n][e], pre_l[m][n][e]);
-                        r[4 + e] = join_bf16(pre_h[m + 1][n][e], pre_l[m + 1][n][e]);
+                        r[e] = join_fmt<FMT>(pre_h[m][n][e], pre_l[m][n][e]);
+                        r[4 + e] = join_fmt<FMT>(pre_h[m + 1][n][e], pre_l[m + 1][n][e]);
                     }
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     u16 h, l;
-                    split_bf16(r[e] + (acc[m][n][e] + b0[e]), h, l);
+                    split_fmt<FMT>(r[e] + (acc[m][n][e] + b0[e]), h, l);
                     hi[e] = h;
                     lo[e] = l;
-                    split_bf16(r[4 + e] + (acc[m + 1][n][e] + b1[e]), h, l);
+                    split_fmt<FMT>(r[4 + e] + (acc[m + 1][n][e] + b1[e]), h, l);
                     hi[4 + e] = h;
                     lo[4 + e] = l;
                 }
@@ -651,9 +659,9 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                         }
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float v = join_bf16(oh[mi][n][e], ol[mi][n][e]) + (acc[m][n][e] + bv[mi][e]);
+                            const float v = join_fmt<FMT>(oh[mi][n][e], ol[mi][n][e]) + (acc[m][n][e] + bv[mi][e]);
                             u16 h, l;
-                            split_bf16(v, h, l);
+                            split_fmt<FMT>(v, h, l);
                             hi[e] = h;
                             lo[e] = l;
                         }
@@ -703,14 +711,14 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                 u16x4 h1, l1, h2, l2;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float av = join_bf16(th[e], tl[e]), gv = join_bf16(gh[e], gl[e]);
+                    const float av = join_fmt<FMT>(th[e], tl[e]), gv = join_fmt<FMT>(gh[e], gl[e]);
                     const float tv = gv != 0.0f ? av / gv : 0.0f;
                     const float da = acc[m][n][e];
                     u16 h, l;
-                    split_bf16(da * gv * (1.0f - tv * tv), h, l);
+                    split_fmt<FMT>(da * gv * (1.0f - tv * tv), h, l);
                     h1[e] = h;
                     l1[e] = l;
-                    split_bf16(da * av * (1.0f - gv), h, l);
+                    split_fmt<FMT>(da * av * (1.0f - gv), h, l);
                     h2[e] = h;
                     l2[e] = l;
                 }
@@ -743,7 +751,7 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
                         else a.out_f32[((size_t)bs * a.C + ch + e) * a.L + t] = v;
                     }
                     u16 h, l;
-                    split_bf16(v, h, l);
+                    split_fmt<FMT>(v, h, l);
                     hi[e] = h;
                     lo[e] = l;
                 }
@@ -756,19 +764,29 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     }
 }
 
-template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false, bool RAG = false>
+template <int EPI, int MT, bool SH = false, int NS = 2, bool X0 = false, bool RAG = false, class FMT = T2sFmt, bool A1 = false>
 static hipError_t launch_one(const ConvGemmArgs& a, hipStream_t stream) {
     const int nwg = a.n_mtiles * a.n_ttiles * a.B;
     constexpr size_t lds = SH ? 2 * (2 * MT * 64) + 4 * 320 * 64 : NS * (2 * MT * 64 + 2 * B_PLANE_BYTES);
     static std::atomic<unsigned long long> attr_mask{0};        // per instantiation; bit d = raised on device d
-    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, SH, NS, X0, RAG>, (int)lds, attr_mask);
+    const hipError_t e = t2s_raise_lds_limit((const void*)conv_gemm_kernel<EPI, MT, SH, NS, X0, RAG, FMT, A1>, (int)lds, attr_mask);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, SH, NS, X0, RAG>), dim3(nwg), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((conv_gemm_kernel<EPI, MT, SH, NS, X0, RAG, FMT, A1>), dim3(nwg), dim3(512), lds, stream, a);
     return hipGetLastError();
 }
 
 // a.n_mtiles must have been computed for the same tile height `mt_rows` (256 or 128)
-hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows) {
+hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows, bool h16) {
+    if (h16) {
+        // fp16 planes with a one-plane A operand (the _h16 entry points): the folded gate GEMM at either tile height and the
+        // residual-only GEMM, plain forms only
+        if (a.lengths || a.x0_z || a.ph_P > 0 || a.ksplit > 1 || a.k0 != 0 || a.kflat != 0 || a.a_bstride != 0) return hipErrorInvalidValue;
+        if (mt_rows == 128 && epi == EPI_RESSKIP) return launch_one<EPI_RESSKIP, 128, false, 2, false, false, T2sFmtF16, true>(a, stream);
+        if (mt_rows == 128 && epi == EPI_GATE) return launch_one<EPI_GATE, 128, false, 2, false, false, T2sFmtF16, true>(a, stream);
+        if (mt_rows == 256 && epi == EPI_GATE && a.nk == a.nk_x + a.sc && a.nk_x == a.taps * a.xc && (a.taps >> 1) * a.dil <= a.halo)
+            return t2s_launch_gate_gemm_pp(a, stream, true);
+        return hipErrorInvalidValue;
+    }
     if (a.lengths && (mt_rows != 128 || epi != EPI_RESSKIP)) return hipErrorInvalidValue;     // the ragged form exists for these only
     if (mt_rows == 128) {
         if (epi == EPI_RESSKIP && a.lengths && a.x0_z) return launch_one<EPI_RESSKIP, 128, false, 2, true, true>(a, stream);

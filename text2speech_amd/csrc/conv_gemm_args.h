@@ -75,8 +75,10 @@ struct ConvGemm {
     }
     // `rows` packed output rows (a gate GEMM has 2 C) on tiles mt_rows high: n_mtiles follows from the two, here and nowhere else.
     // Phase mode exists only on the ping-pong gate schedule; bwd_pp: the caller found bwd_pp256 true (mt_rows = 256).
-    hipError_t launch(int epi, int rows, int mt_rows, void* stream, bool bwd_pp = false) {
+    // h16: fp16 planes, one-plane A operand (the _h16 entry points; the folded gate and the residual-only GEMM have that form).
+    hipError_t launch(int epi, int rows, int mt_rows, void* stream, bool bwd_pp = false, bool h16 = false) {
         a.n_mtiles = cdiv(rows, mt_rows);
+        if (h16) return t2s_launch_conv_gemm(a, epi, (hipStream_t)stream, mt_rows, true);
         if (a.ph_P > 0) return t2s_launch_gate_gemm_pp(a, (hipStream_t)stream);
         if (bwd_pp) return t2s_launch_bwd_gemm_pp(a, epi, (hipStream_t)stream);
         return t2s_launch_conv_gemm(a, epi, (hipStream_t)stream, mt_rows);

@@ -86,8 +86,24 @@ __device__ unsigned long long t2s_pp_stamps[1024 * 8];
 // (t2s_wg_bwd_gate_dgrad).  Those GEMMs have M = C = 512, two 256-row tiles: alone they fill half the chip, but the backward
 // runs them next to the weight-gradient stream, and what counts there is the time a CU spends per unit of work - 2.1 us per
 // 256 x 256 x 32 step on this schedule against 2 x 1.33 us on the lockstep 128-row tiles.
-template <bool PH, int EPI = EPI_GATE>
+// FMT = the operand format of the planes (t2s_common.h), A1 = the A operand is ONE plane (weights that are exact in the format: no lo
+// plane, a.A_lo is never read): two products per MAC, A.B_hi + A.B_lo, and one DMA instruction per A stage.  The LDS layout stays
+// as above - the A_lo 16 KB of each buffer is simply not filled - so every address and the occupancy (one workgroup per CU either
+// way) are those of the two-plane kernel.  What changes is the wait counts.  "Three stages left in flight" after the stage issued
+// in phase p means waiting for everything but the loads of the stages issued in phases p, p - 1 and p - 2; the stage order around
+// the K loop is B, A, A, B (table above, column "stages"), a B stage is 2 loads and an A stage 2 loads (two planes) or 1 (A1):
+//      phase p   stages p-2, p-1, p     loads left in flight (two planes)    (A1)
+//         0         A    B    B              2 + 2 + 2 = 6                 1 + 2 + 2 = 5
+//         1         B    B    A              2 + 2 + 2 = 6                 2 + 2 + 1 = 5
+//         2         B    A    A              2 + 2 + 2 = 6                 2 + 1 + 1 = 4
+//         3         A    A    B              2 + 2 + 2 = 6                 1 + 1 + 2 = 4
+// The prologue issues K-step 0 whole and then A half 0, B half 0 of K-step 1 (the order of phases 2 and 3) and leaves those two
+// stages in flight: 2 + 2 = 4 loads, or 1 + 2 = 3 with A1.  The last two K-steps have stages missing and drain with vmcnt(0) in
+// either form.  A count that is too high would let a phase read a half-tile before it has landed.
+template <bool PH, int EPI = EPI_GATE, class FMT = T2sFmt, bool A1 = false>
 __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a) {
+    typedef typename FMT::frag8 fragT;
+    constexpr int VM_P0 = A1 ? 5 : 6, VM_P1 = A1 ? 5 : 6, VM_P2 = A1 ? 4 : 6, VM_P3 = A1 ? 4 : 6, VM_PRO = A1 ? 3 : 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -205,7 +221,7 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         char* dst = lds_wave + (ks & 1) * PP_BUF + half * PP_HALF;
         const long off = c.aoff + (long)half * PP_HALF;
         pp_glds16(A_hi + off + ((PH && c.in_s) ? a2d_hi : 0), dst);
-        pp_glds16(A_lo + off + ((PH && c.in_s) ? a2d_lo : 0), dst + PP_PLANE);
+        if constexpr (!A1) pp_glds16(A_lo + off + ((PH && c.in_s) ? a2d_lo : 0), dst + PP_PLANE);
     };
     auto stage_b = [&](int ks, const BCursor& c, int half) {
         char* dst = lds_wave + (ks & 1) * PP_BUF + 2 * PP_PLANE + half * PP_HALF;
@@ -224,7 +240,7 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
     for (int m = 0; m < 8; ++m)
 #pragma unroll
         for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    bf16x8 afh[4], afl[4], b0h[2], b0l[2], b1h[2], b1l[2];
+    fragT afh[4], afl[4], b0h[2], b0l[2], b1h[2], b1l[2];
 
     // ---- prologue: K-step 0 whole, A half 0 / B half 0 of K-step 1 (the steady-state lead) ----
     BCursor c1 = cursor_at(0);          // becomes the cursor of K-step ks + 1
@@ -238,36 +254,36 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         stage_a(1, c1, 0);
         stage_b(1, c1, 0);
         advance(c2);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM_PRO) : "memory");
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();          // group 1 runs one barrier behind group 0
 
-#define PP_MFMA(ACC, AH, AL, BH, BL)            \
-    ACC = T2S_MFMA32(AL, BH, ACC, 0, 0, 0);         \
-    ACC = T2S_MFMA32(AH, BL, ACC, 0, 0, 0);         \
-    ACC = T2S_MFMA32(AH, BH, ACC, 0, 0, 0);
+#define PP_MFMA(ACC, AH, AL, BH, BL)                        \
+    if constexpr (!A1) ACC = FMT::mfma(AL, BH, ACC);          \
+    ACC = FMT::mfma(AH, BL, ACC);                             \
+    ACC = FMT::mfma(AH, BH, ACC);
 
     // One phase = read segment, barrier, matrix segment, barrier.  `MAIN` K-steps issue a stage in every phase and wait
-    // with a counted vmcnt(6); the last two K-steps have nothing (or less) left to stage and drain with vmcnt(0).
+    // with a counted vmcnt (VM_P0 .. VM_P3 above); the last two K-steps have nothing (or less) left to stage and drain with vmcnt(0).
     auto kstep = [&](int ks, auto main_tag) {
         constexpr bool MAIN = decltype(main_tag)::value;
         const char* sb = smem + (ks & 1) * PP_BUF;
         // ------------------------------------------------ phase 0: A half 0 x B half 0
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            b0h[n] = *(const bf16x8*)(sb + b_frag + n * 1024);
-            b0l[n] = *(const bf16x8*)(sb + b_frag + PP_PLANE + n * 1024);
+            b0h[n] = *(const fragT*)(sb + b_frag + n * 1024);
+            b0l[n] = *(const fragT*)(sb + b_frag + PP_PLANE + n * 1024);
         }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            afh[m] = *(const bf16x8*)(sb + a_frag + m * 1024);
-            afl[m] = *(const bf16x8*)(sb + a_frag + PP_PLANE + m * 1024);
+            afh[m] = *(const fragT*)(sb + a_frag + m * 1024);
+            if constexpr (!A1) afl[m] = *(const fragT*)(sb + a_frag + PP_PLANE + m * 1024);
         }
         if (MAIN || ks + 1 < nk) stage_b(ks + 1, c1, 1);
-        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM_P0) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -285,11 +301,11 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         // ------------------------------------------------ phase 1: A half 0 x B half 1
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            b1h[n] = *(const bf16x8*)(sb + b_frag + PP_HALF + n * 1024);
-            b1l[n] = *(const bf16x8*)(sb + b_frag + PP_HALF + PP_PLANE + n * 1024);
+            b1h[n] = *(const fragT*)(sb + b_frag + PP_HALF + n * 1024);
+            b1l[n] = *(const fragT*)(sb + b_frag + PP_HALF + PP_PLANE + n * 1024);
         }
         if (MAIN || ks + 1 < nk) stage_a(ks + 1, c1, 1);
-        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM_P1) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -307,11 +323,11 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         // ------------------------------------------------ phase 2: A half 1 x B half 1
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            afh[m] = *(const bf16x8*)(sb + a_frag + PP_HALF + m * 1024);
-            afl[m] = *(const bf16x8*)(sb + a_frag + PP_HALF + PP_PLANE + m * 1024);
+            afh[m] = *(const fragT*)(sb + a_frag + PP_HALF + m * 1024);
+            if constexpr (!A1) afl[m] = *(const fragT*)(sb + a_frag + PP_HALF + PP_PLANE + m * 1024);
         }
         if (MAIN || ks + 2 < nk) stage_a(ks + 2, c2, 0);
-        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM_P2) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -328,7 +344,7 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         asm volatile("" ::: "memory");
         // ------------------------------------------------ phase 3: A half 1 x B half 0 (fragments still in registers)
         if (MAIN || ks + 2 < nk) stage_b(ks + 2, c2, 0);
-        if (MAIN) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        if (MAIN) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM_P3) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -389,13 +405,13 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         bt_all[mp] = *(const f32x4*)(a.bias + prow);
         bs_all[mp] = *(const f32x4*)(a.bias + prow + 16);
     }
-    bf16x8 fw_h[2] = {}, fw_l[2] = {};
+    fragT fw_h[2] = {}, fw_l[2] = {};
     if (a.fold_A) {
 #pragma unroll
         for (int pair = 0; pair < 2; ++pair) {
             const u16* fa = a.fold_A + ((size_t)(mt * 4 + pair * 2 + wr) * 2 * 64 + lane) * 8;
-            fw_h[pair] = *(const bf16x8*)fa;
-            fw_l[pair] = *(const bf16x8*)(fa + 64 * 8);
+            fw_h[pair] = *(const fragT*)fa;
+            fw_l[pair] = *(const fragT*)(fa + 64 * 8);
         }
     }
     f32x4 facc[4];
@@ -438,13 +454,13 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
                             const float tv = (E - 1.0f) * __builtin_amdgcn_rcpf(E + 1.0f);
                             const float gv = __builtin_amdgcn_rcpf(1.0f + F);
                             u16 h, l;
-                            split_bf16(tv * gv, h, l);
+                            split_fmt<FMT>(tv * gv, h, l);
                             hi[e] = h;
                             lo[e] = l;
-                            split_bf16(tv, h, l);
+                            split_fmt<FMT>(tv, h, l);
                             thi[e] = h;
                             tlo[e] = l;
-                            split_bf16(gv, h, l);
+                            split_fmt<FMT>(gv, h, l);
                             ghi[e] = h;
                             glo[e] = l;
                         }
@@ -461,7 +477,7 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
                             const float F = __builtin_amdgcn_exp2f(fmaf(acc[2 * mp + 1][n][e], -L2E, bs[e]));
                             const float v = (E - 1.0f) * __builtin_amdgcn_rcpf((E + 1.0f) * (1.0f + F));
                             u16 h, l;
-                            split_bf16(v, h, l);
+                            split_fmt<FMT>(v, h, l);
                             hi[e] = h;
                             lo[e] = l;
                         }
@@ -475,7 +491,7 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
         }
         if (a.fold_A) {
             // fold_A blocks are indexed by the 32-channel block of the M tile (endfold_weights_kernel: block = c >> 5)
-            const bf16x8 wh = fw_h[pair], wl = fw_l[pair];
+            const fragT wh = fw_h[pair], wl = fw_l[pair];
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
@@ -483,11 +499,11 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
                                    hv[1][n][0], hv[1][n][1], hv[1][n][2], hv[1][n][3]};
                 const u16x8 bl8 = {lv[0][n][0], lv[0][n][1], lv[0][n][2], lv[0][n][3],
                                    lv[1][n][0], lv[1][n][1], lv[1][n][2], lv[1][n][3]};
-                const bf16x8 bh = __builtin_bit_cast(bf16x8, bh8);
-                const bf16x8 bl = __builtin_bit_cast(bf16x8, bl8);
-                facc[n] = T2S_MFMA32(wl, bh, facc[n], 0, 0, 0);
-                facc[n] = T2S_MFMA32(wh, bl, facc[n], 0, 0, 0);
-                facc[n] = T2S_MFMA32(wh, bh, facc[n], 0, 0, 0);
+                const fragT bh = __builtin_bit_cast(fragT, bh8);
+                const fragT bl = __builtin_bit_cast(fragT, bl8);
+                facc[n] = FMT::mfma(wl, bh, facc[n]);         // the folded WN.end is a composed matrix: hi + lo, three products
+                facc[n] = FMT::mfma(wh, bl, facc[n]);
+                facc[n] = FMT::mfma(wh, bh, facc[n]);
             }
         }
     }
@@ -536,7 +552,7 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
             for (int e = 0; e < 8; ++e) {
                 const float add = e < 4 ? acc[m0][n][e & 3] + b0[e & 3] : acc[m0 + 1][n][e & 3] + b1[e & 3];
                 u16 h, l;
-                split_bf16(join_bf16(oh[n][e], ol[n][e]) + add, h, l);
+                split_fmt<FMT>(join_fmt<FMT>(oh[n][e], ol[n][e]) + add, h, l);
                 hi[e] = h;
                 lo[e] = l;
             }
@@ -583,7 +599,7 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     u16 h, l;
-                    split_bf16(join_bf16(oh[mi][n][e], ol[mi][n][e]) + (acc[m0 + mi][n][e] + bv[mi][e]), h, l);
+                    split_fmt<FMT>(join_fmt<FMT>(oh[mi][n][e], ol[mi][n][e]) + (acc[m0 + mi][n][e] + bv[mi][e]), h, l);
                     hi[e] = h;
                     lo[e] = l;
                 }
@@ -626,14 +642,14 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
             u16x8_t h1, l1, h2, l2;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float av = join_bf16(th[n][e], tl[n][e]), gv = join_bf16(gh[n][e], gl[n][e]);
+                const float av = join_fmt<FMT>(th[n][e], tl[n][e]), gv = join_fmt<FMT>(gh[n][e], gl[n][e]);
                 const float tv = gv != 0.0f ? av / gv : 0.0f;
                 const float da = e < 4 ? acc[m0][n][e & 3] : acc[m0 + 1][n][e & 3];
                 u16 h, l;
-                split_bf16(da * gv * (1.0f - tv * tv), h, l);
+                split_fmt<FMT>(da * gv * (1.0f - tv * tv), h, l);
                 h1[e] = h;
                 l1[e] = l;
-                split_bf16(da * av * (1.0f - gv), h, l);
+                split_fmt<FMT>(da * av * (1.0f - gv), h, l);
                 h2[e] = h;
                 l2[e] = l;
             }
@@ -678,14 +694,14 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
                 u16x4 h1, l1, h2, l2;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float av = join_bf16(th[mi][n][e], tl[mi][n][e]), gv = join_bf16(gh[mi][n][e], gl[mi][n][e]);
+                    const float av = join_fmt<FMT>(th[mi][n][e], tl[mi][n][e]), gv = join_fmt<FMT>(gh[mi][n][e], gl[mi][n][e]);
                     const float tv = gv != 0.0f ? av / gv : 0.0f;
                     const float da = acc[m0 + mi][n][e];
                     u16 h, l;
-                    split_bf16(da * gv * (1.0f - tv * tv), h, l);
+                    split_fmt<FMT>(da * gv * (1.0f - tv * tv), h, l);
                     h1[e] = h;
                     l1[e] = l;
-                    split_bf16(da * av * (1.0f - gv), h, l);
+                    split_fmt<FMT>(da * av * (1.0f - gv), h, l);
                     h2[e] = h;
                     l2[e] = l;
                 }
@@ -706,14 +722,14 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
     PP_RSTAMP(5)
 }
 
-template <bool PH = false, int EPI = EPI_GATE>
+template <bool PH = false, int EPI = EPI_GATE, class FMT = T2sFmt, bool A1 = false>
 static hipError_t launch_pp(const ConvGemmArgs& a, hipStream_t stream) {
     const int nwg = PH ? a.n_mtiles * a.ph_P * a.ph_nft * ((a.B + a.ph_bper - 1) / a.ph_bper) : a.n_mtiles * a.n_ttiles * a.B;
     constexpr int lds = 2 * PP_BUF;
     static std::atomic<unsigned long long> attr_mask{0};
-    const hipError_t e = t2s_raise_lds_limit((const void*)gate_gemm_pp_kernel<PH, EPI>, lds, attr_mask);
+    const hipError_t e = t2s_raise_lds_limit((const void*)gate_gemm_pp_kernel<PH, EPI, FMT, A1>, lds, attr_mask);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gate_gemm_pp_kernel<PH, EPI>), dim3(nwg), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((gate_gemm_pp_kernel<PH, EPI, FMT, A1>), dim3(nwg), dim3(512), lds, stream, a);
     return hipGetLastError();
 }
 
@@ -735,7 +751,11 @@ extern "C" int t2s_debug_read_pp_stamps(unsigned long long* host_out, int n_word
 }
 #endif
 
-hipError_t t2s_launch_gate_gemm_pp(const ConvGemmArgs& a, hipStream_t stream) {
+hipError_t t2s_launch_gate_gemm_pp(const ConvGemmArgs& a, hipStream_t stream, bool h16) {
+    if (h16) {      // fp16 planes, one-plane A operand: the plain K order only
+        if (a.ph_P > 0) return hipErrorInvalidValue;
+        return launch_pp<false, EPI_GATE, T2sFmtF16, true>(a, stream);
+    }
     if (a.ph_P > 0) return launch_pp<true>(a, stream);
     return launch_pp<false>(a, stream);
 }

@@ -16,6 +16,67 @@ extern "C" int t2s_internal_fail_hip(int ei) {
     return T2S_EHIP;
 }
 
+// ---- entry points that exist in two operand formats: the build's default planes, and (`h16`, the _h16 symbols) fp16 planes with
+// a one-plane A operand whose lo pointer is never read.  One body each, so that the checks cannot drift apart.
+
+// the A operand: a (hi, lo) pair, or with h16 the hi plane alone
+static inline bool a_operand_ok(const void* A_hi, const void* A_lo, bool h16) { return h16 ? (A_hi && al16(A_hi)) : planes_ok(A_hi, A_lo); }
+
+static int pack_table(const t2s_pack_job* jobs, int n_jobs, long total_rows, void* stream, bool h16) {
+    if (!jobs || n_jobs <= 0 || total_rows <= 0 || total_rows > 0x7fffffffL) return T2S_EINVAL;
+    static_assert(sizeof(t2s_pack_job) == sizeof(PackJob), "t2s_pack_job layout");
+    T2S_CHECK_HIP(t2s_launch_pack_table((const PackJob*)jobs, n_jobs, total_rows, (hipStream_t)stream, h16));
+    return T2S_OK;
+}
+
+static int upsample_squeeze(const float* mel, const float* W, const float* bias, int B, int n_mel, int frames, int ksize, int stride,
+                            int n_group, int L, int Lp, int halo, void* S_hi, void* S_lo, void* stream, bool h16) {
+    if (!mel || !W || !bias || !S_hi || !S_lo) return T2S_EINVAL;
+    if (B <= 0 || n_mel <= 0 || frames <= 0 || L <= 0 || n_group <= 0 || stride <= 0 || ksize % stride) return T2S_EINVAL;
+    if (!al16(W) || !al16(S_hi) || !al16(S_lo)) return T2S_EINVAL;
+    if (Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
+    // every squeezed sample must exist in the transposed-conv output (reference glow.py:216 assert)
+    if ((long)L * n_group > (long)(frames - 1) * stride + ksize) return T2S_EINVAL;
+    if (n_group == 8 && (stride % 8 || ksize % 8)) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_upsample_squeeze(mel, W, bias, B, n_mel, frames, ksize, stride, n_group, L, Lp, halo,
+                                              (u16*)S_hi, (u16*)S_lo, (hipStream_t)stream, h16));
+    return T2S_OK;
+}
+
+static int wg_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C, int L, int Lp,
+                    int halo, void* X_hi, void* X_lo, void* stream, bool h16) {
+    if (!z || !w || !bias || !X_hi || !X_lo) return T2S_EINVAL;
+    if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
+    if (!al16(X_hi) || !al16(X_lo) || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
+                                   (hipStream_t)stream, 0, 0, nullptr, nullptr, nullptr, h16));
+    return T2S_OK;
+}
+
+static int endfold_weights(const t2s_endfold_job* jobs, int n_jobs, int C, void* stream, bool h16) {
+    if (!jobs || n_jobs <= 0 || C <= 0 || (size_t)8 * C * sizeof(float) > 60 * 1024) return T2S_EINVAL;
+    static_assert(sizeof(t2s_endfold_job) == sizeof(EndFoldJob), "t2s_endfold_job layout");
+    T2S_CHECK_HIP(t2s_launch_endfold_weights((const EndFoldJob*)jobs, n_jobs, C, (hipStream_t)stream, h16));
+    return T2S_OK;
+}
+
+static int in_cond_gate_fold(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
+                             const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A, float* fold_acc,
+                             int fold_init, int B, int C, int n_cond, int taps, int dilation, int L, int Lp, int halo, int Mpad,
+                             void* stream, bool h16) {
+    if (!a_operand_ok(A_hi, A_lo, h16) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias)) return T2S_EINVAL;
+    if ((n_cond > 0 && !planes_ok(S_hi, S_lo)) || !fold_ok(fold_A, fold_acc, C)) return T2S_EINVAL;
+    if (!gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad)) return T2S_EINVAL;
+    ConvGemm g(A_hi, A_lo, bias);
+    g.geometry(B, L, Lp, halo, Mpad);
+    g.k_side(X_hi, X_lo, cdiv(C, 32), taps, dilation, S_hi, S_lo, cdiv(n_cond, 32));
+    g.output(acts_hi, acts_lo, cdiv(C, 32));
+    g.fold(fold_A, fold_acc, fold_init);
+    g.a.C = C;
+    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, gate_tile_rows(B, C, L), stream, false, h16));
+    return T2S_OK;
+}
+
 extern "C" {
 
 int t2s_abi_version(void) { return 4; }
@@ -66,10 +127,10 @@ int t2s_pack_conv_weight(const float* v, const float* g, int g_is_scale, const f
 }
 
 int t2s_pack_conv_weight_table(const t2s_pack_job* jobs, int n_jobs, long total_rows, void* stream) {
-    if (!jobs || n_jobs <= 0 || total_rows <= 0 || total_rows > 0x7fffffffL) return T2S_EINVAL;
-    static_assert(sizeof(t2s_pack_job) == sizeof(PackJob), "t2s_pack_job layout");
-    T2S_CHECK_HIP(t2s_launch_pack_table((const PackJob*)jobs, n_jobs, total_rows, (hipStream_t)stream));
-    return T2S_OK;
+    return pack_table(jobs, n_jobs, total_rows, stream, false);
+}
+int t2s_pack_conv_weight_table_h16(const t2s_pack_job* jobs, int n_jobs, long total_rows, void* stream) {
+    return pack_table(jobs, n_jobs, total_rows, stream, true);
 }
 
 int t2s_weightnorm_small(const float* v, const float* g, int O, int K, float* w, void* stream) {
@@ -81,16 +142,12 @@ int t2s_weightnorm_small(const float* v, const float* g, int O, int K, float* w,
 int t2s_wg_upsample_squeeze(const float* mel, const float* W, const float* bias, int B, int n_mel, int frames,
                             int ksize, int stride, int n_group, int L, int Lp, int halo, void* S_hi, void* S_lo,
                             void* stream) {
-    if (!mel || !W || !bias || !S_hi || !S_lo) return T2S_EINVAL;
-    if (B <= 0 || n_mel <= 0 || frames <= 0 || L <= 0 || n_group <= 0 || stride <= 0 || ksize % stride) return T2S_EINVAL;
-    if (!al16(W) || !al16(S_hi) || !al16(S_lo)) return T2S_EINVAL;
-    if (Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    // every squeezed sample must exist in the transposed-conv output (reference glow.py:216 assert)
-    if ((long)L * n_group > (long)(frames - 1) * stride + ksize) return T2S_EINVAL;
-    if (n_group == 8 && (stride % 8 || ksize % 8)) return T2S_EINVAL;
-    T2S_CHECK_HIP(t2s_launch_upsample_squeeze(mel, W, bias, B, n_mel, frames, ksize, stride, n_group, L, Lp, halo,
-                                              (u16*)S_hi, (u16*)S_lo, (hipStream_t)stream));
-    return T2S_OK;
+    return upsample_squeeze(mel, W, bias, B, n_mel, frames, ksize, stride, n_group, L, Lp, halo, S_hi, S_lo, stream, false);
+}
+int t2s_wg_upsample_squeeze_h16(const float* mel, const float* W, const float* bias, int B, int n_mel, int frames,
+                                int ksize, int stride, int n_group, int L, int Lp, int halo, void* S_hi, void* S_lo,
+                                void* stream) {
+    return upsample_squeeze(mel, W, bias, B, n_mel, frames, ksize, stride, n_group, L, Lp, halo, S_hi, S_lo, stream, true);
 }
 
 int t2s_wg_audio_squeeze(float* audio, float* z, int B, int T, int n_group, int L, int unsqueeze, void* stream) {
@@ -128,12 +185,11 @@ int t2s_small_logdet_inv_batch_host(const t2s_small_mat_job* host_jobs, int n_jo
 
 int t2s_wg_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
                  int L, int Lp, int halo, void* X_hi, void* X_lo, void* stream) {
-    if (!z || !w || !bias || !X_hi || !X_lo) return T2S_EINVAL;
-    if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
-    if (!al16(X_hi) || !al16(X_lo) || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
-    T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
-                                   (hipStream_t)stream));
-    return T2S_OK;
+    return wg_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, X_hi, X_lo, stream, false);
+}
+int t2s_wg_start_h16(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                     int L, int Lp, int halo, void* X_hi, void* X_lo, void* stream) {
+    return wg_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, X_hi, X_lo, stream, true);
 }
 
 // window chunks of the folded WN.start: 2 (two column sets per chunk) or 4 (one), each set taps * (n_half + 1) columns wide
@@ -215,10 +271,10 @@ int t2s_wg_res_skip(const void* A_hi, const void* A_lo, const float* bias, const
 }
 
 int t2s_wg_endfold_weights(const t2s_endfold_job* jobs, int n_jobs, int C, void* stream) {
-    if (!jobs || n_jobs <= 0 || C <= 0 || (size_t)8 * C * sizeof(float) > 60 * 1024) return T2S_EINVAL;
-    static_assert(sizeof(t2s_endfold_job) == sizeof(EndFoldJob), "t2s_endfold_job layout");
-    T2S_CHECK_HIP(t2s_launch_endfold_weights((const EndFoldJob*)jobs, n_jobs, C, (hipStream_t)stream));
-    return T2S_OK;
+    return endfold_weights(jobs, n_jobs, C, stream, false);
+}
+int t2s_wg_endfold_weights_h16(const t2s_endfold_job* jobs, int n_jobs, int C, void* stream) {
+    return endfold_weights(jobs, n_jobs, C, stream, true);
 }
 
 int t2s_wg_gate_tile_rows(int B, int C, int L) {
@@ -235,17 +291,15 @@ int t2s_wg_in_cond_gate_fold(const void* A_hi, const void* A_lo, const float* bi
                              const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
                              float* fold_acc, int fold_init, int B, int C, int n_cond, int taps, int dilation, int L,
                              int Lp, int halo, int Mpad, void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias)) return T2S_EINVAL;
-    if ((n_cond > 0 && !planes_ok(S_hi, S_lo)) || !fold_ok(fold_A, fold_acc, C)) return T2S_EINVAL;
-    if (!gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad)) return T2S_EINVAL;
-    ConvGemm g(A_hi, A_lo, bias);
-    g.geometry(B, L, Lp, halo, Mpad);
-    g.k_side(X_hi, X_lo, cdiv(C, 32), taps, dilation, S_hi, S_lo, cdiv(n_cond, 32));
-    g.output(acts_hi, acts_lo, cdiv(C, 32));
-    g.fold(fold_A, fold_acc, fold_init);
-    g.a.C = C;
-    T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, gate_tile_rows(B, C, L), stream));
-    return T2S_OK;
+    return in_cond_gate_fold(A_hi, A_lo, bias, X_hi, X_lo, S_hi, S_lo, acts_hi, acts_lo, fold_A, fold_acc, fold_init, B, C, n_cond, taps,
+                             dilation, L, Lp, halo, Mpad, stream, false);
+}
+int t2s_wg_in_cond_gate_fold_h16(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
+                                 const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
+                                 float* fold_acc, int fold_init, int B, int C, int n_cond, int taps, int dilation, int L,
+                                 int Lp, int halo, int Mpad, void* stream) {
+    return in_cond_gate_fold(A_hi, A_lo, bias, X_hi, X_lo, S_hi, S_lo, acts_hi, acts_lo, fold_A, fold_acc, fold_init, B, C, n_cond, taps,
+                             dilation, L, Lp, halo, Mpad, stream, true);
 }
 
 int t2s_wg_in_win_gate_fold(const void* A_hi, const void* A_lo, const float* bias, const void* W_hi, const void* W_lo,
@@ -326,8 +380,8 @@ int t2s_wg_in_melwin_gate_fold(const void* A_hi, const void* A_lo, const void* A
 // t2s_wg_res_only and, with `lengths`, t2s_wg_res_only_ragged
 static int res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                     void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, const int* lengths,
-                    void* stream) {
-    if (!planes_ok(A_hi, A_lo) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !bias || !al16(bias)) return T2S_EINVAL;
+                    void* stream, bool h16 = false) {
+    if (!a_operand_ok(A_hi, A_lo, h16) || !planes_ok(acts_hi, acts_lo) || !planes_ok(X_hi, X_lo) || !bias || !al16(bias)) return T2S_EINVAL;
     if (C <= 0 || C % 4 || (pair8 && C % 32) || !geometry_ok(B, L, Lp, halo, Mpad, C)) return T2S_EINVAL;
     ConvGemm g(A_hi, A_lo, bias);
     g.geometry(B, L, Lp, halo, Mpad);
@@ -335,8 +389,13 @@ static int res_only(const void* A_hi, const void* A_lo, const float* bias, const
     g.output(X_hi, X_lo, cdiv(C, 32));
     g.a.C = 0; g.a.n_res = C; g.a.pair8 = pair8 ? 1 : 0;
     g.a.lengths = lengths;
-    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, 128, stream));
+    T2S_CHECK_HIP(g.launch(EPI_RESSKIP, C, 128, stream, false, h16));
     return T2S_OK;
+}
+
+int t2s_wg_res_only_h16(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                        void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, void* stream) {
+    return res_only(A_hi, A_lo, bias, acts_hi, acts_lo, X_hi, X_lo, B, C, L, Lp, halo, Mpad, pair8, nullptr, stream, true);
 }
 
 int t2s_wg_res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,

@@ -21,45 +21,64 @@ typedef __attribute__((ext_vector_type(4))) unsigned short u16x4;
 #define T2S_TILE_M 256          // output-channel rows per workgroup
 #define T2S_TILE_N 256          // time steps per workgroup
 
+// ---- operand formats as compile-time traits: fragment types, the 16x16x32 MFMA, f32 <-> 16-bit container.  A kernel templated on
+// a format computes with it whatever the build's default is; the names further down (bf16x8, T2S_MFMA32, bf16_bits, split_bf16 ...)
+// resolve to the build's default format, T2sFmt.
+struct T2sFmtBf16 {            // split-bf16: f32's exponent range, 8 significand bits per plane
+    typedef __attribute__((ext_vector_type(8))) __bf16 frag8;      // one MFMA operand fragment (8 x 16-bit)
+    typedef __attribute__((ext_vector_type(4))) __bf16 frag4;
+    static __device__ __forceinline__ u16 bits(float x) {
+        __bf16 h = (__bf16)x;                      // v_cvt_pk_bf16_f32: RNE, NaN-preserving
+        return __builtin_bit_cast(u16, h);
+    }
+    static __device__ __forceinline__ float to_f32(u16 b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
+    static __device__ __forceinline__ f32x4 mfma(frag8 a, frag8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
+// fp16 planes (v_mfma_f32_16x16x32_f16: same issue rate, profiles/r03_mfma_f8_probe.txt).  hi = fp16(x) keeps 11 significand bits
+// instead of 8, so hi + lo carries ~22 bits where both are normal numbers - but fp16 has no exponent range to spare: |x| > 65504
+// overflows to inf and |x| < 6e-5 loses the low plane to subnormals.  The no-grad WaveGlow forward / infer only (activations and
+// weight-normed weights sit inside that range; GRADIENT planes do not).
+struct T2sFmtF16 {
+    typedef __attribute__((ext_vector_type(8))) _Float16 frag8;
+    typedef __attribute__((ext_vector_type(4))) _Float16 frag4;
+    static __device__ __forceinline__ u16 bits(float x) {
+        _Float16 h = (_Float16)x;                  // v_cvt_f16_f32: RNE
+        return __builtin_bit_cast(u16, h);
+    }
+    static __device__ __forceinline__ float to_f32(u16 b) { return (float)__builtin_bit_cast(_Float16, b); }
+    static __device__ __forceinline__ f32x4 mfma(frag8 a, frag8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
 #ifndef T2S_SPLIT_F16
-// ---- the shipped operand format: split-bf16 ----
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;      // one MFMA operand fragment (8 x 16-bit)
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+typedef T2sFmtBf16 T2sFmt;     // the shipped operand format
 #define T2S_MFMA32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-static __device__ __forceinline__ u16 bf16_bits(float x) {
-    __bf16 h = (__bf16)x;                      // v_cvt_pk_bf16_f32: RNE, NaN-preserving
-    return __builtin_bit_cast(u16, h);
-}
-static __device__ __forceinline__ float bf16_to_f32(u16 b) {
-    return __builtin_bit_cast(float, (uint32_t)b << 16);
-}
 #else
-// ---- DIAGNOSTIC build (-DT2S_SPLIT_F16, `python -m text2speech_amd.build --variant f16x3 -DT2S_SPLIT_F16`): the same three
-// products per MAC with fp16 operand planes instead of bf16 (v_mfma_f32_16x16x32_f16: same issue rate, profiles/r03_mfma_f8_probe.txt).
-// hi = fp16(x) keeps 11 significand bits instead of 8, so hi + lo carries ~22 bits where both are normal numbers - but fp16 has
-// no exponent range to spare: |x| > 65504 overflows to inf and |x| < 6e-5 loses the low plane to subnormals.  The no-grad WaveGlow
-// forward / infer only (activations and weight-normed weights sit inside that range; GRADIENT planes do not, and the training path
-// also builds bf16 constants on the Python side): tests/test_waveglow_gpu.py::test_stress_weights_* runs it next to the shipped
-// library.  The type and function NAMES below stay those of the shipped format so that no kernel source differs between the builds.
-typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) _Float16 bf16x4;
+// DIAGNOSTIC build (-DT2S_SPLIT_F16, `python -m text2speech_amd.build --variant f16x3 -DT2S_SPLIT_F16`): the same three products per
+// MAC with fp16 operand planes in every kernel; tests/test_waveglow_gpu.py::test_stress_weights_* runs it next to the shipped
+// library, and the training path also builds bf16 constants on the Python side.  The type and function NAMES below stay those of
+// the shipped format so that no kernel source differs between the builds.
+typedef T2sFmtF16 T2sFmt;
 #define T2S_MFMA32 __builtin_amdgcn_mfma_f32_16x16x32_f16
-static __device__ __forceinline__ u16 bf16_bits(float x) {
-    _Float16 h = (_Float16)x;                  // v_cvt_f16_f32: RNE
-    return __builtin_bit_cast(u16, h);
-}
-static __device__ __forceinline__ float bf16_to_f32(u16 b) {
-    return (float)__builtin_bit_cast(_Float16, b);
-}
 #endif
-// x -> (hi, lo) with hi = bf16(x), lo = bf16(x - hi); x - hi is exact in f32.
-static __device__ __forceinline__ void split_bf16(float x, u16& hi, u16& lo) {
-    hi = bf16_bits(x);
-    lo = bf16_bits(x - bf16_to_f32(hi));
+typedef T2sFmt::frag8 bf16x8;
+typedef T2sFmt::frag4 bf16x4;
+static __device__ __forceinline__ u16 bf16_bits(float x) { return T2sFmt::bits(x); }
+static __device__ __forceinline__ float bf16_to_f32(u16 b) { return T2sFmt::to_f32(b); }
+// x -> (hi, lo) with hi = F(x), lo = F(x - hi); x - hi is exact in f32.
+template <class F>
+static __device__ __forceinline__ void split_fmt(float x, u16& hi, u16& lo) {
+    hi = F::bits(x);
+    lo = F::bits(x - F::to_f32(hi));
 }
-static __device__ __forceinline__ float join_bf16(u16 hi, u16 lo) {
-    return bf16_to_f32(hi) + bf16_to_f32(lo);
+template <class F>
+static __device__ __forceinline__ float join_fmt(u16 hi, u16 lo) {
+    return F::to_f32(hi) + F::to_f32(lo);
 }
+static __device__ __forceinline__ void split_bf16(float x, u16& hi, u16& lo) { split_fmt<T2sFmt>(x, hi, lo); }
+static __device__ __forceinline__ float join_bf16(u16 hi, u16 lo) { return join_fmt<T2sFmt>(hi, lo); }
 
 static __device__ __forceinline__ float fast_sigmoid(float x) {
     return 1.0f / (1.0f + __expf(-x));

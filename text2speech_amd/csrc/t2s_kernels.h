@@ -71,9 +71,10 @@ struct ConvGemmArgs {
     const int* lengths;    // [B] int32, device
 };
 
-hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows = 256);
+// h16: the planes are fp16 and the A operand is ONE plane (a.A_lo is not read) - the _h16 entry points of include/t2s_hip.h
+hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows = 256, bool h16 = false);
 // EPI_GATE, 256 x 256 tile, plain K order (nk = taps * xc + sc): the ping-pong schedule of csrc/gate_gemm_pp.hip
-hipError_t t2s_launch_gate_gemm_pp(const ConvGemmArgs& a, hipStream_t stream);
+hipError_t t2s_launch_gate_gemm_pp(const ConvGemmArgs& a, hipStream_t stream, bool h16 = false);
 // EPI_RESSKIP (accumulate form: n_res = every row, C = 0) / EPI_GATE_BWD on the same schedule; a.n_mtiles counts 256-row tiles
 hipError_t t2s_launch_bwd_gemm_pp(const ConvGemmArgs& a, int epi, hipStream_t stream);
 bool t2s_pp_shape_ok(const ConvGemmArgs& a);
@@ -120,7 +121,8 @@ struct PackJob {               // mirrors t2s_pack_job in include/t2s_hip.h (all
     long O, Cin, Kt, perm, C_gate, Mpad, koff, Cin_pad, row_off, g_is_scale;
     float* scale_out;          // optional [O]: the per-row factor applied (g/|v|), kept for the backward pass
 };
-hipError_t t2s_launch_pack_table(const PackJob* jobs, int n_jobs, long total_rows, hipStream_t stream);
+// h16: A_hi receives fp16 (RNE) of the effective weight, A_lo is not written
+hipError_t t2s_launch_pack_table(const PackJob* jobs, int n_jobs, long total_rows, hipStream_t stream, bool h16 = false);
 hipError_t t2s_launch_weightnorm_small(const float* v, const float* g, int O, int K, float* w, hipStream_t stream);
 
 hipError_t t2s_launch_upbasis_planes(const float* W, const float* bias, int n_mel, int ksize, int stride, int n_group, int Lp,
@@ -131,7 +133,7 @@ hipError_t t2s_launch_melwin_planes(const float* mel, int B, int n_mel, int fram
                                     hipStream_t stream);
 hipError_t t2s_launch_upsample_squeeze(const float* mel, const float* W, const float* bias, int B, int n_mel,
                                        int frames, int ksize, int stride, int n_group, int L, int Lp, int halo,
-                                       u16* S_hi, u16* S_lo, hipStream_t stream);
+                                       u16* S_hi, u16* S_lo, hipStream_t stream, bool h16 = false);
 hipError_t t2s_launch_audio_squeeze(const float* audio, float* z, int B, int T, int n_group, int L, int unsqueeze,
                                     hipStream_t stream);
 hipError_t t2s_launch_convinv(float* z, const float* W, int B, int n_group, int c_off, int n_rem, int L,
@@ -145,7 +147,8 @@ hipError_t t2s_launch_small_logdet_inv(const float* W, int n, float scale, float
 // lengths ([B] int32, device; optional): the ragged variant - batch entry b ends at column lengths[b] <= L
 hipError_t t2s_launch_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off,
                             int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream,
-                            int taps = 0, int nwc = 0, u16* W_hi = nullptr, u16* W_lo = nullptr, const int* lengths = nullptr);
+                            int taps = 0, int nwc = 0, u16* W_hi = nullptr, u16* W_lo = nullptr, const int* lengths = nullptr,
+                            bool h16 = false);
 hipError_t t2s_launch_startfold_weights(const float* v, const float* g, const float* w_start, const float* b_start, int C,
                                         int n_half, int taps, int Mpad, int nwc, u16* A_hi, u16* A_lo, hipStream_t stream);
 struct EndFoldJob {        // one WN layer: fold_w[c][j] = sum_o W_end[j][o] * scale[o] * v_skip[o][c]
@@ -157,7 +160,7 @@ struct EndFoldJob {        // one WN layer: fold_w[c][j] = sum_o W_end[j][o] * s
     float* bes;            // [8]: W_end . b_skip
     long nj, C;
 };
-hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C, hipStream_t stream);
+hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C, hipStream_t stream, bool h16 = false);
 hipError_t t2s_launch_end_fold_affine(const float* fold_acc, int nslots, const float* bes, int n_layers,
                                       const float* b_end, float* z, float* log_s, float* wn_out, int B, int n_group, int c_off,
                                       int n_half, int L, int reverse, hipStream_t stream);

@@ -95,20 +95,23 @@ static __device__ __forceinline__ int pack_dst_row(const PackJob& j, int o) {
     }
     return o + (int)j.row_off;
 }
+// FMT = operand format; ONE: only the hi plane is written, FMT's rounding (RNE) of the f32 effective weight - the one-plane A operand
+// of the _h16 GEMMs - and j.A_lo is not touched
+template <class FMT, bool ONE>
 static __device__ __forceinline__ void pack_store2(const PackJob& j, int k, int p, float w0, float w1) {
     const size_t idx = ((size_t)(k >> 5) * (int)j.Mpad + p) * 32 + (k & 31);
     u16 h0, l0, h1, l1;
-    split_bf16(w0, h0, l0);
-    split_bf16(w1, h1, l1);
+    split_fmt<FMT>(w0, h0, l0);
+    split_fmt<FMT>(w1, h1, l1);
     *(uint32_t*)(j.A_hi + idx) = h0 | ((uint32_t)h1 << 16);
-    *(uint32_t*)(j.A_lo + idx) = l0 | ((uint32_t)l1 << 16);
+    if constexpr (!ONE) *(uint32_t*)(j.A_lo + idx) = l0 | ((uint32_t)l1 << 16);
 }
 static __device__ __forceinline__ float sum16(float v) {      // over the 16 lanes that share a row
     v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
     return v;
 }
 #define PACK_MAX_CHUNKS 20
-template <int KT>
+template <int KT, class FMT, bool ONE>
 static __device__ __forceinline__ void pack_rows_regs(const PackJob& j, int o0) {
     const int tid = threadIdx.x, r = tid >> 4, cp = tid & 15;
     const int O = (int)j.O, Cin = (int)j.Cin, Cin_pad = (int)j.Cin_pad, koff = (int)j.koff;
@@ -153,11 +156,12 @@ static __device__ __forceinline__ void pack_rows_regs(const PackJob& j, int o0) 
             const int c = cc * 32 + cp * 2;
 #pragma unroll
             for (int tap = 0; tap < KT; ++tap)
-                pack_store2(j, koff + tap * Cin_pad + c, p, x[cc][tap] * scale, x[cc][KT + tap] * scale);
+                pack_store2<FMT, ONE>(j, koff + tap * Cin_pad + c, p, x[cc][tap] * scale, x[cc][KT + tap] * scale);
         }
     }
 }
 
+template <class FMT, bool ONE>
 static __device__ __forceinline__ void pack_rows_two_pass(const PackJob& j, int o0, float* s_scale) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int O = (int)j.O, Cin = (int)j.Cin, Kt = (int)j.Kt, Cin_pad = (int)j.Cin_pad, koff = (int)j.koff;
@@ -205,11 +209,12 @@ static __device__ __forceinline__ void pack_rows_two_pass(const PackJob& j, int 
         for (int tap = 0; tap < Kt; ++tap) {
             const float w0 = c < Cin ? vrow[c * Kt + tap] * scale : 0.f;
             const float w1 = c + 1 < Cin ? vrow[(c + 1) * Kt + tap] * scale : 0.f;
-            pack_store2(j, koff + tap * Cin_pad + c, p, w0, w1);
+            pack_store2<FMT, ONE>(j, koff + tap * Cin_pad + c, p, w0, w1);
         }
     }
 }
 
+template <class FMT = T2sFmt, bool ONE = false>
 __global__ __launch_bounds__(256) void pack_table_kernel(const PackJob* __restrict__ jobs, int n_jobs) {
     __shared__ float s_scale[16];
     const long blk = blockIdx.x;
@@ -222,12 +227,13 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const PackJob* __restri
     const int o0 = (int)(blk - j.row_start) * 16;
     const int nchunk = ((int)j.Cin + 31) >> 5;
     // Cin even keeps a thread's 2*Kt floats inside the row; the register path also needs whole channel pairs
-    if (nchunk <= PACK_MAX_CHUNKS && !((int)j.Cin & 1) && j.Kt == 3) pack_rows_regs<3>(j, o0);
-    else if (nchunk <= PACK_MAX_CHUNKS && !((int)j.Cin & 1) && j.Kt == 1) pack_rows_regs<1>(j, o0);
-    else pack_rows_two_pass(j, o0, s_scale);
+    if (nchunk <= PACK_MAX_CHUNKS && !((int)j.Cin & 1) && j.Kt == 3) pack_rows_regs<3, FMT, ONE>(j, o0);
+    else if (nchunk <= PACK_MAX_CHUNKS && !((int)j.Cin & 1) && j.Kt == 1) pack_rows_regs<1, FMT, ONE>(j, o0);
+    else pack_rows_two_pass<FMT, ONE>(j, o0, s_scale);
 }
-hipError_t t2s_launch_pack_table(const PackJob* jobs, int n_jobs, long total_groups, hipStream_t stream) {
-    hipLaunchKernelGGL(pack_table_kernel, dim3((unsigned)total_groups), dim3(256), 0, stream, jobs, n_jobs);
+hipError_t t2s_launch_pack_table(const PackJob* jobs, int n_jobs, long total_groups, hipStream_t stream, bool h16) {
+    if (h16) hipLaunchKernelGGL((pack_table_kernel<T2sFmtF16, true>), dim3((unsigned)total_groups), dim3(256), 0, stream, jobs, n_jobs);
+    else hipLaunchKernelGGL((pack_table_kernel<>), dim3((unsigned)total_groups), dim3(256), 0, stream, jobs, n_jobs);
     return hipGetLastError();
 }
 
@@ -256,7 +262,7 @@ hipError_t t2s_launch_weightnorm_small(const float* v, const float* g, int O, in
 //   spect[b][co*G + g][t] = bias[co] + sum_{ci,f} mel[b][ci][f] * W[ci][co][G*t + g - stride*f]
 // One thread = 8 consecutive squeezed channels of one time step for up to BB batch elements, so each
 // weight value fetched is reused BB times; the 8 results are one 16-B store per plane.
-template <int BB>
+template <int BB, class FMT = T2sFmt>
 __global__ __launch_bounds__(256) void upsample_squeeze_kernel(const float* __restrict__ mel, const float* __restrict__ W,
                                                                const float* __restrict__ bias, int B, int M, int F,
                                                                int ksize, int stride, int G, int L, int Lp, int halo,
@@ -330,7 +336,7 @@ __global__ __launch_bounds__(256) void upsample_squeeze_kernel(const float* __re
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float v = (c8 + j < nchan) ? acc[bb][j] : 0.f;
-            split_bf16(v, hi[j], lo[j]);
+            split_fmt<FMT>(v, hi[j], lo[j]);
         }
         uint4 ph, pl;
         ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
@@ -354,7 +360,7 @@ __global__ __launch_bounds__(256) void upsample_squeeze_kernel(const float* __re
 // D tile: col = lane & 15 (frame), row = 4 * (lane >> 4) + e -> p = p0 + 4q + e: plane row t = f * (stride / 8) + (p >> 3),
 // squeezed channel co * 8 + (p & 7): the lane's four values are four consecutive channels of one plane row, one 8-B store.
 typedef float f32x4_up __attribute__((ext_vector_type(4)));
-template <int NT, int KB>
+template <int NT, int KB, class FMT = T2sFmt>
 __global__ __launch_bounds__(256) void upsample_mfma_kernel(const float* __restrict__ mel, const float* __restrict__ W,
                                                             const float* __restrict__ bias, int B, int M, int F, int ksize,
                                                             int stride, int L, int Lp, int halo, int tiles_per_b, int n_ctiles,
@@ -440,7 +446,7 @@ __global__ __launch_bounds__(256) void upsample_mfma_kernel(const float* __restr
             const float bo = bias[chunk * 4 + o];
             u16 hi[4], lo[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) split_bf16(acc[o][n][e] + bo, hi[e], lo[e]);
+            for (int e = 0; e < 4; ++e) split_fmt<FMT>(acc[o][n][e] + bo, hi[e], lo[e]);
             uint2 ph, pl;
             ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
             pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
@@ -452,7 +458,7 @@ __global__ __launch_bounds__(256) void upsample_mfma_kernel(const float* __restr
 
 hipError_t t2s_launch_upsample_squeeze(const float* mel, const float* W, const float* bias, int B, int n_mel,
                                        int frames, int ksize, int stride, int n_group, int L, int Lp, int halo,
-                                       u16* S_hi, u16* S_lo, hipStream_t stream) {
+                                       u16* S_hi, u16* S_lo, hipStream_t stream, bool h16) {
     const int nchunks = (n_mel * n_group + 31) / 32;
     if (n_group == 8 && ksize == 4 * stride && stride % 64 == 0 && n_mel % 4 == 0) {
         // frames that reach plane rows < L: f <= (8 * L - 1) / stride
@@ -465,12 +471,20 @@ hipError_t t2s_launch_upsample_squeeze(const float* mel, const float* W, const f
         dim3 grid(8 * ((n_pairs + 7) / 8) * nz);
         // KB = 1: one K-step of operands in flight per wave, 5 waves per SIMD.  KB = 4 (four K-steps per round trip, 96 VGPRs)
         // measured slower on MI355X (145 us against 114 us), as did NT = 4 (132 us): the kernel wants waves, not depth.
+        if (h16)
+            hipLaunchKernelGGL((upsample_mfma_kernel<NT, 1, T2sFmtF16>), grid, dim3(256), 0, stream, mel, W, bias, B, n_mel, frames,
+                               ksize, stride, L, Lp, halo, tiles_per_b, n_ctiles, n_pairs, nz, S_hi, S_lo);
+        else
         hipLaunchKernelGGL((upsample_mfma_kernel<NT, 1>), grid, dim3(256), 0, stream, mel, W, bias, B, n_mel, frames, ksize,
                            stride, L, Lp, halo, tiles_per_b, n_ctiles, n_pairs, nz, S_hi, S_lo);
         return hipGetLastError();
     }
     constexpr int BB = 8;
     dim3 grid((L + 63) / 64, nchunks, (B + BB - 1) / BB);
+    if (h16)
+        hipLaunchKernelGGL((upsample_squeeze_kernel<BB, T2sFmtF16>), grid, dim3(256), 0, stream, mel, W, bias, B, n_mel, frames,
+                           ksize, stride, n_group, L, Lp, halo, S_hi, S_lo);
+    else
     hipLaunchKernelGGL(upsample_squeeze_kernel<BB>, grid, dim3(256), 0, stream, mel, W, bias, B, n_mel, frames, ksize,
                        stride, n_group, L, Lp, halo, S_hi, S_lo);
     return hipGetLastError();
@@ -784,7 +798,7 @@ static __device__ __forceinline__ void start_fold_term(float x, int set, bool is
         lo = 0;
     }
 }
-template <bool RAG>
+template <bool RAG, class FMT = T2sFmt>
 __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                     const float* __restrict__ bias, int G, int c_off, int nh, int C,
                                                     int L, int Lp, int halo, u16* X_hi, u16* X_lo, int taps, int nwc,
@@ -829,7 +843,7 @@ __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z,
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if (j < nh) v += wv[e][j] * a0[j];
-            split_bf16(v, hi[e], lo[e]);
+            split_fmt<FMT>(v, hi[e], lo[e]);
         }
         uint4 ph, pl;
         ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
@@ -867,8 +881,14 @@ __global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ z,
 }
 hipError_t t2s_launch_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off,
                             int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream,
-                            int taps, int nwc, u16* W_hi, u16* W_lo, const int* lengths) {
+                            int taps, int nwc, u16* W_hi, u16* W_lo, const int* lengths, bool h16) {
     dim3 grid((L + 64 * START_TT - 1) / (64 * START_TT), (C + 31) / 32, B);
+    if (h16) {      // fp16 X planes; no window planes and no ragged form in that format
+        if (lengths || W_hi || W_lo) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((start_kernel<false, T2sFmtF16>), grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L, Lp,
+                           halo, X_hi, X_lo, 0, 0, (u16*)nullptr, (u16*)nullptr, (const int*)nullptr);
+        return hipGetLastError();
+    }
     if (lengths)
         hipLaunchKernelGGL(start_kernel<true>, grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L, Lp, halo,
                            X_hi, X_lo, taps, nwc, W_hi, W_lo, lengths);
@@ -1050,6 +1070,7 @@ static __device__ __forceinline__ void endfold_block(const EndFoldJob& j, int C,
     }
     __syncthreads();
 }
+template <class FMT = T2sFmt>
 __global__ __launch_bounds__(256) void endfold_weights_kernel(const EndFoldJob* __restrict__ jobs, int C) {
     extern __shared__ float s_ef[];              // [8][Cp]: W_end[j][o] * scale[o], zero for o >= C; then the partial sums [32][EF_PART]
     __shared__ float s_bes[4 * 8];               // bes per wave
@@ -1069,17 +1090,21 @@ __global__ __launch_bounds__(256) void endfold_weights_kernel(const EndFoldJob* 
         if (blockIdx.y * 32 + cl < C) {
             u16* base = j.fold_A + (size_t)blockIdx.y * 2 * 64 * 8;      // block = c >> 5 = (mt*2 + wr)*2 + pair
             u16 h, l;
-            split_bf16(sum, h, l);
+            split_fmt<FMT>(sum, h, l);
             const int lane = q * 16 + r;
             base[(size_t)lane * 8 + e] = h;
             base[(size_t)(64 + lane) * 8 + e] = l;
         }
     }
 }
-hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C, hipStream_t stream) {
+hipError_t t2s_launch_endfold_weights(const EndFoldJob* jobs, int n_jobs, int C, hipStream_t stream, bool h16) {
     const int Cp = (C + 32 * EF_OROWS - 1) & ~(32 * EF_OROWS - 1);
     const int lds_floats = 8 * Cp > 32 * EF_PART ? 8 * Cp : 32 * EF_PART;
-    hipLaunchKernelGGL(endfold_weights_kernel, dim3(n_jobs, (C + 31) / 32), dim3(256), (size_t)lds_floats * sizeof(float),
+    if (h16)
+        hipLaunchKernelGGL((endfold_weights_kernel<T2sFmtF16>), dim3(n_jobs, (C + 31) / 32), dim3(256),
+                           (size_t)lds_floats * sizeof(float), stream, jobs, C);
+    else
+    hipLaunchKernelGGL((endfold_weights_kernel<>), dim3(n_jobs, (C + 31) / 32), dim3(256), (size_t)lds_floats * sizeof(float),
                        stream, jobs, C);
     return hipGetLastError();
 }

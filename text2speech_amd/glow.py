@@ -182,6 +182,13 @@ def _f32c(t):
 
 _Path = namedtuple("_Path", "start_fold boundary compose")      # which kernels a no-grad call takes: _Engine.path()
 
+# What `infer_w16 = None` does on an eligible call, decided by measurement (tools/bench_vocoder_half.py against the parent commit's
+# library, profiles/infer_w16_ab.txt).  The rule: the fp16 chain is the default only if it beats the split-bf16 infer of a .half()
+# model - which has the folded WN.start and the one-launch flow boundaries the fp16 chain gives up - at 1000 AND 200 frames by
+# more than twice the parent's own two-run spread.  Measured at 512 channels, B = 1: 31.1 / 31.3 -> 26.2 / 27.2 ms at 1000 frames
+# (spread 0.14) and 11.8 / 12.0 -> 10.5 / 11.1 ms at 200 (spread 0.24): it does, at both.
+_INFER_W16_AUTO = True
+
 
 class _Engine:
     """Owns the HBM-resident state of one WaveGlow: packed (hi, lo) bf16 weight
@@ -193,6 +200,12 @@ class _Engine:
         self.packed_key = None
         self.ws = {}
         self.last_path = None       # the _Path of the latest forward / infer / WN.forward
+        # infer() of a .half() model on fp16 planes with one-plane weights (two MFMA products per MAC, the _h16 entry points):
+        # None = automatic (_INFER_W16_AUTO where the call is eligible, see w16_eligible), False = never, True = required
+        self.infer_w16 = None
+        self.last_infer_w16 = False     # whether the latest infer / infer_batch ran that chain
+        self.packed16 = None            # its operands, cached beside the split-bf16 ones under the same kind of key
+        self.packed16_key = None
         self._keep = []             # the current call's temporaries whose pointers went to a kernel
         self._streams = {}
         self.grad_sync = None       # distributed.GradSync: bucketed RCCL all-reduce issued from inside backward
@@ -262,20 +275,83 @@ class _Engine:
             return self.packed
         if self.packed is None or self.packed["device"] != device:
             self.packed = dict(flows=self._alloc_planes(device), device=device)
-        srcs = self._pack_jobs(res_pair8, start_fold)
-        fsrcs = self._fold_jobs()
-        starts = self._launch_pack(start_fold, flow_events)
+        srcs = self._pack_jobs(self.packed, res_pair8, start_fold)
+        fsrcs = self._fold_jobs(self.packed)
+        starts = self._launch_pack(self.packed, start_fold, flow_events)
         self.packed_key = key
         self.packed["res_pair8"] = res_pair8
         self.packed["start_fold"] = start_fold
         self.packed["keep"] = srcs + fsrcs + starts         # what the job tables point at, for as long as the pack is cached
         return self.packed
 
-    def _alloc_planes(self, device):
-        """The per-flow plane set of pack_weights(), zeroed."""
+    def w16_eligible(self, batch=False):
+        """(ok, why not) for the fp16 chain: infer only (not infer_batch), every WN parameter fp16, n_channels % 16 == 0 and the
+        shipped library (the fp16-operand diagnostic build computes everything in fp16 planes already)."""
+        if batch:
+            return False, "infer_batch stays on split-bf16 planes"
+        if any(p.dtype != torch.float16 for wn in self.m.WN for p in wn.parameters()):
+            return False, "not every WN parameter is torch.float16 (a .half() model)"
+        if self.geom()["C"] % 16:
+            return False, "n_channels %% 16 != 0 (%d)" % self.geom()["C"]
+        if _lib.operand_format() != 0:
+            return False, "the loaded library is the fp16-operand diagnostic build"
+        return True, ""
+
+    def use_w16(self, batch=False):
+        """Whether this infer / infer_batch call takes the fp16 chain; raises where infer_w16 = True cannot be honoured."""
+        if self.infer_w16 is False:
+            return False
+        ok, why = self.w16_eligible(batch)
+        if self.infer_w16 is True and not ok:
+            raise _lib.T2SError("infer_w16 = True: %s" % why)
+        return ok and (self.infer_w16 is True or _INFER_W16_AUTO)
+
+    def pack_weights_w16(self, device):
+        """The operands of the fp16 chain, packed once per parameter version: per layer the in / cond and the residual effective
+        weights as ONE fp16 plane each (computed in f32 from the fp16 parameters, then rounded to nearest even - no lo plane), the
+        folded WN.end as fp16 hi / lo fragments, biases and WN.start in f32.  Never the folded WN.start."""
+        res_pair8 = self.geom()["C"] % 32 == 0
+        key = tuple(p._version for p in self.m.parameters()) + (str(device), res_pair8)
+        if self.packed16 is not None and self.packed16_key == key:
+            return self.packed16
+        if self.packed16 is None or self.packed16["device"] != device:
+            self.packed16 = dict(flows=self._alloc_planes(device, w16=True), device=device)
+        pk = self.packed16
+        srcs = self._pack_jobs(pk, res_pair8, False)
+        fsrcs = self._fold_jobs(pk)
+        starts = self._launch_pack(pk, False, None, h16=True)
+        self.packed16_key = key
+        pk["res_pair8"] = res_pair8
+        pk["start_fold"] = False
+        pk["keep"] = srcs + fsrcs + starts
+        return pk
+
+    def _alloc_planes(self, device, w16=False):
+        """The per-flow plane set of pack_weights(), zeroed.  w16 (pack_weights_w16): fp16 containers, no lo planes of the
+        convolution weights and no folded-WN.start operand."""
         m, g = self.m, self.geom()
         C, nl = g["C"], g["nl"]
         flows = []
+        if w16:
+            f16 = dict(dtype=torch.float16, device=device)
+            for k in range(m.n_flows):
+                n_half = m.WN[k].start.in_channels
+                layers = []
+                for i in range(nl):
+                    rows2 = 2 * C if i < nl - 1 else C
+                    Mpad2 = _lib.padded_rows(rows2)
+                    layers.append(dict(
+                        A1h=torch.zeros(g["nk1"], g["Mpad1"], 32, **f16), A1l=None,
+                        b1=torch.zeros(g["Mpad1"], dtype=torch.float32, device=device),
+                        A2h=torch.zeros(g["nk2"], Mpad2, 32, **f16), A2l=None,
+                        b2=torch.zeros(Mpad2, dtype=torch.float32, device=device), Mpad2=Mpad2,
+                        s_in=torch.empty(2 * C, dtype=torch.float32, device=device),
+                        s_cond=torch.empty(2 * C, dtype=torch.float32, device=device),
+                        s_rs=torch.empty(rows2, dtype=torch.float32, device=device),
+                        fold_A=torch.zeros(-(-C // 128) * 8192, **f16)))
+                flows.append(dict(layers=layers, n_half=n_half, bes=torch.zeros(nl, 8, dtype=torch.float32, device=device),
+                                  w_start=torch.empty(C, n_half, dtype=torch.float32, device=device), A0h=None, A0l=None, w_inv=None))
+            return flows
         for k in range(m.n_flows):
             n_half = m.WN[k].start.in_channels
             layers = []
@@ -300,7 +376,7 @@ class _Engine:
                               w_inv=None))
         return flows
 
-    def _pack_jobs(self, res_pair8, start_fold):
+    def _pack_jobs(self, pk, res_pair8, start_fold):
         """The job table of t2s_pack_conv_weight_table: all 3 * n_layers * n_flows convolutions (weight-norm + split + permute),
         rebuilt only when a source tensor moved (job_key).  Returns the f32 sources in job order."""
         m, g = self.m, self.geom()
@@ -308,7 +384,7 @@ class _Engine:
         srcs = []
         specs = []      # one list of jobs per flow
         for k, wn in enumerate(m.WN):
-            fl = self.packed["flows"][k]
+            fl = pk["flows"][k]
             specs.append([])
             for i in range(nl):
                 ly = fl["layers"][i]
@@ -335,7 +411,7 @@ class _Engine:
                 specs[k].append((t[6], t[7], t[8], None, ly["A2h"], ly["A2l"], ly["b2"], t[6].size(0), C, 1, 2 if p8 else 0,
                                  C if p8 else 0, ly["Mpad2"], 0, g["Cpad"], ly["s_rs"]))
         ptr_key = tuple(0 if t is None else t.data_ptr() for t in srcs) + (res_pair8, start_fold)
-        if self.packed.get("job_key") != ptr_key:
+        if pk.get("job_key") != ptr_key:
             rows, flow_rows, flow_jobs = [], [], []
             dp = lambda t: 0 if t is None else t.data_ptr()
             for fspecs in specs:                        # every flow's jobs are a table of their own: row_start restarts per flow
@@ -346,20 +422,20 @@ class _Engine:
                                  O, Cin, Kt, perm, Cg, Mpad, koff, Cin_pad, 0, 0, dp(so)])
                     row_start += -(-O // 16)          # the table kernel packs 16 rows per workgroup
                 flow_rows.append(row_start)
-            self.packed["jobs"] = torch.tensor(rows, dtype=torch.int64).to(self.packed["device"])
-            self.packed["flow_rows"] = flow_rows
-            self.packed["flow_jobs"] = flow_jobs        # (first job, job count) per flow
-            self.packed["job_key"] = ptr_key
+            pk["jobs"] = torch.tensor(rows, dtype=torch.int64).to(pk["device"])
+            pk["flow_rows"] = flow_rows
+            pk["flow_jobs"] = flow_jobs        # (first job, job count) per flow
+            pk["job_key"] = ptr_key
         return srcs
 
-    def _fold_jobs(self):
+    def _fold_jobs(self, pk):
         """The job table of t2s_wg_endfold_weights - WN.end folded into the skip path: (W_end . W_skip_i)^T per layer, from the
         scales the pack writes - rebuilt only when a source tensor moved (fold_key).  Returns the f32 sources."""
         m, g = self.m, self.geom()
         C, nl = g["C"], g["nl"]
         fsrc = []
         for k, wn in enumerate(m.WN):
-            fl = self.packed["flows"][k]
+            fl = pk["flows"][k]
             w_end = _f32c(wn.end.weight)
             for i in range(nl):
                 vr = _f32c(_vg(wn.res_skip_layers[i])[0])
@@ -367,31 +443,33 @@ class _Engine:
                 r0 = C if i < nl - 1 else 0
                 fsrc.append((w_end, vr, br, r0, fl["layers"][i], fl["bes"], i, 2 * fl["n_half"]))
         fkey = tuple((a.data_ptr(), b.data_ptr(), c.data_ptr()) for a, b, c, *_ in fsrc)
-        if self.packed.get("fold_key") != fkey:
+        if pk.get("fold_key") != fkey:
             rows = []
             for (w_end, vr, br, r0, ly, bes, i, nj) in fsrc:
                 rows.append([w_end.data_ptr(), vr.data_ptr() + 4 * r0 * C, ly["s_rs"].data_ptr() + 4 * r0,
                              br.data_ptr() + 4 * r0, ly["fold_A"].data_ptr(), bes.data_ptr() + 4 * 8 * i, nj, C])
-            self.packed["fold_jobs"] = torch.tensor(rows, dtype=torch.int64).to(self.packed["device"])
-            self.packed["fold_key"] = fkey
+            pk["fold_jobs"] = torch.tensor(rows, dtype=torch.int64).to(pk["device"])
+            pk["fold_key"] = fkey
         return [t for tup in fsrc for t in tup[:3]]
 
-    def _launch_pack(self, start_fold, flow_events):
+    def _launch_pack(self, pk, start_fold, flow_events, h16=False):
         """One table-driven launch per flow packs its 3 * n_layers convolutions (weight-norm + split + permute), one more
         builds its folded WN.end matrices, a third its `start` weights - and with start_fold a fourth composes those with
-        in_layers[0] into the first nwc K-chunks of the layer-0 operand.  With `flow_events` (the no-grad forward) the per-flow
+        in_layers[0] into the first nwc K-chunks of the layer-0 operand.  h16: the first two are their _h16 partners (pk is the
+        fp16 chain's plane set).  With `flow_events` (the no-grad forward) the per-flow
         work is enqueued on the caller's current stream - a side stream there - and an event per flow lets the main stream
         start flow k as soon as ITS weights are packed: the pack is HBM-bound (2.1 GB per forward), the GEMMs are not."""
         m, g = self.m, self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
         st = _lib.current_stream()
-        jobs_ptr, fold_ptr = self.packed["jobs"].data_ptr(), self.packed["fold_jobs"].data_ptr()
+        jobs_ptr, fold_ptr = pk["jobs"].data_ptr(), pk["fold_jobs"].data_ptr()
         starts = []
         for k, wn in enumerate(m.WN):
-            fl = self.packed["flows"][k]
-            j0, nj = self.packed["flow_jobs"][k]
-            _lib.call("t2s_pack_conv_weight_table", _lib.c_vp(jobs_ptr + j0 * 19 * 8), nj, self.packed["flow_rows"][k], st)
-            _lib.call("t2s_wg_endfold_weights", _lib.c_vp(fold_ptr + k * nl * 8 * 8), nl, C, st)
+            fl = pk["flows"][k]
+            j0, nj = pk["flow_jobs"][k]
+            sfx = "_h16" if h16 else ""
+            _lib.call("t2s_pack_conv_weight_table" + sfx, _lib.c_vp(jobs_ptr + j0 * 19 * 8), nj, pk["flow_rows"][k], st)
+            _lib.call("t2s_wg_endfold_weights" + sfx, _lib.c_vp(fold_ptr + k * nl * 8 * 8), nl, C, st)
             v, gg = _vg(wn.start)
             v, gg = _f32c(v), (None if gg is None else _f32c(gg))
             starts += [v, gg]
@@ -485,12 +563,12 @@ class _Engine:
                 raise _lib.T2SError("WaveGlow (MI355X build) needs CUDA/HIP tensors; got a %s tensor - there is no "
                                     "CPU fallback" % t.device)
 
-    def _upsample(self, mel, B, L, w):
+    def _upsample(self, mel, B, L, w, h16=False):
         m, g = self.m, self.geom()
         up = m.upsample
         mel32 = _f32c(mel)
         W, bias = _f32c(up.weight), _f32c(up.bias)
-        _lib.call("t2s_wg_upsample_squeeze", _lib.ptr(mel32), _lib.ptr(W), _lib.ptr(bias), B, up.in_channels,
+        _lib.call("t2s_wg_upsample_squeeze_h16" if h16 else "t2s_wg_upsample_squeeze", _lib.ptr(mel32), _lib.ptr(W), _lib.ptr(bias), B, up.in_channels,
                   mel32.size(2), up.kernel_size[0], up.stride[0], m.n_group, L, w["Lp"], g["halo"],
                   _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), _lib.current_stream())
         self._keep += [mel32, W, bias]
@@ -599,6 +677,29 @@ class _Engine:
                           _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
                           g["halo"], ly["Mpad2"], pair8, st)
 
+    def _wn_w16(self, pk, k, z, B, L, w, c_off, n_half):
+        """_wn on the fp16 chain: t2s_wg_start_h16, then per layer the folded gate GEMM and the residual GEMM with one-plane fp16
+        weights (no lo pointer).  The workspace planes are 16-bit containers shared with the split-bf16 path: every row a launch
+        reads was written by this chain, and what neither format writes (halo, rows past L) is zero in both."""
+        m, g = self.m, self.geom()
+        C, nl, ks = g["C"], g["nl"], g["ks"]
+        fl = pk["flows"][k]
+        st = _lib.current_stream()
+        b_start = _f32c(m.WN[k].start.bias)
+        self._keep.append(b_start)
+        _lib.call("t2s_wg_start_h16", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
+                  C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), st)
+        pair8 = 1 if pk["res_pair8"] else 0
+        for i in range(nl):
+            ly = fl["layers"][i]
+            _lib.call("t2s_wg_in_cond_gate_fold_h16", _lib.ptr(ly["A1h"]), None, _lib.ptr(ly["b1"]),
+                      _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
+                      _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
+                      1 if i == 0 else 0, B, C, g["n_cond"], ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], st)
+            if i < nl - 1:      # the last layer has no residual half, and its skip half lives in the fold
+                _lib.call("t2s_wg_res_only_h16", _lib.ptr(ly["A2h"]), None, _lib.ptr(ly["b2"]), _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]),
+                          _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"], ly["Mpad2"], pair8, st)
+
     def wn_forward(self, k, audio, spect):
         """WN[k].forward((audio, spect)) (reference glow.py:154-175) on the no-grad kernels: start, n_layers x (gate GEMM with
         WN.end folded in, residual GEMM), then WN.end's output (b ; log_s) without applying the coupling."""
@@ -626,11 +727,13 @@ class _Engine:
         self._keep += [spect32, z]
         return wn_out.to(audio.dtype)
 
-    def _end_fold(self, k, z, log_s, fold_acc, wn_out, B, L, c_off, n_half, reverse):
-        """WN.end from the sums the gate GEMMs folded it into, and flow k's coupling on z (wn_out: also WN.end's output)."""
+    def _end_fold(self, k, z, log_s, fold_acc, wn_out, B, L, c_off, n_half, reverse, pk=None):
+        """WN.end from the sums the gate GEMMs folded it into, and flow k's coupling on z (wn_out: also WN.end's output).
+        pk: the plane set the sums were built from (default: the split-bf16 one)."""
         b_end = _f32c(self.m.WN[k].end.bias)
         self._keep.append(b_end)
-        _lib.call("t2s_wg_end_fold_affine", _lib.ptr(fold_acc), fold_acc.size(0), _lib.ptr(self.packed["flows"][k]["bes"]),
+        pk = self.packed if pk is None else pk
+        _lib.call("t2s_wg_end_fold_affine", _lib.ptr(fold_acc), fold_acc.size(0), _lib.ptr(pk["flows"][k]["bes"]),
                   self.geom()["nl"], _lib.ptr(b_end), _lib.ptr(z), _lib.ptr(log_s), _lib.ptr(wn_out), B, self.m.n_group, c_off,
                   n_half, L, 1 if reverse else 0, _lib.current_stream())
 
@@ -757,9 +860,14 @@ class _Engine:
         # reference glow.py:254-255: drop the last (kernel - stride) upsampled samples
         T = (frames - 1) * up.stride[0] + up.kernel_size[0] - (up.kernel_size[0] - up.stride[0])
         L = T // G
-        path = self.last_path = self.path(compose=lens is None)      # infer_batch: never the composed conditioning
+        w16 = self.last_infer_w16 = self.use_w16(batch=lens is not None)     # (raises before anything is launched)
+        if w16:
+            # the fp16 chain is the plain one: start -> gate GEMM with WN.end folded in -> residual GEMM -> coupling -> 1x1 conv
+            path = self.last_path = _Path(False, False, None)
+        else:
+            path = self.last_path = self.path(compose=lens is None)      # infer_batch: never the composed conditioning
         self._keep = []
-        self.pack_weights(dev, force=False, res_pair8=True, start_fold=path.start_fold)
+        pk = self.pack_weights_w16(dev) if w16 else self.pack_weights(dev, force=False, res_pair8=True, start_fold=path.start_fold)
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         # Weights are packed once here, so the conditioning path can be composed with the upsampler (K = 640 -> 320 in the gate
@@ -782,7 +890,7 @@ class _Engine:
             self._keep.append(mel32)
             ph = (mw[0], mw[1], Fp, P, K2)
         else:
-            self._upsample(mel, B, L, w)
+            self._upsample(mel, B, L, w, h16=w16)
         # All Gaussian draws of glow.py:260-267,284-289 live in one [B, G, L] buffer: the final
         # n_remaining channels, and in front of them the n_early_size channels re-attached at each early flow.
         z = torch.empty(B, G, L, dtype=torch.float32, device=dev)
@@ -799,7 +907,7 @@ class _Engine:
             z[:, c_off - m.n_early_size:c_off] = sigma * ne.to(dev, torch.float32)
         for k in reversed(range(m.n_flows)):
             c_off, n_rem, n_half = self._flow_geom(k)
-            fl = self.packed["flows"][k]
+            fl = pk["flows"][k]
             if fl["w_inv"] is None:
                 Wk = _f32c(m.convinv[k].conv.weight)
                 fl["w_inv"] = torch.empty(n_rem, n_rem, dtype=torch.float32, device=dev)
@@ -807,8 +915,11 @@ class _Engine:
                 fl["_Wk"] = Wk
             if path.boundary:
                 self._boundary(k, z, None, B, L, w, lens=lens)         # the window planes only
-            self._wn(k, z, B, L, w, c_off, n_half, path, ph=ph, lens=lens)
-            self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True)
+            if w16:
+                self._wn_w16(pk, k, z, B, L, w, c_off, n_half)
+            else:
+                self._wn(k, z, B, L, w, c_off, n_half, path, ph=ph, lens=lens)
+            self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True, pk=pk)
             _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(fl["w_inv"]), B, G, c_off, n_rem, L, st)
         audio = torch.empty(B, L * G, dtype=torch.float32, device=dev)
         _lib.call("t2s_wg_audio_squeeze", _lib.ptr(audio), _lib.ptr(z), B, L * G, G, L, 1, st)
@@ -880,14 +991,16 @@ class WaveGlow(torch.nn.Module):
         return out
 
     @staticmethod
-    def _refuse_overflow(t):
-        """fp16-operand build only: a plane element beyond fp16's range (65504) became inf inside the flow and shows as a non-finite
-        output - an error, not a result (the shipped bf16 planes have f32's exponent range and need no such check)."""
+    def _refuse_overflow(t, w16=False):
+        """fp16 planes only (the fp16-operand build, or infer's fp16 chain for .half() models: w16): a plane element beyond fp16's
+        range (65504) became inf inside the flow and shows as a non-finite output - an error, not a result (split-bf16 planes have
+        f32's exponent range and need no such check)."""
         if os.environ.get("T2S_F16_GUARD", "1") == "0":     # timing runs only: the check is a device read-back per call
             return
         if not bool(torch.isfinite(t).all()):
-            raise _lib.T2SError("fp16 operand planes overflowed (|x| > 65504 somewhere in the flow): result refused; "
-                                "use the shipped split-bf16 library for this checkpoint / input")
+            way_out = ("set model._eng().infer_w16 = False (split-bf16 planes)" if w16
+                       else "use the shipped split-bf16 library") + " for this checkpoint / input"
+            raise _lib.T2SError("fp16 operand planes overflowed (|x| > 65504 somewhere in the flow): result refused; " + way_out)
 
     def infer(self, spect, sigma=1.0, noise=None):
         """mel [B, n_mel, frames] -> audio [B, 256*frames] (reference glow.py:251-292).
@@ -895,7 +1008,9 @@ class WaveGlow(torch.nn.Module):
         Gaussian draws explicit for parity tests; by default they are drawn on the device."""
         with torch.no_grad():
             out = self._eng().infer(spect, float(sigma), noise)
-        if _lib.operand_format() == 1:
+        if self._eng().last_infer_w16:
+            self._refuse_overflow(out, w16=True)
+        elif _lib.operand_format() == 1:
             self._refuse_overflow(out)
         return out.to(spect.dtype) if spect.dtype in (torch.float16, torch.bfloat16) else out
 
@@ -952,6 +1067,7 @@ class WaveGlow(torch.nn.Module):
             wn.res_skip_layers = remove(wn.res_skip_layers)
         if waveglow.__dict__.get("_engine") is not None:
             waveglow.__dict__["_engine"].packed_key = None
+            waveglow.__dict__["_engine"].packed16_key = None
         return waveglow
 
 

@@ -15,8 +15,18 @@ def split_bf16(x):
     return hi, lo
 
 
-def to_planes(x, halo, Lp=None):
-    """[B, C, L] f32 -> (hi, lo) planes [B, ceil(C/32), Lp, 32] bf16, data rows at [halo, halo+L)."""
+def split_f16(x):
+    """x (f32) -> (hi, lo) fp16 with hi = fp16(x), lo = fp16(x - hi): the operand format of the fp16 vocoder planes (the _h16 entry
+    points of include/t2s_hip.h).  |x| > 65504 overflows to inf."""
+    hi = x.to(torch.float16)
+    lo = (x - hi.to(torch.float32)).to(torch.float16)
+    return hi, lo
+
+
+def to_planes(x, halo, Lp=None, fmt="bf16"):
+    """[B, C, L] f32 -> (hi, lo) planes [B, ceil(C/32), Lp, 32] bf16 (fmt = "f16": fp16), data rows at [halo, halo+L)."""
+    if fmt not in ("bf16", "f16"):
+        raise ValueError("to_planes: fmt is 'bf16' or 'f16', not %r" % (fmt,))
     B, C, L = x.shape
     if Lp is None:
         Lp = _lib.plane_rows(L, halo)
@@ -24,8 +34,8 @@ def to_planes(x, halo, Lp=None):
     xp = torch.zeros(B, nc * 32, L, dtype=torch.float32, device=x.device)
     xp[:, :C] = x
     xp = xp.view(B, nc, 32, L).permute(0, 1, 3, 2)            # [B, nc, L, 32]
-    hi, lo = split_bf16(xp)
-    ph = torch.zeros(B, nc, Lp, 32, dtype=torch.bfloat16, device=x.device)
+    hi, lo = split_bf16(xp) if fmt == "bf16" else split_f16(xp)
+    ph = torch.zeros(B, nc, Lp, 32, dtype=hi.dtype, device=x.device)
     pl = torch.zeros_like(ph)
     ph[:, :, halo:halo + L] = hi
     pl[:, :, halo:halo + L] = lo
