@@ -141,3 +141,54 @@ def test_denoiser_and_griffin_lim_vs_reference_golden(golden_dir):
     assert _rel(sig, g["gl_signal"]) < 2e-2                 # the iteration amplifies rounding differences
     mg, _ = st.transform(sig)
     assert _rel(mg, st.transform(torch.from_numpy(g["gl_signal"]).to(DEV))[0]) < 5e-3
+
+
+def test_stft_class_defaults_reconstruct():
+    """STFT() as the class defaults it - (800, 200, 800), no power of two - reconstructs a clip away from the edges: element by element
+    against the float64 transform -> inverse of the same clip, which returns the clip itself there to 1e-6 of its peak."""
+    import tail_ref_util as R
+    from text2speech_amd.audio import STFT
+    _lib.load()
+    st = STFT().to(DEV)
+    assert (st.filter_length, st.hop_length, st.win_length) == (800, 200, 800)
+    gen = torch.Generator().manual_seed(800)
+    audio = torch.rand(2, 4000, generator=gen) - 0.5
+    fwd, inv_t, win_sq = R.stft_operands(800, 200, 800, "hann")
+    _, mag, ph = R.stft_transform_ref(audio, fwd, 800, 200)
+    want = R.stft_inverse_ref(mag, ph, inv_t, 800, 200, win_sq)
+    assert float((want[:, 800:-800] - audio[:, 800:-800].double()).abs().max()) < 1e-6
+    # the float32 floor of the whole chain (transform in f32, its f32 outputs through the inverse in f32), x 4 for another summation order
+    _, mag32, ph32 = R.stft_transform_ref(audio, fwd, 800, 200, dtype=torch.float32)
+    floor = float((R.stft_inverse_ref(mag32, ph32, inv_t, 800, 200, win_sq, dtype=torch.float32).double() - want).abs().max())
+    rec = st(audio.to(DEV))
+    assert tuple(rec.shape) == (2, 1, 4000)
+    err = float((rec[:, 0].cpu().double() - want).abs().max())
+    print("PARITY STFT() defaults, transform -> inverse: worst |err| %.3e  float32 floor %.3e  bound %.3e" % (err, floor, 4 * floor))
+    assert err <= 4 * floor
+    assert float((rec[:, 0, 800:-800].cpu() - audio[:, 800:-800]).abs().max()) <= 4 * floor + 1e-6
+
+
+def test_stft_without_window_vs_oracle():
+    """STFT(64, 16, 64, window=None): no window on either basis, no window-sum-square normalisation and no n_fft / hop scale in the
+    inverse.  Element by element against the oracle; the bound is 4 x the float32 floor for the device plus the oracle's own float32
+    error against float64."""
+    import tail_ref_util as R
+    from oracle import audio_oracle as A
+    from text2speech_amd.audio import STFT
+    _lib.load()
+    st = STFT(64, 16, 64, window=None).to(DEV)
+    gen = torch.Generator().manual_seed(64)
+    audio = torch.rand(2, 256, generator=gen) - 0.5
+    fwd_o, inv_o = A.stft_basis(64, 16, 64, None)
+    mag_o, ph_o = A.stft_transform(audio, fwd_o, 64, 16)
+    fwd, inv_t, win_sq = R.stft_operands(64, 16, 64, None)
+    assert win_sq is None
+    (_, mag64, _), (_, e_mag, _) = R.f32_floor(R.stft_transform_ref, audio, fwd, 64, 16)
+    mag, ph = st.transform(audio.to(DEV))
+    assert tuple(mag.shape) == tuple(mag_o.shape) == (2, 33, 17)
+    assert float((mag.cpu() - mag_o).abs().max()) <= 4 * e_mag + float((mag_o.double() - mag64).abs().max())
+    rec_o = A.stft_inverse(mag_o, ph_o, inv_o, 64, 16, 64, None)
+    want, e_rec = R.f32_floor(R.stft_inverse_ref, mag_o, ph_o, inv_t, 64, 16, None)
+    rec = st.inverse(mag_o.to(DEV), ph_o.to(DEV))
+    assert tuple(rec.shape) == tuple(rec_o.shape) == (2, 1, 256)
+    assert float((rec.cpu() - rec_o).abs().max()) <= 4 * e_rec + float((rec_o[:, 0].double() - want).abs().max())

@@ -199,6 +199,7 @@ def test_adam_step_matches_torch(trained):
     ref = [p.detach().clone().cpu().requires_grad_(True) for p in m.parameters()]
     for r, p in zip(ref, m.parameters()):
         r.grad = p.grad.detach().cpu().clone()
+    before = [r.detach().clone().double() for r in ref]
     opt_ref = torch.optim.Adam(ref, lr=1e-4)
     opt = FusedAdam(m.parameters(), lr=1e-4)
     for _ in range(3):
@@ -207,6 +208,35 @@ def test_adam_step_matches_torch(trained):
     torch.cuda.synchronize()
     worst = max(_rel(p.detach(), r.detach()) for p, r in zip(m.parameters(), ref))
     assert worst < 1e-6, worst
+    # The step itself, p_after - p_before, element by element against torch's: relative to the parameter (above) a step of 3e-4 hides a
+    # relative error of 1e-3.  Both sides are f32 Adam on the same f32 gradients; H = 2^-24 is one rounding.  Two terms:
+    #  * rounding of the parameter.  p' = fl(p - u) on both sides, so the difference d of the two runs obeys
+    #    |d'| <= |d| + |u_a - u_b| + 2 H pmax (half a unit in the last place of p each, and that is at most H |p|): 6 H pmax after three steps,
+    #    pmax = |p_before| + the larger |step|.  This is not an estimate: it is reached only when all six roundings go the same way at the
+    #    bottom of a binade, it cannot be exceeded by any torch build or any choice of fused multiply-adds, and the worst element of a
+    #    model of millions sits close to it (0.98).  Where |p| >> lr this term is all there is, and the check sees no error of the update.
+    #  * the update u = lr / bc1 * m / (sqrt(v) / bc2 + eps), which counts where |p| <~ lr (biases and gains near zero).  Worst case by
+    #    roundings: lr / bc1 3 H; m and v after three steps of the same gradient 6 H each (1.5 per step, older ones decaying), the root
+    #    halves v's and adds one: 4 H; the quotient by bc2 2 H, eps, the product and the division 1 H each: 18 H per side, 36 H for the
+    #    two, every rounding taken at its worst and in the same direction; a fused multiply-add only removes roundings.  The second figure
+    #    printed below is the worst error over the update's 36 H alone, on the elements where that term is at least half the bound: the
+    #    margin that is left there.  (The float powf bias correction t2s_adam_table had put 3.4e-6 = 57 H on steps 2 and 3, 38 H of the
+    #    three; on those elements this check sees it, everywhere else only tests/test_loss_adam_kernels_gpu.py does.)
+    H = 2.0 ** -24
+    worst, worst_update, n_update = 0.0, 0.0, 0
+    for p, r, b in zip(m.parameters(), ref, before):
+        got, want = p.detach().cpu().double() - b, r.detach().double() - b
+        err = (got - want).abs()
+        t_round = 6 * H * (b.abs() + torch.maximum(got.abs(), want.abs()))
+        t_update = 36 * H * want.abs()
+        worst = max(worst, float((err / (t_round + t_update + 1e-300)).max()))
+        sel = t_update >= t_round
+        if bool(sel.any()):
+            n_update += int(sel.sum())
+            worst_update = max(worst_update, float((err[sel] / (t_update[sel] + 1e-300)).max()))
+        assert bool((err <= t_round + t_update).all()), "step differs from torch's by %.3f x its bound" % worst
+    print("PARITY FusedAdam three steps, p_after - p_before vs torch: worst err / bound %.3f; on the %d elements where the update's "
+          "36 H is at least half the bound, worst err / (36 H |step|) %.3f" % (worst, n_update, worst_update))
 
 
 def test_adam_state_interop_and_cache_invalidation():

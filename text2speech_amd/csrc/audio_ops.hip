@@ -83,9 +83,12 @@ __global__ void stft_overlap_add_kernel(const float* __restrict__ frames, const 
 }
 
 // x <- log(max(x, clip))   (dynamic_range_compression, utils/audio_processing.py:78-84 with C = 1)
+// The logarithm in double, rounded once - a precision choice, not a repair: the device's logf is 1.6 units in the last place
+// off at the clamp floor 1e-5 that every silent frame takes (-11.5129271 for -11.5129255; profiles/tail_kernel_tests.md);
+// this form gives the nearest f32, which a test can pin bit for bit, and a mel spectrogram is a few thousand elements.
 __global__ void log_clamp_kernel(float* x, size_t n, float clip) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] = logf(fmaxf(x[i], clip));
+    if (i < n) x[i] = (float)log((double)fmaxf(x[i], clip));
 }
 
 hipError_t t2s_launch_reflect_pad(const float* x, int B, int T, int pad, float* xp, long ldp, hipStream_t s) {
