@@ -63,9 +63,11 @@ def _pack_layer(C, n_cond, ks, w_in, g_in, b_in, w_c, g_c, b_c, w_rs, g_rs, b_rs
     (1, 256, 640, 777, 16, True),     # last layer: skip-only res_skip
 ])
 def test_wn_layer(lib, B, C, n_cond, L, dil, last):
-    """One WN layer through the UNFOLDED entry points t2s_wg_in_cond_gate and t2s_wg_res_skip (the training fallback; no no-grad
-    call reaches them) against stock conv1d on the CPU.  The folded entry points the product path launches are checked one by one
-    in tests/test_waveglow_fwd_kernels_gpu.py."""
+    """One WN layer through the UNFOLDED entry points t2s_wg_in_cond_gate and t2s_wg_res_skip against stock conv1d on the CPU.
+    Nothing in the package calls them: every no-grad call takes the folded entry points, and training calls the _train forms
+    (t2s_wg_in_cond_gate_fold_train / t2s_wg_res_only_train; the unfolded t2s_wg_in_cond_gate_train / t2s_wg_res_skip_train behind
+    fold_train = False).  The folded entry points the product path launches are checked one by one in
+    tests/test_waveglow_fwd_kernels_gpu.py."""
     from text2speech_amd import planes
     gen = torch.Generator().manual_seed(C + L)
     ks = 3

@@ -396,6 +396,45 @@ def test_ragged_channel_tiles_grads_vs_oracle():
     _assert_step_vs_oracle(_train_once(_short_cfg(C=160), 2, 2048, 42))
 
 
+@pytest.mark.parametrize("C", [40, 48])
+def test_channels_no_multiple_of_32_are_refused_before_any_launch(monkeypatch, C):
+    """n_channels % 32 != 0 at 2 x 2048: C = 40 would take the unfolded training forward (fold_train False), C = 48 the folded one
+    with the time-major weight gradients (cl_ok False).  Neither can run: the forward packs the transposed res/skip operand of a
+    flow's last layer with O_pad = C (t2s_pack_transposed wants O_pad % 32 == 0) and the backward's t2s_wg_bwd_gate_dgrad wants
+    C % 32 == 0.  The step raises a T2SError that names n_channels % 32 - before any entry point of the library is called (counted
+    at _lib.call, as tests/test_engine_paths_gpu.py counts), before the training workspace exists and without touching device memory."""
+    import collections
+    from text2speech_amd.glow import WaveGlow
+    _lib.load()
+    cfg = _short_cfg(C=C)
+    mel, audio = synth.waveglow_inputs(2, 2048, n_mel=cfg["n_mel_channels"], seed=47)
+    m = WaveGlow(**cfg)
+    m.load_state_dict(synth.waveglow_state(cfg))
+    m = m.to(DEV).train()
+    mel, audio = mel.to(DEV), audio.to(DEV)
+    eng = m._eng()
+    # the refusal the forward would run into (glow_autograd.forward_train: rows2 = C for a flow's last layer); the backward's is in
+    # tests/test_abi.py ("C % 32" of t2s_wg_bwd_gate_dgrad)
+    v, A = torch.zeros(C, C, device=DEV), torch.zeros(2, 256, 32, dtype=torch.bfloat16, device=DEV)
+    assert _lib.load().t2s_pack_transposed(_lib.ptr(v), None, C, C, 1, 0, C, 256, 0, _lib.ptr(A), _lib.ptr(A), 0, _lib.current_stream()) == -1
+    torch.cuda.synchronize()
+    seen = collections.Counter()
+    real_call = _lib.call
+
+    def counting_call(name, *args):
+        seen[name] += 1
+        return real_call(name, *args)
+    monkeypatch.setattr(_lib, "call", counting_call)
+    before = torch.cuda.memory_allocated()
+    with pytest.raises(_lib.T2SError) as e:
+        m((mel, audio))
+    assert str(e.value) == "WaveGlow's forward with gradients (training) needs n_channels %% 32 == 0, not %d" % C
+    assert not seen, "entry points were called before the refusal: %r" % dict(seen)
+    assert torch.cuda.memory_allocated() == before
+    assert not any(k[0] == "train" for k in eng.ws) and eng.packed is None
+    assert all(p.grad is None for p in m.parameters())
+
+
 def test_kernel_size_5_grads_vs_oracle():
     _assert_step_vs_oracle(_train_once(_short_cfg(ks=5), 2, 2048, 43))
 

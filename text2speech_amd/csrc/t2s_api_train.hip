@@ -180,6 +180,9 @@ int t2s_wgrad_gemm(const void* A_hi, const void* A_lo, const void* X_hi, const v
     ConvGemm g(A_hi, A_lo, zero_bias);
     wgrad_fill(g, X_hi, X_lo, out, B * ksplit, M, N, Mpad, Npad, n_tchunks, k0, k1, cdiv(k1 - k0, ksplit));
     g.a.ksplit = ksplit;
+    // unsplit from chunk 0: the kernel takes its plain path and walks a.nk K-steps from chunk 0, so a.nk is where [0, k1) ends (the
+    // A / X addressing goes by n_tchunks through a_bstride and xc, not by nk); every other form clips to kend in the kernel
+    if (ksplit == 1 && k0 == 0) g.a.nk = k1;
     T2S_CHECK_HIP(g.launch(EPI_BIAS_ACT, M, 256, stream));
     return T2S_OK;
 }

@@ -253,6 +253,14 @@ class _Engine:
                     and self.m.n_group // 2 <= 4)
         return _Path(start_fold, boundary, compose)
 
+    def train_check(self):
+        """What the training forward (glow_autograd.forward_train) asks of the model, checked before it allocates or launches
+        anything: the transposed res/skip operand of a flow's last layer has n_channels rows per tap block (t2s_pack_transposed:
+        O_pad % 32 == 0) and the gate GEMM of the backward works on whole 32-channel chunks (t2s_wg_bwd_gate_dgrad: C % 32 == 0)."""
+        g = self.geom()
+        if g["C"] % 32:
+            raise _lib.T2SError("WaveGlow's forward with gradients (training) needs n_channels %% 32 == 0, not %d" % g["C"])
+
     def start_fold_on(self):
         return self.path().start_fold
 

@@ -202,6 +202,7 @@ def _cl_tables(ts, key, lay_sv, last, xc, sc, ks, d, dev, layer):
 def forward_train(eng, mel, audio):
     """WaveGlow.forward (glow.py:207-249) keeping what the backward needs."""
     m = eng.m
+    eng.train_check()
     eng._check_inputs(mel, audio)
     dev = audio.device
     B, T = audio.shape
