@@ -223,8 +223,8 @@ int t2s_wg_res_only_start(const void* A_hi, const void* A_lo, const float* bias,
  * two v_mfma_f32_16x16x32_f16 where the split-bf16 entry points spend three.  Biases, the fold sums, WN.start / WN.end, the 1x1
  * convolutions and the coupling stay f32.  Every entry point takes its partner's argument list and checks; the A-operand lo
  * pointer is never read and may be NULL.  An fp16 plane overflows at |x| > 65504 (the caller checks its result for non-finite
- * values).  The plain chain only: no window planes (folded WN.start), no flow-boundary launch, no composed conditioning, no ragged
- * batch - their composed weights are not exact in fp16 and have no one-plane form.
+ * values).  The plain chain only: no window planes (folded WN.start), no flow-boundary launch, no composed conditioning - their
+ * composed weights are not exact in fp16 and have no one-plane form.  (A ragged batch: the _h16_ragged entry points further down.)
  *  t2s_pack_conv_weight_table_h16: the same job table; A_hi receives fp16 (round to nearest even) of the f32 effective weight in the
  *    same permuted layout, A_lo is not touched, bias_out / scale_out as before.
  *  t2s_wg_endfold_weights_h16: fold_A as fp16 hi / lo fragments (a composed matrix: it keeps both planes and three products); bes f32.
@@ -282,6 +282,26 @@ int t2s_wg_flow_boundary_ragged(const float* z_in, float* z_out, const float* fo
                                 const float* b_end, float* log_s, int c_off_prev, int n_half_prev, const float* W, int c_off,
                                 int n_rem, int n_half, int B, int n_group, int L, int Lp, int halo, int taps, int win_chunks,
                                 void* W_hi, void* W_lo, const int* lengths, void* stream);
+/* ---- The two above combined: the fp16 chain on a batch of different lengths (ABI v4, compatible addition) ----
+ * Each entry point takes its _h16 partner's arguments and checks with `lengths` ([B] int32, device, columns, clamped to [0, L];
+ * NULL: T2S_EINVAL) in front of `stream`.  The names end in `_ragged`: a name that ends in `_h16` promises its partner's exact argument list.
+ * Below, len = the clamped lengths[b] and a tile = 256 columns starting at a multiple of 256.
+ *  t2s_wg_start_h16_ragged: t2s_wg_start_h16 for rows t < len; rows len <= t < L are stored as zeros, hi and lo.  No window planes.
+ *  t2s_wg_res_only_h16_ragged: t2s_wg_res_only_h16 for rows t < len, zeros for len <= t < L.  A tile that starts at or behind len is
+ *    not computed: its zeros are stored and nothing is loaded.
+ *  t2s_wg_in_cond_gate_fold_h16_ragged: both tile heights.  A tile that starts below len is t2s_wg_in_cond_gate_fold_h16's, bit for
+ *    bit, the columns at and past len of a tile the end cuts included.  A tile that starts at or behind len is not computed: its
+ *    acts columns are NOT written (t2s_wg_res_only_h16_ragged, their reader, drops the same tiles), and its fold_acc elements are
+ *    stored as zeros when fold_init != 0 (t2s_wg_end_fold_affine reads every column) and left alone when fold_init == 0. */
+int t2s_wg_start_h16_ragged(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                            int L, int Lp, int halo, void* X_hi, void* X_lo, const int* lengths, void* stream);
+int t2s_wg_in_cond_gate_fold_h16_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
+                                        const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
+                                        float* fold_acc, int fold_init, int B, int C, int n_cond, int taps, int dilation, int L,
+                                        int Lp, int halo, int Mpad, const int* lengths, void* stream);
+int t2s_wg_res_only_h16_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                               void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8,
+                               const int* lengths, void* stream);
 /* WN.end output from the folded accumulators + affine coupling (forward or reverse) */
 int t2s_wg_end_fold_affine(const float* fold_acc, int nslots, const float* bes, int n_layers, const float* b_end,
                            float* z, float* log_s, float* wn_out, int B, int n_group, int c_off, int n_half, int L, int reverse,

@@ -138,6 +138,9 @@ SIGNATURES = {
 for _n in ("t2s_pack_conv_weight_table", "t2s_wg_endfold_weights", "t2s_wg_upsample_squeeze", "t2s_wg_start",
            "t2s_wg_in_cond_gate_fold", "t2s_wg_res_only"):
     SIGNATURES[_n + "_h16"] = list(SIGNATURES[_n])
+# ... and the fp16 chain of infer_batch: the _h16 partner's argument list with `const int* lengths` in front of `stream`
+for _n in ("t2s_wg_start", "t2s_wg_in_cond_gate_fold", "t2s_wg_res_only"):
+    SIGNATURES[_n + "_h16_ragged"] = SIGNATURES[_n + "_h16"][:-1] + [c_vp, c_vp]
 del _n
 _RESTYPE = {"t2s_error_string": ctypes.c_char_p, "t2s_last_hip_error": ctypes.c_char_p,
             "t2s_small_wgrad_scratch": ctypes.c_long, "t2s_taco_lstm_xbuf_bytes": ctypes.c_long}

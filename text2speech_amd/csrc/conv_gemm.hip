@@ -55,7 +55,10 @@ static __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 // RAG = the 128-row RESSKIP kernels for a batch of entries of different lengths (a.lengths): columns lengths[b] <= t < L of the
 // residual rows are stored as zeros, hi and lo - stored, not skipped: the planes may hold an earlier, longer call's rows - so that
 // the dilated taps of the next gate GEMM read past an entry's end what they read past L when it runs alone.  Columns t < lengths[b]
-// take the arithmetic of the RAG = false kernel in its order.
+// take the arithmetic of the RAG = false kernel in its order.  With A1 (the fp16 chain of infer_batch) RAG also exists for the
+// 128-row GATE kernel, and in both a workgroup whose whole column tile lies behind the entry's end (t0 >= lengths[b]) computes
+// nothing: the residual GEMM stores that tile's zeros, the gate GEMM zeroes its fold_acc elements under fold_init and leaves the acts
+// planes alone - their only reader skips the same tile (t2s_kernels.h, T2S_RAG_SKIP_COLS).  A tile the entry's end cuts is computed whole.
 // FMT = the operand format of the planes (t2s_common.h), A1 = the A operand is ONE plane (weights exact in the format; a.A_lo is never
 // read): two products per MAC, A.B_hi + A.B_lo, and half the A-side DMA instructions per stage, which DMA_PER_ISSUE counts.  The
 // LDS layout stays as it is (the A_lo part of a stage is not filled).
@@ -176,9 +179,34 @@ __global__ __launch_bounds__(512) void conv_gemm_kernel(const ConvGemmArgs a) {
     constexpr bool PREX = EPI == EPI_RESSKIP && MT == 128;
     constexpr bool PRER = PREX && !X0;               // the residual values come from the planes
     static_assert(!X0 || PREX, "X0 is a variant of the 128-row RESSKIP kernel");
-    static_assert(!RAG || PREX, "RAG is a variant of the 128-row RESSKIP kernels");
+    static_assert(!RAG || PREX || (EPI == EPI_GATE && MT == 128 && A1), "RAG: the 128-row RESSKIP kernels and the one-plane gate");
     int len_b = 0;                                   // RAG: this batch entry's columns
     if constexpr (RAG) len_b = min(max(a.lengths[b], 0), a.L);
+    if constexpr (RAG && A1) {
+        // A column tile that lies wholly behind the entry's end: no load, no matrix instruction.  b and t0 are workgroup-uniform, so
+        // the whole workgroup leaves here, in front of the first DMA issue and the first barrier.
+        static_assert(T2S_TILE_N == T2S_RAG_SKIP_COLS, "the gate and the residual GEMM must skip the same column tiles");
+        if (t0 >= len_b) {
+            if constexpr (EPI == EPI_GATE) {
+                t2s_rag_zero_fold(a, mt, b, t0, tid);         // and no acts: the residual GEMM skips this tile as well
+            } else {
+                // the residual rows of this tile's columns [t0, min(t0 + T2S_TILE_N, L)) as zeros, hi and lo: the element set the
+                // RAG epilogue writes (channels in whole groups of 4 below n_res, either row order)
+                const int n8 = min(T2S_TILE_N, a.L - t0) * 8;             // 8-byte pieces per 32-channel chunk
+                for (int c = 0; c < MT / 32; ++c) {
+                    const int ch0 = mt * MT + c * 32;
+                    if (ch0 >= a.n_res) break;
+                    const size_t base = (((size_t)b * a.oc + (ch0 >> 5)) * a.Lp + a.halo + t0) * 32;
+                    for (int idx = tid; idx < n8; idx += NTH) {
+                        if (ch0 + (idx & 7) * 4 >= a.n_res) continue;
+                        *(u16x4*)(a.O_hi + base + (size_t)idx * 4) = (u16x4){0, 0, 0, 0};
+                        *(u16x4*)(a.O_lo + base + (size_t)idx * 4) = (u16x4){0, 0, 0, 0};
+                    }
+                }
+            }
+            return;
+        }
+    }
     u16x4 pre_h[PRER ? MW : 1][PRER ? NWT : 1], pre_l[PRER ? MW : 1][PRER ? NWT : 1];
     typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
     // X0: what WN.start needs for this lane's NWT columns and 8 consecutive channels per m-tile pair - the audio values, 8 x n_half
@@ -779,8 +807,15 @@ static hipError_t launch_one(const ConvGemmArgs& a, hipStream_t stream) {
 hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows, bool h16) {
     if (h16) {
         // fp16 planes with a one-plane A operand (the _h16 entry points): the folded gate GEMM at either tile height and the
-        // residual-only GEMM, plain forms only
-        if (a.lengths || a.x0_z || a.ph_P > 0 || a.ksplit > 1 || a.k0 != 0 || a.kflat != 0 || a.a_bstride != 0) return hipErrorInvalidValue;
+        // residual-only GEMM, plain forms only - each also with a.lengths (the _h16_ragged entry points), never X0, phase or split-K
+        if (a.x0_z || a.ph_P > 0 || a.ksplit > 1 || a.k0 != 0 || a.kflat != 0 || a.a_bstride != 0) return hipErrorInvalidValue;
+        if (a.lengths) {
+            if (mt_rows == 128 && epi == EPI_RESSKIP) return launch_one<EPI_RESSKIP, 128, false, 2, false, true, T2sFmtF16, true>(a, stream);
+            if (mt_rows == 128 && epi == EPI_GATE) return launch_one<EPI_GATE, 128, false, 2, false, true, T2sFmtF16, true>(a, stream);
+            if (mt_rows == 256 && epi == EPI_GATE && a.nk == a.nk_x + a.sc && a.nk_x == a.taps * a.xc && (a.taps >> 1) * a.dil <= a.halo)
+                return t2s_launch_gate_gemm_pp(a, stream, true);
+            return hipErrorInvalidValue;
+        }
         if (mt_rows == 128 && epi == EPI_RESSKIP) return launch_one<EPI_RESSKIP, 128, false, 2, false, false, T2sFmtF16, true>(a, stream);
         if (mt_rows == 128 && epi == EPI_GATE) return launch_one<EPI_GATE, 128, false, 2, false, false, T2sFmtF16, true>(a, stream);
         if (mt_rows == 256 && epi == EPI_GATE && a.nk == a.nk_x + a.sc && a.nk_x == a.taps * a.xc && (a.taps >> 1) * a.dil <= a.halo)

@@ -100,9 +100,15 @@ __device__ unsigned long long t2s_pp_stamps[1024 * 8];
 // The prologue issues K-step 0 whole and then A half 0, B half 0 of K-step 1 (the order of phases 2 and 3) and leaves those two
 // stages in flight: 2 + 2 = 4 loads, or 1 + 2 = 3 with A1.  The last two K-steps have stages missing and drain with vmcnt(0) in
 // either form.  A count that is too high would let a phase read a half-tile before it has landed.
-template <bool PH, int EPI = EPI_GATE, class FMT = T2sFmt, bool A1 = false>
+// RAG (a.lengths, the gate of t2s_wg_in_cond_gate_fold_h16_ragged on 256-row tiles; A1 only): a workgroup whose column tile starts at
+// or behind its entry's end, t0 >= min(max(lengths[b], 0), L), returns right after b and t0 are known - both are workgroup-uniform,
+// so all eight waves leave together - having zeroed its fold_acc elements under fold_init (t2s_kernels.h, t2s_rag_zero_fold) and
+// written no acts.  The return sits in front of the first DMA issue, every s_barrier (the extra one of group 1 included) and every
+// counted wait, so the counts above (5, 5, 4, 4; prologue 3) are not touched; a tile the entry's end cuts runs the whole schedule.
+template <bool PH, int EPI = EPI_GATE, class FMT = T2sFmt, bool A1 = false, bool RAG = false>
 __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a) {
     typedef typename FMT::frag8 fragT;
+    static_assert(!RAG || (!PH && EPI == EPI_GATE && A1), "RAG is a variant of the plain one-plane gate kernel");
     constexpr int VM_P0 = A1 ? 5 : 6, VM_P1 = A1 ? 5 : 6, VM_P2 = A1 ? 4 : 6, VM_P3 = A1 ? 4 : 6, VM_PRO = A1 ? 3 : 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -131,6 +137,13 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
     } else {
         b = tt_all / a.n_ttiles;
         t0 = (tt_all % a.n_ttiles) * T2S_TILE_N;
+    }
+    if constexpr (RAG) {
+        static_assert(T2S_TILE_N == T2S_RAG_SKIP_COLS, "the gate and the residual GEMM must skip the same column tiles");
+        if (t0 >= min(max(a.lengths[b], 0), a.L)) {
+            t2s_rag_zero_fold(a, mt, b, t0, tid);
+            return;
+        }
     }
 
     // ---- DMA sources.  LDS slot p = tid (16 B each) of a half-plane: row = tid >> 2, k-chunk slot = tid & 3, which holds
@@ -722,14 +735,14 @@ __global__ __launch_bounds__(512) void gate_gemm_pp_kernel(const ConvGemmArgs a)
     PP_RSTAMP(5)
 }
 
-template <bool PH = false, int EPI = EPI_GATE, class FMT = T2sFmt, bool A1 = false>
+template <bool PH = false, int EPI = EPI_GATE, class FMT = T2sFmt, bool A1 = false, bool RAG = false>
 static hipError_t launch_pp(const ConvGemmArgs& a, hipStream_t stream) {
     const int nwg = PH ? a.n_mtiles * a.ph_P * a.ph_nft * ((a.B + a.ph_bper - 1) / a.ph_bper) : a.n_mtiles * a.n_ttiles * a.B;
     constexpr int lds = 2 * PP_BUF;
     static std::atomic<unsigned long long> attr_mask{0};
-    const hipError_t e = t2s_raise_lds_limit((const void*)gate_gemm_pp_kernel<PH, EPI, FMT, A1>, lds, attr_mask);
+    const hipError_t e = t2s_raise_lds_limit((const void*)gate_gemm_pp_kernel<PH, EPI, FMT, A1, RAG>, lds, attr_mask);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gate_gemm_pp_kernel<PH, EPI, FMT, A1>), dim3(nwg), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((gate_gemm_pp_kernel<PH, EPI, FMT, A1, RAG>), dim3(nwg), dim3(512), lds, stream, a);
     return hipGetLastError();
 }
 
@@ -752,8 +765,9 @@ extern "C" int t2s_debug_read_pp_stamps(unsigned long long* host_out, int n_word
 #endif
 
 hipError_t t2s_launch_gate_gemm_pp(const ConvGemmArgs& a, hipStream_t stream, bool h16) {
-    if (h16) {      // fp16 planes, one-plane A operand: the plain K order only
+    if (h16) {      // fp16 planes, one-plane A operand: the plain K order only; with a.lengths the form that skips padding tiles
         if (a.ph_P > 0) return hipErrorInvalidValue;
+        if (a.lengths) return launch_pp<false, EPI_GATE, T2sFmtF16, true, true>(a, stream);
         return launch_pp<false, EPI_GATE, T2sFmtF16, true>(a, stream);
     }
     if (a.ph_P > 0) return launch_pp<true>(a, stream);

@@ -43,13 +43,14 @@ static int upsample_squeeze(const float* mel, const float* W, const float* bias,
     return T2S_OK;
 }
 
+// `lengths` (h16 only): t2s_wg_start_h16_ragged
 static int wg_start(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C, int L, int Lp,
-                    int halo, void* X_hi, void* X_lo, void* stream, bool h16) {
+                    int halo, void* X_hi, void* X_lo, void* stream, bool h16, const int* lengths = nullptr) {
     if (!z || !w || !bias || !X_hi || !X_lo) return T2S_EINVAL;
     if (B <= 0 || L <= 0 || C <= 0 || n_half <= 0 || n_half > 8 || c_off < 0 || c_off + n_half > n_group) return T2S_EINVAL;
     if (!al16(X_hi) || !al16(X_lo) || Lp < t2s_plane_rows(L, halo)) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, (u16*)X_hi, (u16*)X_lo,
-                                   (hipStream_t)stream, 0, 0, nullptr, nullptr, nullptr, h16));
+                                   (hipStream_t)stream, 0, 0, nullptr, nullptr, lengths, h16));
     return T2S_OK;
 }
 
@@ -63,7 +64,7 @@ static int endfold_weights(const t2s_endfold_job* jobs, int n_jobs, int C, void*
 static int in_cond_gate_fold(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
                              const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A, float* fold_acc,
                              int fold_init, int B, int C, int n_cond, int taps, int dilation, int L, int Lp, int halo, int Mpad,
-                             void* stream, bool h16) {
+                             void* stream, bool h16, const int* lengths = nullptr) {
     if (!a_operand_ok(A_hi, A_lo, h16) || !planes_ok(X_hi, X_lo) || !planes_ok(acts_hi, acts_lo) || !bias || !al16(bias)) return T2S_EINVAL;
     if ((n_cond > 0 && !planes_ok(S_hi, S_lo)) || !fold_ok(fold_A, fold_acc, C)) return T2S_EINVAL;
     if (!gate_shape_ok(B, C, taps, dilation, L, Lp, halo, Mpad)) return T2S_EINVAL;
@@ -73,6 +74,7 @@ static int in_cond_gate_fold(const void* A_hi, const void* A_lo, const float* bi
     g.output(acts_hi, acts_lo, cdiv(C, 32));
     g.fold(fold_A, fold_acc, fold_init);
     g.a.C = C;
+    g.a.lengths = lengths;      // (h16 only: t2s_wg_in_cond_gate_fold_h16_ragged)
     T2S_CHECK_HIP(g.launch(EPI_GATE, 2 * C, gate_tile_rows(B, C, L), stream, false, h16));
     return T2S_OK;
 }
@@ -191,6 +193,11 @@ int t2s_wg_start_h16(const float* z, const float* w, const float* bias, int B, i
                      int L, int Lp, int halo, void* X_hi, void* X_lo, void* stream) {
     return wg_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, X_hi, X_lo, stream, true);
 }
+int t2s_wg_start_h16_ragged(const float* z, const float* w, const float* bias, int B, int n_group, int c_off, int n_half, int C,
+                            int L, int Lp, int halo, void* X_hi, void* X_lo, const int* lengths, void* stream) {
+    if (!lengths) return T2S_EINVAL;
+    return wg_start(z, w, bias, B, n_group, c_off, n_half, C, L, Lp, halo, X_hi, X_lo, stream, true, lengths);
+}
 
 // window chunks of the folded WN.start: 2 (two column sets per chunk) or 4 (one), each set taps * (n_half + 1) columns wide
 static bool win_chunks_ok(int taps, int n_half, int win_chunks) {
@@ -301,6 +308,14 @@ int t2s_wg_in_cond_gate_fold_h16(const void* A_hi, const void* A_lo, const float
     return in_cond_gate_fold(A_hi, A_lo, bias, X_hi, X_lo, S_hi, S_lo, acts_hi, acts_lo, fold_A, fold_acc, fold_init, B, C, n_cond, taps,
                              dilation, L, Lp, halo, Mpad, stream, true);
 }
+int t2s_wg_in_cond_gate_fold_h16_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* X_hi, const void* X_lo,
+                                        const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
+                                        float* fold_acc, int fold_init, int B, int C, int n_cond, int taps, int dilation, int L,
+                                        int Lp, int halo, int Mpad, const int* lengths, void* stream) {
+    if (!lengths) return T2S_EINVAL;
+    return in_cond_gate_fold(A_hi, A_lo, bias, X_hi, X_lo, S_hi, S_lo, acts_hi, acts_lo, fold_A, fold_acc, fold_init, B, C, n_cond, taps,
+                             dilation, L, Lp, halo, Mpad, stream, true, lengths);
+}
 
 int t2s_wg_in_win_gate_fold(const void* A_hi, const void* A_lo, const float* bias, const void* W_hi, const void* W_lo,
                             const void* S_hi, const void* S_lo, void* acts_hi, void* acts_lo, const void* fold_A,
@@ -377,7 +392,7 @@ int t2s_wg_in_melwin_gate_fold(const void* A_hi, const void* A_lo, const void* A
     return T2S_OK;
 }
 
-// t2s_wg_res_only and, with `lengths`, t2s_wg_res_only_ragged
+// t2s_wg_res_only and, with `lengths`, t2s_wg_res_only_ragged; with h16 their _h16 partners
 static int res_only(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
                     void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8, const int* lengths,
                     void* stream, bool h16 = false) {
@@ -408,6 +423,13 @@ int t2s_wg_res_only_ragged(const void* A_hi, const void* A_lo, const float* bias
                            void* stream) {
     if (!lengths) return T2S_EINVAL;
     return res_only(A_hi, A_lo, bias, acts_hi, acts_lo, X_hi, X_lo, B, C, L, Lp, halo, Mpad, pair8, lengths, stream);
+}
+
+int t2s_wg_res_only_h16_ragged(const void* A_hi, const void* A_lo, const float* bias, const void* acts_hi, const void* acts_lo,
+                               void* X_hi, void* X_lo, int B, int C, int L, int Lp, int halo, int Mpad, int pair8,
+                               const int* lengths, void* stream) {
+    if (!lengths) return T2S_EINVAL;
+    return res_only(A_hi, A_lo, bias, acts_hi, acts_lo, X_hi, X_lo, B, C, L, Lp, halo, Mpad, pair8, lengths, stream, true);
 }
 
 // t2s_wg_res_only_start and, with `lengths`, t2s_wg_res_only_start_ragged

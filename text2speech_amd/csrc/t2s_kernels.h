@@ -68,8 +68,29 @@ struct ConvGemmArgs {
     int x0_G, x0_coff, x0_nh;      // x0_nh <= 4
     // RESSKIP, 128-row tiles, the ragged variants (t2s_wg_res_only_ragged / _start_ragged): columns lengths[b] <= t < L of batch entry b
     // get zeros (hi and lo) in place of the residual update; null everywhere else.  Last, so that no other field moves.
+    // With fp16 planes and a one-plane A operand (the _h16_ragged entry points) the folded gate GEMM takes them too, at either tile
+    // height, and a workgroup whose column tile starts at or behind lengths[b] leaves without computing (t2s_rag_zero_fold below).
     const int* lengths;    // [B] int32, device
 };
+
+// The tile skip of the _h16_ragged GEMMs.  The gate GEMM (conv_gemm_kernel on 128-row tiles, gate_gemm_pp_kernel on 256-row ones) and
+// the residual GEMM that reads its acts planes drop the SAME column tiles - t0 >= min(max(lengths[b], 0), L) - so the acts columns
+// the gate leaves unwritten are columns nobody reads.  That holds only while all three cut the columns alike: each asserts
+// T2S_TILE_N == T2S_RAG_SKIP_COLS.
+#define T2S_RAG_SKIP_COLS 256
+#ifdef __HIPCC__
+// What a skipped gate workgroup (512 threads; tile row mt, batch entry b, first column t0) leaves behind: with fold_init the zeros
+// of exactly the fold_acc elements it would have stored - slots 2 mt and 2 mt + 1, 8 rows, the tile's columns below L -
+// because end_fold_affine reads every column and the padding of z has to stay finite; with fold_init == 0 (or no fold) nothing.
+static __device__ __forceinline__ void t2s_rag_zero_fold(const ConvGemmArgs& a, int mt, int b, int t0, int tid) {
+    if (!a.fold_A || !a.fold_init) return;
+    const int ncols = min(T2S_RAG_SKIP_COLS, a.L - t0);
+    for (int idx = tid; idx < 16 * T2S_RAG_SKIP_COLS; idx += 512) {
+        const int col = idx % T2S_RAG_SKIP_COLS, sj = idx / T2S_RAG_SKIP_COLS;      // sj = (slot - 2 mt) * 8 + row
+        if (col < ncols) a.fold_acc[(((size_t)(mt * 2 + (sj >> 3)) * a.B + b) * 8 + (sj & 7)) * a.L + t0 + col] = 0.f;
+    }
+}
+#endif
 
 // h16: the planes are fp16 and the A operand is ONE plane (a.A_lo is not read) - the _h16 entry points of include/t2s_hip.h
 hipError_t t2s_launch_conv_gemm(const ConvGemmArgs& a, int epi, hipStream_t stream, int mt_rows = 256, bool h16 = false);

@@ -883,10 +883,14 @@ hipError_t t2s_launch_start(const float* z, const float* w, const float* bias, i
                             int n_half, int C, int L, int Lp, int halo, u16* X_hi, u16* X_lo, hipStream_t stream,
                             int taps, int nwc, u16* W_hi, u16* W_lo, const int* lengths, bool h16) {
     dim3 grid((L + 64 * START_TT - 1) / (64 * START_TT), (C + 31) / 32, B);
-    if (h16) {      // fp16 X planes; no window planes and no ragged form in that format
-        if (lengths || W_hi || W_lo) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((start_kernel<false, T2sFmtF16>), grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L, Lp,
-                           halo, X_hi, X_lo, 0, 0, (u16*)nullptr, (u16*)nullptr, (const int*)nullptr);
+    if (h16) {      // fp16 X planes, plain or ragged (t2s_wg_start_h16_ragged); no window planes in that format
+        if (W_hi || W_lo) return hipErrorInvalidValue;
+        if (lengths)
+            hipLaunchKernelGGL((start_kernel<true, T2sFmtF16>), grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L,
+                               Lp, halo, X_hi, X_lo, 0, 0, (u16*)nullptr, (u16*)nullptr, lengths);
+        else
+            hipLaunchKernelGGL((start_kernel<false, T2sFmtF16>), grid, dim3(256), 0, stream, z, w, bias, n_group, c_off, n_half, C, L,
+                               Lp, halo, X_hi, X_lo, 0, 0, (u16*)nullptr, (u16*)nullptr, (const int*)nullptr);
         return hipGetLastError();
     }
     if (lengths)

@@ -204,7 +204,12 @@ class _Engine:
         # None = automatic (_INFER_W16_AUTO where the call is eligible, see w16_eligible), False = never, True = required
         self.infer_w16 = None
         self.last_infer_w16 = False     # whether the latest infer / infer_batch ran that chain
-        self.packed16 = None            # its operands, cached beside the split-bf16 ones under the same kind of key
+        # infer_batch() of a .half() model on the same chain through the _h16_ragged entry points, whose GEMMs skip the column tiles
+        # behind an entry's end.  Opt-in: False = never (infer_batch as infer_w16 leaves it), True = required (see
+        # w16_batch_eligible; infer_w16 then governs infer only); None is reserved for "automatic" and is treated as False.
+        self.infer_batch_w16 = False
+        self.last_infer_batch_w16 = False       # whether the latest infer_batch ran it (last_infer_w16 is True as well then)
+        self.packed16 = None           # its operands, cached beside the split-bf16 ones under the same kind of key
         self.packed16_key = None
         self._keep = []             # the current call's temporaries whose pointers went to a kernel
         self._streams = {}
@@ -313,6 +318,30 @@ class _Engine:
         if self.infer_w16 is True and not ok:
             raise _lib.T2SError("infer_w16 = True: %s" % why)
         return ok and (self.infer_w16 is True or _INFER_W16_AUTO)
+
+    _W16_BATCH_SYMBOLS = ("t2s_wg_start_h16_ragged", "t2s_wg_in_cond_gate_fold_h16_ragged", "t2s_wg_res_only_h16_ragged")
+
+    def w16_batch_eligible(self):
+        """(ok, why not) for infer_batch on the fp16 chain: what w16_eligible asks of infer - every WN parameter fp16,
+        n_channels % 16 == 0, the shipped library - and a library that exports the three _h16_ragged entry points."""
+        ok, why = self.w16_eligible(batch=False)
+        if not ok:
+            return False, why
+        lib = _lib.load()
+        missing = [n for n in self._W16_BATCH_SYMBOLS if not hasattr(lib, n)]
+        if missing:
+            return False, "the loaded library does not export %s" % ", ".join(missing)
+        return True, ""
+
+    def use_batch_w16(self):
+        """Whether this infer_batch call takes the fp16 chain (infer_batch_w16 is True; None and False: no); raises where True
+        cannot be honoured.  Called before anything is packed, allocated or launched."""
+        if self.infer_batch_w16 is not True:
+            return False
+        ok, why = self.w16_batch_eligible()
+        if not ok:
+            raise _lib.T2SError("infer_batch_w16 = True: %s" % why)
+        return True
 
     def pack_weights_w16(self, device):
         """The operands of the fp16 chain, packed once per parameter version: per layer the in / cond and the residual effective
@@ -685,28 +714,34 @@ class _Engine:
                           _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
                           g["halo"], ly["Mpad2"], pair8, st)
 
-    def _wn_w16(self, pk, k, z, B, L, w, c_off, n_half):
+    def _wn_w16(self, pk, k, z, B, L, w, c_off, n_half, lens=None):
         """_wn on the fp16 chain: t2s_wg_start_h16, then per layer the folded gate GEMM and the residual GEMM with one-plane fp16
         weights (no lo pointer).  The workspace planes are 16-bit containers shared with the split-bf16 path: every row a launch
-        reads was written by this chain, and what neither format writes (halo, rows past L) is zero in both."""
+        reads was written by this chain, and what neither format writes (halo, rows past L) is zero in both.
+        lens (int32 [B] on the device, columns; infer_batch only): the three _h16_ragged partners.  The writers of the X planes
+        store zeros from an entry's end on, and both GEMMs drop the column tiles that start at or behind it:
+        the acts columns of such a tile keep whatever an earlier call left there, and nothing reads them."""
         m, g = self.m, self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
         fl = pk["flows"][k]
         st = _lib.current_stream()
         b_start = _f32c(m.WN[k].start.bias)
         self._keep.append(b_start)
-        _lib.call("t2s_wg_start_h16", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
-                  C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), st)
+        rag = "" if lens is None else "_ragged"
+        tail = (st,) if lens is None else (_lib.ptr(lens), st)
+        _lib.call("t2s_wg_start_h16%s" % rag, _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
+                  C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), *tail)
         pair8 = 1 if pk["res_pair8"] else 0
         for i in range(nl):
             ly = fl["layers"][i]
-            _lib.call("t2s_wg_in_cond_gate_fold_h16", _lib.ptr(ly["A1h"]), None, _lib.ptr(ly["b1"]),
+            _lib.call("t2s_wg_in_cond_gate_fold_h16%s" % rag, _lib.ptr(ly["A1h"]), None, _lib.ptr(ly["b1"]),
                       _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
                       _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
-                      1 if i == 0 else 0, B, C, g["n_cond"], ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], st)
+                      1 if i == 0 else 0, B, C, g["n_cond"], ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], *tail)
             if i < nl - 1:      # the last layer has no residual half, and its skip half lives in the fold
-                _lib.call("t2s_wg_res_only_h16", _lib.ptr(ly["A2h"]), None, _lib.ptr(ly["b2"]), _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]),
-                          _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"], ly["Mpad2"], pair8, st)
+                _lib.call("t2s_wg_res_only_h16%s" % rag, _lib.ptr(ly["A2h"]), None, _lib.ptr(ly["b2"]), _lib.ptr(w["Ah"]),
+                          _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"], ly["Mpad2"], pair8,
+                          *tail)
 
     def wn_forward(self, k, audio, spect):
         """WN[k].forward((audio, spect)) (reference glow.py:154-175) on the no-grad kernels: start, n_layers x (gate GEMM with
@@ -846,7 +881,8 @@ class _Engine:
         """infer() on a padded batch whose entry b is lengths[b] frames long (host int64 [B], validated by the caller): the same
         launches with every writer of the X and window planes replaced by its _ragged partner, which shows each entry zeros past
         its own end as its solo run shows it past L, and one more that zeroes the audio tails.  Always the
-        plain conditioning path.  Returns (audio [B, stride * frames], audio lengths int64 [B] on the device)."""
+        plain conditioning path.  With infer_batch_w16 = True the launches are those of infer's fp16 chain, through the _h16_ragged
+        partners (_wn_w16).  Returns (audio [B, stride * frames], audio lengths int64 [B] on the device)."""
         m = self.m
         self._check_inputs(mel)
         stride = m.upsample.stride[0]
@@ -868,7 +904,10 @@ class _Engine:
         # reference glow.py:254-255: drop the last (kernel - stride) upsampled samples
         T = (frames - 1) * up.stride[0] + up.kernel_size[0] - (up.kernel_size[0] - up.stride[0])
         L = T // G
-        w16 = self.last_infer_w16 = self.use_w16(batch=lens is not None)     # (raises before anything is launched)
+        # (either raises before anything is launched.)  infer_batch_w16 = True puts infer_batch on the fp16 chain whatever infer_w16
+        # says, which governs infer only then; otherwise infer_batch goes through use_w16(batch=True) as it always did.
+        batch_w16 = self.last_infer_batch_w16 = lens is not None and self.use_batch_w16()
+        w16 = self.last_infer_w16 = batch_w16 or self.use_w16(batch=lens is not None)
         if w16:
             # the fp16 chain is the plain one: start -> gate GEMM with WN.end folded in -> residual GEMM -> coupling -> 1x1 conv
             path = self.last_path = _Path(False, False, None)
@@ -924,7 +963,7 @@ class _Engine:
             if path.boundary:
                 self._boundary(k, z, None, B, L, w, lens=lens)         # the window planes only
             if w16:
-                self._wn_w16(pk, k, z, B, L, w, c_off, n_half)
+                self._wn_w16(pk, k, z, B, L, w, c_off, n_half, lens=lens)
             else:
                 self._wn(k, z, B, L, w, c_off, n_half, path, ph=ph, lens=lens)
             self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True, pk=pk)
@@ -1000,13 +1039,14 @@ class WaveGlow(torch.nn.Module):
 
     @staticmethod
     def _refuse_overflow(t, w16=False):
-        """fp16 planes only (the fp16-operand build, or infer's fp16 chain for .half() models: w16): a plane element beyond fp16's
-        range (65504) became inf inside the flow and shows as a non-finite output - an error, not a result (split-bf16 planes have
-        f32's exponent range and need no such check)."""
+        """fp16 planes only (the fp16-operand build, or the fp16 chain for .half() models: w16 = True for infer, the switch's name
+        for infer_batch): a plane element beyond fp16's range (65504) became inf inside the flow and shows as a non-finite output -
+        an error, not a result (split-bf16 planes have f32's exponent range and need no such check)."""
         if os.environ.get("T2S_F16_GUARD", "1") == "0":     # timing runs only: the check is a device read-back per call
             return
         if not bool(torch.isfinite(t).all()):
-            way_out = ("set model._eng().infer_w16 = False (split-bf16 planes)" if w16
+            switch = w16 if isinstance(w16, str) else "infer_w16"
+            way_out = ("set model._eng().%s = False (split-bf16 planes)" % switch if w16
                        else "use the shipped split-bf16 library") + " for this checkpoint / input"
             raise _lib.T2SError("fp16 operand planes overflowed (|x| > 65504 somewhere in the flow): result refused; " + way_out)
 
@@ -1031,7 +1071,11 @@ class WaveGlow(torch.nn.Module):
         Returns (audio [B, stride * F], audio_lengths int64 [B] on the device): ``audio[b, :stride * lengths[b]]`` is what
         ``infer(spect[b:b+1, :, :lengths[b]], sigma, noise sliced to entry b's columns)`` returns, up to float rounding, and the
         rest of the row is 0.  What the padding of ``spect`` and of ``noise`` holds does not reach a valid sample.  Always the plain
-        conditioning path (``T2S_COND_COMPOSE`` is not read)."""
+        conditioning path (``T2S_COND_COMPOSE`` is not read).
+
+        A ``.half()`` model runs on split-bf16 planes here unless ``model._eng().infer_batch_w16 = True`` (opt-in): then the batch
+        takes ``infer``'s fp16 chain, its GEMMs skip the column tiles that lie wholly behind an entry's end, and a result that
+        overflowed fp16 is refused as ``infer`` refuses it, judged on the valid samples."""
         T2SError = _lib.T2SError
         if not spect.is_cuda:
             raise T2SError("WaveGlow (MI355X build) needs CUDA/HIP tensors; got a %s tensor - there is no CPU fallback" % spect.device)
@@ -1060,8 +1104,10 @@ class WaveGlow(torch.nn.Module):
                                % (B, self.n_remaining_channels, Lmax, len(early), B, self.n_early_size, Lmax))
         with torch.no_grad():
             out, out_lens = self._eng().infer_batch(spect, lens, float(sigma), noise)
-        if _lib.operand_format() == 1:
-            self._refuse_overflow(out)         # (the tails are zeros by now: the valid samples decide)
+        if self._eng().last_infer_batch_w16:   # (the tails are zeros by now: the valid samples decide, never what the padding held)
+            self._refuse_overflow(out, w16="infer_batch_w16")
+        elif _lib.operand_format() == 1:
+            self._refuse_overflow(out)
         return (out.to(spect.dtype) if spect.dtype in (torch.float16, torch.bfloat16) else out), out_lens
 
     @staticmethod

@@ -6,7 +6,8 @@
 
 Kernels are matched by demangled name.  A kernel that gained template parameters with defaults shows them in its mangled name, so
 the operand-format parameters (`T2sFmtBf16`, and the `false` behind it where the kernel also has the one-plane switch) are
-dropped from the "after" names before matching; what is left unmatched on the "after" side is listed as new.
+dropped from the "after" names before matching, as is the ping-pong gate kernel's `RAG` parameter where it is `false`; what is left
+unmatched on the "after" side is listed as new.
 """
 import re
 import subprocess
@@ -39,6 +40,8 @@ def demangle(names):
 
 def normalise(name):
     name = re.sub(r"^void ", "", name)
+    # gate_gemm_pp_kernel's fifth parameter (RAG, default false) came after the format parameters: drop it where it is false
+    name = re.sub(r"^(gate_gemm_pp_kernel<[^,<>]+, [^,<>]+, [^,<>]+, [^,<>]+), false>", r"\1>", name)
     for pat, rep in ((", T2sFmtBf16, false>", ">"), ("<T2sFmtBf16, false>", ""), (", T2sFmtBf16>", ">"), ("<T2sFmtBf16>", "")):
         name = name.replace(pat, rep)
     return name
