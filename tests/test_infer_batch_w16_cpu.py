@@ -122,3 +122,34 @@ def test_h16_ragged_signatures():
         assert sig == psig[:-1] + [_lib.c_vp, _lib.c_vp] and psig[-1] is _lib.c_vp, n
         assert list(getattr(lib, n).argtypes) == sig
     assert lib.t2s_abi_version() == 4
+
+
+def test_engine_entry_point_table():
+    """The engine's stage table (glow._ENTRY_POINTS: split-bf16, its infer_batch form, the fp16 chain, its infer_batch form): every
+    name it can resolve is in the ctypes table; an infer_batch column differs from the column before it only by an entry point
+    listed in glow._TAKES_LENGTHS; each of those has its partner's argument list with exactly one more pointer in front of
+    `stream`; and a plan hands `lengths` to exactly those.  A typo in the table fails here, without a GPU."""
+    table, takes = glow._ENTRY_POINTS, glow._TAKES_LENGTHS
+    names = {n for row in table.values() for n in row if n is not None}
+    assert names | set(takes.values()) | set(glow._START_TAKES_WINDOW) <= set(_lib.SIGNATURES)
+    assert set(takes) <= names and set(RAGGED_H16) <= set(takes)
+    for stage, row in table.items():
+        assert len(row) == 4 and row[0] is not None, stage
+        for plain, batch in ((row[0], row[1]), (row[2], row[3])):
+            assert plain not in takes and (batch is None or batch == plain or batch in takes), stage
+    for n, partner in takes.items():
+        sig, psig = _lib.SIGNATURES[n], _lib.SIGNATURES[partner]
+        assert psig[-1] is _lib.c_vp and sig == psig[:-1] + [_lib.c_vp, _lib.c_vp], n
+    _lib.load()
+    eng = _model()._eng()
+    lens = torch.tensor([4, 2], dtype=torch.int32)
+    for h16 in (False, True):
+        for col, ln in ((2 * h16, None), (2 * h16 + 1, lens)):
+            plan = eng._plan(h16, ln)
+            assert plan.h16 is h16 and plan.lens is ln and plan.pk is None and plan.melwin is None
+            assert plan.path == ((False, False, None) if h16 else eng.path(compose=ln is None)) == eng.last_path
+            for stage, row in table.items():
+                name, lengths = plan.entry[stage]
+                assert name == row[col], (stage, h16)
+                assert [a.value for a in lengths] == ([lens.data_ptr()] if name in takes else []), (stage, h16)
+    assert eng.packed is None and eng.packed16 is None

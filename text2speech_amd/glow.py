@@ -182,6 +182,51 @@ def _f32c(t):
 
 _Path = namedtuple("_Path", "start_fold boundary compose")      # which kernels a no-grad call takes: _Engine.path()
 
+# Everything a no-grad call decides, once: the path; h16 - the operand format, False: split-bf16 (hi, lo)
+# planes, True: the fp16 chain of a .half() model (fp16 planes, one-plane weights); lens - None, or infer_batch's int32 [B] columns
+# per entry on the device; entry - stage -> (entry point, its arguments between the stage's own and `stream`), resolved from the
+# table below; pk - the plane set (_Engine.packed or .packed16) once it is packed; melwin - (M_hi, M_lo, Fp, P, K2), the mel-window
+# planes of the composed conditioning, where the call takes it.
+_Plan = namedtuple("_Plan", "path h16 lens entry pk melwin")
+
+# The entry point of every stage that has more than one: a row per stage, a column per variant -
+#   split-bf16 planes | infer_batch on them | the fp16 chain | infer_batch on the fp16 chain
+# None: the library has no such form.  There is no fp16 form of the folded WN.start, the flow boundary, the composed conditioning
+# or the x0-rebuilding residual GEMM, so the fp16 chain is the plain path; infer_batch never takes the composed conditioning; and
+# the split-bf16 gate GEMMs have no _ragged partner (only the writers of the planes they read do): infer_batch launches the plain
+# ones, whereas the fp16 gate GEMM has one, which skips the column tiles behind an entry's end.
+_ENTRY_POINTS = {
+    "pack":         ("t2s_pack_conv_weight_table", "t2s_pack_conv_weight_table",
+                     "t2s_pack_conv_weight_table_h16", "t2s_pack_conv_weight_table_h16"),
+    "endfold":      ("t2s_wg_endfold_weights", "t2s_wg_endfold_weights", "t2s_wg_endfold_weights_h16", "t2s_wg_endfold_weights_h16"),
+    "upsample":     ("t2s_wg_upsample_squeeze", "t2s_wg_upsample_squeeze", "t2s_wg_upsample_squeeze_h16", "t2s_wg_upsample_squeeze_h16"),
+    "boundary":     ("t2s_wg_flow_boundary", "t2s_wg_flow_boundary_ragged", None, None),
+    "start":        ("t2s_wg_start", "t2s_wg_start_ragged", "t2s_wg_start_h16", "t2s_wg_start_h16_ragged"),
+    "start_window": ("t2s_wg_start_window", "t2s_wg_start_ragged", None, None),
+    "gate":         ("t2s_wg_in_cond_gate_fold", "t2s_wg_in_cond_gate_fold",
+                     "t2s_wg_in_cond_gate_fold_h16", "t2s_wg_in_cond_gate_fold_h16_ragged"),
+    "gate_window":  ("t2s_wg_in_win_gate_fold", "t2s_wg_in_win_gate_fold", None, None),
+    "gate_melwin":  ("t2s_wg_in_melwin_gate_fold", None, None, None),
+    "res":          ("t2s_wg_res_only", "t2s_wg_res_only_ragged", "t2s_wg_res_only_h16", "t2s_wg_res_only_h16_ragged"),
+    "res_start":    ("t2s_wg_res_only_start", "t2s_wg_res_only_start_ragged", None, None),
+}
+# The entry points that take `lengths` (the plan's lens) in front of `stream`, each with the partner whose argument list it
+# extends by that one pointer.
+_TAKES_LENGTHS = {
+    "t2s_wg_flow_boundary_ragged": "t2s_wg_flow_boundary",
+    "t2s_wg_start_ragged": "t2s_wg_start_window",       # (the window arguments always: zeros and NULLs where nothing is folded)
+    "t2s_wg_res_only_ragged": "t2s_wg_res_only",
+    "t2s_wg_res_only_start_ragged": "t2s_wg_res_only_start",
+    "t2s_wg_start_h16_ragged": "t2s_wg_start_h16",
+    "t2s_wg_in_cond_gate_fold_h16_ragged": "t2s_wg_in_cond_gate_fold_h16",
+    "t2s_wg_res_only_h16_ragged": "t2s_wg_res_only_h16",
+}
+_START_TAKES_WINDOW = ("t2s_wg_start_window", "t2s_wg_start_ragged")   # ks, nwc and the window planes behind the X planes
+
+
+def _entry_point(stage, h16, ragged=False):
+    return _ENTRY_POINTS[stage][2 * bool(h16) + bool(ragged)]
+
 # What `infer_w16 = None` does on an eligible call, decided by measurement (tools/bench_vocoder_half.py against the parent commit's
 # library, profiles/infer_w16_ab.txt).  The rule: the fp16 chain is the default only if it beats the split-bf16 infer of a .half()
 # model - which has the folded WN.start and the one-launch flow boundaries the fp16 chain gives up - at 1000 AND 200 frames by
@@ -269,6 +314,24 @@ class _Engine:
     def start_fold_on(self):
         return self.path().start_fold
 
+    def _plan(self, h16=False, lens=None):
+        """The call's _Plan, made once at the top of forward, wn_forward and _infer, before anything is packed, allocated or
+        launched; every stage reads its choices from it and from nothing else, and its path becomes last_path.  The fp16 chain is
+        the plain path: start -> gate GEMM with WN.end folded in -> residual GEMM -> coupling -> 1x1 convolution.  infer_batch
+        (lens) never takes the composed conditioning."""
+        path = self.last_path = _Path(False, False, None) if h16 else self.path(compose=lens is None)
+        lengths = () if lens is None else (_lib.ptr(lens),)
+        entry = {}
+        for stage in _ENTRY_POINTS:
+            name = _entry_point(stage, h16, lens is not None)
+            entry[stage] = (name, lengths if name in _TAKES_LENGTHS else ())
+        return _Plan(path, h16, lens, entry, None, None)
+
+    def _pack(self, plan, device, force=False, flow_events=None):
+        """The plan with its plane set packed (pack_weights(): cached unless forced)."""
+        return plan._replace(pk=self.pack_weights(device, force=force, flow_events=flow_events, res_pair8=True,
+                                                  start_fold=plan.path.start_fold, h16=plan.h16))
+
     def _stream(self, name, device):
         """The engine's side stream of that name on that device, made on first use."""
         key = (name, str(device))
@@ -277,25 +340,33 @@ class _Engine:
         return self._streams[key]
 
     # ------------------------------------------------------------------ weights
-    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False, start_fold=False):
+    def pack_weights(self, device, force=True, flow_events=None, res_pair8=False, start_fold=False, h16=False):
         """res_pair8: pack the residual rows of every res/skip convolution in the 8-consecutive-channels order the folded no-grad
         path's residual GEMM wants (t2s_wg_res_only(pair8 = 1)); the training path keeps the identity order.
         start_fold: layer 0 of every flow gets the operand of the folded WN.start (A0h / A0l: the composed block, then the
-        conditioning weights) and its in_layers[0] planes are NOT packed (A1h / A1l of layer 0 are stale then)."""
+        conditioning weights) and its in_layers[0] planes are NOT packed (A1h / A1l of layer 0 are stale then).
+        h16: the operands of the fp16 chain, kept as `packed16` beside the split-bf16 `packed` under the same kind of key: per
+        layer the in / cond and the residual effective weights as ONE fp16 plane each (computed in f32 from the fp16 parameters,
+        then rounded to nearest even - no lo plane), the folded WN.end as fp16 hi / lo fragments, biases and WN.start in f32.
+        That set is packed once per parameter version, never forced, and never with the folded WN.start or per-flow events."""
+        assert not (h16 and (start_fold or flow_events is not None))
         res_pair8 = bool(res_pair8) and self.geom()["C"] % 32 == 0
         key = tuple(p._version for p in self.m.parameters()) + (str(device), res_pair8, start_fold)
-        if not force and self.packed is not None and self.packed_key == key:
-            return self.packed
-        if self.packed is None or self.packed["device"] != device:
-            self.packed = dict(flows=self._alloc_planes(device), device=device)
-        srcs = self._pack_jobs(self.packed, res_pair8, start_fold)
-        fsrcs = self._fold_jobs(self.packed)
-        starts = self._launch_pack(self.packed, start_fold, flow_events)
-        self.packed_key = key
-        self.packed["res_pair8"] = res_pair8
-        self.packed["start_fold"] = start_fold
-        self.packed["keep"] = srcs + fsrcs + starts         # what the job tables point at, for as long as the pack is cached
-        return self.packed
+        slot = "packed16" if h16 else "packed"
+        pk = getattr(self, slot)
+        if (h16 or not force) and pk is not None and getattr(self, slot + "_key") == key:
+            return pk
+        if pk is None or pk["device"] != device:
+            pk = dict(flows=self._alloc_planes(device, h16), device=device, h16=h16)
+            setattr(self, slot, pk)
+        srcs = self._pack_jobs(pk, res_pair8, start_fold)
+        fsrcs = self._fold_jobs(pk)
+        starts = self._launch_pack(pk, start_fold, flow_events)
+        setattr(self, slot + "_key", key)
+        pk["res_pair8"] = res_pair8
+        pk["start_fold"] = start_fold
+        pk["keep"] = srcs + fsrcs + starts         # what the job tables point at, for as long as the pack is cached
+        return pk
 
     def w16_eligible(self, batch=False):
         """(ok, why not) for the fp16 chain: infer only (not infer_batch), every WN parameter fp16, n_channels % 16 == 0 and the
@@ -343,52 +414,16 @@ class _Engine:
             raise _lib.T2SError("infer_batch_w16 = True: %s" % why)
         return True
 
-    def pack_weights_w16(self, device):
-        """The operands of the fp16 chain, packed once per parameter version: per layer the in / cond and the residual effective
-        weights as ONE fp16 plane each (computed in f32 from the fp16 parameters, then rounded to nearest even - no lo plane), the
-        folded WN.end as fp16 hi / lo fragments, biases and WN.start in f32.  Never the folded WN.start."""
-        res_pair8 = self.geom()["C"] % 32 == 0
-        key = tuple(p._version for p in self.m.parameters()) + (str(device), res_pair8)
-        if self.packed16 is not None and self.packed16_key == key:
-            return self.packed16
-        if self.packed16 is None or self.packed16["device"] != device:
-            self.packed16 = dict(flows=self._alloc_planes(device, w16=True), device=device)
-        pk = self.packed16
-        srcs = self._pack_jobs(pk, res_pair8, False)
-        fsrcs = self._fold_jobs(pk)
-        starts = self._launch_pack(pk, False, None, h16=True)
-        self.packed16_key = key
-        pk["res_pair8"] = res_pair8
-        pk["start_fold"] = False
-        pk["keep"] = srcs + fsrcs + starts
-        return pk
-
-    def _alloc_planes(self, device, w16=False):
-        """The per-flow plane set of pack_weights(), zeroed.  w16 (pack_weights_w16): fp16 containers, no lo planes of the
-        convolution weights and no folded-WN.start operand."""
+    def _alloc_planes(self, device, h16=False):
+        """The per-flow plane set of pack_weights(), zeroed.  h16: fp16 containers, no lo planes of the convolution weights and no
+        folded-WN.start operand."""
         m, g = self.m, self.geom()
         C, nl = g["C"], g["nl"]
+        f32 = dict(dtype=torch.float32, device=device)
+        plane = lambda *shape: torch.zeros(*shape, dtype=torch.float16 if h16 else torch.bfloat16, device=device)
+        bf16_only = (lambda *shape: None) if h16 else plane
+        a0 = (g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32)
         flows = []
-        if w16:
-            f16 = dict(dtype=torch.float16, device=device)
-            for k in range(m.n_flows):
-                n_half = m.WN[k].start.in_channels
-                layers = []
-                for i in range(nl):
-                    rows2 = 2 * C if i < nl - 1 else C
-                    Mpad2 = _lib.padded_rows(rows2)
-                    layers.append(dict(
-                        A1h=torch.zeros(g["nk1"], g["Mpad1"], 32, **f16), A1l=None,
-                        b1=torch.zeros(g["Mpad1"], dtype=torch.float32, device=device),
-                        A2h=torch.zeros(g["nk2"], Mpad2, 32, **f16), A2l=None,
-                        b2=torch.zeros(Mpad2, dtype=torch.float32, device=device), Mpad2=Mpad2,
-                        s_in=torch.empty(2 * C, dtype=torch.float32, device=device),
-                        s_cond=torch.empty(2 * C, dtype=torch.float32, device=device),
-                        s_rs=torch.empty(rows2, dtype=torch.float32, device=device),
-                        fold_A=torch.zeros(-(-C // 128) * 8192, **f16)))
-                flows.append(dict(layers=layers, n_half=n_half, bes=torch.zeros(nl, 8, dtype=torch.float32, device=device),
-                                  w_start=torch.empty(C, n_half, dtype=torch.float32, device=device), A0h=None, A0l=None, w_inv=None))
-            return flows
         for k in range(m.n_flows):
             n_half = m.WN[k].start.in_channels
             layers = []
@@ -396,21 +431,12 @@ class _Engine:
                 rows2 = 2 * C if i < nl - 1 else C
                 Mpad2 = _lib.padded_rows(rows2)
                 layers.append(dict(
-                    A1h=torch.zeros(g["nk1"], g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                    A1l=torch.zeros(g["nk1"], g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                    b1=torch.zeros(g["Mpad1"], dtype=torch.float32, device=device),
-                    A2h=torch.zeros(g["nk2"], Mpad2, 32, dtype=torch.bfloat16, device=device),
-                    A2l=torch.zeros(g["nk2"], Mpad2, 32, dtype=torch.bfloat16, device=device),
-                    b2=torch.zeros(Mpad2, dtype=torch.float32, device=device), Mpad2=Mpad2,
-                    s_in=torch.empty(2 * C, dtype=torch.float32, device=device),
-                    s_cond=torch.empty(2 * C, dtype=torch.float32, device=device),
-                    s_rs=torch.empty(rows2, dtype=torch.float32, device=device),
-                    fold_A=torch.zeros(-(-C // 128) * 8192, dtype=torch.bfloat16, device=device)))
-            flows.append(dict(layers=layers, n_half=n_half, bes=torch.zeros(nl, 8, dtype=torch.float32, device=device),
-                              w_start=torch.empty(C, n_half, dtype=torch.float32, device=device),
-                              A0h=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                              A0l=torch.zeros(g["nwc"] + g["Spad"] // 32, g["Mpad1"], 32, dtype=torch.bfloat16, device=device),
-                              w_inv=None))
+                    A1h=plane(g["nk1"], g["Mpad1"], 32), A1l=bf16_only(g["nk1"], g["Mpad1"], 32), b1=torch.zeros(g["Mpad1"], **f32),
+                    A2h=plane(g["nk2"], Mpad2, 32), A2l=bf16_only(g["nk2"], Mpad2, 32), b2=torch.zeros(Mpad2, **f32), Mpad2=Mpad2,
+                    s_in=torch.empty(2 * C, **f32), s_cond=torch.empty(2 * C, **f32), s_rs=torch.empty(rows2, **f32),
+                    fold_A=plane(-(-C // 128) * 8192)))
+            flows.append(dict(layers=layers, n_half=n_half, bes=torch.zeros(nl, 8, **f32), w_start=torch.empty(C, n_half, **f32),
+                              A0h=bf16_only(*a0), A0l=bf16_only(*a0), w_inv=None))
         return flows
 
     def _pack_jobs(self, pk, res_pair8, start_fold):
@@ -489,24 +515,24 @@ class _Engine:
             pk["fold_key"] = fkey
         return [t for tup in fsrc for t in tup[:3]]
 
-    def _launch_pack(self, pk, start_fold, flow_events, h16=False):
+    def _launch_pack(self, pk, start_fold, flow_events):
         """One table-driven launch per flow packs its 3 * n_layers convolutions (weight-norm + split + permute), one more
         builds its folded WN.end matrices, a third its `start` weights - and with start_fold a fourth composes those with
-        in_layers[0] into the first nwc K-chunks of the layer-0 operand.  h16: the first two are their _h16 partners (pk is the
-        fp16 chain's plane set).  With `flow_events` (the no-grad forward) the per-flow
+        in_layers[0] into the first nwc K-chunks of the layer-0 operand.  The first two are the entry points of the plane set's
+        operand format.  With `flow_events` (the no-grad forward) the per-flow
         work is enqueued on the caller's current stream - a side stream there - and an event per flow lets the main stream
         start flow k as soon as ITS weights are packed: the pack is HBM-bound (2.1 GB per forward), the GEMMs are not."""
         m, g = self.m, self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
         st = _lib.current_stream()
         jobs_ptr, fold_ptr = pk["jobs"].data_ptr(), pk["fold_jobs"].data_ptr()
+        pack, endfold = _entry_point("pack", pk["h16"]), _entry_point("endfold", pk["h16"])
         starts = []
         for k, wn in enumerate(m.WN):
             fl = pk["flows"][k]
             j0, nj = pk["flow_jobs"][k]
-            sfx = "_h16" if h16 else ""
-            _lib.call("t2s_pack_conv_weight_table" + sfx, _lib.c_vp(jobs_ptr + j0 * 19 * 8), nj, pk["flow_rows"][k], st)
-            _lib.call("t2s_wg_endfold_weights" + sfx, _lib.c_vp(fold_ptr + k * nl * 8 * 8), nl, C, st)
+            _lib.call(pack, _lib.c_vp(jobs_ptr + j0 * 19 * 8), nj, pk["flow_rows"][k], st)
+            _lib.call(endfold, _lib.c_vp(fold_ptr + k * nl * 8 * 8), nl, C, st)
             v, gg = _vg(wn.start)
             v, gg = _f32c(v), (None if gg is None else _f32c(gg))
             starts += [v, gg]
@@ -600,20 +626,22 @@ class _Engine:
                 raise _lib.T2SError("WaveGlow (MI355X build) needs CUDA/HIP tensors; got a %s tensor - there is no "
                                     "CPU fallback" % t.device)
 
-    def _upsample(self, mel, B, L, w, h16=False):
+    def _upsample(self, mel, B, L, w, plan=None):
+        """plan: the no-grad call's; None (the training forward): split-bf16 planes."""
         m, g = self.m, self.geom()
         up = m.upsample
         mel32 = _f32c(mel)
         W, bias = _f32c(up.weight), _f32c(up.bias)
-        _lib.call("t2s_wg_upsample_squeeze_h16" if h16 else "t2s_wg_upsample_squeeze", _lib.ptr(mel32), _lib.ptr(W), _lib.ptr(bias), B, up.in_channels,
+        name = plan.entry["upsample"][0] if plan is not None else _entry_point("upsample", False)
+        _lib.call(name, _lib.ptr(mel32), _lib.ptr(W), _lib.ptr(bias), B, up.in_channels,
                   mel32.size(2), up.kernel_size[0], up.stride[0], m.n_group, L, w["Lp"], g["halo"],
                   _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), _lib.current_stream())
         self._keep += [mel32, W, bias]
 
-    def _boundary(self, k, z_in, z_out, B, L, w, prev=None, W=None, lens=None):
-        """t2s_wg_flow_boundary in front of flow k: prev = (flow index, log_s) applies that flow's coupling, W this flow's 1x1
-        convolution, both to z_in -> z_out; always writes flow k's window planes.  prev = W = None: the window planes only.
-        lens (int32 [B] on the device, columns; infer_batch only): the _ragged entry point."""
+    def _boundary(self, plan, k, z_in, z_out, B, L, w, prev=None, W=None):
+        """The plan's flow-boundary launch in front of flow k: prev = (flow index, log_s) applies that flow's coupling, W this
+        flow's 1x1 convolution, both to z_in -> z_out; always writes flow k's window planes.  prev = W = None: the window planes
+        only."""
         m, g = self.m, self.geom()
         c_off, n_rem, n_half = self._flow_geom(k)
         fold_acc = bes = b_end = log_s = None
@@ -622,46 +650,48 @@ class _Engine:
             kp, log_s = prev
             c_off_p, _, nh_p = self._flow_geom(kp)
             fold_acc, nslots = w["fold_acc"], w["fold_acc"].size(0)
-            bes = self.packed["flows"][kp]["bes"]
+            bes = plan.pk["flows"][kp]["bes"]
             b_end = _f32c(m.WN[kp].end.bias)
             self._keep.append(b_end)
         # Stream order makes the reuse of fold_acc and of the window planes safe: this launch reads the sums of the flow before
         # ahead of flow k's layer-0 gate GEMM, which re-initialises them, and writes the window planes behind the last launch (the
         # layer-0 gate GEMM of the flow before) that read them.
-        args = (_lib.ptr(z_in), _lib.ptr(z_out), _lib.ptr(fold_acc), nslots, _lib.ptr(bes), g["nl"],
-                _lib.ptr(b_end), _lib.ptr(log_s), c_off_p, nh_p, _lib.ptr(W), c_off, n_rem, n_half, B, m.n_group, L, w["Lp"],
-                g["halo"], g["ks"], g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]))
-        if lens is None:
-            _lib.call("t2s_wg_flow_boundary", *args, _lib.current_stream())
-        else:
-            _lib.call("t2s_wg_flow_boundary_ragged", *args, _lib.ptr(lens), _lib.current_stream())
+        name, lengths = plan.entry["boundary"]
+        _lib.call(name, _lib.ptr(z_in), _lib.ptr(z_out), _lib.ptr(fold_acc), nslots, _lib.ptr(bes), g["nl"],
+                  _lib.ptr(b_end), _lib.ptr(log_s), c_off_p, nh_p, _lib.ptr(W), c_off, n_rem, n_half, B, m.n_group, L, w["Lp"],
+                  g["halo"], g["ks"], g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), *lengths, _lib.current_stream())
 
-    def _wn(self, k, z, B, L, w, c_off, n_half, path, ph=None, lens=None):
-        """start -> n_layers x (gate GEMM with WN.end folded in, residual GEMM) on the call's `path`; leaves WN.end's sums in
+    def _wn(self, plan, k, z, B, L, w, c_off, n_half):
+        """start -> n_layers x (gate GEMM with WN.end folded in, residual GEMM) as the call's plan has it; leaves WN.end's sums in
         w['fold_acc'].  With path.boundary the caller's _boundary() has written this flow's window planes from z, and x0 is rebuilt
-        by the layer-0 residual GEMM.  ph = (M_hi, M_lo, Fp, P, K2): composed conditioning from the mel-window planes (inverse flow).
-        lens (int32 [B] on the device, columns; infer_batch only): every writer of the X and window planes is the _ragged entry
-        point in place of its partner; the gate GEMMs are the same launches."""
+        by the layer-0 residual GEMM.  On the fp16 chain the lo planes of the weights are None (NULL).  The workspace planes are
+        16-bit containers shared by both operand formats: every row a launch reads was written by the same call's chain, and what
+        neither format writes (halo, rows past L) is zero in both.  With plan.lens every writer of the X and window planes stores
+        zeros from an entry's end on, and the fp16 chain's GEMMs drop the column tiles that start at or behind it (DESIGN.md
+        section 5): the acts columns of such a tile keep whatever an earlier call left there, and nothing reads them."""
         m, g = self.m, self.geom()
         C, nl, ks = g["C"], g["nl"], g["ks"]
-        fl = self.packed["flows"][k]
+        path, P = plan.path, _lib.ptr
+        fl = plan.pk["flows"][k]
         st = _lib.current_stream()
         b_start = _f32c(m.WN[k].start.bias)
         self._keep.append(b_start)
-        if lens is not None and not path.boundary:
-            win = (ks, g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"])) if path.start_fold else (0, 0, None, None)
-            _lib.call("t2s_wg_start_ragged", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
-                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), *win, _lib.ptr(lens), st)
-        elif lens is not None:
-            pass            # _boundary(lens=...) wrote the window planes
-        elif not path.start_fold:
-            _lib.call("t2s_wg_start", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
-                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), st)
-        elif not path.boundary:
-            # layer 0 through the folded WN.start: the X planes are still written (the residual stream needs x0), the gate GEMM
-            # reads the window planes instead
-            _lib.call("t2s_wg_start_window", _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
-                      C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), ks, g["nwc"], _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), st)
+        X, S, win, acts = ((P(w[n + "h"]), P(w[n + "l"])) for n in "XSWA")
+        if not path.boundary:
+            # with the folded WN.start the X planes are still written (the residual stream needs x0); the layer-0 gate GEMM reads
+            # the window planes instead
+            name, lengths = plan.entry["start_window" if path.start_fold else "start"]
+            window = ()
+            if name in _START_TAKES_WINDOW:
+                window = (ks, g["nwc"], *win) if path.start_fold else (0, 0, None, None)
+            _lib.call(name, P(z), P(fl["w_start"]), P(b_start), B, m.n_group, c_off, n_half, C, L, w["Lp"], g["halo"], *X,
+                      *window, *lengths, st)
+        gate, gate_lengths = plan.entry["gate" if plan.melwin is None else "gate_melwin"]
+        gate_window = plan.entry["gate_window"][0]
+        res, res_lengths = plan.entry["res"]
+        res_start, res_start_lengths = plan.entry["res_start"]
+        pair8 = 1 if plan.pk["res_pair8"] else 0
+        dims1 = (L, w["Lp"], g["halo"], g["Mpad1"])
         for i in range(nl):
             ly = fl["layers"][i]
             # bench.py divides the sampled launch time into the FLOPs of a full-K layer: the short folded layer 0 is neither
@@ -673,75 +703,28 @@ class _Engine:
             if timed:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
+            out = (*acts, P(ly["fold_A"]), P(w["fold_acc"]))
             if not full_k:
-                _lib.call("t2s_wg_in_win_gate_fold", _lib.ptr(fl["A0h"]), _lib.ptr(fl["A0l"]), _lib.ptr(ly["b1"]),
-                          _lib.ptr(w["Wh"]), _lib.ptr(w["Wl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
-                          1, B, C, g["n_cond"], g["nwc"], L, w["Lp"], g["halo"], g["Mpad1"], st)
-            elif ph is not None:
-                Mh, Ml, Fp, P, K2 = ph
-                _lib.call("t2s_wg_in_melwin_gate_fold", _lib.ptr(ly["A1h"]), _lib.ptr(ly["A1l"]), _lib.ptr(ly["Ach"]),
-                          _lib.ptr(ly["Acl"]), _lib.ptr(ly["b1c"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(Mh), _lib.ptr(Ml),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
-                          1 if i == 0 else 0, B, C, K2, ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], P, Fp, st)
+                _lib.call(gate_window, P(fl["A0h"]), P(fl["A0l"]), P(ly["b1"]), *win, *S, *out, 1, B, C, g["n_cond"], g["nwc"], *dims1, st)
+            elif plan.melwin is not None:       # composed conditioning from the mel-window planes (inverse flow)
+                Mh, Ml, Fp, n_phase, K2 = plan.melwin
+                _lib.call(gate, P(ly["A1h"]), P(ly["A1l"]), P(ly["Ach"]), P(ly["Acl"]), P(ly["b1c"]), *X, P(Mh), P(Ml), *out,
+                          1 if i == 0 else 0, B, C, K2, ks, 2 ** i, *dims1, n_phase, Fp, st)
             else:
-                _lib.call("t2s_wg_in_cond_gate_fold", _lib.ptr(ly["A1h"]), _lib.ptr(ly["A1l"]), _lib.ptr(ly["b1"]),
-                          _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
-                          1 if i == 0 else 0, B, C, g["n_cond"], ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], st)
+                _lib.call(gate, P(ly["A1h"]), P(ly["A1l"]), P(ly["b1"]), *X, *S, *out,
+                          1 if i == 0 else 0, B, C, g["n_cond"], ks, 2 ** i, *dims1, *gate_lengths, st)
             if timed:
                 e1.record()
                 self.gemm_events.append((e0, e1))
             if i == nl - 1:     # the last layer has no residual half, and its skip half lives in the fold
                 continue
-            pair8 = 1 if self.packed["res_pair8"] else 0
-            if lens is not None and path.boundary and i == 0:
-                _lib.call("t2s_wg_res_only_start_ragged", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start),
-                          m.n_group, c_off, n_half, _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"],
-                          ly["Mpad2"], _lib.ptr(lens), st)
-            elif lens is not None:
-                _lib.call("t2s_wg_res_only_ragged", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
-                          g["halo"], ly["Mpad2"], pair8, _lib.ptr(lens), st)
-            elif path.boundary and i == 0:
-                _lib.call("t2s_wg_res_only_start", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start),
-                          m.n_group, c_off, n_half, _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"],
-                          ly["Mpad2"], st)
+            weights = (P(ly["A2h"]), P(ly["A2l"]), P(ly["b2"]), *acts)
+            dims2 = (B, C, L, w["Lp"], g["halo"], ly["Mpad2"])
+            if path.boundary and i == 0:
+                _lib.call(res_start, *weights, P(z), P(fl["w_start"]), P(b_start), m.n_group, c_off, n_half, *X, *dims2,
+                          *res_start_lengths, st)
             else:
-                _lib.call("t2s_wg_res_only", _lib.ptr(ly["A2h"]), _lib.ptr(ly["A2l"]), _lib.ptr(ly["b2"]),
-                          _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"],
-                          g["halo"], ly["Mpad2"], pair8, st)
-
-    def _wn_w16(self, pk, k, z, B, L, w, c_off, n_half, lens=None):
-        """_wn on the fp16 chain: t2s_wg_start_h16, then per layer the folded gate GEMM and the residual GEMM with one-plane fp16
-        weights (no lo pointer).  The workspace planes are 16-bit containers shared with the split-bf16 path: every row a launch
-        reads was written by this chain, and what neither format writes (halo, rows past L) is zero in both.
-        lens (int32 [B] on the device, columns; infer_batch only): the three _h16_ragged partners.  The writers of the X planes
-        store zeros from an entry's end on, and both GEMMs drop the column tiles that start at or behind it:
-        the acts columns of such a tile keep whatever an earlier call left there, and nothing reads them."""
-        m, g = self.m, self.geom()
-        C, nl, ks = g["C"], g["nl"], g["ks"]
-        fl = pk["flows"][k]
-        st = _lib.current_stream()
-        b_start = _f32c(m.WN[k].start.bias)
-        self._keep.append(b_start)
-        rag = "" if lens is None else "_ragged"
-        tail = (st,) if lens is None else (_lib.ptr(lens), st)
-        _lib.call("t2s_wg_start_h16%s" % rag, _lib.ptr(z), _lib.ptr(fl["w_start"]), _lib.ptr(b_start), B, m.n_group, c_off, n_half,
-                  C, L, w["Lp"], g["halo"], _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), *tail)
-        pair8 = 1 if pk["res_pair8"] else 0
-        for i in range(nl):
-            ly = fl["layers"][i]
-            _lib.call("t2s_wg_in_cond_gate_fold_h16%s" % rag, _lib.ptr(ly["A1h"]), None, _lib.ptr(ly["b1"]),
-                      _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]),
-                      _lib.ptr(w["Ah"]), _lib.ptr(w["Al"]), _lib.ptr(ly["fold_A"]), _lib.ptr(w["fold_acc"]),
-                      1 if i == 0 else 0, B, C, g["n_cond"], ks, 2 ** i, L, w["Lp"], g["halo"], g["Mpad1"], *tail)
-            if i < nl - 1:      # the last layer has no residual half, and its skip half lives in the fold
-                _lib.call("t2s_wg_res_only_h16%s" % rag, _lib.ptr(ly["A2h"]), None, _lib.ptr(ly["b2"]), _lib.ptr(w["Ah"]),
-                          _lib.ptr(w["Al"]), _lib.ptr(w["Xh"]), _lib.ptr(w["Xl"]), B, C, L, w["Lp"], g["halo"], ly["Mpad2"], pair8,
-                          *tail)
+                _lib.call(res, *weights, *X, *dims2, pair8, *res_lengths, st)
 
     def wn_forward(self, k, audio, spect):
         """WN[k].forward((audio, spect)) (reference glow.py:154-175) on the no-grad kernels: start, n_layers x (gate GEMM with
@@ -753,29 +736,29 @@ class _Engine:
         g = self.geom()
         if n_in != n_half or spect.size(1) != g["n_cond"] or spect.size(2) != L:
             raise ValueError("WN[%d] takes audio [B, %d, L] and spect [B, %d, L]" % (k, n_half, g["n_cond"]))
-        path = self.last_path = self.path()
+        plan = self._plan()
         self._keep = []
-        self.pack_weights(dev, force=False, res_pair8=True, start_fold=path.start_fold)
+        plan = self._pack(plan, dev)
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         spect32 = _f32c(spect)
         _lib.call("t2s_f32_to_planes", _lib.ptr(spect32), B, g["n_cond"], L, w["Lp"], g["halo"], _lib.ptr(w["Sh"]), _lib.ptr(w["Sl"]), st)
         z = torch.zeros(B, self.m.n_group, L, dtype=torch.float32, device=dev)
         z[:, c_off:c_off + n_half] = audio.detach().to(torch.float32)
-        if path.boundary:
-            self._boundary(k, z, None, B, L, w)
-        self._wn(k, z, B, L, w, c_off, n_half, path)
-        wn_out = torch.empty(B, 2 * n_half, L, dtype=torch.float32, device=dev)
-        self._end_fold(k, z, None, w["fold_acc"], wn_out, B, L, c_off, n_half, reverse=False)
+        if plan.path.boundary:
+            self._boundary(plan, k, z, None, B, L, w)
+        self._wn(plan, k, z, B, L, w, c_off, n_half)
+        wn_out =torch.empty(B, 2 * n_half, L, dtype=torch.float32, device=dev)
+        self._end_fold(k, z, None, w["fold_acc"], wn_out, B, L, c_off, n_half, reverse=False, plan=plan)
         self._keep += [spect32, z]
         return wn_out.to(audio.dtype)
 
-    def _end_fold(self, k, z, log_s, fold_acc, wn_out, B, L, c_off, n_half, reverse, pk=None):
+    def _end_fold(self, k, z, log_s, fold_acc, wn_out, B, L, c_off, n_half, reverse, plan=None):
         """WN.end from the sums the gate GEMMs folded it into, and flow k's coupling on z (wn_out: also WN.end's output).
-        pk: the plane set the sums were built from (default: the split-bf16 one)."""
+        plan: the no-grad call's, whose plane set the sums were built from; None (the training forward): the split-bf16 set."""
         b_end = _f32c(self.m.WN[k].end.bias)
         self._keep.append(b_end)
-        pk = self.packed if pk is None else pk
+        pk = self.packed if plan is None else plan.pk
         _lib.call("t2s_wg_end_fold_affine", _lib.ptr(fold_acc), fold_acc.size(0), _lib.ptr(pk["flows"][k]["bes"]),
                   self.geom()["nl"], _lib.ptr(b_end), _lib.ptr(z), _lib.ptr(log_s), _lib.ptr(wn_out), B, self.m.n_group, c_off,
                   n_half, L, 1 if reverse else 0, _lib.current_stream())
@@ -810,7 +793,8 @@ class _Engine:
         up = m.upsample
         if (mel.size(2) - 1) * up.stride[0] + up.kernel_size[0] < T:
             raise AssertionError("upsampled spectrogram shorter than audio (reference glow.py:216)")
-        path = self.last_path = self.path()
+        plan = self._plan()
+        path = plan.path
         self._keep = []
         w = self.workspace(B, L, dev)
         # The input-side work (conditioning upsampler: compute-bound; audio squeeze; 12 log-determinants) does not depend on
@@ -837,7 +821,7 @@ class _Engine:
         with torch.cuda.stream(side):
             st2 = _lib.current_stream()
             _lib.call("t2s_wg_audio_squeeze", _lib.ptr(audio32), _lib.ptr(z), B, T, G, L, 0, st2)
-            self._upsample(mel, B, L, w)
+            self._upsample(mel, B, L, w, plan)
             ev_inputs = torch.cuda.Event()       # flow 0 needs z and the conditioning planes; the log-determinants are only
             ev_inputs.record()                   # outputs and join at the end
             if use_val:
@@ -852,7 +836,7 @@ class _Engine:
         pack_events = []
         pack_s.wait_stream(main)
         with torch.cuda.stream(pack_s):
-            self.pack_weights(dev, force=True, flow_events=pack_events, res_pair8=True, start_fold=path.start_fold)
+            plan = self._pack(plan, dev, force=True, flow_events=pack_events)
         main.wait_event(ev_inputs)
         st = _lib.current_stream()
         for k in range(m.n_flows):
@@ -862,13 +846,13 @@ class _Engine:
             if path.boundary:
                 # boundary(k): coupling of flow k - 1 (none in front of flow 0), this flow's 1x1 convolution, the window planes
                 z_out = bufs[(k + 1) % 2]
-                self._boundary(k, z, z_out, B, L, w, prev=(k - 1, log_s_list[k - 1]) if k else None, W=Ws[k])
+                self._boundary(plan, k, z, z_out, B, L, w, prev=(k - 1, log_s_list[k - 1]) if k else None, W=Ws[k])
                 z = z_out
             else:
                 _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(Ws[k]), B, G, c_off, n_rem, L, st)
-            self._wn(k, z, B, L, w, c_off, n_half, path)
+            self._wn(plan, k, z, B, L, w, c_off, n_half)
             if not path.boundary or k == m.n_flows - 1:     # the last coupling has no boundary behind it: in place on the current buffer
-                self._end_fold(k, z, log_s, w["fold_acc"], None, B, L, c_off, n_half, reverse=False)
+                self._end_fold(k, z, log_s, w["fold_acc"], None, B, L, c_off, n_half, reverse=False, plan=plan)
             log_s_list.append(log_s)
             log_det_list.append(log_det[k])
         main.wait_stream(side)               # log_det
@@ -879,14 +863,14 @@ class _Engine:
 
     def infer_batch(self, mel, lengths, sigma, noise):
         """infer() on a padded batch whose entry b is lengths[b] frames long (host int64 [B], validated by the caller): the same
-        launches with every writer of the X and window planes replaced by its _ragged partner, which shows each entry zeros past
-        its own end as its solo run shows it past L, and one more that zeroes the audio tails.  Always the
-        plain conditioning path.  With infer_batch_w16 = True the launches are those of infer's fp16 chain, through the _h16_ragged
-        partners (_wn_w16).  Returns (audio [B, stride * frames], audio lengths int64 [B] on the device)."""
+        launches with every writer of the X and window planes replaced by the partner that takes the lengths, which shows each
+        entry zeros past its own end as its solo run shows it past L, and one more that zeroes the audio
+        tails.  Always the plain conditioning path.  With infer_batch_w16 = True the launches are those of infer's fp16 chain,
+        through its partners.  Returns (audio [B, stride * frames], audio lengths int64 [B] on the device)."""
         m = self.m
         self._check_inputs(mel)
         stride = m.upsample.stride[0]
-        # columns per entry, once per call: the only host -> device copy, and the array every _ragged launch reads
+        # columns per entry, once per call: the only host -> device copy, and the array every launch that takes lengths reads
         lens = (lengths * (stride // m.n_group)).to(torch.int32).to(mel.device)
         audio = self._infer(mel, sigma, noise, lens)
         B, T = audio.shape
@@ -906,22 +890,20 @@ class _Engine:
         L = T // G
         # (either raises before anything is launched.)  infer_batch_w16 = True puts infer_batch on the fp16 chain whatever infer_w16
         # says, which governs infer only then; otherwise infer_batch goes through use_w16(batch=True) as it always did.
-        batch_w16 = self.last_infer_batch_w16 = lens is not None and self.use_batch_w16()
-        w16 = self.last_infer_w16 = batch_w16 or self.use_w16(batch=lens is not None)
-        if w16:
-            # the fp16 chain is the plain one: start -> gate GEMM with WN.end folded in -> residual GEMM -> coupling -> 1x1 conv
-            path = self.last_path = _Path(False, False, None)
-        else:
-            path = self.last_path = self.path(compose=lens is None)      # infer_batch: never the composed conditioning
+        batch = lens is not None
+        batch_w16 = self.last_infer_batch_w16 = batch and self.use_batch_w16()
+        h16 = self.last_infer_w16 = batch_w16 or self.use_w16(batch=batch)
+        plan = self._plan(h16, lens)
+        path = plan.path
         self._keep = []
-        pk = self.pack_weights_w16(dev) if w16 else self.pack_weights(dev, force=False, res_pair8=True, start_fold=path.start_fold)
+        plan = self._pack(plan, dev)
         w = self.workspace(B, L, dev)
         st = _lib.current_stream()
         # Weights are packed once here, so the conditioning path can be composed with the upsampler (K = 640 -> 320 in the gate
         # GEMM, no upsampler launch) - wherever the grid is large enough for the 256-row ping-pong tiles anyway.  Opt-in
         # (T2S_COND_COMPOSE=1): with the activations in time-major planes the phase tiles read rows 2 KB apart and the gate GEMM
         # gains 3.5 % instead of 14.7 % (1000 frames: 32.5 -> 31.7 ms; 300-400 frames lose to tile padding)
-        ph = None       # (256: the library's own tile-height decision)
+        # (256: the library's own tile-height decision)
         if path.compose is not None and _lib.load().t2s_wg_gate_tile_rows(B, self.geom()["C"], L) == 256:
             P, nlag, K2 = path.compose
             self.compose_cond(dev)
@@ -935,9 +917,9 @@ class _Engine:
             mel32 = _f32c(mel)
             _lib.call("t2s_wg_melwin_planes", _lib.ptr(mel32), B, mel32.size(1), frames, nlag, Fp, _lib.ptr(mw[0]), _lib.ptr(mw[1]), st)
             self._keep.append(mel32)
-            ph = (mw[0], mw[1], Fp, P, K2)
+            plan = plan._replace(melwin=(mw[0], mw[1], Fp, P, K2))
         else:
-            self._upsample(mel, B, L, w, h16=w16)
+            self._upsample(mel, B, L, w, plan)
         # All Gaussian draws of glow.py:260-267,284-289 live in one [B, G, L] buffer: the final
         # n_remaining channels, and in front of them the n_early_size channels re-attached at each early flow.
         z = torch.empty(B, G, L, dtype=torch.float32, device=dev)
@@ -954,19 +936,16 @@ class _Engine:
             z[:, c_off - m.n_early_size:c_off] = sigma * ne.to(dev, torch.float32)
         for k in reversed(range(m.n_flows)):
             c_off, n_rem, n_half = self._flow_geom(k)
-            fl = pk["flows"][k]
+            fl = plan.pk["flows"][k]
             if fl["w_inv"] is None:
                 Wk = _f32c(m.convinv[k].conv.weight)
                 fl["w_inv"] = torch.empty(n_rem, n_rem, dtype=torch.float32, device=dev)
                 _lib.call("t2s_small_logdet_inv", _lib.ptr(Wk), n_rem, 1.0, None, _lib.ptr(fl["w_inv"]), st)
                 fl["_Wk"] = Wk
             if path.boundary:
-                self._boundary(k, z, None, B, L, w, lens=lens)         # the window planes only
-            if w16:
-                self._wn_w16(pk, k, z, B, L, w, c_off, n_half, lens=lens)
-            else:
-                self._wn(k, z, B, L, w, c_off, n_half, path, ph=ph, lens=lens)
-            self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True, pk=pk)
+                self._boundary(plan, k, z, None, B, L, w)         # the window planes only
+            self._wn(plan, k, z, B, L, w, c_off, n_half)
+            self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True, plan=plan)
             _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(fl["w_inv"]), B, G, c_off, n_rem, L, st)
         audio = torch.empty(B, L * G, dtype=torch.float32, device=dev)
         _lib.call("t2s_wg_audio_squeeze", _lib.ptr(audio), _lib.ptr(z), B, L * G, G, L, 1, st)
@@ -1056,8 +1035,14 @@ class WaveGlow(torch.nn.Module):
         Gaussian draws explicit for parity tests; by default they are drawn on the device."""
         with torch.no_grad():
             out = self._eng().infer(spect, float(sigma), noise)
-        if self._eng().last_infer_w16:
-            self._refuse_overflow(out, w16=True)
+        return self._finish(out, spect)
+
+    def _finish(self, out, spect):
+        """The ending of infer and infer_batch: refuse audio that overflowed fp16 planes (the fp16 chain - infer_batch's runs on
+        its own switch, and infer's never runs there - or the diagnostic build), then the mel's dtype."""
+        eng = self._eng()
+        if eng.last_infer_w16:
+            self._refuse_overflow(out, w16="infer_batch_w16" if eng.last_infer_batch_w16 else True)
         elif _lib.operand_format() == 1:
             self._refuse_overflow(out)
         return out.to(spect.dtype) if spect.dtype in (torch.float16, torch.bfloat16) else out
@@ -1104,11 +1089,7 @@ class WaveGlow(torch.nn.Module):
                                % (B, self.n_remaining_channels, Lmax, len(early), B, self.n_early_size, Lmax))
         with torch.no_grad():
             out, out_lens = self._eng().infer_batch(spect, lens, float(sigma), noise)
-        if self._eng().last_infer_batch_w16:   # (the tails are zeros by now: the valid samples decide, never what the padding held)
-            self._refuse_overflow(out, w16="infer_batch_w16")
-        elif _lib.operand_format() == 1:
-            self._refuse_overflow(out)
-        return (out.to(spect.dtype) if spect.dtype in (torch.float16, torch.bfloat16) else out), out_lens
+        return self._finish(out, spect), out_lens      # (the tails are zeros by now: the valid samples decide, never what the padding held)
 
     @staticmethod
     def remove_weightnorm(model):
