@@ -825,6 +825,40 @@ int t2s_mel_from_mag(const float* magT, long ld_mt, int B, int F, const float* m
 int t2s_stft_inverse(const float* mag, const float* phase, int B, int F, int n_fft, int hop, const float* inv_basis_t, long ld_rc,
                      const float* bias, float strength, const float* win_sq, float tiny, float* rc, float* frames, float* out,
                      void* stream);
+/* ---- The three above on a padded batch whose entries differ in length, and int16 PCM (ABI v4, compatible additions) ----
+ * Entry b of the batch holds lengths[b] samples (or frames[b] frames); every entry gets what it gets alone, whatever the padding
+ * holds, and +0 behind its end.  Each entry point takes its partner's arguments and checks plus the lengths twice: `lengths` /
+ * `frames` ([B] int32 in device memory, read by the kernels; NULL: T2S_EINVAL) and `lengths_host` / `frames_host` (the same values
+ * in host memory; NULL: T2S_EINVAL).  The host copy is read before the call returns and validated before the first launch (a value
+ * out of range: T2S_EINVAL, nothing launched); the contractions are launched per entry with the entry's own item count from it,
+ * because the GEMV / matrix-core dispatcher chooses by item count - that is what makes an entry's bits those of its solo call.  The
+ * kernels clamp the device values to the validated range.  B <= 65535.
+ *  t2s_stft_transform_ragged: audio [B][T], n_fft/2 < lengths[b] <= T; the layouts of t2s_stft_transform at F = T/hop + 1.  Entry b
+ *    has F_b = lengths[b]/hop + 1 frames; the reflect padding mirrors about sample lengths[b] - 1 and audio[b][t >= lengths[b]] is
+ *    never read.  For f < F_b mag, phase and magT hold, bit for bit, what t2s_stft_transform stores for the entry alone (B = 1,
+ *    T = lengths[b], the same ldp and ld_mt); for f >= F_b they are stored as +0.  The scratch xp and ft behind an entry's end are
+ *    not written.
+ *  t2s_mel_from_mag_ragged: 1 <= frames[b] <= F; columns f < frames[b] are t2s_mel_from_mag's for the entry alone (the double-
+ *    precision log-clamp included), columns behind are +0 - not log(clip): zero is what a collate function pads mels with - and
+ *    the rows of magT behind are not read.  clip <= 0 skips the log, as in the partner; the zeros are stored all the same.
+ *  t2s_stft_inverse_ragged: 2 <= frames[b] <= F; out [B][hop (F - 1)].  Samples n < hop (frames[b] - 1) are t2s_stft_inverse's for
+ *    the entry alone: recombination, contraction, overlap-add bounds and window-sum-square all use frames[b], never F.  Samples
+ *    behind are +0; mag and phase at f >= frames[b] are never read; the scratch rc and frames_buf ([B][F][n_fft]) are not written
+ *    there.
+ *  t2s_pcm16: x [B] rows of N samples, ldx elements apart (ldx >= N), f32 (is_half = 0) or fp16 (is_half != 0);
+ *    out int16 [B][N] = (int16) trunc(float(x) * 32768.f), saturated to [-32768, 32767] (+1.0 gives 32767; the reference's numpy cast
+ *    of an out-of-range float is undefined), NaN gives 0.  lengths ([B] int32, device) may be NULL: every sample; otherwise samples
+ *    at or behind lengths[b] give 0 and are not read (any value of lengths[b] is safe: below 0 counts as 0, above N as N).  No
+ *    alignment beyond the element: odd N and odd ldx work. */
+int t2s_stft_transform_ragged(const float* audio, int B, int T, const int* lengths, const int* lengths_host, const float* fwd_basis,
+                              int n_fft, int hop, float* xp, long ldp, float* ft, float* mag, float* phase, float* magT, long ld_mt,
+                              void* stream);
+int t2s_mel_from_mag_ragged(const float* magT, long ld_mt, int B, int F, const int* frames, const int* frames_host,
+                            const float* mel_basis_p, int n_mel, float clip, float* mel, void* stream);
+int t2s_stft_inverse_ragged(const float* mag, const float* phase, int B, int F, const int* frames, const int* frames_host, int n_fft,
+                            int hop, const float* inv_basis_t, long ld_rc, const float* bias, float strength, const float* win_sq,
+                            float tiny, float* rc, float* frames_buf, float* out, void* stream);
+int t2s_pcm16(const void* x, int is_half, int B, int N, long ldx, const int* lengths, short* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,9 @@
 All arithmetic after construction runs in libt2s_hip.so (csrc/audio_ops.hip + the GEMV / f32 matrix-core GEMM of the
 Tacotron path); there is no CPU or eager fallback - without the library every call raises.  The reference bounces the
 waveform host -> GPU -> host inside STFT.transform (utils/stft.py:85-89); here input and output stay in HBM.
+Padded batches of different lengths go through the *_batch methods (STFT.transform_batch / inverse_batch,
+TacotronSTFT.mel_spectrogram_batch, Denoiser.denoise_batch) and to_pcm16: every entry gets what the plain method gives it alone, bit
+for bit, and zeros behind its end.
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
 window); the mel filterbank restates librosa.filters.mel's defaults (Slaney scale, area normalisation) because librosa is
 an unpinned dependency that this image does not have.
@@ -20,7 +23,7 @@ from scipy.signal import get_window
 from . import _lib
 
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
-           "dynamic_range_decompression"]
+           "dynamic_range_decompression", "to_pcm16"]
 
 
 def _ru(a, b):
@@ -30,6 +33,65 @@ def _ru(a, b):
 def _need_cuda(t, what):
     if not (torch.is_tensor(t) and t.is_cuda):
         raise RuntimeError("%s: expected a tensor in HBM (cuda); there is no CPU path" % what)
+
+
+def _host_lengths(lengths, B, lo, hi, what, unit):
+    """`lengths` (host or device tensor, or a sequence of integers) as a validated host int64 [B], every value in [lo, hi]: the
+    checks of WaveGlow.infer_batch.  One read-back when they live on the device."""
+    T2SError = _lib.T2SError
+    try:
+        lens = torch.as_tensor(lengths)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise T2SError("%s: lengths must be a tensor or a sequence of integers (%s)" % (what, e))
+    if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+        raise T2SError("%s: lengths must be integers, got %s" % (what, lens.dtype))
+    lens = lens.detach().to("cpu", torch.int64)
+    if lens.dim() != 1 or lens.numel() != B:
+        raise T2SError("%s: lengths has shape %s, the batch holds %d entries" % (what, tuple(lens.shape), B))
+    if B == 0:
+        raise T2SError("%s: an empty batch" % what)
+    if int(lens.min()) < lo:
+        b = int(lens.argmin())
+        raise T2SError("%s: entry %d has %d %s, the minimum is %d (lengths %s)" % (what, b, int(lens[b]), unit, lo, lens.tolist()))
+    if int(lens.max()) > hi:
+        b = int(lens.argmax())
+        raise T2SError("%s: entry %d has %d %s, the padded batch holds %d (lengths %s)" % (what, b, int(lens[b]), unit, hi,
+                                                                                         lens.tolist()))
+    return lens
+
+
+def _both(lens, dev):
+    """host int64 [B] -> (int32 on the device for the kernels, int32 on the host for the entry point's own reads)"""
+    host = lens.to(torch.int32).contiguous()
+    return host.to(dev), host
+
+
+def to_pcm16(audio, lengths=None):
+    """Waveform in [-1, 1) -> int16 PCM on the device, the reference's `audio * 32768` then `astype('int16')` (truncation toward
+    zero) - with saturation, which is a stated departure: numpy's cast of an out-of-range float is undefined, here +1.0 gives
+    32767, anything beyond the range its nearest end, NaN 0.  `audio` [..., N] float32 or float16 in HBM; `lengths` (one per row,
+    host or device or a sequence; None: every sample) zeroes the samples at and behind each row's end, which are not read.
+    Returns an int16 tensor of audio's shape."""
+    _need_cuda(audio, "to_pcm16")
+    if audio.dim() == 0 or audio.numel() == 0:
+        raise _lib.T2SError("to_pcm16: audio must hold samples, got shape %s" % (tuple(audio.shape),))
+    x = audio.detach()
+    if x.dtype not in (torch.float32, torch.float16):
+        x = x.to(torch.float32)
+    N = x.size(-1)
+    rows = x.numel() // N
+    if x.dim() == 2 and x.stride(1) == 1 and (rows == 1 or x.stride(0) >= N):
+        ldx = x.stride(0) if rows > 1 else N                  # a view of wider rows goes in as it is
+    else:
+        x = x.contiguous()
+        ldx = N
+    lens_d = None
+    if lengths is not None:
+        lens_d, _ = _both(_host_lengths(lengths, rows, 0, N, "to_pcm16", "samples"), x.device)
+    out = torch.empty(audio.shape, dtype=torch.int16, device=x.device)
+    _lib.call("t2s_pcm16", _lib.ptr(x), int(x.dtype == torch.float16), rows, N, ldx, _lib.ptr(lens_d), _lib.ptr(out),
+              _lib.current_stream())
+    return out
 
 
 def dynamic_range_compression(x, C=1, clip_val=1e-5):
@@ -164,6 +226,83 @@ class STFT(torch.nn.Module):
         self.magnitude, self.phase = self.transform(input_data)
         return self.inverse(self.magnitude, self.phase)
 
+    # -- padded batches of different lengths ----------------------------------------------------------------------------
+    # Entry b of a padded batch gets what it gets alone (bit for bit: the same kernels' arithmetic on its own extent, the
+    # contractions launched at its own frame count) whatever the padding holds, and zeros behind its end.
+    def _transform_ragged(self, input_data, lens, want_mag=True, want_phase=True, ld_mt=0):
+        """`lens`: validated host int64 [B] (samples).  Returns (mag, phase, magT, F, frame counts host int64)."""
+        _need_cuda(self.forward_basis, "STFT (call .cuda() on the module)")
+        x = input_data.detach().to(torch.float32).contiguous()
+        B, T = x.shape
+        n_fft, hop = self.filter_length, self.hop_length
+        c, F = n_fft // 2 + 1, T // hop + 1
+        dev = x.device
+        ldp = _ru(T + n_fft, 4)
+        xp = torch.empty(B, ldp, device=dev)
+        ft = torch.empty(B, F, 2 * c, device=dev)
+        mag = torch.empty(B, c, F, device=dev) if want_mag else None
+        ph = torch.empty(B, c, F, device=dev) if want_phase else None
+        magT = torch.empty(B * F, ld_mt, device=dev) if ld_mt else None
+        lens_d, lens_h = _both(lens, dev)
+        p = _lib.ptr
+        _lib.call("t2s_stft_transform_ragged", p(x), B, T, p(lens_d), p(lens_h), p(self.forward_basis), n_fft, hop, p(xp), ldp,
+                  p(ft), p(mag) if mag is not None else None, p(ph) if ph is not None else None,
+                  p(magT) if magT is not None else None, ld_mt, _lib.current_stream())
+        self._keep = (x, xp, ft, lens_d)
+        return mag, ph, magT, F, lens // hop + 1
+
+    def _batch_audio(self, audio, lengths, what):
+        """[B, T] or [B, 1, T] in HBM and its lengths -> ([B, T], validated host int64 lengths in (filter_length / 2, T])"""
+        _need_cuda(audio, what)
+        if audio.dim() == 3 and audio.size(1) == 1:
+            audio = audio[:, 0]
+        if audio.dim() != 2:
+            raise _lib.T2SError("%s: audio must be [B, T] or [B, 1, T], got %s" % (what, tuple(audio.shape)))
+        B, T = audio.shape
+        # (an entry of at most filter_length / 2 samples cannot be reflect-padded: the solo call refuses it too)
+        return audio, _host_lengths(lengths, B, self.filter_length // 2 + 1, T, what, "samples")
+
+    def transform_batch(self, audio, lengths):
+        """audio [B, T] padded, lengths [B] -> (magnitude, phase, frame_lengths): entry b's first 1 + lengths[b] // hop_length
+        frames are transform(audio[b:b+1, :lengths[b]])'s, the rest zeros; frame_lengths int64 [B] on the device."""
+        audio, lens = self._batch_audio(audio, lengths, "STFT.transform_batch")
+        mag, ph, _, _, fl = self._transform_ragged(audio, lens)
+        return mag, ph, fl.to(audio.device)
+
+    def _inverse_ragged(self, magnitude, phase, fl, _bias=None, _strength=0.0):
+        """`fl`: validated host int64 [B] (frames, in [2, F]).  Returns audio [B, 1, hop (F - 1)]."""
+        mag = magnitude.detach().to(torch.float32).contiguous()
+        ph = phase.detach().to(torch.float32).contiguous()
+        B, c, F = mag.shape
+        n_fft, hop = self.filter_length, self.hop_length
+        dev = mag.device
+        rc = torch.empty(B * F, self._ld_rc, device=dev)
+        frames = torch.empty(B, F, n_fft, device=dev)
+        out = torch.empty(B, 1, hop * (F - 1), device=dev)
+        fl_d, fl_h = _both(fl, dev)
+        p = _lib.ptr
+        has_win = self.window is not None
+        _lib.call("t2s_stft_inverse_ragged", p(mag), p(ph), B, F, p(fl_d), p(fl_h), n_fft, hop, p(self._inv_basis_t), self._ld_rc,
+                  p(_bias) if _bias is not None else None, float(_strength), p(self._win_sq) if has_win else None,
+                  float(np.finfo(np.float32).tiny), p(rc), p(frames), p(out), _lib.current_stream())
+        self._keep_inv = (mag, ph, rc, frames, _bias, fl_d)
+        return out
+
+    def inverse_batch(self, magnitude, phase, frame_lengths):
+        """(magnitude, phase) [B, filter_length/2 + 1, F] padded, frame_lengths [B] in [2, F] -> (audio [B, 1, hop (F - 1)],
+        audio_lengths): entry b's first hop (frame_lengths[b] - 1) samples are inverse() of its own frames, the rest zeros;
+        frames behind an entry's end are not read.  audio_lengths int64 [B] on the device."""
+        what = "STFT.inverse_batch"
+        _need_cuda(magnitude, what)
+        _need_cuda(phase, what)
+        if magnitude.dim() != 3 or magnitude.shape != phase.shape or magnitude.size(1) != self.filter_length // 2 + 1:
+            raise _lib.T2SError("%s: magnitude and phase must both be [B, %d, F], got %s and %s"
+                                % (what, self.filter_length // 2 + 1, tuple(magnitude.shape), tuple(phase.shape)))
+        B, _, F = magnitude.shape
+        fl = _host_lengths(frame_lengths, B, 2, F, what, "frames")
+        out = self._inverse_ragged(magnitude, phase, fl)
+        return out, ((fl - 1) * self.hop_length).to(out.device)
+
 
 class TacotronSTFT(torch.nn.Module):
     """log-mel spectrogram of the reference (utils/layers.py:42-79)."""
@@ -202,6 +341,28 @@ class TacotronSTFT(torch.nn.Module):
         self._keep = magT
         return mel
 
+    def mel_spectrogram_batch(self, y, lengths):
+        """y [B, T] padded (in HBM), lengths [B] -> (mel [B, n_mel_channels, 1 + T // hop], mel_lengths): entry b's first
+        1 + lengths[b] // hop columns are mel_spectrogram(y[b:b+1, :lengths[b]])'s, the columns behind are zeros (what the
+        reference's collate pads with, not log(clip)).  The [-1, 1] assertion judges the valid samples; the padding may hold
+        anything.  mel_lengths int64 [B] on the device."""
+        what = "TacotronSTFT.mel_spectrogram_batch"
+        y, lens = self.stft_fn._batch_audio(y, lengths, what)
+        B, T = y.shape
+        lens_d = lens.to(y.device)
+        valid = torch.arange(T, device=y.device)[None, :] < lens_d[:, None]
+        lo, hi = torch.aminmax(torch.where(valid, y.detach(), torch.zeros((), dtype=y.dtype, device=y.device)))
+        if float(lo) < -1 or float(hi) > 1:
+            raise AssertionError("audio outside [-1, 1]")
+        _, _, magT, F, fl = self.stft_fn._transform_ragged(y, lens, want_mag=False, want_phase=False, ld_mt=self._ld_mt)
+        mel = torch.empty(B, self.n_mel_channels, F, device=y.device)
+        fl_d, fl_h = _both(fl, y.device)
+        p = _lib.ptr
+        _lib.call("t2s_mel_from_mag_ragged", p(magT), self._ld_mt, B, F, p(fl_d), p(fl_h), p(self._mel_basis_p),
+                  self.n_mel_channels, 1e-5, p(mel), _lib.current_stream())
+        self._keep = (magT, fl_d)
+        return mel, fl.to(y.device)
+
 
 class Denoiser(torch.nn.Module):
     """Removes the vocoder's bias spectrum from its output (waveglow/denoiser.py:7-40)."""
@@ -226,3 +387,15 @@ class Denoiser(torch.nn.Module):
         mag, ph = self.stft.transform(audio.float())
         # spectral subtraction + clamp are fused into the recombination kernel of the inverse transform
         return self.stft.inverse(mag, ph, _bias=self.bias_spec.reshape(-1).contiguous(), _strength=strength)
+
+    def denoise_batch(self, audio, lengths, strength=0.1):
+        """forward() on a padded batch: audio [B, T] (or [B, 1, T]) float32 or float16 and lengths [B], e.g. WaveGlow.infer_batch's
+        two results as returned.  Returns (audio [B, 1, hop (T // hop)] float32, audio_lengths int64 [B] on the device): entry b's
+        first hop (lengths[b] // hop) samples are forward(audio[b:b+1, :lengths[b]], strength)'s bit for bit - its reflect padding
+        mirrors about its own end and its overlap-add counts its own frames - and the rest of its row is zeros.  An entry of at
+        most filter_length / 2 samples is refused, as forward() refuses it alone."""
+        what = "Denoiser.denoise_batch"
+        audio, lens = self.stft._batch_audio(audio, lengths, what)
+        mag, ph, _, _, fl = self.stft._transform_ragged(audio.float(), lens)
+        out = self.stft._inverse_ragged(mag, ph, fl, _bias=self.bias_spec.reshape(-1).contiguous(), _strength=strength)
+        return out, ((fl - 1) * self.stft.hop_length).to(out.device)

@@ -62,4 +62,68 @@ int t2s_stft_inverse(const float* mag, const float* phase, int B, int F, int n_f
     return T2S_OK;
 }
 
+// ---- a padded batch with per-entry lengths (include/t2s_hip.h) -------------------------------------------------------------------
+// Each contraction is launched per entry with the entry's own item count, read from the host copy of the lengths: the dispatcher
+// behind frames_gemm chooses GEMV or matrix cores by item count, so this is what makes an entry's bits those of its solo call.
+
+int t2s_stft_transform_ragged(const float* audio, int B, int T, const int* lengths, const int* lengths_host, const float* fwd_basis,
+                              int n_fft, int hop, float* xp, long ldp, float* ft, float* mag, float* phase, float* magT, long ld_mt,
+                              void* stream) {
+    const int c = n_fft / 2 + 1;
+    if (!audio || !lengths || !lengths_host || !fwd_basis || !xp || !ft || B <= 0 || B > 65535 || T <= n_fft / 2 || n_fft <= 0 ||
+        (n_fft & 15) || hop <= 0 || (hop & 3) || (ldp & 3) || ldp < T + n_fft || n_fft > 4096 ||
+        (magT && (ld_mt < c || (ld_mt & 15))))
+        return T2S_EINVAL;
+    const int F = T / hop + 1;
+    for (int b = 0; b < B; ++b)
+        if (lengths_host[b] <= n_fft / 2 || lengths_host[b] > T) return T2S_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    T2S_CHECK_HIP(t2s_launch_reflect_pad_ragged(audio, B, T, lengths, n_fft / 2, xp, ldp, s));
+    for (int b = 0; b < B; ++b)
+        T2S_CHECK_HIP(frames_gemm(fwd_basis, 2 * c, n_fft, xp + (size_t)b * ldp, hop, lengths_host[b] / hop + 1,
+                                  ft + (size_t)b * F * 2 * c, 2 * c, 1, s));
+    if (mag || phase || magT)
+        T2S_CHECK_HIP(t2s_launch_stft_mag_phase_ragged(ft, B, F, c, 2 * c, lengths, hop, T, n_fft / 2, mag, phase, magT, ld_mt, s));
+    return T2S_OK;
+}
+
+int t2s_mel_from_mag_ragged(const float* magT, long ld_mt, int B, int F, const int* frames, const int* frames_host,
+                            const float* mel_basis_p, int n_mel, float clip, float* mel, void* stream) {
+    if (!magT || !frames || !frames_host || !mel_basis_p || !mel || B <= 0 || F <= 0 || n_mel <= 0 || ld_mt <= 0 || (ld_mt & 15))
+        return T2S_EINVAL;
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] < 1 || frames_host[b] > F) return T2S_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    for (int b = 0; b < B; ++b)
+        T2S_CHECK_HIP(frames_gemm(mel_basis_p, n_mel, (int)ld_mt, magT + (size_t)b * F * ld_mt, ld_mt, frames_host[b],
+                                  mel + (size_t)b * n_mel * F, 1, F, s));
+    T2S_CHECK_HIP(t2s_launch_log_clamp_ragged(mel, B, n_mel, F, frames, clip, s));      // (clip <= 0: only the zeros behind)
+    return T2S_OK;
+}
+
+int t2s_stft_inverse_ragged(const float* mag, const float* phase, int B, int F, const int* frames, const int* frames_host, int n_fft,
+                            int hop, const float* inv_basis_t, long ld_rc, const float* bias, float strength, const float* win_sq,
+                            float tiny, float* rc, float* frames_buf, float* out, void* stream) {
+    const int c = n_fft / 2 + 1;
+    if (!mag || !phase || !frames || !frames_host || !inv_basis_t || !rc || !frames_buf || !out || B <= 0 || B > 65535 || F <= 1 ||
+        n_fft <= 0 || hop <= 0 || ld_rc < 2 * c || (ld_rc & 15))
+        return T2S_EINVAL;
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] < 2 || frames_host[b] > F) return T2S_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    T2S_CHECK_HIP(t2s_launch_stft_recombine_ragged(mag, phase, B, F, c, frames, bias, strength, rc, ld_rc, s));
+    for (int b = 0; b < B; ++b)
+        T2S_CHECK_HIP(frames_gemm(inv_basis_t, n_fft, (int)ld_rc, rc + (size_t)b * F * ld_rc, ld_rc, frames_host[b],
+                                  frames_buf + (size_t)b * F * n_fft, n_fft, 1, s));
+    T2S_CHECK_HIP(t2s_launch_stft_overlap_add_ragged(frames_buf, win_sq, B, F, frames, n_fft, hop, (float)n_fft / (float)hop, tiny,
+                                                     out, hop * (F - 1), s));
+    return T2S_OK;
+}
+
+int t2s_pcm16(const void* x, int is_half, int B, int N, long ldx, const int* lengths, short* out, void* stream) {
+    if (!x || !out || B <= 0 || B > 65535 || N <= 0 || ldx < N) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_pcm16(x, is_half, B, N, ldx, lengths, out, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 }  // extern "C"
