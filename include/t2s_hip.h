@@ -808,6 +808,10 @@ int t2s_planes_to_f32(const void* X_hi, const void* X_lo, int B, int C, int L, i
                       int accumulate, void* stream);
 
 /* ---- audio front-end / back-end ------------------------------------------------------------------
+ * Each of the three stages below is one body and one set of kernels behind two entry points: the plain one here is the
+ * lengths-free form (every entry has the batch's extent, T samples or F frames) of its _ragged partner further down, with the same
+ * checks.  B <= 65535 for t2s_stft_transform and t2s_stft_inverse (the batch index is a grid y / z dimension; a larger B is
+ * T2S_EINVAL); ld_mt > 0 for t2s_mel_from_mag.
  * STFT.transform (utils/stft.py:72-99): audio [B][T] -> frames F = T/hop + 1, bins c = n_fft/2 + 1.
  *   fwd_basis [2c][n_fft] (windowed Fourier basis, real rows then imaginary rows); scratch xp [B][ldp] (ldp >= T + n_fft,
  *   ldp % 4 == 0) and ft [B][F][2c]; outputs (each optional) mag / phase [B][c][F] and magT [B*F][ld_mt] (zero padded rows:
@@ -827,7 +831,8 @@ int t2s_stft_inverse(const float* mag, const float* phase, int B, int F, int n_f
                      void* stream);
 /* ---- The three above on a padded batch whose entries differ in length, and int16 PCM (ABI v4, compatible additions) ----
  * Entry b of the batch holds lengths[b] samples (or frames[b] frames); every entry gets what it gets alone, whatever the padding
- * holds, and +0 behind its end.  Each entry point takes its partner's arguments and checks plus the lengths twice: `lengths` /
+ * holds, and +0 behind its end.  Each entry point runs its partner's code with the lengths: it takes the partner's arguments and
+ * checks plus the lengths twice: `lengths` /
  * `frames` ([B] int32 in device memory, read by the kernels; NULL: T2S_EINVAL) and `lengths_host` / `frames_host` (the same values
  * in host memory; NULL: T2S_EINVAL).  The host copy is read before the call returns and validated before the first launch (a value
  * out of range: T2S_EINVAL, nothing launched); the contractions are launched per entry with the entry's own item count from it,

@@ -273,6 +273,27 @@ def test_audio_refusals():
 
     for kw in (dict(F=1), dict(ld_rc=64), dict(ld_rc=48)):
         assert inv(**kw) == EINVAL, kw
+    # the batch index is a grid y / z dimension: B = 65536 is refused, not left to fail at the launch
+    big_B = 65536
+    assert lib.t2s_stft_transform(_p(audio), big_B, T, _p(fwd), n_fft, hop, _p(outs[0]), R.ru(T + n_fft, 4), _p(outs[1]), _p(outs[2]),
+                                  _p(outs[3]), _p(outs[4]), 48, _st()) == EINVAL
+    assert lib.t2s_stft_inverse(_p(mag), _p(ph), big_B, F_, n_fft, hop, _p(inv_t), 80, None, 0.0, _p(win_sq), TINY, _p(iouts[0]),
+                                _p(iouts[1]), _p(iouts[2]), _st()) == EINVAL
+    # t2s_mel_from_mag: rows of no columns
+    basis, mel = torch.zeros(17, 48, device=DEV), Guarded(B, 17, F_)
+    outs.append(mel)
+    before.append(_bits(mel))
+    assert lib.t2s_mel_from_mag(_p(outs[4]), 0, B, F_, _p(basis), 17, 1e-5, _p(mel), _st()) == EINVAL
+    # the partners that take lengths refuse a NULL device array and a NULL host copy
+    ld, lh = torch.full((B,), T, dtype=torch.int32, device=DEV), torch.full((B,), T, dtype=torch.int32)
+    fd, fh = torch.full((B,), F_, dtype=torch.int32, device=DEV), torch.full((B,), F_, dtype=torch.int32)
+    for d, h in ((None, lh), (ld, None)):
+        assert lib.t2s_stft_transform_ragged(_p(audio), B, T, _p(d), _p(h), _p(fwd), n_fft, hop, _p(outs[0]), R.ru(T + n_fft, 4),
+                                             _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(outs[4]), 48, _st()) == EINVAL
+    for d, h in ((None, fh), (fd, None)):
+        assert lib.t2s_mel_from_mag_ragged(_p(outs[4]), 48, B, F_, _p(d), _p(h), _p(basis), 17, 1e-5, _p(mel), _st()) == EINVAL
+        assert lib.t2s_stft_inverse_ragged(_p(mag), _p(ph), B, F_, _p(d), _p(h), n_fft, hop, _p(inv_t), 80, None, 0.0, _p(win_sq), TINY,
+                                           _p(iouts[0]), _p(iouts[1]), _p(iouts[2]), _st()) == EINVAL
     torch.cuda.synchronize()
     for g, b in zip(outs + iouts, before + ibefore):
         assert torch.equal(_bits(g), b), "a refused call wrote"

@@ -288,6 +288,45 @@ def test_stft_inverse_ragged(name, order):
             _same(tag + " equal lengths", _inverse(dev(mag_row), dev(ph_row), inv_d, n_fft, hop, ws_d, frames=[F_] * B, **dkw), row)
 
 
+# ---- a whole batch with and without lengths -----------------------------------------------------------------------------------------
+# (n_fft, hop, window, T): 8 frames (the GEMV path), 41 frames (matrix cores), a hop that does not divide n_fft, no window
+FULL = {"64-16-F8": (64, 16, "hann", 127), "64-16-F41": (64, 16, "hann", 645), "48-20": (48, 20, "hann", 215),
+        "64-16-nowin": (64, 16, None, 645)}
+
+
+@pytest.mark.parametrize("name", list(FULL))
+def test_full_lengths_are_the_plain_call(name):
+    """One plain call on a batch of 3 against one ragged call on the same batch with every length T (every frame count F): the same
+    kernels without and with the lengths pointer at the same item counts, so mag, phase, magT, the waveform of the inverse (plain
+    and with the denoiser's bias) and the mel (log and raw) are the same bits."""
+    _lib.load()
+    n_fft, hop, window, T = FULL[name]
+    B, c, F_ = 3, n_fft // 2 + 1, T // hop + 1
+    gen = torch.Generator().manual_seed(sum(map(ord, name)))
+    audio = 0.4 * torch.rand(B, T, generator=gen) - 0.2 + 0.5 * torch.sin(0.21 * torch.arange(T).float())[None] * torch.rand(
+        B, 1, generator=gen)
+    fwd, inv_t, win_sq = R.stft_operands(n_fft, hop, n_fft, window)
+    audio_d, fwd_d, inv_d = dev(audio), dev(fwd), dev(inv_t)
+    ws_d = dev(win_sq) if win_sq is not None else None
+    ldp, ld_mt = R.ru(T + n_fft, 4), R.ru(c, 16)
+    mag, ph, magT = _transform(audio_d, fwd_d, n_fft, hop, ldp, ld_mt)
+    assert float(mag.t.abs().max()) > 0.0
+    for nm, got, want in zip(("mag", "phase", "magT"), _transform(audio_d, fwd_d, n_fft, hop, ldp, ld_mt, [T] * B), (mag, ph, magT)):
+        _same("%s %s" % (name, nm), got, want)
+    bias_d = dev((torch.rand(c, generator=gen) + 0.1) * float(mag.t.mean()))
+    for dkw in ({}, dict(bias_d=bias_d, strength=1.0)):
+        want = _inverse(mag.t, ph.t, inv_d, n_fft, hop, ws_d, **dkw)
+        assert float(want.t.abs().max()) > 0.0
+        _same("%s inverse %s" % (name, sorted(dkw)), _inverse(mag.t, ph.t, inv_d, n_fft, hop, ws_d, frames=[F_] * B, **dkw), want)
+    n_mel = 17
+    basis = torch.zeros(n_mel, ld_mt)
+    basis[:, :c] = torch.rand(n_mel, c, generator=gen) * (torch.rand(n_mel, c, generator=gen) < 0.3).float() * 0.05
+    basis_d = dev(basis)
+    for clip in (1e-5, 0.0):
+        _same("%s mel clip %g" % (name, clip), _mel(magT.t, ld_mt, B, F_, basis_d, n_mel, clip, [F_] * B),
+              _mel(magT.t, ld_mt, B, F_, basis_d, n_mel, clip))
+
+
 # ---- PCM ----------------------------------------------------------------------------------------------------------------------------
 PCM_GUARD, PCM_SENTINEL = 63, 0x7A5A          # an odd guard: the output starts at an odd element
 

@@ -175,7 +175,12 @@ class STFT(torch.nn.Module):
         self.register_buffer("_win_sq", win_sq if win_sq is not None else torch.zeros(0), persistent=False)
 
     # -- helpers ------------------------------------------------------------------------------------------------------
-    def _transform(self, input_data, want_mag=True, want_phase=True, ld_mt=0):
+    # Without lengths a call is the whole batch at its full extent.  With them (a padded batch), entry b gets what it gets alone
+    # (bit for bit: the same kernels' arithmetic on its own extent, the contractions launched at its own frame count) whatever the
+    # padding holds, and zeros behind its end.
+    def _transform(self, input_data, lens=None, want_mag=True, want_phase=True, ld_mt=0):
+        """`lens`: None, or validated host int64 [B] (samples).  Returns (mag, phase, magT, F, frame counts: host int64 [B], None
+        without `lens`)."""
         _need_cuda(input_data, "STFT.transform")
         _need_cuda(self.forward_basis, "STFT (call .cuda() on the module)")
         x = input_data.detach().to(torch.float32).contiguous()
@@ -190,22 +195,18 @@ class STFT(torch.nn.Module):
         ph = torch.empty(B, c, F, device=dev) if want_phase else None
         magT = torch.empty(B * F, ld_mt, device=dev) if ld_mt else None
         p = _lib.ptr
-        _lib.call("t2s_stft_transform", p(x), B, T, p(self.forward_basis), n_fft, hop, p(xp), ldp, p(ft),
-                  p(mag) if mag is not None else None, p(ph) if ph is not None else None,
-                  p(magT) if magT is not None else None, ld_mt, _lib.current_stream())
-        self._keep = (x, xp, ft)
-        return mag, ph, magT, F
+        rest = (p(self.forward_basis), n_fft, hop, p(xp), ldp, p(ft), p(mag), p(ph), p(magT), ld_mt, _lib.current_stream())
+        if lens is None:
+            _lib.call("t2s_stft_transform", p(x), B, T, *rest)
+            self._keep = (x, xp, ft)
+            return mag, ph, magT, F, None
+        lens_d, lens_h = _both(lens, dev)
+        _lib.call("t2s_stft_transform_ragged", p(x), B, T, p(lens_d), p(lens_h), *rest)
+        self._keep = (x, xp, ft, lens_d)
+        return mag, ph, magT, F, lens // hop + 1
 
-    # -- reference surface --------------------------------------------------------------------------------------------
-    def transform(self, input_data):
-        """audio [B, T] -> (magnitude, phase), each [B, filter_length/2 + 1, 1 + T // hop_length]"""
-        self.num_samples = input_data.size(1)
-        mag, ph, _, _ = self._transform(input_data)
-        return mag, ph
-
-    def inverse(self, magnitude, phase, _bias=None, _strength=0.0):
-        """(magnitude, phase) -> audio [B, 1, hop_length * (frames - 1)]"""
-        _need_cuda(magnitude, "STFT.inverse")
+    def _inverse(self, magnitude, phase, fl=None, _bias=None, _strength=0.0):
+        """`fl`: None, or validated host int64 [B] (frames, in [2, F]).  Returns audio [B, 1, hop (F - 1)]."""
         mag = magnitude.detach().to(torch.float32).contiguous()
         ph = phase.detach().to(torch.float32).contiguous()
         B, c, F = mag.shape
@@ -215,42 +216,35 @@ class STFT(torch.nn.Module):
         frames = torch.empty(B, F, n_fft, device=dev)
         out = torch.empty(B, 1, hop * (F - 1), device=dev)
         p = _lib.ptr
-        has_win = self.window is not None
-        _lib.call("t2s_stft_inverse", p(mag), p(ph), B, F, n_fft, hop, p(self._inv_basis_t), self._ld_rc,
-                  p(_bias) if _bias is not None else None, float(_strength), p(self._win_sq) if has_win else None,
-                  float(np.finfo(np.float32).tiny), p(rc), p(frames), p(out), _lib.current_stream())
-        self._keep_inv = (mag, ph, rc, frames, _bias)
+        rest = (n_fft, hop, p(self._inv_basis_t), self._ld_rc, p(_bias), float(_strength),
+                p(self._win_sq) if self.window is not None else None, float(np.finfo(np.float32).tiny), p(rc), p(frames), p(out),
+                _lib.current_stream())
+        if fl is None:
+            _lib.call("t2s_stft_inverse", p(mag), p(ph), B, F, *rest)
+            self._keep_inv = (mag, ph, rc, frames, _bias)
+            return out
+        fl_d, fl_h = _both(fl, dev)
+        _lib.call("t2s_stft_inverse_ragged", p(mag), p(ph), B, F, p(fl_d), p(fl_h), *rest)
+        self._keep_inv = (mag, ph, rc, frames, _bias, fl_d)
         return out
+
+    # -- reference surface --------------------------------------------------------------------------------------------
+    def transform(self, input_data):
+        """audio [B, T] -> (magnitude, phase), each [B, filter_length/2 + 1, 1 + T // hop_length]"""
+        self.num_samples = input_data.size(1)
+        mag, ph, _, _, _ = self._transform(input_data)
+        return mag, ph
+
+    def inverse(self, magnitude, phase, _bias=None, _strength=0.0):
+        """(magnitude, phase) -> audio [B, 1, hop_length * (frames - 1)]"""
+        _need_cuda(magnitude, "STFT.inverse")
+        return self._inverse(magnitude, phase, None, _bias, _strength)
 
     def forward(self, input_data):
         self.magnitude, self.phase = self.transform(input_data)
         return self.inverse(self.magnitude, self.phase)
 
     # -- padded batches of different lengths ----------------------------------------------------------------------------
-    # Entry b of a padded batch gets what it gets alone (bit for bit: the same kernels' arithmetic on its own extent, the
-    # contractions launched at its own frame count) whatever the padding holds, and zeros behind its end.
-    def _transform_ragged(self, input_data, lens, want_mag=True, want_phase=True, ld_mt=0):
-        """`lens`: validated host int64 [B] (samples).  Returns (mag, phase, magT, F, frame counts host int64)."""
-        _need_cuda(self.forward_basis, "STFT (call .cuda() on the module)")
-        x = input_data.detach().to(torch.float32).contiguous()
-        B, T = x.shape
-        n_fft, hop = self.filter_length, self.hop_length
-        c, F = n_fft // 2 + 1, T // hop + 1
-        dev = x.device
-        ldp = _ru(T + n_fft, 4)
-        xp = torch.empty(B, ldp, device=dev)
-        ft = torch.empty(B, F, 2 * c, device=dev)
-        mag = torch.empty(B, c, F, device=dev) if want_mag else None
-        ph = torch.empty(B, c, F, device=dev) if want_phase else None
-        magT = torch.empty(B * F, ld_mt, device=dev) if ld_mt else None
-        lens_d, lens_h = _both(lens, dev)
-        p = _lib.ptr
-        _lib.call("t2s_stft_transform_ragged", p(x), B, T, p(lens_d), p(lens_h), p(self.forward_basis), n_fft, hop, p(xp), ldp,
-                  p(ft), p(mag) if mag is not None else None, p(ph) if ph is not None else None,
-                  p(magT) if magT is not None else None, ld_mt, _lib.current_stream())
-        self._keep = (x, xp, ft, lens_d)
-        return mag, ph, magT, F, lens // hop + 1
-
     def _batch_audio(self, audio, lengths, what):
         """[B, T] or [B, 1, T] in HBM and its lengths -> ([B, T], validated host int64 lengths in (filter_length / 2, T])"""
         _need_cuda(audio, what)
@@ -266,27 +260,8 @@ class STFT(torch.nn.Module):
         """audio [B, T] padded, lengths [B] -> (magnitude, phase, frame_lengths): entry b's first 1 + lengths[b] // hop_length
         frames are transform(audio[b:b+1, :lengths[b]])'s, the rest zeros; frame_lengths int64 [B] on the device."""
         audio, lens = self._batch_audio(audio, lengths, "STFT.transform_batch")
-        mag, ph, _, _, fl = self._transform_ragged(audio, lens)
+        mag, ph, _, _, fl = self._transform(audio, lens)
         return mag, ph, fl.to(audio.device)
-
-    def _inverse_ragged(self, magnitude, phase, fl, _bias=None, _strength=0.0):
-        """`fl`: validated host int64 [B] (frames, in [2, F]).  Returns audio [B, 1, hop (F - 1)]."""
-        mag = magnitude.detach().to(torch.float32).contiguous()
-        ph = phase.detach().to(torch.float32).contiguous()
-        B, c, F = mag.shape
-        n_fft, hop = self.filter_length, self.hop_length
-        dev = mag.device
-        rc = torch.empty(B * F, self._ld_rc, device=dev)
-        frames = torch.empty(B, F, n_fft, device=dev)
-        out = torch.empty(B, 1, hop * (F - 1), device=dev)
-        fl_d, fl_h = _both(fl, dev)
-        p = _lib.ptr
-        has_win = self.window is not None
-        _lib.call("t2s_stft_inverse_ragged", p(mag), p(ph), B, F, p(fl_d), p(fl_h), n_fft, hop, p(self._inv_basis_t), self._ld_rc,
-                  p(_bias) if _bias is not None else None, float(_strength), p(self._win_sq) if has_win else None,
-                  float(np.finfo(np.float32).tiny), p(rc), p(frames), p(out), _lib.current_stream())
-        self._keep_inv = (mag, ph, rc, frames, _bias, fl_d)
-        return out
 
     def inverse_batch(self, magnitude, phase, frame_lengths):
         """(magnitude, phase) [B, filter_length/2 + 1, F] padded, frame_lengths [B] in [2, F] -> (audio [B, 1, hop (F - 1)],
@@ -300,7 +275,7 @@ class STFT(torch.nn.Module):
                                 % (what, self.filter_length // 2 + 1, tuple(magnitude.shape), tuple(phase.shape)))
         B, _, F = magnitude.shape
         fl = _host_lengths(frame_lengths, B, 2, F, what, "frames")
-        out = self._inverse_ragged(magnitude, phase, fl)
+        out = self._inverse(magnitude, phase, fl)
         return out, ((fl - 1) * self.hop_length).to(out.device)
 
 
@@ -332,14 +307,23 @@ class TacotronSTFT(torch.nn.Module):
         lo, hi = torch.aminmax(y.detach())
         if float(lo) < -1 or float(hi) > 1:
             raise AssertionError("audio outside [-1, 1]")
-        _, _, magT, F = self.stft_fn._transform(y, want_mag=False, want_phase=False, ld_mt=self._ld_mt)
+        return self._mel(y)[0]
+
+    def _mel(self, y, lens=None):
+        """y [B, T] and None or validated host int64 lengths -> (log-mel [B, n_mel_channels, F], frame counts as STFT._transform's)"""
+        _, _, magT, F, fl = self.stft_fn._transform(y, lens, want_mag=False, want_phase=False, ld_mt=self._ld_mt)
         B = y.size(0)
         mel = torch.empty(B, self.n_mel_channels, F, device=y.device)
         p = _lib.ptr
-        _lib.call("t2s_mel_from_mag", p(magT), self._ld_mt, B, F, p(self._mel_basis_p), self.n_mel_channels, 1e-5, p(mel),
-                  _lib.current_stream())
-        self._keep = magT
-        return mel
+        rest = (p(self._mel_basis_p), self.n_mel_channels, 1e-5, p(mel), _lib.current_stream())
+        if fl is None:
+            _lib.call("t2s_mel_from_mag", p(magT), self._ld_mt, B, F, *rest)
+            self._keep = magT
+        else:
+            fl_d, fl_h = _both(fl, y.device)
+            _lib.call("t2s_mel_from_mag_ragged", p(magT), self._ld_mt, B, F, p(fl_d), p(fl_h), *rest)
+            self._keep = (magT, fl_d)
+        return mel, fl
 
     def mel_spectrogram_batch(self, y, lengths):
         """y [B, T] padded (in HBM), lengths [B] -> (mel [B, n_mel_channels, 1 + T // hop], mel_lengths): entry b's first
@@ -354,13 +338,7 @@ class TacotronSTFT(torch.nn.Module):
         lo, hi = torch.aminmax(torch.where(valid, y.detach(), torch.zeros((), dtype=y.dtype, device=y.device)))
         if float(lo) < -1 or float(hi) > 1:
             raise AssertionError("audio outside [-1, 1]")
-        _, _, magT, F, fl = self.stft_fn._transform_ragged(y, lens, want_mag=False, want_phase=False, ld_mt=self._ld_mt)
-        mel = torch.empty(B, self.n_mel_channels, F, device=y.device)
-        fl_d, fl_h = _both(fl, y.device)
-        p = _lib.ptr
-        _lib.call("t2s_mel_from_mag_ragged", p(magT), self._ld_mt, B, F, p(fl_d), p(fl_h), p(self._mel_basis_p),
-                  self.n_mel_channels, 1e-5, p(mel), _lib.current_stream())
-        self._keep = (magT, fl_d)
+        mel, fl = self._mel(y, lens)
         return mel, fl.to(y.device)
 
 
@@ -396,6 +374,6 @@ class Denoiser(torch.nn.Module):
         most filter_length / 2 samples is refused, as forward() refuses it alone."""
         what = "Denoiser.denoise_batch"
         audio, lens = self.stft._batch_audio(audio, lengths, what)
-        mag, ph, _, _, fl = self.stft._transform_ragged(audio.float(), lens)
-        out = self.stft._inverse_ragged(mag, ph, fl, _bias=self.bias_spec.reshape(-1).contiguous(), _strength=strength)
+        mag, ph, _, _, fl = self.stft._transform(audio.float(), lens)
+        out = self.stft._inverse(mag, ph, fl, _bias=self.bias_spec.reshape(-1).contiguous(), _strength=strength)
         return out, ((fl - 1) * self.stft.hop_length).to(out.device)

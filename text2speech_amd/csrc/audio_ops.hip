@@ -10,100 +10,21 @@
 #include "t2s_kernels.h"
 #include "audio_ops.h"
 
-// xp[b][i] = x[b][reflect(i - pad)], i in [0, T + 2 pad)   (F.pad(..., mode='reflect'), utils/stft.py:79-83)
-__global__ void reflect_pad_kernel(const float* __restrict__ x, int T, int pad, float* __restrict__ xp, long ldp) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = blockIdx.y;
-    if (i >= T + 2 * pad) return;
-    int j = i - pad;
-    if (j < 0) j = -j;
-    if (j >= T) j = 2 * (T - 1) - j;
-    xp[(size_t)b * ldp + i] = x[(size_t)b * T + j];
-}
-
-// ft [B][F][ld_ft] (real rows 0..c-1, imaginary rows c..2c-1)  ->  mag, phase [B][c][F]  and  magT [B*F][ld_mt] (zero padded)
-__global__ void stft_mag_phase_kernel(const float* __restrict__ ft, int F, int c, long ld_ft, float* __restrict__ mag,
-                                      float* __restrict__ phase, float* __restrict__ magT, long ld_mt) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;       // bin (or padding column of magT)
-    const int f = blockIdx.y, b = blockIdx.z;
-    if (k >= ld_mt && k >= c) return;
-    float m = 0.f;
-    if (k < c) {
-        const float* row = ft + ((size_t)b * F + f) * ld_ft;
-        const float re = row[k], im = row[c + k];
-        m = sqrtf(re * re + im * im);
-        if (mag) mag[((size_t)b * c + k) * F + f] = m;
-        if (phase) phase[((size_t)b * c + k) * F + f] = atan2f(im, re);
-    }
-    if (magT && k < ld_mt) magT[((size_t)b * F + f) * ld_mt + k] = m;
-}
-
-// rc[b*F + f][k] = k < c ? m cos(ph) : k < 2c ? m sin(ph) : 0,  m = max(mag - strength * bias[k], 0) when bias is given
-// (utils/stft.py:102-103; waveglow/denoiser.py:36-38)
-__global__ void stft_recombine_kernel(const float* __restrict__ mag, const float* __restrict__ phase, int F, int c,
-                                      const float* __restrict__ bias, float strength, float* __restrict__ rc, long ld_rc) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    const int f = blockIdx.y, b = blockIdx.z;
-    if (k >= ld_rc) return;
-    float v = 0.f;
-    if (k < 2 * c) {
-        const int bin = k < c ? k : k - c;
-        const size_t i = ((size_t)b * c + bin) * F + f;
-        float m = mag[i];
-        if (bias) m = fmaxf(m - bias[bin] * strength, 0.f);
-        const float ph = phase[i];
-        v = k < c ? m * cosf(ph) : m * sinf(ph);
-    }
-    rc[((size_t)b * F + f) * ld_rc + k] = v;
-}
-
-// out[b][n] = scale / wss[p] * sum_f frames[b][f][p - f hop],  p = n + n_fft/2,  wss[p] = sum_f win_sq[p - f hop]
-// (conv_transpose1d overlap-add, window-sum-square normalisation where it exceeds tiny, trim: utils/stft.py:105-127)
-__global__ void stft_overlap_add_kernel(const float* __restrict__ frames, const float* __restrict__ win_sq, int F, int n_fft,
-                                        int hop, float scale, float tiny, float* __restrict__ out, int n_out) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = blockIdx.y;
-    if (n >= n_out) return;
-    const int p = n + n_fft / 2;
-    int f_lo = (p - n_fft + hop) / hop;            // ceil((p - n_fft + 1) / hop) for p - n_fft + 1 > 0
-    if (p - n_fft + 1 <= 0) f_lo = 0;
-    int f_hi = p / hop;
-    if (f_hi > F - 1) f_hi = F - 1;
-    float acc = 0.f, wss = 0.f;
-    for (int f = f_lo; f <= f_hi; ++f) {
-        const int j = p - f * hop;
-        acc += frames[((size_t)b * F + f) * n_fft + j];
-        if (win_sq) wss += win_sq[j];
-    }
-    if (win_sq) {
-        if (wss > tiny) acc /= wss;
-        acc *= scale;
-    }
-    out[(size_t)b * n_out + n] = acc;
-}
-
-// x <- log(max(x, clip))   (dynamic_range_compression, utils/audio_processing.py:78-84 with C = 1)
-// The logarithm in double, rounded once - a precision choice, not a repair: the device's logf is 1.6 units in the last place
-// off at the clamp floor 1e-5 that every silent frame takes (-11.5129271 for -11.5129255; profiles/tail_kernel_tests.md);
-// this form gives the nearest f32, which a test can pin bit for bit, and a mel spectrogram is a few thousand elements.
-__global__ void log_clamp_kernel(float* x, size_t n, float clip) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] = (float)log((double)fmaxf(x[i], clip));
-}
-
 // ---- a padded batch whose entry b holds lengths[b] samples / frames[b] frames (device int32 [B]) ---------------------------------
-// New kernels beside the ones above, which keep their argument lists: for an element below the entry's end each evaluates its
-// partner's expression on the entry's own extent, behind the end it stores +0 (outputs) or nothing (scratch) and loads nothing.
-// The device values are clamped to the range the entry point has validated on the host copy, so an array that disagrees with its
-// host copy cannot move an address out of a buffer.
+// Every stage below is one kernel whose `lengths` / `frames` may be NULL: then each entry's extent is the batch's (T samples,
+// F frames).  With a pointer, an element below the entry's end gets the same expression evaluated on the entry's own extent;
+// behind the end the kernel stores +0 (outputs) or nothing (scratch) and loads nothing.  The device values are clamped to the range
+// the entry point has validated on the host copy, so an array that disagrees with its host copy cannot move an address out of a
+// buffer.
 static __device__ __forceinline__ int clamp_len(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// xp[b][i] = x[b][reflect(i - pad)] about sample lengths[b] - 1, i in [0, lengths[b] + 2 pad); the rest of the row is left alone
-__global__ void reflect_pad_ragged_kernel(const float* __restrict__ x, int T, const int* __restrict__ lengths, int pad,
-                                          float* __restrict__ xp, long ldp) {
+// xp[b][i] = x[b][reflect(i - pad)] about sample len - 1, i in [0, len + 2 pad), len = lengths ? lengths[b] : T; the rest of the row
+// is left alone   (F.pad(..., mode='reflect'), utils/stft.py:79-83)
+__global__ void reflect_pad_kernel(const float* __restrict__ x, int T, const int* __restrict__ lengths, int pad,
+                                   float* __restrict__ xp, long ldp) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
-    const int len = clamp_len(lengths[b], pad + 1, T);
+    const int len = lengths ? clamp_len(lengths[b], pad + 1, T) : T;
     if (i >= len + 2 * pad) return;
     int j = i - pad;
     if (j < 0) j = -j;
@@ -111,22 +32,23 @@ __global__ void reflect_pad_ragged_kernel(const float* __restrict__ x, int T, co
     xp[(size_t)b * ldp + i] = x[(size_t)b * T + j];
 }
 
-// stft_mag_phase_kernel for f < lengths[b] / hop + 1; +0 in mag, phase and magT behind (ft is not read there)
-__global__ void stft_mag_phase_ragged_kernel(const float* __restrict__ ft, int F, int c, long ld_ft, const int* __restrict__ lengths,
-                                             int hop, int T, int pad, float* __restrict__ mag, float* __restrict__ phase,
-                                             float* __restrict__ magT, long ld_mt) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+// ft [B][F][ld_ft] (real rows 0..c-1, imaginary rows c..2c-1)  ->  mag, phase [B][c][F]  and  magT [B*F][ld_mt] (zero padded);
+// with lengths, for f < lengths[b] / hop + 1, and +0 in mag, phase and magT behind (ft is not read there)
+__global__ void stft_mag_phase_kernel(const float* __restrict__ ft, int F, int c, long ld_ft, const int* __restrict__ lengths,
+                                      int hop, int T, int pad, float* __restrict__ mag, float* __restrict__ phase,
+                                      float* __restrict__ magT, long ld_mt) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;       // bin (or padding column of magT)
     const int f = blockIdx.y, b = blockIdx.z;
     if (k >= ld_mt && k >= c) return;
-    const bool live = f < clamp_len(lengths[b], pad + 1, T) / hop + 1;
+    const bool live = !lengths || f < clamp_len(lengths[b], pad + 1, T) / hop + 1;
     float m = 0.f;
     if (k < c) {
         float ph = 0.f;
         if (live) {
             const float* row = ft + ((size_t)b * F + f) * ld_ft;
             const float re = row[k], im = row[c + k];
-            // the contraction the compiler chooses for stft_mag_phase_kernel's `re * re + im * im`, spelled out: left to itself it
-            // rounds both squares here (a packed multiply), which moves the last bit of one magnitude in fifty
+            // the pinned rounding of the magnitude: im * im rounded, then one fused multiply-add.  Written `re * re + im * im` the
+            // compiler is free to round both squares (a packed multiply), which moves the last bit of one magnitude in fifty
             m = sqrtf(__builtin_fmaf(re, re, im * im));
             if (phase) ph = atan2f(im, re);
         }
@@ -136,13 +58,15 @@ __global__ void stft_mag_phase_ragged_kernel(const float* __restrict__ ft, int F
     if (magT && k < ld_mt) magT[((size_t)b * F + f) * ld_mt + k] = m;
 }
 
-// stft_recombine_kernel for f < frames[b]; behind, mag and phase are not read and rc (scratch) is not written
-__global__ void stft_recombine_ragged_kernel(const float* __restrict__ mag, const float* __restrict__ phase, int F, int c,
-                                             const int* __restrict__ frames, const float* __restrict__ bias, float strength,
-                                             float* __restrict__ rc, long ld_rc) {
+// rc[b*F + f][k] = k < c ? m cos(ph) : k < 2c ? m sin(ph) : 0,  m = max(mag - strength * bias[k], 0) when bias is given
+// (utils/stft.py:102-103; waveglow/denoiser.py:36-38); with frames, for f < frames[b]: behind, mag and phase are not read and rc
+// (scratch) is not written
+__global__ void stft_recombine_kernel(const float* __restrict__ mag, const float* __restrict__ phase, int F, int c,
+                                      const int* __restrict__ frames, const float* __restrict__ bias, float strength,
+                                      float* __restrict__ rc, long ld_rc) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     const int f = blockIdx.y, b = blockIdx.z;
-    if (k >= ld_rc || f >= clamp_len(frames[b], 2, F)) return;
+    if (k >= ld_rc || (frames && f >= clamp_len(frames[b], 2, F))) return;
     float v = 0.f;
     if (k < 2 * c) {
         const int bin = k < c ? k : k - c;
@@ -155,20 +79,22 @@ __global__ void stft_recombine_ragged_kernel(const float* __restrict__ mag, cons
     rc[((size_t)b * F + f) * ld_rc + k] = v;
 }
 
-// stft_overlap_add_kernel with frames[b] for F in the frame bounds (so in the window-sum-square too); +0 from sample hop (frames[b] - 1)
-__global__ void stft_overlap_add_ragged_kernel(const float* __restrict__ frames_buf, const float* __restrict__ win_sq, int F,
-                                               const int* __restrict__ frames, int n_fft, int hop, float scale, float tiny,
-                                               float* __restrict__ out, int n_out) {
+// out[b][n] = scale / wss[p] * sum_f frames_buf[b][f][p - f hop],  p = n + n_fft/2,  wss[p] = sum_f win_sq[p - f hop]
+// (conv_transpose1d overlap-add, window-sum-square normalisation where it exceeds tiny, trim: utils/stft.py:105-127), f below
+// Fb = frames ? frames[b] : F (so in the window-sum-square too); +0 from sample hop (Fb - 1), which without frames is n_out
+__global__ void stft_overlap_add_kernel(const float* __restrict__ frames_buf, const float* __restrict__ win_sq, int F,
+                                        const int* __restrict__ frames, int n_fft, int hop, float scale, float tiny,
+                                        float* __restrict__ out, int n_out) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     if (n >= n_out) return;
-    const int Fb = clamp_len(frames[b], 2, F);
+    const int Fb = frames ? clamp_len(frames[b], 2, F) : F;
     if (n >= hop * (Fb - 1)) {
         out[(size_t)b * n_out + n] = 0.f;
         return;
     }
     const int p = n + n_fft / 2;
-    int f_lo = (p - n_fft + hop) / hop;
+    int f_lo = (p - n_fft + hop) / hop;            // ceil((p - n_fft + 1) / hop) for p - n_fft + 1 > 0
     if (p - n_fft + 1 <= 0) f_lo = 0;
     int f_hi = p / hop;
     if (f_hi > Fb - 1) f_hi = Fb - 1;
@@ -185,13 +111,22 @@ __global__ void stft_overlap_add_ragged_kernel(const float* __restrict__ frames_
     out[(size_t)b * n_out + n] = acc;
 }
 
-// mel [B][n_mel][F]: log_clamp_kernel's expression for f < frames[b] (clip <= 0: the product stays), +0 behind (not read there)
-__global__ void log_clamp_ragged_kernel(float* x, int n_mel, int F, const int* __restrict__ frames, size_t n, float clip) {
+// x [B][n_mel][F] <- log(max(x, clip)) where clip > 0 (dynamic_range_compression, utils/audio_processing.py:78-84 with C = 1;
+// clip <= 0: the product stays); with frames, for f < frames[b], and +0 behind (not read there).
+// The logarithm in double, rounded once - a precision choice, not a repair: the device's logf is 1.6 units in the last place
+// off at the clamp floor 1e-5 that every silent frame takes (-11.5129271 for -11.5129255; profiles/tail_kernel_tests.md);
+// this form gives the nearest f32, which a test can pin bit for bit, and a mel spectrogram is a few thousand elements.
+__global__ void log_clamp_kernel(float* x, int n_mel, int F, const int* __restrict__ frames, size_t n, float clip) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int f = (int)(i % (size_t)F), b = (int)(i / ((size_t)n_mel * F));
-    if (f >= clamp_len(frames[b], 1, F)) x[i] = 0.f;
-    else if (clip > 0.f) x[i] = (float)log((double)fmaxf(x[i], clip));
+    if (frames) {
+        const int f = (int)(i % (size_t)F), b = (int)(i / ((size_t)n_mel * F));
+        if (f >= clamp_len(frames[b], 1, F)) {
+            x[i] = 0.f;
+            return;
+        }
+    }
+    if (clip > 0.f) x[i] = (float)log((double)fmaxf(x[i], clip));
 }
 
 // out[b][n] = (int16) trunc(x[b][n] * 32768), saturated to [-32768, 32767], NaN -> 0; 0 at and behind lengths[b] (x is not read there).
@@ -211,61 +146,32 @@ __global__ void pcm16_kernel(const TIn* __restrict__ x, int N, long ldx, const i
     out[(size_t)b * N + n] = v;
 }
 
-hipError_t t2s_launch_reflect_pad(const float* x, int B, int T, int pad, float* xp, long ldp, hipStream_t s) {
-    hipLaunchKernelGGL(reflect_pad_kernel, dim3((T + 2 * pad + 255) / 256, B), dim3(256), 0, s, x, T, pad, xp, ldp);
+hipError_t t2s_launch_reflect_pad(const float* x, int B, int T, const int* lengths, int pad, float* xp, long ldp, hipStream_t s) {
+    hipLaunchKernelGGL(reflect_pad_kernel, dim3((T + 2 * pad + 255) / 256, B), dim3(256), 0, s, x, T, lengths, pad, xp, ldp);
     return hipGetLastError();
 }
-hipError_t t2s_launch_stft_mag_phase(const float* ft, int B, int F, int c, long ld_ft, float* mag, float* phase, float* magT,
-                                     long ld_mt, hipStream_t s) {
+hipError_t t2s_launch_stft_mag_phase(const float* ft, int B, int F, int c, long ld_ft, const int* lengths, int hop, int T, int pad,
+                                     float* mag, float* phase, float* magT, long ld_mt, hipStream_t s) {
     const int cols = (int)(ld_mt > c ? ld_mt : c);
-    hipLaunchKernelGGL(stft_mag_phase_kernel, dim3((cols + 255) / 256, F, B), dim3(256), 0, s, ft, F, c, ld_ft, mag, phase, magT,
-                       magT ? ld_mt : 0);
+    hipLaunchKernelGGL(stft_mag_phase_kernel, dim3((cols + 255) / 256, F, B), dim3(256), 0, s, ft, F, c, ld_ft, lengths, hop, T, pad,
+                       mag, phase, magT, magT ? ld_mt : 0);
     return hipGetLastError();
 }
-hipError_t t2s_launch_stft_recombine(const float* mag, const float* phase, int B, int F, int c, const float* bias,
+hipError_t t2s_launch_stft_recombine(const float* mag, const float* phase, int B, int F, int c, const int* frames, const float* bias,
                                      float strength, float* rc, long ld_rc, hipStream_t s) {
-    hipLaunchKernelGGL(stft_recombine_kernel, dim3((unsigned)((ld_rc + 255) / 256), F, B), dim3(256), 0, s, mag, phase, F, c, bias,
-                       strength, rc, ld_rc);
+    hipLaunchKernelGGL(stft_recombine_kernel, dim3((unsigned)((ld_rc + 255) / 256), F, B), dim3(256), 0, s, mag, phase, F, c, frames,
+                       bias, strength, rc, ld_rc);
     return hipGetLastError();
 }
-hipError_t t2s_launch_stft_overlap_add(const float* frames, const float* win_sq, int B, int F, int n_fft, int hop, float scale,
-                                       float tiny, float* out, int n_out, hipStream_t s) {
-    hipLaunchKernelGGL(stft_overlap_add_kernel, dim3((n_out + 255) / 256, B), dim3(256), 0, s, frames, win_sq, F, n_fft, hop,
-                       scale, tiny, out, n_out);
+hipError_t t2s_launch_stft_overlap_add(const float* frames_buf, const float* win_sq, int B, int F, const int* frames, int n_fft,
+                                       int hop, float scale, float tiny, float* out, int n_out, hipStream_t s) {
+    hipLaunchKernelGGL(stft_overlap_add_kernel, dim3((n_out + 255) / 256, B), dim3(256), 0, s, frames_buf, win_sq, F, frames, n_fft,
+                       hop, scale, tiny, out, n_out);
     return hipGetLastError();
 }
-hipError_t t2s_launch_log_clamp(float* x, size_t n, float clip, hipStream_t s) {
-    hipLaunchKernelGGL(log_clamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, clip);
-    return hipGetLastError();
-}
-
-hipError_t t2s_launch_reflect_pad_ragged(const float* x, int B, int T, const int* lengths, int pad, float* xp, long ldp,
-                                         hipStream_t s) {
-    hipLaunchKernelGGL(reflect_pad_ragged_kernel, dim3((T + 2 * pad + 255) / 256, B), dim3(256), 0, s, x, T, lengths, pad, xp, ldp);
-    return hipGetLastError();
-}
-hipError_t t2s_launch_stft_mag_phase_ragged(const float* ft, int B, int F, int c, long ld_ft, const int* lengths, int hop, int T,
-                                            int pad, float* mag, float* phase, float* magT, long ld_mt, hipStream_t s) {
-    const int cols = (int)(ld_mt > c ? ld_mt : c);
-    hipLaunchKernelGGL(stft_mag_phase_ragged_kernel, dim3((cols + 255) / 256, F, B), dim3(256), 0, s, ft, F, c, ld_ft, lengths, hop,
-                       T, pad, mag, phase, magT, magT ? ld_mt : 0);
-    return hipGetLastError();
-}
-hipError_t t2s_launch_stft_recombine_ragged(const float* mag, const float* phase, int B, int F, int c, const int* frames,
-                                            const float* bias, float strength, float* rc, long ld_rc, hipStream_t s) {
-    hipLaunchKernelGGL(stft_recombine_ragged_kernel, dim3((unsigned)((ld_rc + 255) / 256), F, B), dim3(256), 0, s, mag, phase, F, c,
-                       frames, bias, strength, rc, ld_rc);
-    return hipGetLastError();
-}
-hipError_t t2s_launch_stft_overlap_add_ragged(const float* frames_buf, const float* win_sq, int B, int F, const int* frames,
-                                              int n_fft, int hop, float scale, float tiny, float* out, int n_out, hipStream_t s) {
-    hipLaunchKernelGGL(stft_overlap_add_ragged_kernel, dim3((n_out + 255) / 256, B), dim3(256), 0, s, frames_buf, win_sq, F, frames,
-                       n_fft, hop, scale, tiny, out, n_out);
-    return hipGetLastError();
-}
-hipError_t t2s_launch_log_clamp_ragged(float* x, int B, int n_mel, int F, const int* frames, float clip, hipStream_t s) {
+hipError_t t2s_launch_log_clamp(float* x, int B, int n_mel, int F, const int* frames, float clip, hipStream_t s) {
     const size_t n = (size_t)B * n_mel * F;
-    hipLaunchKernelGGL(log_clamp_ragged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n_mel, F, frames, n, clip);
+    hipLaunchKernelGGL(log_clamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n_mel, F, frames, n, clip);
     return hipGetLastError();
 }
 hipError_t t2s_launch_pcm16(const void* x, int is_half, int B, int N, long ldx, const int* lengths, short* out, hipStream_t s) {

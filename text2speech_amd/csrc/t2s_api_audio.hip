@@ -7,7 +7,6 @@
 
 #include <string.h>
 
-
 // y[item][row] = sum_k W[row][k] x[item * sx + k]  per batch element, through the GEMV / matrix-core dispatcher
 static hipError_t frames_gemm(const float* W, int rows, int K, const float* x, long sx, int items, float* y, long sy_item,
                               long sy_row, hipStream_t s) {
@@ -18,106 +17,105 @@ static hipError_t frames_gemm(const float* W, int rows, int K, const float* x, l
     return t2s_launch_gemv(g, s);
 }
 
+// ---- one body per stage: the plain entry point passes no lengths, its _ragged partner a padded batch's (include/t2s_hip.h) --------
+// `lengths` / `frames` ([B] int32 on the device, for the kernels) and their host copy (for the checks and the item counts here) are
+// both given or both NULL.  Each contraction is launched per entry with the entry's own item count: the dispatcher behind
+// frames_gemm chooses GEMV or matrix cores by item count, so this is what makes an entry's bits those of its solo call.
+// B is a grid y / z dimension of the glue kernels, hence B <= 65535 where one is launched over the batch.
+static int stft_transform(const float* audio, int B, int T, const int* lengths, const int* lengths_host, const float* fwd_basis,
+                          int n_fft, int hop, float* xp, long ldp, float* ft, float* mag, float* phase, float* magT, long ld_mt,
+                          void* stream) {
+    const int c = n_fft / 2 + 1;
+    if (!audio || !fwd_basis || !xp || !ft || B <= 0 || B > 65535 || T <= n_fft / 2 || n_fft <= 0 || (n_fft & 15) || hop <= 0 ||
+        (hop & 3) || (ldp & 3) || ldp < T + n_fft || n_fft > 4096 || (magT && (ld_mt < c || (ld_mt & 15))))
+        return T2S_EINVAL;
+    const int F = T / hop + 1;
+    if (lengths_host)
+        for (int b = 0; b < B; ++b)
+            if (lengths_host[b] <= n_fft / 2 || lengths_host[b] > T) return T2S_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    T2S_CHECK_HIP(t2s_launch_reflect_pad(audio, B, T, lengths, n_fft / 2, xp, ldp, s));
+    for (int b = 0; b < B; ++b)
+        T2S_CHECK_HIP(frames_gemm(fwd_basis, 2 * c, n_fft, xp + (size_t)b * ldp, hop, lengths_host ? lengths_host[b] / hop + 1 : F,
+                                  ft + (size_t)b * F * 2 * c, 2 * c, 1, s));
+    if (mag || phase || magT)
+        T2S_CHECK_HIP(t2s_launch_stft_mag_phase(ft, B, F, c, 2 * c, lengths, hop, T, n_fft / 2, mag, phase, magT, ld_mt, s));
+    return T2S_OK;
+}
+
+static int mel_from_mag(const float* magT, long ld_mt, int B, int F, const int* frames, const int* frames_host,
+                        const float* mel_basis_p, int n_mel, float clip, float* mel, void* stream) {
+    if (!magT || !mel_basis_p || !mel || B <= 0 || F <= 0 || n_mel <= 0 || ld_mt <= 0 || (ld_mt & 15)) return T2S_EINVAL;
+    if (frames_host)
+        for (int b = 0; b < B; ++b)
+            if (frames_host[b] < 1 || frames_host[b] > F) return T2S_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    for (int b = 0; b < B; ++b)
+        T2S_CHECK_HIP(frames_gemm(mel_basis_p, n_mel, (int)ld_mt, magT + (size_t)b * F * ld_mt, ld_mt, frames_host ? frames_host[b] : F,
+                                  mel + (size_t)b * n_mel * F, 1, F, s));
+    // with frames the kernel also stores the zeros behind every end, so it runs whatever the clip
+    if (frames || clip > 0.f) T2S_CHECK_HIP(t2s_launch_log_clamp(mel, B, n_mel, F, frames, clip, s));
+    return T2S_OK;
+}
+
+static int stft_inverse(const float* mag, const float* phase, int B, int F, const int* frames, const int* frames_host, int n_fft,
+                        int hop, const float* inv_basis_t, long ld_rc, const float* bias, float strength, const float* win_sq,
+                        float tiny, float* rc, float* frames_buf, float* out, void* stream) {
+    const int c = n_fft / 2 + 1;
+    if (!mag || !phase || !inv_basis_t || !rc || !frames_buf || !out || B <= 0 || B > 65535 || F <= 1 || n_fft <= 0 || hop <= 0 ||
+        ld_rc < 2 * c || (ld_rc & 15))
+        return T2S_EINVAL;
+    if (frames_host)
+        for (int b = 0; b < B; ++b)
+            if (frames_host[b] < 2 || frames_host[b] > F) return T2S_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    T2S_CHECK_HIP(t2s_launch_stft_recombine(mag, phase, B, F, c, frames, bias, strength, rc, ld_rc, s));
+    for (int b = 0; b < B; ++b)
+        T2S_CHECK_HIP(frames_gemm(inv_basis_t, n_fft, (int)ld_rc, rc + (size_t)b * F * ld_rc, ld_rc, frames_host ? frames_host[b] : F,
+                                  frames_buf + (size_t)b * F * n_fft, n_fft, 1, s));
+    T2S_CHECK_HIP(t2s_launch_stft_overlap_add(frames_buf, win_sq, B, F, frames, n_fft, hop, (float)n_fft / (float)hop, tiny, out,
+                                              hop * (F - 1), s));
+    return T2S_OK;
+}
+
 extern "C" {
 
 int t2s_stft_transform(const float* audio, int B, int T, const float* fwd_basis, int n_fft, int hop, float* xp, long ldp,
                        float* ft, float* mag, float* phase, float* magT, long ld_mt, void* stream) {
-    const int c = n_fft / 2 + 1, F = T / hop + 1;
-    if (!audio || !fwd_basis || !xp || !ft || B <= 0 || T <= n_fft / 2 || n_fft <= 0 || (n_fft & 15) || hop <= 0 || (hop & 3) ||
-        (ldp & 3) || ldp < T + n_fft || n_fft > 4096 || (magT && (ld_mt < c || (ld_mt & 15))))
-        return T2S_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    T2S_CHECK_HIP(t2s_launch_reflect_pad(audio, B, T, n_fft / 2, xp, ldp, s));
-    for (int b = 0; b < B; ++b)
-        T2S_CHECK_HIP(frames_gemm(fwd_basis, 2 * c, n_fft, xp + (size_t)b * ldp, hop, F, ft + (size_t)b * F * 2 * c, 2 * c, 1, s));
-    if (mag || phase || magT) T2S_CHECK_HIP(t2s_launch_stft_mag_phase(ft, B, F, c, 2 * c, mag, phase, magT, ld_mt, s));
-    return T2S_OK;
+    return stft_transform(audio, B, T, nullptr, nullptr, fwd_basis, n_fft, hop, xp, ldp, ft, mag, phase, magT, ld_mt, stream);
+}
+
+int t2s_stft_transform_ragged(const float* audio, int B, int T, const int* lengths, const int* lengths_host, const float* fwd_basis,
+                              int n_fft, int hop, float* xp, long ldp, float* ft, float* mag, float* phase, float* magT, long ld_mt,
+                              void* stream) {
+    if (!lengths || !lengths_host) return T2S_EINVAL;
+    return stft_transform(audio, B, T, lengths, lengths_host, fwd_basis, n_fft, hop, xp, ldp, ft, mag, phase, magT, ld_mt, stream);
 }
 
 int t2s_mel_from_mag(const float* magT, long ld_mt, int B, int F, const float* mel_basis_p, int n_mel, float clip, float* mel,
                      void* stream) {
-    if (!magT || !mel_basis_p || !mel || B <= 0 || F <= 0 || n_mel <= 0 || (ld_mt & 15)) return T2S_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    for (int b = 0; b < B; ++b)
-        T2S_CHECK_HIP(frames_gemm(mel_basis_p, n_mel, (int)ld_mt, magT + (size_t)b * F * ld_mt, ld_mt, F,
-                                  mel + (size_t)b * n_mel * F, 1, F, s));
-    if (clip > 0.f) T2S_CHECK_HIP(t2s_launch_log_clamp(mel, (size_t)B * n_mel * F, clip, s));
-    return T2S_OK;
+    return mel_from_mag(magT, ld_mt, B, F, nullptr, nullptr, mel_basis_p, n_mel, clip, mel, stream);
+}
+
+int t2s_mel_from_mag_ragged(const float* magT, long ld_mt, int B, int F, const int* frames, const int* frames_host,
+                            const float* mel_basis_p, int n_mel, float clip, float* mel, void* stream) {
+    if (!frames || !frames_host) return T2S_EINVAL;
+    return mel_from_mag(magT, ld_mt, B, F, frames, frames_host, mel_basis_p, n_mel, clip, mel, stream);
 }
 
 int t2s_stft_inverse(const float* mag, const float* phase, int B, int F, int n_fft, int hop, const float* inv_basis_t, long ld_rc,
                      const float* bias, float strength, const float* win_sq, float tiny, float* rc, float* frames, float* out,
                      void* stream) {
-    const int c = n_fft / 2 + 1;
-    if (!mag || !phase || !inv_basis_t || !rc || !frames || !out || B <= 0 || F <= 1 || n_fft <= 0 || hop <= 0 ||
-        ld_rc < 2 * c || (ld_rc & 15))
-        return T2S_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    T2S_CHECK_HIP(t2s_launch_stft_recombine(mag, phase, B, F, c, bias, strength, rc, ld_rc, s));
-    for (int b = 0; b < B; ++b)
-        T2S_CHECK_HIP(frames_gemm(inv_basis_t, n_fft, (int)ld_rc, rc + (size_t)b * F * ld_rc, ld_rc, F,
-                                  frames + (size_t)b * F * n_fft, n_fft, 1, s));
-    T2S_CHECK_HIP(t2s_launch_stft_overlap_add(frames, win_sq, B, F, n_fft, hop, (float)n_fft / (float)hop, tiny, out,
-                                              hop * (F - 1), s));
-    return T2S_OK;
-}
-
-// ---- a padded batch with per-entry lengths (include/t2s_hip.h) -------------------------------------------------------------------
-// Each contraction is launched per entry with the entry's own item count, read from the host copy of the lengths: the dispatcher
-// behind frames_gemm chooses GEMV or matrix cores by item count, so this is what makes an entry's bits those of its solo call.
-
-int t2s_stft_transform_ragged(const float* audio, int B, int T, const int* lengths, const int* lengths_host, const float* fwd_basis,
-                              int n_fft, int hop, float* xp, long ldp, float* ft, float* mag, float* phase, float* magT, long ld_mt,
-                              void* stream) {
-    const int c = n_fft / 2 + 1;
-    if (!audio || !lengths || !lengths_host || !fwd_basis || !xp || !ft || B <= 0 || B > 65535 || T <= n_fft / 2 || n_fft <= 0 ||
-        (n_fft & 15) || hop <= 0 || (hop & 3) || (ldp & 3) || ldp < T + n_fft || n_fft > 4096 ||
-        (magT && (ld_mt < c || (ld_mt & 15))))
-        return T2S_EINVAL;
-    const int F = T / hop + 1;
-    for (int b = 0; b < B; ++b)
-        if (lengths_host[b] <= n_fft / 2 || lengths_host[b] > T) return T2S_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    T2S_CHECK_HIP(t2s_launch_reflect_pad_ragged(audio, B, T, lengths, n_fft / 2, xp, ldp, s));
-    for (int b = 0; b < B; ++b)
-        T2S_CHECK_HIP(frames_gemm(fwd_basis, 2 * c, n_fft, xp + (size_t)b * ldp, hop, lengths_host[b] / hop + 1,
-                                  ft + (size_t)b * F * 2 * c, 2 * c, 1, s));
-    if (mag || phase || magT)
-        T2S_CHECK_HIP(t2s_launch_stft_mag_phase_ragged(ft, B, F, c, 2 * c, lengths, hop, T, n_fft / 2, mag, phase, magT, ld_mt, s));
-    return T2S_OK;
-}
-
-int t2s_mel_from_mag_ragged(const float* magT, long ld_mt, int B, int F, const int* frames, const int* frames_host,
-                            const float* mel_basis_p, int n_mel, float clip, float* mel, void* stream) {
-    if (!magT || !frames || !frames_host || !mel_basis_p || !mel || B <= 0 || F <= 0 || n_mel <= 0 || ld_mt <= 0 || (ld_mt & 15))
-        return T2S_EINVAL;
-    for (int b = 0; b < B; ++b)
-        if (frames_host[b] < 1 || frames_host[b] > F) return T2S_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    for (int b = 0; b < B; ++b)
-        T2S_CHECK_HIP(frames_gemm(mel_basis_p, n_mel, (int)ld_mt, magT + (size_t)b * F * ld_mt, ld_mt, frames_host[b],
-                                  mel + (size_t)b * n_mel * F, 1, F, s));
-    T2S_CHECK_HIP(t2s_launch_log_clamp_ragged(mel, B, n_mel, F, frames, clip, s));      // (clip <= 0: only the zeros behind)
-    return T2S_OK;
+    return stft_inverse(mag, phase, B, F, nullptr, nullptr, n_fft, hop, inv_basis_t, ld_rc, bias, strength, win_sq, tiny, rc, frames,
+                        out, stream);
 }
 
 int t2s_stft_inverse_ragged(const float* mag, const float* phase, int B, int F, const int* frames, const int* frames_host, int n_fft,
                             int hop, const float* inv_basis_t, long ld_rc, const float* bias, float strength, const float* win_sq,
                             float tiny, float* rc, float* frames_buf, float* out, void* stream) {
-    const int c = n_fft / 2 + 1;
-    if (!mag || !phase || !frames || !frames_host || !inv_basis_t || !rc || !frames_buf || !out || B <= 0 || B > 65535 || F <= 1 ||
-        n_fft <= 0 || hop <= 0 || ld_rc < 2 * c || (ld_rc & 15))
-        return T2S_EINVAL;
-    for (int b = 0; b < B; ++b)
-        if (frames_host[b] < 2 || frames_host[b] > F) return T2S_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    T2S_CHECK_HIP(t2s_launch_stft_recombine_ragged(mag, phase, B, F, c, frames, bias, strength, rc, ld_rc, s));
-    for (int b = 0; b < B; ++b)
-        T2S_CHECK_HIP(frames_gemm(inv_basis_t, n_fft, (int)ld_rc, rc + (size_t)b * F * ld_rc, ld_rc, frames_host[b],
-                                  frames_buf + (size_t)b * F * n_fft, n_fft, 1, s));
-    T2S_CHECK_HIP(t2s_launch_stft_overlap_add_ragged(frames_buf, win_sq, B, F, frames, n_fft, hop, (float)n_fft / (float)hop, tiny,
-                                                     out, hop * (F - 1), s));
-    return T2S_OK;
+    if (!frames || !frames_host) return T2S_EINVAL;
+    return stft_inverse(mag, phase, B, F, frames, frames_host, n_fft, hop, inv_basis_t, ld_rc, bias, strength, win_sq, tiny, rc,
+                        frames_buf, out, stream);
 }
 
 int t2s_pcm16(const void* x, int is_half, int B, int N, long ldx, const int* lengths, short* out, void* stream) {
