@@ -691,6 +691,23 @@ typedef struct t2s_adam_job {
 int t2s_adam_table(const t2s_adam_job* jobs, int n_jobs, long total_blocks, float lr, float beta1, float beta2,
                    float eps, int step, float gscale, float weight_decay, void* stream);
 
+/* Global gradient norm, clipping and the non-finite skip over the same job table (torch.nn.utils.clip_grad_norm_ semantics,
+ * train.py:228-229), all without a host read.  Added within ABI v4.
+ * t2s_grad_norm_table: the L2 norm of every job's `g` (only `g`, `n` and `blk_start` of a job are read).  Squares and sums are in
+ * double, per-workgroup partials in `partial` (scratch of t2s_grad_norm_partials() doubles, every slot overwritten), added in a fixed
+ * order: the same data gives the same bits.  out[4] (f32, device): out[0] = sqrt(sum) * gscale, the norm of the scaled gradients;
+ * out[1] = min(1, max_norm / (out[0] + 1e-6)) in f32, torch's clip coefficient (a NaN norm gives NaN; max_norm = +inf gives exactly 1:
+ * report only); out[2] = 1 if out[0] is not finite, else 0; out[3] = 0.  max_norm must be >= 0.
+ * t2s_grad_scale_table: g[i] *= clip[1].  It WRITES through the jobs' `g` pointers, which every other entry point only reads.
+ * t2s_adam_table_clip: t2s_adam_table with the gradient scale gscale * clip[1], `clip` being the `out` above; with clip[1] == 1 the
+ * same bits as t2s_adam_table.  skip_nonfinite != 0 and clip[2] != 0: nothing is written, p, m and v keep their bits. */
+int t2s_grad_norm_partials(void);
+int t2s_grad_norm_table(const t2s_adam_job* jobs, int n_jobs, long total_blocks, float gscale, float max_norm,
+                        double* partial, float* out, void* stream);
+int t2s_grad_scale_table(const t2s_adam_job* jobs, int n_jobs, long total_blocks, const float* clip, void* stream);
+int t2s_adam_table_clip(const t2s_adam_job* jobs, int n_jobs, long total_blocks, float lr, float beta1, float beta2, float eps,
+                        int step, float gscale, float weight_decay, const float* clip, int skip_nonfinite, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Tacotron-2 training step, backward (reference: autograd over tacotron/tacotron.py:36-49,355-429 and
  * tacotron/modules.py:19-22,94-137; loop train.py:219-225).  Weight gradients of every Linear / LSTM matrix contract

@@ -139,6 +139,10 @@ SIGNATURES = {
     "t2s_wg_upsample_wgrad": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
                               c_vp],
     "t2s_adam_table": [c_vp, c_int, c_long, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_vp],
+    "t2s_grad_norm_partials": [],
+    "t2s_grad_norm_table": [c_vp, c_int, c_long, c_float, c_float, c_vp, c_vp, c_vp],
+    "t2s_grad_scale_table": [c_vp, c_int, c_long, c_vp, c_vp],
+    "t2s_adam_table_clip": [c_vp, c_int, c_long, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_vp, c_int, c_vp],
 }
 # fp16 vocoder planes (WaveGlow.infer for .half() models): every _h16 entry point takes its partner's argument list
 for _n in ("t2s_pack_conv_weight_table", "t2s_wg_endfold_weights", "t2s_wg_upsample_squeeze", "t2s_wg_start",

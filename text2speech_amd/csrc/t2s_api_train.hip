@@ -337,4 +337,34 @@ int t2s_adam_table(const t2s_adam_job* jobs, int n_jobs, long total_blocks, floa
     return T2S_OK;
 }
 
+static bool table_ok(const t2s_adam_job* jobs, int n_jobs, long total_blocks) {
+    return jobs && n_jobs > 0 && total_blocks > 0 && total_blocks <= 0x7fffffffL;
+}
+
+int t2s_grad_norm_partials(void) { return T2S_GRAD_NORM_BLOCKS; }
+
+int t2s_grad_norm_table(const t2s_adam_job* jobs, int n_jobs, long total_blocks, float gscale, float max_norm, double* partial,
+                        float* out, void* stream) {
+    if (!table_ok(jobs, n_jobs, total_blocks) || !partial || !out || !(max_norm >= 0.f)) return T2S_EINVAL;      // (a NaN fails >=)
+    T2S_CHECK_HIP(t2s_launch_grad_norm_table((const AdamJob*)jobs, n_jobs, total_blocks, gscale, max_norm, partial, out,
+                                             (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_grad_scale_table(const t2s_adam_job* jobs, int n_jobs, long total_blocks, const float* clip, void* stream) {
+    if (!table_ok(jobs, n_jobs, total_blocks) || !clip) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_grad_scale_table((const AdamJob*)jobs, n_jobs, total_blocks, clip, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_adam_table_clip(const t2s_adam_job* jobs, int n_jobs, long total_blocks, float lr, float beta1, float beta2, float eps,
+                        int step, float gscale, float weight_decay, const float* clip, int skip_nonfinite, void* stream) {
+    if (!table_ok(jobs, n_jobs, total_blocks) || step <= 0 || !clip) return T2S_EINVAL;
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));      // as t2s_adam_table
+    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    T2S_CHECK_HIP(t2s_launch_adam_table_clip((const AdamJob*)jobs, n_jobs, total_blocks, lr, beta1, beta2, eps, bc1, bc2s, gscale,
+                                             weight_decay, clip, skip_nonfinite, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 }  // extern "C"

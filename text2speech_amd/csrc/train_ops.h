@@ -57,3 +57,15 @@ hipError_t t2s_launch_upsample_bgrad(const u16* D_hi, const u16* D_lo, int B, in
 hipError_t t2s_launch_adam_table(const AdamJob* jobs, int n_jobs, long total_blocks, float lr, float b1, float b2,
                                  float eps, float bc1, float bc2_sqrt, float gscale, float weight_decay,
                                  hipStream_t stream);
+// Global L2 norm of every gradient of a job table: a fixed grid of T2S_GRAD_NORM_BLOCKS workgroups (eight per CU, all resident; four
+// per CU measured a fifth slower over a table of many jobs) writes one double each into `partial`, one wave adds them.
+// out[4] = norm of the scaled gradients, clip coefficient, non-finite flag, 0.
+#define T2S_GRAD_NORM_BLOCKS 2048
+hipError_t t2s_launch_grad_norm_table(const AdamJob* jobs, int n_jobs, long total_blocks, float gscale, float max_norm,
+                                      double* partial, float* out, hipStream_t stream);
+// g *= clip[1]: WRITES through the job's `g` pointer, const in AdamJob for every other kernel
+hipError_t t2s_launch_grad_scale_table(const AdamJob* jobs, int n_jobs, long total_blocks, const float* clip, hipStream_t stream);
+// t2s_launch_adam_table with gscale * clip[1]; skip_nonfinite: nothing is written where clip[2] != 0
+hipError_t t2s_launch_adam_table_clip(const AdamJob* jobs, int n_jobs, long total_blocks, float lr, float b1, float b2,
+                                      float eps, float bc1, float bc2_sqrt, float gscale, float weight_decay, const float* clip,
+                                      int skip_nonfinite, hipStream_t stream);

@@ -538,3 +538,131 @@ hipError_t t2s_launch_adam_table(const AdamJob* jobs, int n_jobs, long total_blo
                        bc1, bc2_sqrt, gscale, weight_decay);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Global gradient norm, clipping and the non-finite skip over the same job table (torch.nn.utils.clip_grad_norm_ semantics, reference
+// train.py:228-229).  The norm is a pass of its own: every update depends on all gradients.  Reduction as in loss_ops.hip: a fixed
+// grid, one double per workgroup, one wave that adds them in a fixed order; no float atomics, so the same data gives the same bits.
+// (adam_table_kernel above is left as it was, so that it compiles to what it always did; its search is the one below.)
+__device__ __forceinline__ int table_job_index(const AdamJob* __restrict__ jobs, int lo, int n_jobs, long blk) {
+    int hi = n_jobs - 1;        // the last job of [lo, n_jobs) that starts at or before blk; jobs[lo] does
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].blk_start <= blk) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+__device__ __forceinline__ AdamJob table_job(const AdamJob* __restrict__ jobs, int n_jobs, long blk) {
+    return jobs[table_job_index(jobs, 0, n_jobs, blk)];
+}
+
+// Workgroup b takes table blocks b, b + gridDim.x, ...; the square of a widened f32 is exact in double.  A whole, 16-byte aligned
+// block is one float4 per thread; a job's last block and a gradient view that starts off 16 bytes go element by element.
+// The search's dependent table reads, not HBM, bound this pass where nearly every step lands in another job (938 WaveGlow tensors;
+// profiles/grad_norm.md), so a workgroup keeps its job while its blocks stay inside it and searches the later jobs only.
+typedef float global_f4 __attribute__((ext_vector_type(4)));      // loaded through an address_space(1) pointer: global_load, not flat_load
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const AdamJob* __restrict__ jobs, int n_jobs, long total_blocks,
+                                                                double* __restrict__ partial) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    int lo = 0;
+    AdamJob j = jobs[0];
+    for (long blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
+        if (blk >= j.blk_start + ((j.n + 1023) >> 10)) {      // past the job of the block before: it is a later one
+            lo = table_job_index(jobs, lo, n_jobs, blk);
+            j = jobs[lo];
+        }
+        const long base = (blk - j.blk_start) * 1024;
+        const float* g = j.g + base;
+        if (j.n - base >= 1024 && ((uintptr_t)g & 15) == 0) {
+            const global_f4 q = ((const __attribute__((address_space(1))) global_f4*)g)[threadIdx.x];
+            const double x = q.x, y = q.y, z = q.z, w = q.w;
+            acc += (x * x + y * y) + (z * z + w * w);
+        } else {
+            for (int e = 0; e < 4; ++e) {
+                const long i = base + e * 256 + threadIdx.x;
+                if (i < j.n) {
+                    const double x = j.g[i];
+                    acc += x * x;
+                }
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);      // 0.0 from a workgroup without a block
+}
+
+// out[0] = norm of the scaled gradients, out[1] = torch's clip coefficient in f32 (a NaN norm gives a NaN coefficient, as
+// torch.clamp keeps it), out[2] = 1 where the norm is not finite, out[3] = 0.
+__global__ void grad_norm_final_kernel(const double* __restrict__ partial, int nb, float gscale, float max_norm, float* out) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 64) s += partial[b];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)(sqrt(s) * (double)gscale);
+    const float coef = max_norm / (norm + 1e-6f);
+    out[0] = norm;
+    out[1] = coef > 1.0f ? 1.0f : coef;
+    out[2] = isfinite(norm) ? 0.0f : 1.0f;
+    out[3] = 0.0f;
+}
+hipError_t t2s_launch_grad_norm_table(const AdamJob* jobs, int n_jobs, long total_blocks, float gscale, float max_norm,
+                                      double* partial, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(T2S_GRAD_NORM_BLOCKS), dim3(256), 0, stream, jobs, n_jobs, total_blocks,
+                       partial);
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(64), 0, stream, partial, T2S_GRAD_NORM_BLOCKS, gscale, max_norm, out);
+    return hipGetLastError();
+}
+
+// g *= clip[1] through the job's g pointer (the in-place half of clip_grad_norm_); a coefficient of 1 leaves every bit.
+__global__ __launch_bounds__(256) void grad_scale_table_kernel(const AdamJob* __restrict__ jobs, int n_jobs,
+                                                               const float* __restrict__ clip) {
+    const long blk = blockIdx.x;
+    const AdamJob j = table_job(jobs, n_jobs, blk);
+    const long base = (blk - j.blk_start) * 1024;
+    float* g = const_cast<float*>(j.g);
+    const float c = clip[1];
+    for (int e = 0; e < 4; ++e) {
+        const long i = base + e * 256 + threadIdx.x;
+        if (i < j.n) g[i] *= c;
+    }
+}
+hipError_t t2s_launch_grad_scale_table(const AdamJob* jobs, int n_jobs, long total_blocks, const float* clip, hipStream_t stream) {
+    hipLaunchKernelGGL(grad_scale_table_kernel, dim3((unsigned)total_blocks), dim3(256), 0, stream, jobs, n_jobs, clip);
+    return hipGetLastError();
+}
+
+// adam_table_kernel's expression with the gradient scale gscale * clip[1] read from device memory (grad_norm_final_kernel's out):
+// with clip[1] == 1 the same bits as adam_table_kernel.  skip_nonfinite: a non-finite norm (clip[2] != 0) leaves p, m and v alone.
+__global__ __launch_bounds__(256) void adam_table_clip_kernel(const AdamJob* __restrict__ jobs, int n_jobs, float lr, float b1,
+                                                              float b2, float eps, float bc1, float bc2_sqrt, float gscale,
+                                                              float weight_decay, const float* __restrict__ clip,
+                                                              int skip_nonfinite) {
+    if (skip_nonfinite && clip[2] != 0.f) return;
+    const float gs = gscale * clip[1];
+    const long blk = blockIdx.x;
+    const AdamJob j = table_job(jobs, n_jobs, blk);
+    const long base = (blk - j.blk_start) * 1024;
+    for (int e = 0; e < 4; ++e) {
+        const long i = base + e * 256 + threadIdx.x;
+        if (i < j.n) {
+            float g = j.g[i] * gs;
+            const float p = j.p[i];
+            if (weight_decay != 0.f) g += weight_decay * p;
+            const float m = b1 * j.m[i] + (1.f - b1) * g;
+            const float v = b2 * j.v[i] + (1.f - b2) * g * g;
+            j.m[i] = m;
+            j.v[i] = v;
+            j.p[i] = p - (lr / bc1) * m / (sqrtf(v) / bc2_sqrt + eps);
+        }
+    }
+}
+hipError_t t2s_launch_adam_table_clip(const AdamJob* jobs, int n_jobs, long total_blocks, float lr, float b1, float b2,
+                                      float eps, float bc1, float bc2_sqrt, float gscale, float weight_decay, const float* clip,
+                                      int skip_nonfinite, hipStream_t stream) {
+    hipLaunchKernelGGL(adam_table_clip_kernel, dim3((unsigned)total_blocks), dim3(256), 0, stream, jobs, n_jobs, lr, b1, b2, eps,
+                       bc1, bc2_sqrt, gscale, weight_decay, clip, skip_nonfinite);
+    return hipGetLastError();
+}
