@@ -882,6 +882,22 @@ int t2s_stft_inverse_ragged(const float* mag, const float* phase, int B, int F, 
                             float tiny, float* rc, float* frames_buf, float* out, void* stream);
 int t2s_pcm16(const void* x, int is_half, int B, int N, long ldx, const int* lengths, short* out, void* stream);
 
+/* ---- training batches from a pool of int16 clips in device memory (additive to ABI version 4; text2speech_amd/data.py) ----------------
+ *  t2s_pcm16_gather: t2s_pcm16's inverse, with each row's samples taken from anywhere in a pool.  pool: int16 [pool_len] (any 2-byte
+ *    alignment); table: int64 [B][2] in device memory, (start, count) per row in samples of pool; out: f32 [B] rows of N, ldo floats
+ *    apart (ldo >= N; rows need 4-byte alignment only, 16-byte aligned rows get 16-byte stores).  For row b let c = count clamped to
+ *    [0, N] and then so that [start, start + c) lies inside [0, pool_len); a start outside the pool gives c = 0.  Then
+ *    out[b][t] = (float)pool[start + t] / max_wav_value for t < c (an IEEE division: with 32768 it is exact, the bits of
+ *    tensor.float() / 32768) and +0 for c <= t < N; columns N .. ldo are not written.  Any table value is safe and no sample outside
+ *    [0, pool_len) is read (inside the pool, samples next to a row's own may be).  T2S_EINVAL, with nothing launched: a NULL pool,
+ *    table or out, pool_len <= 0, B <= 0, B > 65535, N <= 0, ldo < N, max_wav_value not finite or not > 0.
+ *  t2s_gate_targets: the stop-token targets of a collated Tacotron batch, gate [B][T] f32 = (t >= frames[b] - 1) ? 1 : 0 (the
+ *    reference's gate_padded[i, mel.size(1) - 1:] = 1, utils/data_utils.py:146).  frames: int32 [B] on the device; frames[b] <= 0
+ *    makes the whole row 1, frames[b] > T the whole row 0.  T2S_EINVAL: NULL pointers, B <= 0, B > 65535, T <= 0. */
+int t2s_pcm16_gather(const short* pool, long pool_len, const long* table, int B, int N, float max_wav_value, float* out, long ldo,
+                     void* stream);
+int t2s_gate_targets(const int* frames, int B, int T, float* gate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ Tacotron path); there is no CPU or eager fallback - without the library every ca
 waveform host -> GPU -> host inside STFT.transform (utils/stft.py:85-89); here input and output stay in HBM.
 Padded batches of different lengths go through the *_batch methods (STFT.transform_batch / inverse_batch,
 TacotronSTFT.mel_spectrogram_batch, Denoiser.denoise_batch) and to_pcm16: every entry gets what the plain method gives it alone, bit
-for bit, and zeros behind its end.
+for bit, and zeros behind its end.  from_pcm16 is to_pcm16's inverse; training batches from a pool of int16
+clips are text2speech_amd/data.py.
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
 window); the mel filterbank restates librosa.filters.mel's defaults (Slaney scale, area normalisation) because librosa is
 an unpinned dependency that this image does not have.
@@ -23,7 +24,7 @@ from scipy.signal import get_window
 from . import _lib
 
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
-           "dynamic_range_decompression", "to_pcm16"]
+           "dynamic_range_decompression", "to_pcm16", "from_pcm16"]
 
 
 def _ru(a, b):
@@ -60,10 +61,16 @@ def _host_lengths(lengths, B, lo, hi, what, unit):
     return lens
 
 
+def _to_device(host, dev):
+    """A small host tensor -> the device through page-locked memory, without waiting for the copy (the caching host allocator keeps
+    the staging block until the copy has run): what lets a batch be assembled with no synchronising call."""
+    return host.pin_memory().to(dev, non_blocking=True)
+
+
 def _both(lens, dev):
     """host int64 [B] -> (int32 on the device for the kernels, int32 on the host for the entry point's own reads)"""
     host = lens.to(torch.int32).contiguous()
-    return host.to(dev), host
+    return _to_device(host, dev), host
 
 
 def to_pcm16(audio, lengths=None):
@@ -92,6 +99,38 @@ def to_pcm16(audio, lengths=None):
     _lib.call("t2s_pcm16", _lib.ptr(x), int(x.dtype == torch.float16), rows, N, ldx, _lib.ptr(lens_d), _lib.ptr(out),
               _lib.current_stream())
     return out
+
+
+def _pcm16_gather(pool, table, N, max_wav_value, out=None):
+    """Rows of `N` float32 samples gathered from the flat int16 `pool` (in HBM) at `table` (host int64 [B, 2]: start, count), each
+    divided by max_wav_value, zeros behind its count (t2s_pcm16_gather).  One small host-to-device copy, no read-back."""
+    B = table.size(0)
+    if out is None:
+        out = torch.empty(B, N, dtype=torch.float32, device=pool.device)
+    table_d = _to_device(table.contiguous(), pool.device)
+    _lib.call("t2s_pcm16_gather", _lib.ptr(pool), pool.numel(), _lib.ptr(table_d), B, N, float(max_wav_value), _lib.ptr(out),
+              out.stride(0) if B > 1 else N, _lib.current_stream())
+    return out
+
+
+def from_pcm16(pcm, lengths=None, max_wav_value=32768.0):
+    """int16 PCM [..., N] in HBM -> float32 of the same shape, `pcm / max_wav_value`: to_pcm16's inverse (the round trip over all
+    65536 codes is the identity; with max_wav_value = 32768 the division is exact).  `lengths` (one per row, as to_pcm16's) zeroes
+    the samples at and behind each row's end."""
+    _need_cuda(pcm, "from_pcm16")
+    if pcm.dtype != torch.int16:
+        raise _lib.T2SError("from_pcm16: expected int16 PCM, got %s (there is no silent cast)" % pcm.dtype)
+    if pcm.dim() == 0 or pcm.numel() == 0:
+        raise _lib.T2SError("from_pcm16: pcm must hold samples, got shape %s" % (tuple(pcm.shape),))
+    if not (np.isfinite(max_wav_value) and max_wav_value > 0):
+        raise _lib.T2SError("from_pcm16: max_wav_value must be finite and positive, got %r" % (max_wav_value,))
+    x = pcm.detach().contiguous()
+    N = x.size(-1)
+    rows = x.numel() // N
+    table = torch.empty(rows, 2, dtype=torch.int64)
+    table[:, 0] = torch.arange(rows, dtype=torch.int64) * N
+    table[:, 1] = N if lengths is None else _host_lengths(lengths, rows, 0, N, "from_pcm16", "samples")
+    return _pcm16_gather(x.view(-1), table, N, max_wav_value).view(pcm.shape)
 
 
 def dynamic_range_compression(x, C=1, clip_val=1e-5):

@@ -13,3 +13,7 @@ hipError_t t2s_launch_stft_overlap_add(const float* frames_buf, const float* win
                                        int hop, float scale, float tiny, float* out, int n_out, hipStream_t s);
 hipError_t t2s_launch_log_clamp(float* x, int B, int n_mel, int F, const int* frames, float clip, hipStream_t s);
 hipError_t t2s_launch_pcm16(const void* x, int is_half, int B, int N, long ldx, const int* lengths, short* out, hipStream_t s);
+// training batches from a pool of int16 clips: `table` [B][2] int64 (start, count) on the device, any value safe
+hipError_t t2s_launch_pcm16_gather(const short* pool, long pool_len, const long* table, int B, int N, float max_wav, float* out,
+                                   long ldo, hipStream_t s);
+hipError_t t2s_launch_gate_targets(const int* frames, int B, int T, float* gate, hipStream_t s);

@@ -146,6 +146,97 @@ __global__ void pcm16_kernel(const TIn* __restrict__ x, int N, long ldx, const i
     out[(size_t)b * N + n] = v;
 }
 
+// ---- training batches from a pool of int16 clips (text2speech_amd/data.py) ------------------------------------------------------------
+// out[b][t] = (float)pool[start_b + t] / max_wav for t < c_b, +0 for c_b <= t < N: t2s_pcm16's inverse, row b's samples taken at
+// table[b] = (start, count).  c_b is count clamped to [0, N] and to what the pool holds behind start; a start outside the pool
+// gives 0, so no table value moves a load out of [pool, pool + pool_len).
+// A lane makes 8 consecutive outputs.  Their 16 source bytes begin at any 2-byte phase of a 16-byte granule, so the lane loads the
+// two aligned granules that straddle them and shifts: whole words first (two conditional stages, no register indexing), then the odd
+// half-word.  Where either granule crosses one of the pool's two ends the lane loads its valid samples one by one instead.  The
+// stores are two float4 where the lane's 8 outputs are all inside the row and 16-byte aligned, single floats otherwise.
+#define GATHER_PER_LANE 8
+__global__ __launch_bounds__(256) void pcm16_gather_kernel(const short* __restrict__ pool, long pool_len, const long* __restrict__ table,
+                                                            int N, float max_wav, float* __restrict__ out, long ldo) {
+    const long first = ((long)blockIdx.x * 256 + threadIdx.x) * GATHER_PER_LANE;
+    const int b = blockIdx.y;
+    if (first >= N) return;
+    const int t0 = (int)first;
+    const long start = table[2 * (size_t)b], count = table[2 * (size_t)b + 1];
+    long c = count < 0 ? 0 : (count > N ? (long)N : count);
+    if (start < 0 || start >= pool_len) c = 0;
+    else if (c > pool_len - start) c = pool_len - start;
+    const int live = c - t0 >= GATHER_PER_LANE ? GATHER_PER_LANE : (c > t0 ? (int)(c - t0) : 0);      // samples this lane converts
+    const int room = N - t0 >= GATHER_PER_LANE ? GATHER_PER_LANE : N - t0;                            // outputs this lane stores
+
+    short v[GATHER_PER_LANE];
+#pragma unroll
+    for (int i = 0; i < GATHER_PER_LANE; ++i) v[i] = 0;
+    if (live > 0) {
+        const short* src = pool + start + t0;
+        const uintptr_t a = (uintptr_t)src, a0 = a & ~(uintptr_t)15;
+        const uintptr_t lo = (uintptr_t)pool, hi = lo + 2 * (uintptr_t)pool_len;
+        if (a0 >= lo && a0 + 32 <= hi) {
+            const uint4 g0 = *(const uint4*)a0, g1 = *(const uint4*)(a0 + 16);
+            unsigned w[9] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, 0u};
+            const unsigned phase = (unsigned)(a - a0) >> 1;                   // 0 .. 7 half-words into the first granule
+            if (phase & 4) {
+#pragma unroll
+                for (int k = 0; k < 7; ++k) w[k] = w[k + 2];
+            }
+            if (phase & 2) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) w[k] = w[k + 1];
+            }
+            if (phase & 1) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) w[k] = (w[k] >> 16) | (w[k + 1] << 16);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                v[2 * k] = (short)(w[k] & 0xffffu);
+                v[2 * k + 1] = (short)(w[k] >> 16);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < GATHER_PER_LANE; ++i)
+                if (i < live) v[i] = src[i];
+        }
+    }
+    float f[GATHER_PER_LANE];
+#pragma unroll
+    for (int i = 0; i < GATHER_PER_LANE; ++i) f[i] = i < live ? (float)v[i] / max_wav : 0.f;
+    float* dst = out + (size_t)b * ldo + t0;
+    if (room == GATHER_PER_LANE && ((uintptr_t)dst & 15) == 0) {
+        ((float4*)dst)[0] = make_float4(f[0], f[1], f[2], f[3]);
+        ((float4*)dst)[1] = make_float4(f[4], f[5], f[6], f[7]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < GATHER_PER_LANE; ++i)
+            if (i < room) dst[i] = f[i];
+    }
+}
+
+// gate[b][t] = 1 from frame frames[b] - 1 on, 0 in front (the reference's gate_padded[i, mel.size(1) - 1:] = 1, utils/data_utils.py:146):
+// frames[b] <= 0 makes the row 1, frames[b] > T makes it 0
+__global__ void gate_targets_kernel(const int* __restrict__ frames, int T, float* __restrict__ gate) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (t >= T) return;
+    gate[(size_t)b * T + t] = t + 1 >= frames[b] ? 1.f : 0.f;
+}
+
+hipError_t t2s_launch_pcm16_gather(const short* pool, long pool_len, const long* table, int B, int N, float max_wav, float* out,
+                                   long ldo, hipStream_t s) {
+    const int per_block = 256 * GATHER_PER_LANE;
+    hipLaunchKernelGGL(pcm16_gather_kernel, dim3((N + per_block - 1) / per_block, B), dim3(256), 0, s, pool, pool_len, table, N,
+                       max_wav, out, ldo);
+    return hipGetLastError();
+}
+hipError_t t2s_launch_gate_targets(const int* frames, int B, int T, float* gate, hipStream_t s) {
+    hipLaunchKernelGGL(gate_targets_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, frames, T, gate);
+    return hipGetLastError();
+}
+
 hipError_t t2s_launch_reflect_pad(const float* x, int B, int T, const int* lengths, int pad, float* xp, long ldp, hipStream_t s) {
     hipLaunchKernelGGL(reflect_pad_kernel, dim3((T + 2 * pad + 255) / 256, B), dim3(256), 0, s, x, T, lengths, pad, xp, ldp);
     return hipGetLastError();

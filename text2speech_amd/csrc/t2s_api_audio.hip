@@ -124,4 +124,20 @@ int t2s_pcm16(const void* x, int is_half, int B, int N, long ldx, const int* len
     return T2S_OK;
 }
 
+int t2s_pcm16_gather(const short* pool, long pool_len, const long* table, int B, int N, float max_wav_value, float* out, long ldo,
+                     void* stream) {
+    // (the comparison is false for NaN, the subtraction is NaN for an infinity)
+    if (!pool || !table || !out || pool_len <= 0 || B <= 0 || B > 65535 || N <= 0 || ldo < N || !(max_wav_value > 0.f) ||
+        max_wav_value - max_wav_value != 0.f)
+        return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_pcm16_gather(pool, pool_len, table, B, N, max_wav_value, out, ldo, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_gate_targets(const int* frames, int B, int T, float* gate, void* stream) {
+    if (!frames || !gate || B <= 0 || B > 65535 || T <= 0) return T2S_EINVAL;
+    T2S_CHECK_HIP(t2s_launch_gate_targets(frames, B, T, gate, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 }  // extern "C"

@@ -1,0 +1,228 @@
+"""Training batches assembled on the MI355X from int16 PCM: a corpus of clips lives in HBM, and one call turns
+a list of clip indices into the tensors `WaveGlow.forward` / `Tacotron.forward` take.
+
+  PcmPool(clips, sampling_rate)                 the clips back to back in one int16 device tensor; .from_wav_files(paths, rate)
+  Mel2SampBatch(pool, segment_length, ...)      waveglow/mel2samp.py:60-105 (Mel2Samp.__getitem__ + the default collate): (mel, audio)
+  TextMelBatch(pool, sequences, ...)            utils/data_utils.py:46-150 (TextMelLoader + TextMelCollate) and Tacotron.parse_batch
+
+Cropping, zero padding, the division by max_wav_value (t2s_pcm16_gather), the mels (TacotronSTFT) and the gate targets
+(t2s_gate_targets) run in libt2s_hip.so; the host chooses crop starts, sorts text lengths and pads token ids.  A call copies a few
+small tables to the device and reads nothing back.  Decoding files, file lists, shuffling and epochs stay host work of the caller.
+
+Stated departure: the reference's TextMelLoader loads floats with librosa (resampling to the target rate) and then divides them by
+max_wav_value a second time (utils/data_utils.py:18-20, 82).  TextMelBatch does what Mel2Samp does: int16 samples at the target
+rate, divided once.
+"""
+import random
+
+import numpy as np
+import torch
+
+from . import _lib
+from .audio import TacotronSTFT, _pcm16_gather, _to_device
+
+__all__ = ["PcmPool", "Mel2SampBatch", "TextMelBatch", "gather_width"]
+
+T2SError = _lib.T2SError
+
+
+def gather_width(longest, t_out, hop):
+    """Row width T' of the gathered batch whose ragged mel is `mel_padded` itself: 1 + T' // hop == t_out and T' >= longest, for
+    t_out >= 1 + longest // hop.  The smallest such width, rounded up to a multiple of 4 samples (16-byte rows) where that keeps the
+    frame count."""
+    if t_out < 1 + longest // hop:
+        raise ValueError("t_out %d is below the %d frames of %d samples" % (t_out, 1 + longest // hop, longest))
+    width = max(longest, (t_out - 1) * hop)
+    up = -(-width // 4) * 4
+    return up if up < t_out * hop else width
+
+
+class PcmPool:
+    """A corpus of int16 clips in HBM.  `clips`: a sequence of 1-D int16 numpy arrays or tensors (anything else raises T2SError:
+    there is no silent cast).  `.pcm` is one int16 device tensor with all clips back to back, `.offsets` / `.lengths` host int64
+    [n_clips], `.sampling_rate` the rate they were recorded at."""
+
+    def __init__(self, clips, sampling_rate, device="cuda"):
+        parts = []
+        for i, c in enumerate(clips):
+            if isinstance(c, np.ndarray):
+                c = torch.from_numpy(np.ascontiguousarray(c)) if c.dtype == np.int16 and c.ndim == 1 else c
+            if not torch.is_tensor(c) or c.dtype != torch.int16 or c.dim() != 1:
+                raise T2SError("PcmPool: clip %d must be a 1-D int16 array or tensor, got %s %s" % (
+                    i, getattr(c, "dtype", type(c).__name__), tuple(getattr(c, "shape", ()))))
+            if c.numel() == 0:
+                raise T2SError("PcmPool: clip %d is empty" % i)
+            parts.append(c.detach())
+        if not parts:
+            raise T2SError("PcmPool: no clips")
+        self.sampling_rate = sampling_rate
+        self.lengths = torch.tensor([p.numel() for p in parts], dtype=torch.int64)
+        self.offsets = torch.cumsum(self.lengths, 0) - self.lengths
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise T2SError("PcmPool: the pool lives in HBM (cuda); there is no CPU path")
+        if any(p.is_cuda for p in parts):
+            self.pcm = torch.cat([p.to(dev) for p in parts])
+        else:
+            self.pcm = torch.cat(parts).to(dev)             # one copy of the whole corpus
+
+    def __len__(self):
+        return self.lengths.numel()
+
+    @classmethod
+    def from_wav_files(cls, paths, sampling_rate, device="cuda"):
+        """Reads each file with scipy.io.wavfile.read.  A file at another rate raises the reference's ValueError
+        (waveglow/mel2samp.py:90-92); a file that is not mono int16 is refused."""
+        return cls(cls.read_wav_files(paths, sampling_rate), sampling_rate, device)
+
+    @staticmethod
+    def read_wav_files(paths, sampling_rate):
+        """The host half of from_wav_files: the files' samples as a list of 1-D int16 arrays."""
+        from scipy.io.wavfile import read
+        clips = []
+        for path in paths:
+            rate, data = read(path)
+            if rate != sampling_rate:
+                raise ValueError("{} SR doesn't match target {} SR".format(rate, sampling_rate))
+            if data.dtype != np.int16 or data.ndim != 1:
+                raise T2SError("%s: expected mono int16 PCM, got %s with shape %s" % (path, data.dtype, data.shape))
+            clips.append(data)
+        return clips
+
+    def _indices(self, indices, what):
+        idx = [int(i) for i in indices]
+        if not idx:
+            raise T2SError("%s: an empty batch" % what)
+        for i in idx:
+            if not 0 <= i < len(self):
+                raise T2SError("%s: clip index %d outside the pool's %d clips" % (what, i, len(self)))
+        return idx
+
+
+def crop_starts(lengths, segment_length, rng):
+    """Mel2Samp's crop per entry (waveglow/mel2samp.py:94-100): a clip of at least segment_length samples starts at
+    rng.randint(0, len - segment_length), drawn in entry order; a shorter clip starts at 0 and consumes no draw."""
+    return [rng.randint(0, n - segment_length) if n >= segment_length else 0 for n in lengths]
+
+
+class Mel2SampBatch:
+    """Mel2Samp's arguments with the pool in place of the file list (max_wav_value and n_mel_channels, constants of the reference's
+    module, are keywords).  Called with clip indices it returns what a DataLoader over Mel2Samp hands `model((mel, audio))`:
+    mel [B, n_mel_channels, 1 + segment_length // hop_length] and audio [B, segment_length], float32 in HBM.
+    `rng`: a random.Random (default: seeded 1234, the reference's seed) that draws the crops; `starts` overrides the draws and
+    `last_starts` keeps what was used.  The mel is the mel of the padded segment, as the reference computes it.  With
+    max_wav_value >= 32768 every sample lies in [-1, 1] by construction, so mel_spectrogram's assertion and its read-back are
+    skipped; any other value goes through mel_spectrogram."""
+
+    def __init__(self, pool, segment_length, filter_length, hop_length, win_length, sampling_rate, mel_fmin, mel_fmax, rng=None,
+                 max_wav_value=32768.0, n_mel_channels=80):
+        if sampling_rate != pool.sampling_rate:
+            raise ValueError("{} SR doesn't match target {} SR".format(pool.sampling_rate, sampling_rate))
+        if segment_length <= filter_length // 2:
+            raise T2SError("Mel2SampBatch: segment_length %d must exceed filter_length / 2" % segment_length)
+        self.pool, self.segment_length, self.sampling_rate = pool, int(segment_length), sampling_rate
+        self.max_wav_value = float(max_wav_value)
+        self.rng = rng if rng is not None else random.Random(1234)
+        self.stft = TacotronSTFT(filter_length=filter_length, hop_length=hop_length, win_length=win_length,
+                                 n_mel_channels=n_mel_channels, sampling_rate=sampling_rate, mel_fmin=mel_fmin,
+                                 mel_fmax=mel_fmax).to(pool.pcm.device)
+        self.last_starts = None
+
+    def __call__(self, indices, starts=None):
+        what = "Mel2SampBatch"
+        idx = self.pool._indices(indices, what)
+        seg = self.segment_length
+        lens = [int(self.pool.lengths[i]) for i in idx]
+        if starts is None:
+            starts = crop_starts(lens, seg, self.rng)
+        else:
+            starts = [int(s) for s in starts]
+            if len(starts) != len(idx):
+                raise T2SError("%s: %d starts for %d entries" % (what, len(starts), len(idx)))
+            for s, n in zip(starts, lens):
+                if not 0 <= s <= max(n - seg, 0):
+                    raise T2SError("%s: start %d leaves no %d samples in a clip of %d" % (what, s, seg, n))
+        self.last_starts = list(starts)
+        table = torch.tensor([[int(self.pool.offsets[i]) + s, min(n - s, seg)] for i, s, n in zip(idx, starts, lens)],
+                             dtype=torch.int64)
+        audio = _pcm16_gather(self.pool.pcm, table, seg, self.max_wav_value)
+        mel = self.stft._mel(audio)[0] if self.max_wav_value >= 32768.0 else self.stft.mel_spectrogram(audio)
+        return mel, audio
+
+
+class TextMelBatch:
+    """TextMelLoader + TextMelCollate + Tacotron.parse_batch over a pool.  `sequences`: one list of symbol ids per clip
+    (text.text_to_sequence); `speaker_ids`: one per clip (default 0).
+
+    collate(indices) returns TextMelCollate's six results with the reference's shapes and dtypes - entries sorted by decreasing text
+    length (torch.sort's order on ties), text_padded int64 zero padded, mel_padded [B, n_mel_channels, T_out] with zeros behind each
+    entry (T_out: the most frames, rounded up to a multiple of n_frames_per_step), gate_padded 1 from each entry's last frame on,
+    speaker_id float, output_lengths int64 - already in HBM, except input_lengths, which is on the host as the reference's is.
+    Entry b's frames are, bit for bit, mel_spectrogram(clip / max_wav_value) of its clip alone.  __call__(indices) returns
+    parse_batch's (x, y) of that batch, max_len a Python int.
+
+    The clips are gathered in sorted order into rows just wide enough (gather_width) that the ragged mel is mel_padded itself.  A
+    clip of at most filter_length / 2 samples is refused, as the mel refuses it alone.  With max_wav_value >= 32768 the [-1, 1]
+    assertion holds by construction and nothing is read back; a smaller value goes through mel_spectrogram_batch and its assertion.
+
+    speaker_id is in the order of `indices`, NOT in sorted order: that is what the reference's collate returns (it fills speaker_id
+    before it walks the sorted ids, utils/data_utils.py:132-135), so with more than one speaker a row's id can belong to another
+    row; pass indices already sorted by decreasing text length and every row has its own.
+
+    Stated departure: the reference's TextMelLoader loads floats with librosa (resampling) and divides them by max_wav_value again
+    (utils/data_utils.py:18-20, 82); this class does what Mel2Samp does - int16 at the target rate, divided once."""
+
+    def __init__(self, pool, sequences, n_frames_per_step, filter_length, hop_length, win_length, n_mel_channels, sampling_rate,
+                 mel_fmin, mel_fmax, max_wav_value=32768.0, speaker_ids=None):
+        if sampling_rate != pool.sampling_rate:
+            raise ValueError("{} SR doesn't match target {} SR".format(pool.sampling_rate, sampling_rate))
+        if len(sequences) != len(pool):
+            raise T2SError("TextMelBatch: %d sequences for %d clips" % (len(sequences), len(pool)))
+        if speaker_ids is not None and len(speaker_ids) != len(pool):
+            raise T2SError("TextMelBatch: %d speaker ids for %d clips" % (len(speaker_ids), len(pool)))
+        if n_frames_per_step < 1:
+            raise T2SError("TextMelBatch: n_frames_per_step must be at least 1")
+        self.pool, self.n_frames_per_step, self.max_wav_value = pool, int(n_frames_per_step), float(max_wav_value)
+        self.sequences = [torch.as_tensor(s, dtype=torch.int64).reshape(-1) for s in sequences]
+        if any(s.numel() == 0 for s in self.sequences):
+            raise T2SError("TextMelBatch: an empty sequence")
+        self.speaker_ids = [0.0] * len(pool) if speaker_ids is None else [float(s) for s in speaker_ids]
+        self.stft = TacotronSTFT(filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin,
+                                 mel_fmax).to(pool.pcm.device)
+
+    def collate(self, indices):
+        what = "TextMelBatch"
+        pool, dev = self.pool, self.pool.pcm.device
+        idx = pool._indices(indices, what)
+        hop, n_fft, step = self.stft.stft_fn.hop_length, self.stft.stft_fn.filter_length, self.n_frames_per_step
+        input_lengths, order = torch.sort(torch.LongTensor([self.sequences[i].numel() for i in idx]), dim=0, descending=True)
+        given, idx = idx, [idx[k] for k in order.tolist()]
+        B = len(idx)
+        lens = pool.lengths[idx]
+        if int(lens.min()) <= n_fft // 2:
+            raise T2SError("%s: clip %d has %d samples, the mel needs more than filter_length / 2 = %d" % (
+                what, idx[int(lens.argmin())], int(lens.min()), n_fft // 2))
+        t_out = 1 + int(lens.max()) // hop
+        t_out = -(-t_out // step) * step
+        width = gather_width(int(lens.max()), t_out, hop)
+        text_padded = torch.zeros(B, int(input_lengths[0]), dtype=torch.int64)
+        for k, i in enumerate(idx):
+            text_padded[k, :self.sequences[i].numel()] = self.sequences[i]
+        y = _pcm16_gather(pool.pcm, torch.stack([pool.offsets[idx], lens], 1), width, self.max_wav_value)
+        if self.max_wav_value >= 32768.0:
+            mel_padded, frames = self.stft._mel(y, lens)
+        else:
+            mel_padded, _ = self.stft.mel_spectrogram_batch(y, lens)
+            frames = lens // hop + 1
+        assert mel_padded.size(2) == t_out
+        frames_d = _to_device(frames.to(torch.int32), dev)
+        gate_padded = torch.empty(B, t_out, dtype=torch.float32, device=dev)
+        _lib.call("t2s_gate_targets", _lib.ptr(frames_d), B, t_out, _lib.ptr(gate_padded), _lib.current_stream())
+        speaker_id = _to_device(torch.tensor([self.speaker_ids[i] for i in given], dtype=torch.float32), dev)
+        return _to_device(text_padded, dev), input_lengths, mel_padded, gate_padded, speaker_id, _to_device(frames, dev)
+
+    def __call__(self, indices):
+        text_padded, input_lengths, mel_padded, gate_padded, speaker_id, output_lengths = self.collate(indices)
+        max_len = int(input_lengths[0])                  # sorted: the first is the longest; a host value, no .item() on the device
+        x = (text_padded, _to_device(input_lengths, text_padded.device), mel_padded, max_len, speaker_id, output_lengths)
+        return x, (mel_padded, gate_padded)
