@@ -898,6 +898,38 @@ int t2s_pcm16_gather(const short* pool, long pool_len, const long* table, int B,
                      void* stream);
 int t2s_gate_targets(const int* frames, int B, int T, float* gate, void* stream);
 
+/* ---- sample-rate conversion by up / down in device memory (additive to ABI version 4; audio.py Resampler, data.py PcmPool.resample) ----
+ * The polyphase FIR of scipy.signal.resample_poly(x, up, down) with zero extension.  h: the filter, double [n_taps] in device memory
+ * (8-byte aligned), n_taps = 2 half + 1, built by the caller (audio.resample_filter restates scipy's default Kaiser design).  A row of
+ * n_in samples gives n_out = ceil(n_in up / down) samples
+ *     y[m] = sum_k x[k] h[half + m down - k up]        over 0 <= k < n_in with 0 <= half + m down - k up < n_taps,
+ * each one loop of its own in double precision: k ascending, one fused multiply-add per tap from +0.  The loop depends on m, n_in and
+ * the filter only, so a row's bits are the same alone and in any batch or pool.  An int16 destination stores rint(y) (ties to even)
+ * saturated to [-32768, 32767], NaN as 0; an f32 destination the one rounding of the double sum; an f16 source is widened exactly.
+ * One kernel serves both entry points and every type pair; a workgroup makes t2s_resample_tile() consecutive outputs of one row.
+ *  t2s_resample_tile: host only, that number (1024).
+ *  t2s_resample_table: src [src_len] of src_kind (0 int16, 1 f32, 2 f16); dst [dst_len] of dst_kind (0 int16, 1 f32); table: int64
+ *    [n_rows][4] in device memory, (src_start, src_count, dst_start, dst_cap) per row, in samples.  Row r's input is its own
+ *    src_count samples from src_start - nothing next to them enters its sums.  It gets v = min(ceil(src_count up / down), dst_cap)
+ *    samples of y at dst_start and +0 behind them up to dst_cap.  Any table value is safe: a negative src_count or a src_start
+ *    outside [0, src_len) counts as no samples (the row is all +0), a src_count that runs past src_len is cut there; dst_cap is cut
+ *    to max_out and to what dst holds behind dst_start, and a negative one or a dst_start outside [0, dst_len) writes nothing.
+ *    Nothing outside [0, src_len) is read and nothing outside a row's [dst_start, dst_start + dst_cap) is written; rows whose
+ *    destination ranges overlap are the caller's error.  max_out bounds the grid: ceil(max_out / tile) x n_rows workgroups.
+ *    out_lengths: NULL, or int32 [n_rows] in device memory that receives every row's v.  No alignment beyond the element.
+ *  t2s_resample_batch: the padded-batch form.  x [B] rows of N samples, ldx elements apart, f32 (is_half = 0) or f16; out f32 [B]
+ *    rows of N_out, ldo apart: table rows (b ldx, lengths[b], b ldo, N_out).  lengths: int32 [B] in device memory, clamped to
+ *    [0, N]; NULL: every row holds N.  Samples at or behind lengths[b] are never read.
+ *  T2S_EINVAL, with nothing launched: a NULL src / x, table, h or dst / out; src_len, dst_len, n_rows, B, N, N_out or max_out <= 0;
+ *    n_rows or B > 65535; max_out > 2^40; up or down < 1, gcd(up, down) != 1, max(up, down) > 512; n_taps even or < 3, or so long that
+ *    its phase table, up (ceil(n_taps / up) | 1) doubles, exceeds 96 KB of LDS (half_width 10 needs 84 KB at most); ldx < N or
+ *    ldo < N_out; a kind out of range; h not 8-byte aligned. */
+int t2s_resample_tile(void);
+int t2s_resample_table(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* h, int n_taps, int up,
+                       int down, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream);
+int t2s_resample_batch(const void* x, int is_half, int B, int N, long ldx, const int* lengths, const double* h, int n_taps, int up,
+                       int down, float* out, int N_out, long ldo, int* out_lengths, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

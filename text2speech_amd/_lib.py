@@ -111,6 +111,9 @@ SIGNATURES = {
     "t2s_pcm16": [c_vp, c_int, c_int, c_int, c_long, c_vp, c_vp, c_vp],
     "t2s_pcm16_gather": [c_vp, c_long, c_vp, c_int, c_int, c_float, c_vp, c_long, c_vp],
     "t2s_gate_targets": [c_vp, c_int, c_int, c_vp, c_vp],
+    "t2s_resample_tile": [],
+    "t2s_resample_table": [c_vp, c_int, c_long, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_long, c_long, c_vp, c_vp],
+    "t2s_resample_batch": [c_vp, c_int, c_int, c_int, c_long, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_long, c_vp, c_vp],
     "t2s_sum_axis0": [c_vp, c_int, c_int, c_vp, c_vp],
     "t2s_add3": [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp],
     "t2s_scale_by_scalar": [c_vp, ctypes.c_size_t, c_vp, c_float, c_vp, c_vp],

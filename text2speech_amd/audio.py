@@ -12,7 +12,8 @@ waveform host -> GPU -> host inside STFT.transform (utils/stft.py:85-89); here i
 Padded batches of different lengths go through the *_batch methods (STFT.transform_batch / inverse_batch,
 TacotronSTFT.mel_spectrogram_batch, Denoiser.denoise_batch) and to_pcm16: every entry gets what the plain method gives it alone, bit
 for bit, and zeros behind its end.  from_pcm16 is to_pcm16's inverse; training batches from a pool of int16
-clips are text2speech_amd/data.py.
+clips are text2speech_amd/data.py.  Resampler converts the sample rate of a batch (forward / resample_batch) or, through
+PcmPool.resample, of a pool: scipy.signal.resample_poly's polyphase filter with every sum in double precision (csrc/resample.hip).
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
 window); the mel filterbank restates librosa.filters.mel's defaults (Slaney scale, area normalisation) because librosa is
 an unpinned dependency that this image does not have.
@@ -24,7 +25,7 @@ from scipy.signal import get_window
 from . import _lib
 
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
-           "dynamic_range_decompression", "to_pcm16", "from_pcm16"]
+           "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter"]
 
 
 def _ru(a, b):
@@ -131,6 +132,126 @@ def from_pcm16(pcm, lengths=None, max_wav_value=32768.0):
     table[:, 0] = torch.arange(rows, dtype=torch.int64) * N
     table[:, 1] = N if lengths is None else _host_lengths(lengths, rows, 0, N, "from_pcm16", "samples")
     return _pcm16_gather(x.view(-1), table, N, max_wav_value).view(pcm.shape)
+
+
+RESAMPLE_MAX_FACTOR = 512      # the library's limit on max(up, down) (include/t2s_hip.h)
+
+
+def resample_filter(orig_rate, new_rate, half_width=10, beta=5.0):
+    """(up, down, h) of scipy.signal.resample_poly(x, up, down) at its defaults (window=('kaiser', 5.0)): up / down is
+    new_rate / orig_rate reduced, h float64 [2 half_width max(up, down) + 1] = up * firwin(n_taps, 1 / max(up, down), window).
+    numpy only; the filter is scipy's, not librosa's kaiser_best or soxr."""
+    if int(orig_rate) != orig_rate or int(new_rate) != new_rate or orig_rate < 1 or new_rate < 1 or half_width < 1:
+        raise ValueError("resample_filter: rates and half_width must be positive integers, got %r, %r, %r"
+                         % (orig_rate, new_rate, half_width))
+    g = int(np.gcd(int(orig_rate), int(new_rate)))
+    up, down = int(new_rate) // g, int(orig_rate) // g
+    R = max(up, down)
+    half = int(half_width) * R
+    t = np.arange(-half, half + 1, dtype=np.float64) / R
+    h = np.kaiser(2 * half + 1, beta) * (np.sinc(t) / R)
+    return up, down, up * (h / h.sum())
+
+
+class Resampler:
+    """Sample-rate conversion orig_rate -> new_rate in HBM: scipy.signal.resample_poly(x, up, down) at its defaults (zero extension,
+    Kaiser-windowed sinc of resample_filter) as one HIP kernel, every sum in double precision (csrc/resample.hip).  The filter lives
+    in HBM from construction.  A reduced ratio with max(up, down) > 512 (e.g. 44100 -> 48000 is 160 / 147; 44100 -> 44101 is not
+    supported) raises T2SError.  Equal rates give a copy without a launch of the filter."""
+
+    def __init__(self, orig_rate, new_rate, half_width=10, beta=5.0, device="cuda"):
+        self.orig_rate, self.new_rate = int(orig_rate), int(new_rate)
+        self.up, self.down, h = resample_filter(orig_rate, new_rate, half_width, beta)
+        if max(self.up, self.down) > RESAMPLE_MAX_FACTOR:
+            raise _lib.T2SError("Resampler: %d -> %d Hz is the ratio %d / %d; max(up, down) may be at most %d"
+                                % (orig_rate, new_rate, self.up, self.down, RESAMPLE_MAX_FACTOR))
+        self.n_taps = h.size
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.T2SError("Resampler: the filter lives in HBM (cuda); there is no CPU path")
+        self.h = torch.from_numpy(h).to(dev)
+
+    def out_length(self, n):
+        """samples that n input samples give: ceil(n up / down)"""
+        return -(-int(n) * self.up // self.down)
+
+    def _filter(self):
+        return _lib.ptr(self.h), self.n_taps, self.up, self.down
+
+    def _table(self, src, table, dst, max_out):
+        """t2s_resample_table over `table` (host int64 [n, 4]: src_start, src_count, dst_start, dst_cap) from the flat device tensor
+        `src` (int16 / f32 / f16) into the flat `dst` (int16 / f32), 65535 rows a launch."""
+        kinds = {torch.int16: 0, torch.float32: 1, torch.float16: 2}
+        table_d = _to_device(table.contiguous(), src.device)
+        for r0 in range(0, table.size(0), 65535):
+            rows = min(65535, table.size(0) - r0)
+            _lib.call("t2s_resample_table", _lib.ptr(src), kinds[src.dtype], src.numel(), _lib.ptr(table_d[r0:]), rows,
+                      *self._filter(), _lib.ptr(dst), kinds[dst.dtype], dst.numel(), int(max_out), None, _lib.current_stream())
+        return dst
+
+    def _rows(self, audio, what):
+        """[N], [B, N] or [B, 1, N] f32 / f16 in HBM -> (rows [B, N] with unit stride inside a row, B, N, ldx)"""
+        _need_cuda(audio, what)
+        if audio.device != self.h.device:
+            raise _lib.T2SError("%s: audio is on %s, the filter on %s" % (what, audio.device, self.h.device))
+        if audio.dim() not in (1, 2, 3) or (audio.dim() == 3 and audio.size(1) != 1) or audio.numel() == 0:
+            raise _lib.T2SError("%s: audio must be [N], [B, N] or [B, 1, N] and hold samples, got %s" % (what, tuple(audio.shape)))
+        x = audio.detach()
+        if x.dtype not in (torch.float32, torch.float16):
+            raise _lib.T2SError("%s: expected float32 or float16, got %s (int16 pools go through PcmPool.resample)" % (what, x.dtype))
+        N = x.size(-1)
+        x = x.reshape(-1, N)
+        B = x.size(0)
+        if B > 65535:
+            raise _lib.T2SError("%s: %d rows, the most is 65535" % (what, B))
+        if x.stride(1) != 1 or (B > 1 and x.stride(0) < N):
+            x = x.contiguous()
+        return x, B, N, (x.stride(0) if B > 1 else N)
+
+    def _batch(self, x, B, N, ldx, lens_d, want_lengths):
+        n_out = self.out_length(N)
+        out = torch.empty(B, n_out, dtype=torch.float32, device=x.device)
+        out_lens = torch.empty(B, dtype=torch.int32, device=x.device) if want_lengths else None
+        _lib.call("t2s_resample_batch", _lib.ptr(x), int(x.dtype == torch.float16), B, N, ldx, _lib.ptr(lens_d), *self._filter(),
+                  _lib.ptr(out), n_out, n_out, _lib.ptr(out_lens), _lib.current_stream())
+        return out, out_lens
+
+    def forward(self, audio):
+        """audio [N], [B, N] or [B, 1, N], float32 or float16 in HBM -> float32 of the same rank with out_length(N) samples a row"""
+        x, B, N, ldx = self._rows(audio, "Resampler.forward")
+        if self.up == self.down:
+            return audio.detach().to(torch.float32, copy=True)
+        out, _ = self._batch(x, B, N, ldx, None, False)
+        return out.view(audio.shape[:-1] + (out.size(1),))
+
+    __call__ = forward
+
+    def resample_batch(self, audio, lengths):
+        """A padded batch, e.g. Denoiser.denoise_batch's two results as returned: audio [B, T] or [B, 1, T] float32 or float16 and
+        lengths [B] (a device tensor is used where it is - nothing is read back; a host tensor or a sequence is copied over).
+        Returns (audio_out float32 of the same rank with out_length(T) samples a row, out_lengths int64 [B] on the device): entry
+        b's first ceil(lengths[b] up / down) samples are forward(audio[b, :lengths[b]])'s bit for bit, the rest zeros; samples at and
+        behind lengths[b] are never read, and lengths are clamped to [0, T] on the device."""
+        what = "Resampler.resample_batch"
+        if audio.dim() not in (2, 3):
+            raise _lib.T2SError("%s: audio must be [B, T] or [B, 1, T], got %s" % (what, tuple(audio.shape)))
+        x, B, N, ldx = self._rows(audio, what)
+        try:
+            lens = torch.as_tensor(lengths)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise _lib.T2SError("%s: lengths must be a tensor or a sequence of integers (%s)" % (what, e))
+        if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+            raise _lib.T2SError("%s: lengths must be integers, got %s" % (what, lens.dtype))
+        if lens.dim() != 1 or lens.numel() != B:
+            raise _lib.T2SError("%s: lengths has shape %s, the batch holds %d entries" % (what, tuple(lens.shape), B))
+        if lens.is_cuda:
+            lens_d = lens.detach().clamp(0, N).to(torch.int32).contiguous()
+        else:
+            lens_d = _to_device(lens.detach().clamp(0, N).to(torch.int32).contiguous(), x.device)
+        if self.up == self.down:
+            return audio.detach().to(torch.float32, copy=True), lens_d.to(torch.int64)
+        out, out_lens = self._batch(x, B, N, ldx, lens_d, True)
+        return out.view(audio.shape[:-1] + (out.size(1),)), out_lens.to(torch.int64)
 
 
 def dynamic_range_compression(x, C=1, clip_val=1e-5):

@@ -17,3 +17,24 @@ hipError_t t2s_launch_pcm16(const void* x, int is_half, int B, int N, long ldx, 
 hipError_t t2s_launch_pcm16_gather(const short* pool, long pool_len, const long* table, int B, int N, float max_wav, float* out,
                                    long ldo, hipStream_t s);
 hipError_t t2s_launch_gate_targets(const int* frames, int B, int T, float* gate, hipStream_t s);
+
+// sample-rate conversion (resample.hip): one kernel for a pool addressed through a table and for a padded batch
+#define T2S_RESAMPLE_TILE 1024                  // consecutive outputs of one row per workgroup
+#define T2S_RESAMPLE_LDS_MAX (96 * 1024)        // the filter's polyphase table must fit: 84 KB at max(up, down) = 512, half_width 10
+struct ResampleArgs {
+    const void* src;            // int16 / f32 / f16 [src_len]
+    long src_len;
+    const long* table;          // [n_rows][4] int64 on the device: src_start, src_count, dst_start, dst_cap; NULL: the batch form below
+    const int* lengths;         // batch form: [n_rows] int32 on the device or NULL (every row holds N)
+    long N, ldx, N_out, ldo;    // batch form: row b reads src + b ldx, writes dst + b ldo, dst_cap = N_out
+    const double* h;            // [n_taps], n_taps odd
+    int n_taps, up, down;
+    int lp;                     // (filled in by the launcher) doubles between two phases of the table in LDS
+    void* dst;                  // int16 / f32 [dst_len]
+    long dst_len;
+    long max_out;               // outputs the grid covers per row
+    int* out_lengths;           // [n_rows] int32 or NULL
+};
+int t2s_resample_lds_bytes(int n_taps, int up);
+// src_kind 0 int16, 1 f32, 2 f16; dst_kind 0 int16, 1 f32
+hipError_t t2s_launch_resample(const ResampleArgs& a, int src_kind, int dst_kind, int n_rows, hipStream_t s);

@@ -140,4 +140,40 @@ int t2s_gate_targets(const int* frames, int B, int T, float* gate, void* stream)
     return T2S_OK;
 }
 
+// ---- sample-rate conversion: both entry points launch resample.hip's one kernel --------------------------------------------------------
+static bool resample_filter_ok(const double* h, int n_taps, int up, int down) {
+    if (!h || ((uintptr_t)h & 7) || n_taps < 3 || !(n_taps & 1) || up < 1 || down < 1 || up > 512 || down > 512) return false;
+    int a = up, b = down;
+    while (b) { const int t = a % b; a = b; b = t; }
+    return a == 1 && t2s_resample_lds_bytes(n_taps, up) <= T2S_RESAMPLE_LDS_MAX;
+}
+
+int t2s_resample_tile(void) { return T2S_RESAMPLE_TILE; }
+
+int t2s_resample_table(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* h, int n_taps, int up,
+                       int down, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream) {
+    if (!src || !table || !dst || src_kind < 0 || src_kind > 2 || dst_kind < 0 || dst_kind > 1 || src_len <= 0 || dst_len <= 0 ||
+        n_rows <= 0 || n_rows > 65535 || max_out <= 0 || max_out > (1L << 40) || !resample_filter_ok(h, n_taps, up, down))
+        return T2S_EINVAL;
+    ResampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.src_len = src_len; a.table = table; a.h = h; a.n_taps = n_taps; a.up = up; a.down = down;
+    a.dst = dst; a.dst_len = dst_len; a.max_out = max_out; a.out_lengths = out_lengths;
+    T2S_CHECK_HIP(t2s_launch_resample(a, src_kind, dst_kind, n_rows, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_resample_batch(const void* x, int is_half, int B, int N, long ldx, const int* lengths, const double* h, int n_taps, int up,
+                       int down, float* out, int N_out, long ldo, int* out_lengths, void* stream) {
+    if (!x || !out || B <= 0 || B > 65535 || N <= 0 || N_out <= 0 || ldx < N || ldo < N_out || !resample_filter_ok(h, n_taps, up, down))
+        return T2S_EINVAL;
+    ResampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = x; a.src_len = (long)(B - 1) * ldx + N; a.lengths = lengths; a.N = N; a.ldx = ldx; a.N_out = N_out; a.ldo = ldo;
+    a.h = h; a.n_taps = n_taps; a.up = up; a.down = down;
+    a.dst = out; a.dst_len = (long)(B - 1) * ldo + N_out; a.max_out = N_out; a.out_lengths = out_lengths;
+    T2S_CHECK_HIP(t2s_launch_resample(a, is_half ? 2 : 1, 1, B, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 }  // extern "C"

@@ -1,7 +1,8 @@
 """Training batches assembled on the MI355X from int16 PCM: a corpus of clips lives in HBM, and one call turns
 a list of clip indices into the tensors `WaveGlow.forward` / `Tacotron.forward` take.
 
-  PcmPool(clips, sampling_rate)                 the clips back to back in one int16 device tensor; .from_wav_files(paths, rate)
+  PcmPool(clips, sampling_rate)                 the clips back to back in one int16 device tensor; .from_wav_files(paths, rate);
+                                                .resample(new_rate) / from_wav_files(..., resample=True): rate conversion in HBM
   Mel2SampBatch(pool, segment_length, ...)      waveglow/mel2samp.py:60-105 (Mel2Samp.__getitem__ + the default collate): (mel, audio)
   TextMelBatch(pool, sequences, ...)            utils/data_utils.py:46-150 (TextMelLoader + TextMelCollate) and Tacotron.parse_batch
 
@@ -11,7 +12,8 @@ small tables to the device and reads nothing back.  Decoding files, file lists, 
 
 Stated departure: the reference's TextMelLoader loads floats with librosa (resampling to the target rate) and then divides them by
 max_wav_value a second time (utils/data_utils.py:18-20, 82).  TextMelBatch does what Mel2Samp does: int16 samples at the target
-rate, divided once.
+rate, divided once.  A corpus at another rate is brought to the target rate by PcmPool.resample / from_wav_files(resample=True) -
+scipy.signal.resample_poly's filter, not librosa's.
 """
 import random
 
@@ -19,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import TacotronSTFT, _pcm16_gather, _to_device
+from .audio import Resampler, TacotronSTFT, _pcm16_gather, _to_device
 
 __all__ = ["PcmPool", "Mel2SampBatch", "TextMelBatch", "gather_width"]
 
@@ -70,24 +72,82 @@ class PcmPool:
         return self.lengths.numel()
 
     @classmethod
-    def from_wav_files(cls, paths, sampling_rate, device="cuda"):
-        """Reads each file with scipy.io.wavfile.read.  A file at another rate raises the reference's ValueError
-        (waveglow/mel2samp.py:90-92); a file that is not mono int16 is refused."""
-        return cls(cls.read_wav_files(paths, sampling_rate), sampling_rate, device)
+    def _of(cls, pcm, lengths, sampling_rate):
+        """A pool around an int16 device tensor that already holds the clips back to back"""
+        pool = cls.__new__(cls)
+        pool.sampling_rate, pool.pcm = sampling_rate, pcm
+        pool.lengths = lengths.to(torch.int64)
+        pool.offsets = torch.cumsum(pool.lengths, 0) - pool.lengths
+        return pool
+
+    def resample(self, new_rate):
+        """The pool at `new_rate`: every clip converted alone (Resampler: scipy.signal.resample_poly's filter, zero extension at the
+        clip's own two ends, rounded to int16 with saturation), int16 to int16 in HBM in one launch.  Clip order and count are kept;
+        clip i holds ceil(lengths[i] up / down) samples.  The same rate gives a copy."""
+        if new_rate == self.sampling_rate:
+            return self._of(self.pcm.clone(), self.lengths, new_rate)
+        rs = Resampler(self.sampling_rate, new_rate, device=self.pcm.device)
+        lengths = (self.lengths * rs.up + (rs.down - 1)) // rs.down
+        pool = self._of(torch.empty(int(lengths.sum()), dtype=torch.int16, device=self.pcm.device), lengths, new_rate)
+        rs._table(self.pcm, torch.stack([self.offsets, self.lengths, pool.offsets, pool.lengths], 1), pool.pcm, int(lengths.max()))
+        return pool
+
+    @classmethod
+    def from_wav_files(cls, paths, sampling_rate, device="cuda", resample=False):
+        """Reads each file with scipy.io.wavfile.read.  A file that is not mono int16 is refused.  A file at another rate raises the
+        reference's ValueError (waveglow/mel2samp.py:90-92) - unless `resample` is set: then files are uploaded as read, grouped by
+        their rate, and each group is converted to sampling_rate on the device straight into its clips' places in the pool (one
+        launch per source rate; PcmPool.resample's conversion, clip by clip), in the order of `paths`."""
+        if not resample:
+            return cls(cls.read_wav_files(paths, sampling_rate), sampling_rate, device)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise T2SError("PcmPool: the pool lives in HBM (cuda); there is no CPU path")
+        files = [cls._read_wav(path) for path in paths]
+        if not files:
+            raise T2SError("PcmPool: no clips")
+        by_rate = {}
+        for i, (rate, data) in enumerate(files):
+            if data.size == 0:
+                raise T2SError("PcmPool: clip %d is empty" % i)
+            by_rate.setdefault(rate, []).append(i)
+        converters = {rate: Resampler(rate, sampling_rate, device=dev) for rate in by_rate if rate != sampling_rate}
+        lengths = torch.tensor([d.size if r == sampling_rate else converters[r].out_length(d.size) for r, d in files],
+                               dtype=torch.int64)
+        pool = cls._of(torch.empty(int(lengths.sum()), dtype=torch.int16, device=dev), lengths, sampling_rate)
+        for rate, members in by_rate.items():
+            if rate == sampling_rate:               # copied: one host-to-device copy per run of neighbouring files
+                k = 0
+                while k < len(members):
+                    e = k
+                    while e + 1 < len(members) and members[e + 1] == members[e] + 1:
+                        e += 1
+                    run = torch.from_numpy(np.concatenate([files[i][1] for i in members[k:e + 1]]))
+                    first = int(pool.offsets[members[k]])
+                    pool.pcm[first:first + run.numel()].copy_(run)
+                    k = e + 1
+                continue
+            src_len = torch.tensor([files[i][1].size for i in members], dtype=torch.int64)
+            src = torch.from_numpy(np.concatenate([files[i][1] for i in members])).to(dev)
+            table = torch.stack([torch.cumsum(src_len, 0) - src_len, src_len, pool.offsets[members], lengths[members]], 1)
+            converters[rate]._table(src, table, pool.pcm, int(lengths[members].max()))
+        return pool
+
+    @staticmethod
+    def _read_wav(path, sampling_rate=None):
+        """(rate, samples) of one file; a rate other than `sampling_rate` (where given) and a file that is not mono int16 are refused"""
+        from scipy.io.wavfile import read
+        rate, data = read(path)
+        if sampling_rate is not None and rate != sampling_rate:
+            raise ValueError("{} SR doesn't match target {} SR".format(rate, sampling_rate))
+        if data.dtype != np.int16 or data.ndim != 1:
+            raise T2SError("%s: expected mono int16 PCM, got %s with shape %s" % (path, data.dtype, data.shape))
+        return rate, data
 
     @staticmethod
     def read_wav_files(paths, sampling_rate):
         """The host half of from_wav_files: the files' samples as a list of 1-D int16 arrays."""
-        from scipy.io.wavfile import read
-        clips = []
-        for path in paths:
-            rate, data = read(path)
-            if rate != sampling_rate:
-                raise ValueError("{} SR doesn't match target {} SR".format(rate, sampling_rate))
-            if data.dtype != np.int16 or data.ndim != 1:
-                raise T2SError("%s: expected mono int16 PCM, got %s with shape %s" % (path, data.dtype, data.shape))
-            clips.append(data)
-        return clips
+        return [PcmPool._read_wav(path, sampling_rate)[1] for path in paths]
 
     def _indices(self, indices, what):
         idx = [int(i) for i in indices]
