@@ -930,6 +930,50 @@ int t2s_resample_table(const void* src, int src_kind, long src_len, const long* 
 int t2s_resample_batch(const void* x, int is_half, int B, int N, long ldx, const int* lengths, const double* h, int n_taps, int up,
                        int down, float* out, int N_out, long ldo, int* out_lengths, void* stream);
 
+/* ---- peak rescaling and silence trimming in device memory (additive to ABI version 4; audio.py Trimmer, data.py PcmPool.rescale_trim) ----
+ * librosa.effects.trim's decision and the reference's `wav / abs(wav).max() * rescaling_max` (datasets/kss.py:68-74).  For a row of n
+ * samples x, frame length fl, hop h, pad = fl / 2 samples of padding at both ends (pad_mode 0: reflected about the first and the last
+ * sample, needs n > pad; pad_mode 1: zeros): n_frames = 1 + (n + 2 pad - fl) / h, E_f = the sum of the squares of padded samples
+ * f h .. f h + fl - 1, peak = max |x| (a non-finite sample counts as +inf), peak_eff = max(peak, peak_floor), and the view gain g =
+ * rescaling_max / peak_eff with rescaling and peak_eff > 0, else 1 / 32768 for an int16 source and 1 for floats.  Frame f is loud iff
+ *     max(E_f, F) > rho max(E_max, F)        rho = 10^(-top_db / 10), F = 1e-10 fl / g^2, E_max = max_f E_f,
+ * evaluated in double - librosa's 10 log10(max(1e-10, g^2 E_f / fl)) - 10 log10(max(1e-10, g^2 E_max / fl)) > -top_db without the
+ * logarithms.  start = h (the first loud frame), end = min(n, h (the last loud frame + 1)); no loud frame, a non-finite sample in the
+ * row, a pad_mode 0 row with n <= pad or a row of zeros (E_max = 0: no frame counts as loud, where librosa's floor would keep the row
+ * whole) give (0, 0).  Every E_f is one double-precision sum in an order that depends on fl alone
+ * (an int16 row's is the exact integer), so a row's energies, bounds and samples are the same bits alone and in any batch or pool.
+ * Tables are int64 in device memory and any value in them is safe: a negative src_count or a src_start outside [0, src_len) counts
+ * as no samples, a src_count that runs past src_len is cut there; nothing outside [0, src_len) is read.  src_kind 0 int16, 1 f32,
+ * 2 f16; no alignment beyond the element (tables, energy, stats and bounds: 8 bytes).
+ *  t2s_trim_tile: host only, the frames one workgroup of the energy pass makes (64).
+ *  t2s_trim_energy: table [n_rows][3] = (src_start, src_count, energy_start).  Writes row r's E_f to energy[energy_start + f] - as many
+ *    frames as max_frames and the scratch behind energy_start allow (an energy_start outside [0, energy_len): none) - and
+ *    stats[r] = (peak, E_max), which the call zeroes first; a pad_mode 0 row with 0 < n <= pad gets no frames and E_max = -1.
+ *    energy = NULL: the peaks only.  max_frames bounds the grid: ceil(max_frames / tile) x n_rows workgroups.
+ *  t2s_trim_bounds: from the same table, energies and stats, bounds[r] = (start, end), int64.  rescale 0 / 1: whether g carries the
+ *    peak (rescaling_max is ignored without).
+ *  t2s_trim_gather: table [n_rows][4] = (src_start, src_count, dst_start, dst_cap), as t2s_resample_table's.  bounds (or NULL: the
+ *    whole row) narrows row r's source to [src_start + start, src_start + end), cut to the row; stats (or NULL: no rescaling) makes
+ *    every sample x -> x s with s = rescaling_max / peak_eff formed in double (int16: s = rescaling_max 32768 / peak_eff), where
+ *    peak_eff > 0.  int16 -> int16 stores rint((double)x s), ties to even, saturated; f32 / f16 -> f32 stores (float)((double)x s);
+ *    without rescaling samples are copied bit for bit (f16 widened exactly).  dst_kind must be 0 for an int16 source and 1 for a
+ *    float one.  The row gets v = min(kept, dst_cap) samples at dst_start and +0 behind them up to dst_cap; dst_cap is cut to max_out
+ *    and to what dst holds; out_lengths: NULL or int32 [n_rows] that receives v.  src and dst must not overlap.
+ *  T2S_EINVAL, with nothing launched: a NULL src, table, stats (energy, bounds pass), energy (bounds pass), bounds (bounds pass) or
+ *    dst; src_len, dst_len, n_rows, energy_len, max_frames or max_out <= 0; n_rows > 65535; max_frames or max_out > 2^40;
+ *    frame_length outside [2, 8192]; hop outside [1, frame_length]; pad_mode not 0 or 1; a kind out of range or a pair other than
+ *    the three above; top_db, rescaling_max or peak_floor negative or not finite; rescaling (rescale = 1, or stats given) with
+ *    rescaling_max = 0; a misaligned table, energy, stats or bounds; overlapping src and dst. */
+int t2s_trim_tile(void);
+int t2s_trim_energy(const void* src, int src_kind, long src_len, const long* table, int n_rows, int frame_length, int hop, int pad_mode,
+                    long max_frames, double* energy, long energy_len, double* stats, void* stream);
+int t2s_trim_bounds(const long* table, int n_rows, int src_kind, long src_len, int frame_length, int hop, int pad_mode, long max_frames,
+                    const double* energy, long energy_len, const double* stats, double top_db, int rescale, double rescaling_max,
+                    double peak_floor, long* bounds, void* stream);
+int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* table, int n_rows, const long* bounds, const double* stats,
+                    double rescaling_max, double peak_floor, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T2S_LIB_PATH") or os.path.join(HERE, "libt2s_hip.so")      # (override: diagnostic builds)
 
 c_int, c_float, c_vp, c_long = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_long
+c_double = ctypes.c_double
 
 # name -> argtypes (every function returns int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -114,6 +115,11 @@ SIGNATURES = {
     "t2s_resample_tile": [],
     "t2s_resample_table": [c_vp, c_int, c_long, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_long, c_long, c_vp, c_vp],
     "t2s_resample_batch": [c_vp, c_int, c_int, c_int, c_long, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_long, c_vp, c_vp],
+    "t2s_trim_tile": [],
+    "t2s_trim_energy": [c_vp, c_int, c_long, c_vp, c_int, c_int, c_int, c_int, c_long, c_vp, c_long, c_vp, c_vp],
+    "t2s_trim_bounds": [c_vp, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_vp, c_long, c_vp, c_double, c_int, c_double,
+                        c_double, c_vp, c_vp],
+    "t2s_trim_gather": [c_vp, c_int, c_long, c_vp, c_int, c_vp, c_vp, c_double, c_double, c_vp, c_int, c_long, c_long, c_vp, c_vp],
     "t2s_sum_axis0": [c_vp, c_int, c_int, c_vp, c_vp],
     "t2s_add3": [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp],
     "t2s_scale_by_scalar": [c_vp, ctypes.c_size_t, c_vp, c_float, c_vp, c_vp],

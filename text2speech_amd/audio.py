@@ -14,6 +14,8 @@ TacotronSTFT.mel_spectrogram_batch, Denoiser.denoise_batch) and to_pcm16: every 
 for bit, and zeros behind its end.  from_pcm16 is to_pcm16's inverse; training batches from a pool of int16
 clips are text2speech_amd/data.py.  Resampler converts the sample rate of a batch (forward / resample_batch) or, through
 PcmPool.resample, of a pool: scipy.signal.resample_poly's polyphase filter with every sum in double precision (csrc/resample.hip).
+Trimmer cuts leading and trailing silence (librosa.effects.trim's decision) and rescales to a peak, on a batch (forward /
+trim_batch / bounds_batch) or, through PcmPool.rescale_trim, on a pool (csrc/trim.hip).
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
 window); the mel filterbank restates librosa.filters.mel's defaults (Slaney scale, area normalisation) because librosa is
 an unpinned dependency that this image does not have.
@@ -25,7 +27,7 @@ from scipy.signal import get_window
 from . import _lib
 
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
-           "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter"]
+           "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer"]
 
 
 def _ru(a, b):
@@ -252,6 +254,161 @@ class Resampler:
             return audio.detach().to(torch.float32, copy=True), lens_d.to(torch.int64)
         out, out_lens = self._batch(x, B, N, ldx, lens_d, True)
         return out.view(audio.shape[:-1] + (out.size(1),)), out_lens.to(torch.int64)
+
+
+TRIM_MAX_FRAME = 8192          # the library's limit on frame_length (include/t2s_hip.h)
+_KINDS = {torch.int16: 0, torch.float32: 1, torch.float16: 2}
+
+
+class Trimmer:
+    """Silence trimming and peak rescaling in HBM (csrc/trim.hip): librosa.effects.trim(x, top_db, frame_length, hop_length)'s cut
+    points - the first and the last frame whose RMS lies less than top_db below the loudest frame's, frames centred with
+    frame_length // 2 samples of padding (`pad_mode` "reflect": librosa < 0.10, what the reference ran; "constant": zeros,
+    librosa >= 0.10) - and the reference's `wav / abs(wav).max() * rescaling_max` (datasets/kss.py:68-74; utils/audio.py:14-17 with
+    its 0.01 as `peak_floor`: the gain is rescaling_max / max(peak, peak_floor)).  Either half is optional: top_db=None keeps every
+    sample, rescaling_max=None copies them bit for bit.  The decision is taken on the source samples with the gain inside its
+    1e-10 floor, which is what trimming the rescaled floats decides (include/t2s_hip.h states the rule); a clip with a non-finite
+    sample trims to nothing, and so does a clip of zeros (librosa's floor would keep that one whole).  librosa is restated, not
+    imported."""
+
+    def __init__(self, frame_length=512, hop_length=128, top_db=23, pad_mode="reflect", rescaling_max=None, peak_floor=0.0):
+        T2SError = _lib.T2SError
+        if int(frame_length) != frame_length or not 2 <= frame_length <= TRIM_MAX_FRAME:
+            raise T2SError("Trimmer: frame_length must be an integer in [2, %d], got %r" % (TRIM_MAX_FRAME, frame_length))
+        if int(hop_length) != hop_length or not 1 <= hop_length <= frame_length:
+            raise T2SError("Trimmer: hop_length must be an integer in [1, frame_length], got %r" % (hop_length,))
+        if pad_mode not in ("reflect", "constant"):
+            raise T2SError("Trimmer: pad_mode must be 'reflect' or 'constant', got %r" % (pad_mode,))
+        for name, v, positive in (("top_db", top_db, False), ("rescaling_max", rescaling_max, True), ("peak_floor", peak_floor, False)):
+            if v is None and name != "peak_floor":
+                continue
+            if v is None or not np.isfinite(v) or v < 0 or (positive and v == 0):
+                raise T2SError("Trimmer: %s must be finite and %s, got %r" % (name, "positive" if positive else "not negative", v))
+        self.frame_length, self.hop_length, self.pad_mode = int(frame_length), int(hop_length), pad_mode
+        self.top_db = None if top_db is None else float(top_db)
+        self.rescaling_max = None if rescaling_max is None else float(rescaling_max)
+        self.peak_floor = float(peak_floor)
+
+    @property
+    def pad(self):
+        return self.frame_length // 2
+
+    def n_frames(self, n):
+        """frames of a clip of n samples: 1 + (n + 2 pad - frame_length) // hop_length"""
+        return 1 + (int(n) + 2 * self.pad - self.frame_length) // self.hop_length
+
+    def _stats_bounds(self, src, table3, n_rows, max_count, energy_len, stats=None):
+        """The energy pass and (with top_db) the bounds pass over `table3` (device int64 [n_rows, 3]: src_start, src_count,
+        energy_start) of the flat device tensor `src` -> (stats [n_rows, 2] float64, bounds [n_rows, 2] int64 or None)."""
+        p, dev = _lib.ptr, src.device
+        if stats is None:
+            stats = torch.empty(n_rows, 2, dtype=torch.float64, device=dev)
+        mode = 0 if self.pad_mode == "reflect" else 1
+        max_frames = max(1, self.n_frames(max_count))
+        energy = torch.empty(int(energy_len), dtype=torch.float64, device=dev) if self.top_db is not None else None
+        frames = (self.frame_length, self.hop_length, mode, max_frames)
+        _lib.call("t2s_trim_energy", p(src), _KINDS[src.dtype], src.numel(), p(table3), n_rows, *frames, p(energy),
+                  0 if energy is None else energy.numel(), p(stats), _lib.current_stream())
+        if energy is None:
+            return stats, None
+        bounds = torch.empty(n_rows, 2, dtype=torch.int64, device=dev)
+        _lib.call("t2s_trim_bounds", p(table3), n_rows, _KINDS[src.dtype], src.numel(), *frames, p(energy), energy.numel(), p(stats),
+                  self.top_db, int(self.rescaling_max is not None), self.rescaling_max or 0.0, self.peak_floor, p(bounds),
+                  _lib.current_stream())
+        return stats, bounds
+
+    def _gather(self, src, table4, n_rows, bounds, stats, dst, max_out, out_lengths=None):
+        p = _lib.ptr
+        rescale = self.rescaling_max is not None
+        _lib.call("t2s_trim_gather", p(src), _KINDS[src.dtype], src.numel(), p(table4), n_rows, p(bounds), p(stats if rescale else None),
+                  self.rescaling_max or 0.0, self.peak_floor, p(dst), _KINDS[dst.dtype], dst.numel(), int(max_out), p(out_lengths),
+                  _lib.current_stream())
+
+    def _rows(self, audio, lengths, what):
+        """audio [N], [B, N] or [B, 1, N] f32 / f16 in HBM and lengths (None: every row whole) -> (flat view over the rows, B, N,
+        ldx, int64 lengths on the device clamped to [0, N]); nothing is read back"""
+        _need_cuda(audio, what)
+        if audio.dim() not in (1, 2, 3) or (audio.dim() == 3 and audio.size(1) != 1) or audio.numel() == 0:
+            raise _lib.T2SError("%s: audio must be [N], [B, N] or [B, 1, N] and hold samples, got %s" % (what, tuple(audio.shape)))
+        x = audio.detach()
+        if x.dtype not in (torch.float32, torch.float16):
+            raise _lib.T2SError("%s: expected float32 or float16, got %s (int16 pools go through PcmPool.rescale_trim)" % (what, x.dtype))
+        N = x.size(-1)
+        x = x.reshape(-1, N)
+        B = x.size(0)
+        if B > 65535:
+            raise _lib.T2SError("%s: %d rows, the most is 65535" % (what, B))
+        if x.stride(1) != 1 or (B > 1 and x.stride(0) < N):
+            x = x.contiguous()
+        ldx = x.stride(0) if B > 1 else N
+        if lengths is None:
+            lens_d = torch.full((B,), N, dtype=torch.int64, device=x.device)
+        else:
+            try:
+                lens = torch.as_tensor(lengths)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise _lib.T2SError("%s: lengths must be a tensor or a sequence of integers (%s)" % (what, e))
+            if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+                raise _lib.T2SError("%s: lengths must be integers, got %s" % (what, lens.dtype))
+            if lens.dim() != 1 or lens.numel() != B:
+                raise _lib.T2SError("%s: lengths has shape %s, the batch holds %d entries" % (what, tuple(lens.shape), B))
+            lens = lens.detach().to(torch.int64).clamp(0, N)
+            lens_d = lens if lens.is_cuda else _to_device(lens.contiguous(), x.device)
+        return torch.as_strided(x, ((B - 1) * ldx + N,), (1,)), B, N, ldx, lens_d
+
+    def _batch_bounds(self, flat, B, N, ldx, lens_d):
+        """(stats, bounds, row index) of a padded batch; the tables are built on the device"""
+        rows = torch.arange(B, dtype=torch.int64, device=flat.device)
+        per_row = max(1, self.n_frames(N))
+        table3 = torch.stack([rows * ldx, lens_d, rows * per_row], 1).contiguous()
+        stats, bounds = self._stats_bounds(flat, table3, B, N, B * per_row)
+        return stats, bounds, rows
+
+    def bounds_batch(self, audio, lengths):
+        """(start, end), int64 [B] on the device: entry b keeps audio[b, start[b]:end[b]]; (0, 0) where nothing is loud.  Without
+        top_db: (0, lengths).  Nothing is read back."""
+        flat, B, N, ldx, lens_d = self._rows(audio, lengths, "Trimmer.bounds_batch")
+        if self.top_db is None:
+            return torch.zeros_like(lens_d), lens_d.clone()
+        _, bounds, _ = self._batch_bounds(flat, B, N, ldx, lens_d)
+        return bounds[:, 0].contiguous(), bounds[:, 1].contiguous()
+
+    def _trim(self, audio, lengths, what):
+        flat, B, N, ldx, lens_d = self._rows(audio, lengths, what)
+        stats = bounds = None
+        rows = torch.arange(B, dtype=torch.int64, device=flat.device)
+        if self.top_db is not None or self.rescaling_max is not None:
+            stats, bounds, rows = self._batch_bounds(flat, B, N, ldx, lens_d)
+        out = torch.empty(B, N, dtype=torch.float32, device=flat.device)
+        out_lens = torch.empty(B, dtype=torch.int32, device=flat.device)
+        table4 = torch.stack([rows * ldx, lens_d, rows * N, torch.full_like(rows, N)], 1).contiguous()
+        self._gather(flat, table4, B, bounds, stats, out.view(-1), N, out_lens)
+        return out, out_lens
+
+    def forward(self, audio):
+        """One clip: audio [T], [1, T] or [1, 1, T], float32 or float16 in HBM -> the kept samples, rescaled where rescaling_max is
+        set, float32 of the same rank.  One read-back, of the kept length (none without top_db)."""
+        what = "Trimmer.forward"
+        if torch.is_tensor(audio) and (audio.dim() not in (1, 2, 3) or audio.numel() != audio.size(-1)):
+            raise _lib.T2SError("%s: audio must be one clip, [T], [1, T] or [1, 1, T], got %s" % (what, tuple(audio.shape)))
+        out, out_lens = self._trim(audio, None, what)
+        keep = audio.size(-1) if self.top_db is None else int(out_lens[0])
+        return out[0, :keep].view(audio.shape[:-1] + (keep,))
+
+    __call__ = forward
+
+    def trim_batch(self, audio, lengths):
+        """A padded batch, e.g. Denoiser.denoise_batch's two results as returned: audio [B, T] or [B, 1, T] float32 or float16 and
+        lengths [B] (a device tensor is used where it is; a host tensor or a sequence is copied over).  Returns (audio_out float32
+        of audio's shape, out_lengths int32 [B] on the device): entry b's first out_lengths[b] samples are
+        forward(audio[b, :lengths[b]])'s bit for bit, moved to column 0, the rest of its row zeros; an entry in which nothing is
+        loud gets length 0.  Samples at and behind lengths[b] are never read, lengths are clamped to [0, T] on the device, and
+        nothing is read back."""
+        what = "Trimmer.trim_batch"
+        if not torch.is_tensor(audio) or audio.dim() not in (2, 3):
+            raise _lib.T2SError("%s: audio must be [B, T] or [B, 1, T], got %s" % (what, tuple(getattr(audio, "shape", ()))))
+        out, out_lens = self._trim(audio, lengths, what)
+        return out.view(audio.shape), out_lens
 
 
 def dynamic_range_compression(x, C=1, clip_val=1e-5):

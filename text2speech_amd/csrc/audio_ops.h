@@ -38,3 +38,47 @@ struct ResampleArgs {
 int t2s_resample_lds_bytes(int n_taps, int up);
 // src_kind 0 int16, 1 f32, 2 f16; dst_kind 0 int16, 1 f32
 hipError_t t2s_launch_resample(const ResampleArgs& a, int src_kind, int dst_kind, int n_rows, hipStream_t s);
+
+// peak rescaling and silence trimming (trim.hip): frame energies and per-row maxima, the kept range per row, the gather
+#define T2S_TRIM_TILE 64                        // consecutive frames of one row per workgroup of the energy pass
+#define T2S_TRIM_MAX_FRAME 8192                 // the longest frame_length
+struct TrimEnergyArgs {
+    const void* src;            // int16 / f32 / f16 [src_len]
+    long src_len;
+    const long* table;          // [n_rows][3] int64 on the device: src_start, src_count, energy_start
+    int frame_length, hop, reflect;
+    long max_frames;            // frames the grid covers per row
+    double* energy;             // [energy_len] or NULL: the peaks only
+    long energy_len;
+    double* stats;              // [n_rows][2]: max |x|, max E_f (-1: a reflect row of at most frame_length / 2 samples); zeroed by the launcher
+};
+struct TrimBoundsArgs {
+    const long* table;          // the energy pass's
+    long src_len;
+    int frame_length, hop, reflect, rescale;
+    long max_frames;
+    const double* energy;
+    long energy_len;
+    const double* stats;
+    double rho;                 // 10^(-top_db / 10)
+    double rescaling_max, peak_floor;
+    double unit_gain;           // the view gain without rescaling: 1 / 32768 for int16 sources, 1 for floats
+    long* bounds;               // [n_rows][2]: start, end
+};
+struct TrimGatherArgs {
+    const void* src;
+    long src_len;
+    const long* table;          // [n_rows][4] int64 on the device: src_start, src_count, dst_start, dst_cap
+    const long* bounds;         // [n_rows][2] or NULL: the whole row
+    const double* stats;        // [n_rows][2] or NULL: no rescaling
+    double scale_num;           // a sample is multiplied by scale_num / max(peak, peak_floor): rescaling_max (x 32768 for int16)
+    double peak_floor;
+    void* dst;                  // int16 / f32 [dst_len]
+    long dst_len;
+    long max_out;               // outputs the grid covers per row
+    int* out_lengths;           // [n_rows] int32 or NULL
+};
+hipError_t t2s_launch_trim_energy(const TrimEnergyArgs& a, int src_kind, int n_rows, hipStream_t s);
+hipError_t t2s_launch_trim_bounds(const TrimBoundsArgs& a, int n_rows, hipStream_t s);
+// (src_kind, dst_kind): int16 -> int16, f32 -> f32, f16 -> f32
+hipError_t t2s_launch_trim_gather(const TrimGatherArgs& a, int src_kind, int dst_kind, int n_rows, hipStream_t s);

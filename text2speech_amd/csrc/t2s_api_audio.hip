@@ -5,6 +5,7 @@
 #include "audio_ops.h"
 #include "tacotron_ops.h"
 
+#include <math.h>
 #include <string.h>
 
 // y[item][row] = sum_k W[row][k] x[item * sx + k]  per batch element, through the GEMV / matrix-core dispatcher
@@ -173,6 +174,66 @@ int t2s_resample_batch(const void* x, int is_half, int B, int N, long ldx, const
     a.h = h; a.n_taps = n_taps; a.up = up; a.down = down;
     a.dst = out; a.dst_len = (long)(B - 1) * ldo + N_out; a.max_out = N_out; a.out_lengths = out_lengths;
     T2S_CHECK_HIP(t2s_launch_resample(a, is_half ? 2 : 1, 1, B, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+// ---- peak rescaling and silence trimming: trim.hip's three kernels ------------------------------------------------------------------
+// (a comparison with NaN is false, the subtraction is NaN for an infinity)
+static bool finite_nonneg(double v) { return v >= 0.0 && v - v == 0.0; }
+static bool trim_frames_ok(int frame_length, int hop, int pad_mode, long max_frames) {
+    return frame_length >= 2 && frame_length <= T2S_TRIM_MAX_FRAME && hop >= 1 && hop <= frame_length && (pad_mode == 0 || pad_mode == 1) &&
+           max_frames > 0 && max_frames <= (1L << 40);
+}
+static bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+int t2s_trim_tile(void) { return T2S_TRIM_TILE; }
+
+int t2s_trim_energy(const void* src, int src_kind, long src_len, const long* table, int n_rows, int frame_length, int hop, int pad_mode,
+                    long max_frames, double* energy, long energy_len, double* stats, void* stream) {
+    if (!src || !table || !stats || !al8(table) || !al8(stats) || !al8(energy) || src_kind < 0 || src_kind > 2 || src_len <= 0 ||
+        n_rows <= 0 || n_rows > 65535 || (energy && energy_len <= 0) || !trim_frames_ok(frame_length, hop, pad_mode, max_frames))
+        return T2S_EINVAL;
+    TrimEnergyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.src_len = src_len; a.table = table; a.frame_length = frame_length; a.hop = hop; a.reflect = pad_mode == 0;
+    a.max_frames = max_frames; a.energy = energy; a.energy_len = energy ? energy_len : 0; a.stats = stats;
+    T2S_CHECK_HIP(t2s_launch_trim_energy(a, src_kind, n_rows, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_trim_bounds(const long* table, int n_rows, int src_kind, long src_len, int frame_length, int hop, int pad_mode, long max_frames,
+                    const double* energy, long energy_len, const double* stats, double top_db, int rescale, double rescaling_max,
+                    double peak_floor, long* bounds, void* stream) {
+    if (!table || !energy || !stats || !bounds || !al8(table) || !al8(energy) || !al8(stats) || !al8(bounds) || src_kind < 0 ||
+        src_kind > 2 || src_len <= 0 || n_rows <= 0 || n_rows > 65535 || energy_len <= 0 ||
+        !trim_frames_ok(frame_length, hop, pad_mode, max_frames) || !finite_nonneg(top_db) || !finite_nonneg(rescaling_max) ||
+        !finite_nonneg(peak_floor) || (rescale != 0 && rescale != 1) || (rescale && !(rescaling_max > 0.0)))
+        return T2S_EINVAL;
+    TrimBoundsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.table = table; a.src_len = src_len; a.frame_length = frame_length; a.hop = hop; a.reflect = pad_mode == 0; a.rescale = rescale;
+    a.max_frames = max_frames; a.energy = energy; a.energy_len = energy_len; a.stats = stats; a.rho = pow(10.0, -top_db / 10.0);
+    a.rescaling_max = rescaling_max; a.peak_floor = peak_floor; a.unit_gain = src_kind == 0 ? 1.0 / 32768.0 : 1.0; a.bounds = bounds;
+    T2S_CHECK_HIP(t2s_launch_trim_bounds(a, n_rows, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* table, int n_rows, const long* bounds, const double* stats,
+                    double rescaling_max, double peak_floor, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths,
+                    void* stream) {
+    if (!src || !table || !dst || !al8(table) || !al8(bounds) || !al8(stats) || src_kind < 0 || src_kind > 2 ||
+        dst_kind != (src_kind == 0 ? 0 : 1) || src_len <= 0 || dst_len <= 0 || n_rows <= 0 || n_rows > 65535 || max_out <= 0 ||
+        max_out > (1L << 40) || !finite_nonneg(rescaling_max) || !finite_nonneg(peak_floor) || (stats && !(rescaling_max > 0.0)))
+        return T2S_EINVAL;
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)src_len * (src_kind == 1 ? 4 : 2);
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)dst_len * (dst_kind == 1 ? 4 : 2);
+    if (s0 < d1 && d0 < s1) return T2S_EINVAL;                  // never in place
+    TrimGatherArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.src_len = src_len; a.table = table; a.bounds = bounds; a.stats = stats;
+    a.scale_num = src_kind == 0 ? rescaling_max * 32768.0 : rescaling_max; a.peak_floor = peak_floor;
+    a.dst = dst; a.dst_len = dst_len; a.max_out = max_out; a.out_lengths = out_lengths;
+    T2S_CHECK_HIP(t2s_launch_trim_gather(a, src_kind, dst_kind, n_rows, (hipStream_t)stream));
     return T2S_OK;
 }
 

@@ -2,7 +2,8 @@
 a list of clip indices into the tensors `WaveGlow.forward` / `Tacotron.forward` take.
 
   PcmPool(clips, sampling_rate)                 the clips back to back in one int16 device tensor; .from_wav_files(paths, rate);
-                                                .resample(new_rate) / from_wav_files(..., resample=True): rate conversion in HBM
+                                                .resample(new_rate) / from_wav_files(..., resample=True): rate conversion in HBM;
+                                                .rescale_trim(rescaling_max, top_db): the reference's peak rescaling and silence trim
   Mel2SampBatch(pool, segment_length, ...)      waveglow/mel2samp.py:60-105 (Mel2Samp.__getitem__ + the default collate): (mel, audio)
   TextMelBatch(pool, sequences, ...)            utils/data_utils.py:46-150 (TextMelLoader + TextMelCollate) and Tacotron.parse_batch
 
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import Resampler, TacotronSTFT, _pcm16_gather, _to_device
+from .audio import Resampler, TacotronSTFT, Trimmer, _pcm16_gather, _to_device
 
 __all__ = ["PcmPool", "Mel2SampBatch", "TextMelBatch", "gather_width"]
 
@@ -90,6 +91,52 @@ class PcmPool:
         lengths = (self.lengths * rs.up + (rs.down - 1)) // rs.down
         pool = self._of(torch.empty(int(lengths.sum()), dtype=torch.int16, device=self.pcm.device), lengths, new_rate)
         rs._table(self.pcm, torch.stack([self.offsets, self.lengths, pool.offsets, pool.lengths], 1), pool.pcm, int(lengths.max()))
+        return pool
+
+    def rescale_trim(self, rescaling_max=None, top_db=None, frame_length=512, hop_length=128, pad_mode="reflect"):
+        """The reference's corpus preparation between decoding and the mel (datasets/kss.py:68-74), as a new pool at the same rate
+        and in the same clip order, int16 to int16 in HBM: every clip alone is scaled so that its largest sample becomes
+        rescaling_max (`wav / abs(wav).max() * rescaling_max`, rounded to int16, ties to even) and cut to what
+        librosa.effects.trim(wav, top_db, frame_length, hop_length) keeps (audio.Trimmer states the rule and pad_mode).  Either
+        half is optional (None).  `pool.resample(rate).rescale_trim(0.999, 23)` is the reference's load, rescale, trim.
+
+        With top_db the [n_clips, 2] cut points are read back once - the new offsets are their prefix sum on the host - and that is
+        the only read.  A clip in which nothing is loud, or with pad_mode "reflect" one of at most frame_length // 2 samples, raises
+        T2SError naming the clips; a pool holds no empty clip.  Stated departure: the reference keeps floats after rescaling, the
+        pool rounds them to int16 (at most half an LSB); the cut points are decided on the source samples."""
+        what = "PcmPool.rescale_trim"
+        tr = Trimmer(frame_length, hop_length, top_db, pad_mode, rescaling_max)
+        if top_db is None and rescaling_max is None:
+            return self._of(self.pcm.clone(), self.lengths, self.sampling_rate)
+        n, dev, chunk = len(self), self.pcm.device, 65535
+        stats = torch.empty(n, 2, dtype=torch.float64, device=dev)
+        frames = (1 + (self.lengths + 2 * tr.pad - tr.frame_length) // tr.hop_length).clamp(min=1)
+        found = []
+        for r0 in range(0, n, chunk):                       # 65535 rows a launch
+            sl = slice(r0, min(n, r0 + chunk))
+            e_off = torch.cumsum(frames[sl], 0) - frames[sl]
+            table3 = _to_device(torch.stack([self.offsets[sl], self.lengths[sl], e_off], 1).contiguous(), dev)
+            _, b = tr._stats_bounds(self.pcm, table3, table3.size(0), int(self.lengths[sl].max()), int(frames[sl].sum()), stats[sl])
+            found.append(b)
+        bounds_d, lengths = None, self.lengths
+        if top_db is not None:
+            bounds_d = found[0] if len(found) == 1 else torch.cat(found)
+            bounds = bounds_d.cpu()                         # the one read: the new pool's offsets are a host prefix sum
+            lengths = bounds[:, 1] - bounds[:, 0]
+            short = torch.nonzero(self.lengths <= tr.pad).flatten().tolist() if pad_mode == "reflect" else []
+            if short:
+                raise T2SError("%s: clips %s have at most frame_length // 2 = %d samples (pad_mode 'reflect' needs more)"
+                               % (what, short, tr.pad))
+            empty = torch.nonzero(lengths <= 0).flatten().tolist()
+            if empty:
+                raise T2SError("%s: clips %s trim to nothing (no frame within %g dB of the loudest, or a clip of zeros)"
+                               % (what, empty, tr.top_db))
+        pool = self._of(torch.empty(int(lengths.sum()), dtype=torch.int16, device=dev), lengths, self.sampling_rate)
+        table4 = _to_device(torch.stack([self.offsets, self.lengths, pool.offsets, pool.lengths], 1).contiguous(), dev)
+        for r0 in range(0, n, chunk):
+            sl = slice(r0, min(n, r0 + chunk))
+            tr._gather(self.pcm, table4[sl], sl.stop - r0, None if bounds_d is None else bounds_d[sl], stats[sl], pool.pcm,
+                       int(pool.lengths[sl].max()))
         return pool
 
     @classmethod
