@@ -974,6 +974,33 @@ int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* tab
                     double rescaling_max, double peak_floor, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths,
                     void* stream);
 
+/* ---- keyed sampling: random draws that are a function of (the entry's seed, the element's index) only (additive to ABI version 4;
+ *      tacotron.py inference_batch(seeds=), glow.py infer(seed=) / infer_batch(seeds=) / draw_noise) ----
+ * An entry of a batch draws the same bits alone and in any batch: nothing depends on B, on the entry's place, on the padded length
+ * or on a generator's state.  seeds: unsigned 64-bit [B] in device memory, one per entry.  All arithmetic below is wrapping uint64;
+ *     mix(x):  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31      (splitmix64's finaliser)
+ *     GOLD = 0x9E3779B97F4A7C15.
+ *  t2s_bernoulli_mask_keyed: mask unsigned char [n_steps][B][row].  mask[t][b][j] = (mix((t row + j) GOLD + seeds[b]) >> 40) <
+ *    (unsigned)(keep_prob 2^24) - exactly what t2s_bernoulli_mask(buf, n_steps row, seeds[b], 0, keep_prob) stores at index
+ *    t row + j.  B = 1 with seed s is therefore that call bit for bit, and entry b of any batch is its solo mask.
+ *    T2S_EINVAL, with nothing launched: a NULL pointer; n_steps, B or row <= 0; B > 65535; n_steps row > (2^31 - 1) 256; keep_prob outside
+ *    (0, 1].
+ *  t2s_wg_noise_keyed: z float [B][G][L], contiguous (the buffer WaveGlow's inverse flow starts from, glow.py:260-267,284-289).
+ *    key_b = mix(seeds[b] GOLD + 0x5741564547)  (the constant keeps this domain apart from the mask hash: one user seed feeds both).
+ *    For channel c and column t:  p = (c << 40) | (t >> 1),  a = mix((2 p) GOLD + key_b),  h = mix((2 p + 1) GOLD + key_b),
+ *        u1 = ((a >> 11) + 1) 2^-53  in (0, 1],   u2 = (h >> 11) 2^-53  in [0, 1),   r = sqrt(-2 ln u1),
+ *        n = r cos(2 pi u2) for even t,  r sin(2 pi u2) for odd t        (evaluated in double precision, sincospi(2 u2)),
+ *        z[b][c][t] = sigma_b * (float)n        (one f32 rounding of n, then one f32 multiply),
+ *    sigma_b = sigmas[b] where sigmas (NULL, or float [B] in device memory) is given, else sigma.  |n| <= sqrt(106 ln 2) = 8.58: no
+ *    inf, no NaN.  The value depends on (seeds[b], c, t) only.  sigmas' values are not read on the host and so not checked.
+ *    T2S_EINVAL, with nothing launched: a NULL z or seeds; B, G or L <= 0; B or G > 65535; L >= 2^40; B G L > 2^60; a sigma that is
+ *    not finite or < 0.  No alignment beyond the element.
+ *  t2s_noise_tile: host only, the columns of one row that a workgroup of the noise kernel makes (1024). */
+int t2s_bernoulli_mask_keyed(unsigned char* mask, int n_steps, int B, int row, const unsigned long long* seeds, float keep_prob,
+                             void* stream);
+int t2s_noise_tile(void);
+int t2s_wg_noise_keyed(float* z, int B, int G, long L, const unsigned long long* seeds, float sigma, const float* sigmas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

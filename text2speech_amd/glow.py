@@ -18,7 +18,7 @@ from collections import namedtuple
 import torch
 import torch.nn.functional as F  # noqa: F401  (kept for API parity with the reference module)
 
-from . import _lib
+from . import _lib, sampling
 
 
 class _WaveGlowLossFn(torch.autograd.Function):
@@ -858,10 +858,25 @@ class _Engine:
         main.wait_stream(side)               # log_det
         return z, log_s_list, log_det_list
 
-    def infer(self, mel, sigma, noise):
-        return self._infer(mel, sigma, noise, None)
+    def infer(self, mel, sigma, noise, seeds=None, sigmas=None):
+        return self._infer(mel, sigma, noise, None, seeds, sigmas)
 
-    def infer_batch(self, mel, lengths, sigma, noise):
+    def early_flows(self):
+        """The flows that re-attach early channels, in the order the inverse flow meets them (the order of ``noise``'s early draws)."""
+        m = self.m
+        return [k for k in reversed(range(m.n_flows)) if k % m.n_early_every == 0 and k > 0]
+
+    def noise_slices(self, z):
+        """The (final, [early draws]) views of a [B, G, L] buffer of draws, as ``_infer`` assigns a ``noise`` tuple to it."""
+        m = self.m
+        final = z[:, m.n_group - m.n_remaining_channels:]
+        early = []
+        for k in self.early_flows():
+            c_off = m.n_early_size * (k // m.n_early_every)
+            early.append(z[:, c_off - m.n_early_size:c_off])
+        return final, early
+
+    def infer_batch(self, mel, lengths, sigma, noise, seeds=None, sigmas=None):
         """infer() on a padded batch whose entry b is lengths[b] frames long (host int64 [B], validated by the caller): the same
         launches with every writer of the X and window planes replaced by the partner that takes the lengths, which shows each
         entry zeros past its own end as its solo run shows it past L, and one more that zeroes the audio
@@ -872,13 +887,13 @@ class _Engine:
         stride = m.upsample.stride[0]
         # columns per entry, once per call: the only host -> device copy, and the array every launch that takes lengths reads
         lens = (lengths * (stride // m.n_group)).to(torch.int32).to(mel.device)
-        audio = self._infer(mel, sigma, noise, lens)
+        audio = self._infer(mel, sigma, noise, lens, seeds, sigmas)
         B, T = audio.shape
         _lib.call("t2s_zero_rows_f32", _lib.ptr(audio), _lib.ptr(lens), B, T // m.n_group, m.n_group, _lib.current_stream())
         self._keep.append(lens)
         return audio, (lengths * stride).to(mel.device)
 
-    def _infer(self, mel, sigma, noise, lens):
+    def _infer(self, mel, sigma, noise, lens, seeds=None, sigmas=None):
         m = self.m
         self._check_inputs(mel)
         dev = mel.device
@@ -924,16 +939,21 @@ class _Engine:
         # n_remaining channels, and in front of them the n_early_size channels re-attached at each early flow.
         z = torch.empty(B, G, L, dtype=torch.float32, device=dev)
         n_rem_final = m.n_remaining_channels
-        early_ks = [k for k in reversed(range(m.n_flows)) if k % m.n_early_every == 0 and k > 0]
-        if noise is None:
-            noise_final = torch.randn(B, n_rem_final, L, dtype=torch.float32, device=dev)
-            noise_early = [torch.randn(B, m.n_early_size, L, dtype=torch.float32, device=dev) for _ in early_ks]
+        early_ks = self.early_flows()
+        if seeds is not None:
+            # keyed draws (csrc/sampling.hip): z[b] is a function of (seeds[b], channel, column) - one launch, scaled as it is stored
+            sampling.noise_keyed(z, seeds, sigma, sigmas)
+            self._keep += [seeds, sigmas]
         else:
-            noise_final, noise_early = noise
-        z[:, G - n_rem_final:] = sigma * noise_final.to(dev, torch.float32)
-        for k, ne in zip(early_ks, noise_early):
-            c_off = m.n_early_size * (k // m.n_early_every)
-            z[:, c_off - m.n_early_size:c_off] = sigma * ne.to(dev, torch.float32)
+            if noise is None:
+                noise_final = torch.randn(B, n_rem_final, L, dtype=torch.float32, device=dev)
+                noise_early = [torch.randn(B, m.n_early_size, L, dtype=torch.float32, device=dev) for _ in early_ks]
+            else:
+                noise_final, noise_early = noise
+            z[:, G - n_rem_final:] = sigma * noise_final.to(dev, torch.float32)
+            for k, ne in zip(early_ks, noise_early):
+                c_off = m.n_early_size * (k // m.n_early_every)
+                z[:, c_off - m.n_early_size:c_off] = sigma * ne.to(dev, torch.float32)
         for k in reversed(range(m.n_flows)):
             c_off, n_rem, n_half = self._flow_geom(k)
             fl = plan.pk["flows"][k]
@@ -1029,13 +1049,60 @@ class WaveGlow(torch.nn.Module):
                        else "use the shipped split-bf16 library") + " for this checkpoint / input"
             raise _lib.T2SError("fp16 operand planes overflowed (|x| > 65504 somewhere in the flow): result refused; " + way_out)
 
-    def infer(self, spect, sigma=1.0, noise=None):
+    def infer(self, spect, sigma=1.0, noise=None, seed=None):
         """mel [B, n_mel, frames] -> audio [B, 256*frames] (reference glow.py:251-292).
         ``noise`` = (final [B, n_remaining, L], [early draws in the reference's order]) makes the
-        Gaussian draws explicit for parity tests; by default they are drawn on the device."""
+        Gaussian draws explicit for parity tests; by default they are drawn on the device.
+
+        ``seed`` (an int in [0, 2^63), used for every entry; or one per entry as ``infer_batch``'s ``seeds``): the draws are keyed -
+        a function of (seed, channel, column) alone, made by one kernel launch straight into the flow's buffer, whatever torch's
+        generator holds.  ``infer(seed=s)`` is bit for bit ``infer(noise=draw_noise([s], L))``, and entry b of
+        ``infer_batch(seeds=S)`` gets the draws of ``infer(seed=S[b])``.  With a seed ``sigma`` may be a float [B] tensor."""
+        seeds, sigma, sigmas = self._keyed_args("infer", spect, sigma, noise, seed)
         with torch.no_grad():
-            out = self._eng().infer(spect, float(sigma), noise)
+            out = self._eng().infer(spect, sigma, noise, seeds, sigmas)
         return self._finish(out, spect)
+
+    def _keyed_args(self, who, spect, sigma, noise, seeds):
+        """(seeds int64 [B] on the device or None, sigma float, per-entry sigmas or None) of infer / infer_batch; raises before any
+        launch: ValueError for bad seed or sigma values, T2SError for arguments that exclude each other."""
+        T2SError = _lib.T2SError
+        if seeds is None:
+            if torch.is_tensor(sigma) and sigma.dim() > 0:
+                raise T2SError("%s: a tensor sigma (one temperature per entry) needs seed(s)" % who)
+            return None, float(sigma), None
+        if noise is not None:
+            raise T2SError("%s: give noise or seed(s), not both" % who)
+        if not spect.is_cuda or spect.dim() != 3:
+            raise T2SError("%s: spect must be a [B, n_mel, F] CUDA/HIP tensor, got %s on %s" % (who, tuple(spect.shape), spect.device))
+        B = spect.size(0)
+        if isinstance(seeds, int) and not isinstance(seeds, bool):
+            seeds = [seeds] * B
+        seeds = sampling.seeds_tensor(seeds, B, spect.device, who + ": seed(s)")
+        sigma, sigmas = sampling.sigmas_tensor(sigma, B, spect.device, who + ": sigma")
+        if sigmas is None and not (sigma >= 0.0 and sigma != float("inf")):
+            raise ValueError("%s: sigma must be finite and >= 0, got %r" % (who, sigma))
+        return seeds, sigma, sigmas
+
+    def draw_noise(self, seeds, L, sigma=1.0):
+        """The keyed draws of ``infer(seed=)`` / ``infer_batch(seeds=)`` as the tuple ``noise=`` takes: (final [B, n_remaining, L],
+        [early draws in the inverse flow's order]), B = len(seeds), on the model's device - views of one [B, n_group, L] buffer filled
+        by one launch, sliced the way the engine assigns a ``noise`` tuple.  L = frames * stride / n_group columns.  With the default
+        sigma = 1 it is the bridge to the injected path: ``infer(spect, sigma, noise=draw_noise([s], L))`` equals
+        ``infer(spect, sigma, seed=s)`` bit for bit, because the kernel stores sigma * float32(draw) as that path computes it."""
+        dev = self.upsample.weight.device
+        if dev.type != "cuda":
+            raise _lib.T2SError("WaveGlow (MI355X build) draws on the device; the model is on %s - there is no CPU fallback" % dev)
+        B = int(seeds.numel()) if torch.is_tensor(seeds) else len(seeds)
+        L = int(L)
+        if B < 1 or L < 1:
+            raise ValueError("draw_noise: needs at least one seed and one column, got %d seeds and L = %d" % (B, L))
+        seeds = sampling.seeds_tensor(seeds, B, dev, "draw_noise: seeds")
+        sigma, sigmas = sampling.sigmas_tensor(sigma, B, dev, "draw_noise: sigma")
+        with torch.no_grad():
+            z = torch.empty(B, self.n_group, L, dtype=torch.float32, device=dev)
+            sampling.noise_keyed(z, seeds, sigma, sigmas)
+        return self._eng().noise_slices(z)
 
     def _finish(self, out, spect):
         """The ending of infer and infer_batch: refuse audio that overflowed fp16 planes (the fp16 chain - infer_batch's runs on
@@ -1047,7 +1114,7 @@ class WaveGlow(torch.nn.Module):
             self._refuse_overflow(out)
         return out.to(spect.dtype) if spect.dtype in (torch.float16, torch.bfloat16) else out
 
-    def infer_batch(self, spect, lengths, sigma=1.0, noise=None):
+    def infer_batch(self, spect, lengths, sigma=1.0, noise=None, seeds=None):
         """Vocode a batch of mels of different lengths: ``spect`` [B, n_mel, F] padded, ``lengths`` [B] integers (host or device,
         e.g. ``Tacotron.inference_batch``'s ``output_lengths`` as returned), 1 <= lengths[b] <= F.  ``noise`` = (final
         [B, n_remaining, Lmax], [early draws]) padded to Lmax = F * stride / n_group columns, entry b using its first
@@ -1057,6 +1124,14 @@ class WaveGlow(torch.nn.Module):
         ``infer(spect[b:b+1, :, :lengths[b]], sigma, noise sliced to entry b's columns)`` returns, up to float rounding, and the
         rest of the row is 0.  What the padding of ``spect`` and of ``noise`` holds does not reach a valid sample.  Always the plain
         conditioning path (``T2S_COND_COMPOSE`` is not read).
+
+        ``seeds`` (one int in [0, 2^63) per entry: a sequence, or an int64 tensor on the host or the device) keys the draws: entry
+        b's noise is a function of (seeds[b], channel, column) alone, made by one kernel launch, so the entry gets the draws of
+        ``infer(spect[b:b+1, :, :lengths[b]], sigma, seed=seeds[b])`` whatever the batch size, its place in the batch, the padded
+        length or torch's generator - without ``seeds`` (and without ``noise``) the draws depend on all four.  A wrong count or a
+        negative value raises ValueError before any launch; a device tensor is used as it is, with no read-back, so its values are
+        not checked.  With ``seeds``, ``sigma`` may be a float [B] tensor, one temperature per entry; ``noise`` together with
+        ``seeds`` raises.
 
         A ``.half()`` model runs on split-bf16 planes here unless ``model._eng().infer_batch_w16 = True`` (opt-in): then the batch
         takes ``infer``'s fp16 chain, its GEMMs skip the column tiles that lie wholly behind an entry's end, and a result that
@@ -1087,8 +1162,9 @@ class WaveGlow(torch.nn.Module):
             if not ok:
                 raise T2SError("infer_batch: noise must be (final [%d, %d, %d], %d early draws of [%d, %d, %d])"
                                % (B, self.n_remaining_channels, Lmax, len(early), B, self.n_early_size, Lmax))
+        seeds, sigma, sigmas = self._keyed_args("infer_batch", spect, sigma, noise, seeds)
         with torch.no_grad():
-            out, out_lens = self._eng().infer_batch(spect, lens, float(sigma), noise)
+            out, out_lens = self._eng().infer_batch(spect, lens, sigma, noise, seeds, sigmas)
         return self._finish(out, spect), out_lens      # (the tails are zeros by now: the valid samples decide, never what the padding held)
 
     @staticmethod

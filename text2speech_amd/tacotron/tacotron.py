@@ -20,7 +20,7 @@ from math import sqrt
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _lib, sampling
 from .modules import ConvNorm, LinearNorm, Postnet, Prenet, get_mask_from_lengths, OwnedModule
 
 BN_EPS = 1e-5
@@ -395,6 +395,7 @@ class _TacoEngine:
         self.decode_w16 = None
         self.last_decode_w16 = False    # whether the last decode_free went through t2s_taco_decode_steps_w16 ...
         self.last_decode_lstm_bytes = None      # ... and the bytes of LSTM weights one of its steps read (t2s_taco_decode_plan_w16)
+        self.last_prenet_masks = None   # the mask buffer [n, B, 2, prenet_dim] the last decode_free read (tests compare batch and solo draws)
 
     # ------------------------------------------------------------------ weight preparation
     def _pack_conv_bn(self, seq, dev, halo):
@@ -785,11 +786,15 @@ class _TacoEngine:
                 self._conv(layer, Xh, Xl, B, T, Lp, halo, 0, out_planes=False, out_f32=out)
         return out
 
-    def _masks(self, prenet_masks, n, B, Pd, dev, seed):
+    def _masks(self, prenet_masks, n, B, Pd, dev, seed, seeds=None):
+        """The prenet dropout masks [n, B, 2, Pd]: injected, or keyed by one seed per entry (``seeds`` int64 [B] on the device: entry
+        b's bytes are those of a solo call under seeds[b]), or drawn under the engine seed over the flat index of the whole buffer."""
         if prenet_masks is not None:
             mk = prenet_masks.to(device=dev, dtype=torch.uint8).contiguous()
             assert mk.numel() >= n * B * 2 * Pd, "prenet_masks too short"
             return mk
+        if seeds is not None:
+            return sampling.masks_keyed(n, B, 2 * Pd, seeds, 0.5, dev).view(n, B, 2, Pd)
         mk = torch.empty(n, B, 2, Pd, dtype=torch.uint8, device=dev)
         _lib.call("t2s_bernoulli_mask", _lib.ptr(mk), mk.numel(), int(seed), 0, 0.5, _lib.current_stream())
         return mk
@@ -871,18 +876,20 @@ class _TacoEngine:
         mel_post = mel + self.postnet(mel, train_masks, seed)
         return [mel, mel_post, gate, align]
 
-    def inference_batch(self, ids, lengths, prenet_masks=None, seed=None, chunk=64):
+    def inference_batch(self, ids, lengths, prenet_masks=None, seed=None, chunk=64, seeds=None):
         """Tacotron.inference_batch (eval mode): ``ids`` [B, T] padded, ``lengths`` int64 [B] on the host, 1 <= lengths <= T.
         Entry b computes what ``inference(ids[b:b+1, :lengths[b]])`` computes: the encoder and postnet zero its rows past its
         length before every convolution (their solo halo), the attention reads its first lengths[b] positions.  Returns
         ([mel, mel_post, gate, align] padded to the longest output, output lengths int64 [B] on the device); past each output
-        length mel / mel_post are 0, the gate 1e3 (Tacotron.parse_output) and the alignment rows 0."""
+        length mel / mel_post are 0, the gate 1e3 (Tacotron.parse_output) and the alignment rows 0.  ``seeds`` (int64 [B] on the
+        device): entry b's prenet masks are those of ``inference(..., seed=seeds[b])``; the engine seed then draws nothing (eval
+        mode has no other dropout) and torch's generator is not touched."""
         if seed is None:
-            seed = self.fresh_seed()
+            seed = 0 if seeds is not None else self.fresh_seed()
         dev = ids.device
         self.prepare(dev)
         memory, len32 = self.encode(ids, lengths, seed=seed, max_len=int(lengths.max()), zero_pad=True)
-        mel, gate, align, olen = self.decode_free(memory, prenet_masks, seed, chunk, lengths=len32)
+        mel, gate, align, olen = self.decode_free(memory, prenet_masks, seed, chunk, lengths=len32, seeds=seeds)
         olen32 = olen.to(torch.int32)
         mel_post = mel + self.postnet(mel, seed=seed, lengths=olen32)
         B, n_mel, N = mel.shape
@@ -891,7 +898,7 @@ class _TacoEngine:
         _lib.call("t2s_zero_rows_f32", _lib.ptr(align), _lib.ptr(olen32), B, N, align.size(2), st)
         return [mel, mel_post, gate, align], olen
 
-    def decode_free(self, memory, prenet_masks=None, seed=None, chunk=64, train_masks=None, lengths=None):
+    def decode_free(self, memory, prenet_masks=None, seed=None, chunk=64, train_masks=None, lengths=None, seeds=None):
         """Decoder.inference (reference tacotron.py:431-466): autoregressive decode of encoder outputs ``memory`` [B, T_in, E]
         until every entry's gate passes the threshold or max_decoder_steps.  Returns (mel [B, n_mel, T], gate [B, T, 1],
         alignments [B, T, T_in]).  ``lengths`` (int32 [B] on the device): the attention of entry b sees its first lengths[b]
@@ -907,7 +914,7 @@ class _TacoEngine:
         B = memory.size(0)
         T_cap = int(dec.max_decoder_steps)
         n_mel = dec.n_mel_channels * dec.n_frames_per_step
-        mk = self._masks(prenet_masks, T_cap, B, dec.prenet_dim, dev, seed)
+        mk = self.last_prenet_masks = self._masks(prenet_masks, T_cap, B, dec.prenet_dim, dev, seed, seeds)
         mel_gate = torch.zeros(B, n_mel + 1, T_cap, dtype=torch.float32, device=dev)
         extra = dict(prenet_masks=mk, mel_gate_out=mel_gate)
         if m.training:
@@ -1143,15 +1150,22 @@ class Tacotron(nn.Module):
             return int(max_len)
         return None
 
-    def inference(self, inputs, speaker_id=None, prenet_masks=None, train_masks=None):
+    def inference(self, inputs, speaker_id=None, prenet_masks=None, train_masks=None, seed=None):
         """Autoregressive decode (reference tacotron.py:51-65).  Works in ``.train()`` mode as the reference's does (batch-statistics
-        BatchNorm and live dropout everywhere; ``train_masks`` injects the draws), although inference.py:61 calls it in eval mode."""
+        BatchNorm and live dropout everywhere; ``train_masks`` injects the draws), although inference.py:61 calls it in eval mode.
+        ``seed`` (an int in [0, 2^63)): the engine's dropout seed, instead of a fresh one drawn from torch's generator - the same
+        text with the same seed gives the same prenet masks, and ``inference_batch(..., seeds=S)`` gives entry b the masks of
+        ``inference(text b, seed=S[b])``.  ``seed`` together with ``prenet_masks`` raises."""
         self._check(inputs)
+        if seed is not None:
+            if prenet_masks is not None:
+                raise _lib.T2SError("inference: give prenet_masks or seed, not both")
+            seed = sampling.check_seed(seed, "inference: seed")
         with torch.no_grad():
-            out = self._eng().inference(inputs, prenet_masks, train_masks=train_masks)
+            out = self._eng().inference(inputs, prenet_masks, seed=seed, train_masks=train_masks)
         return self._as_module_dtype(self.parse_output(out))
 
-    def inference_batch(self, inputs, input_lengths, speaker_id=None, prenet_masks=None):
+    def inference_batch(self, inputs, input_lengths, speaker_id=None, prenet_masks=None, seeds=None):
         """Autoregressive decode of a batch of texts of different lengths, in eval mode: ``inputs`` [B, T] padded ids,
         ``input_lengths`` [B] integers (host or device), 1 <= length <= T; ``prenet_masks`` [n, B, 2, prenet_dim] as for
         ``inference`` (entry b uses [:, b]).  Returns (mel [B, n_mel, N], mel_post [B, n_mel, N], gate [B, N, 1],
@@ -1163,7 +1177,15 @@ class Tacotron(nn.Module):
         and the alignment rows 0; alignment columns past the entry's input length are 0.  To get there the encoder and postnet
         convolutions see zeros past each entry's length, as a solo run sees its halo - unlike the teacher-forced ``forward``,
         whose convolutions read the padding, as the reference's do.  ``.train()`` mode is refused: batch-statistics BatchNorm
-        and live dropout would couple the entries."""
+        and live dropout would couple the entries.
+
+        Entry b equals the solo run **with the same seed** only through ``seeds=``: one int in [0, 2^63) per entry (a sequence, or
+        an int64 tensor on the host or the device).  Entry b then draws the prenet masks of ``inference(text b, seed=seeds[b])``,
+        bit for bit, whatever the batch size, its place in the batch or torch's generator.  Without ``seeds`` (and without
+        ``prenet_masks``) the masks are drawn over the whole [n, B, 2, prenet_dim] buffer from one fresh seed, so an entry's draws
+        change with B and with its position.  A wrong count or a negative value raises ValueError before any launch; a device
+        tensor is used as it is, with no read-back, so its values are not checked.  ``seeds`` together with ``prenet_masks``
+        raises."""
         self._check(inputs)
         if self.training:
             raise _lib.T2SError("inference_batch runs in eval mode only (call .eval())")
@@ -1178,8 +1200,12 @@ class Tacotron(nn.Module):
             raise _lib.T2SError("inference_batch: input_lengths has shape %s, inputs hold %d texts" % (tuple(lengths.shape), B))
         if B == 0 or int(lengths.min()) < 1 or int(lengths.max()) > T:
             raise _lib.T2SError("inference_batch: input_lengths must lie in [1, %d], got %s" % (T, lengths.tolist()))
+        if seeds is not None:
+            if prenet_masks is not None:
+                raise _lib.T2SError("inference_batch: give prenet_masks or seeds, not both")
+            seeds = sampling.seeds_tensor(seeds, B, inputs.device, "inference_batch: seeds")
         with torch.no_grad():
-            out, output_lengths = self._eng().inference_batch(inputs, lengths, prenet_masks)
+            out, output_lengths = self._eng().inference_batch(inputs, lengths, prenet_masks, seeds=seeds)
         return self._as_module_dtype(out) + [output_lengths]
 
     def _as_module_dtype(self, outputs):
