@@ -103,6 +103,13 @@ int t2s_wg_upsample_squeeze(const float* mel, const float* W, const float* bias,
 /* audio[B][T] -> z[B][n_group][L] (unsqueeze=0, reference glow.py:223) or back (unsqueeze=1, glow.py:291) */
 int t2s_wg_audio_squeeze(float* audio, float* z, int B, int T, int n_group, int L, int unsqueeze, void* stream);
 
+/* The kept columns of a vocoded window, written straight into the caller's rows (additive to ABI version 4; streaming.py):
+ *   dst[b][dst_off + (k - k0) G + g] = z[b][g][k]   for k0 <= k < k1,   z float [B][G][L] contiguous, dst rows ld_dst floats apart.
+ * What the unsqueeze above, a slice and a copy would give, in one launch.  No alignment beyond the element for dst, dst_off or ld_dst.
+ * T2S_EINVAL, with nothing launched: a NULL z or dst; B, G, L or ld_dst <= 0; B > 65535; k0 < 0, k0 >= k1 or k1 > L; dst_off < 0;
+ * (k1 - k0) G > ld_dst - dst_off. */
+int t2s_wg_audio_window(const float* z, int B, int G, int L, int k0, int k1, float* dst, long ld_dst, long dst_off, void* stream);
+
 /* in-place invertible 1x1 conv on channels [c_off, c_off+n_rem) of z[B][n_group][L] (reference glow.py:82-102) */
 int t2s_wg_convinv(float* z, const float* W, int B, int n_group, int c_off, int n_rem, int L, void* stream);
 
@@ -995,11 +1002,18 @@ int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* tab
  *    inf, no NaN.  The value depends on (seeds[b], c, t) only.  sigmas' values are not read on the host and so not checked.
  *    T2S_EINVAL, with nothing launched: a NULL z or seeds; B, G or L <= 0; B or G > 65535; L >= 2^40; B G L > 2^60; a sigma that is
  *    not finite or < 0.  No alignment beyond the element.
+ *  t2s_wg_noise_keyed_at: a window of those columns.  z float [B][G][L]; z[b][c][j] is exactly what t2s_wg_noise_keyed stores at
+ *    column c0_b + j of a buffer long enough to hold it, c0_b = col0s[b] where col0s (NULL, or long long [B] in device memory) is
+ *    given, else col0.  Any parity of c0_b and of L: the member of a Box-Muller pair that lies outside the window is not stored.
+ *    col0s' values are not read on the host and so not checked; whatever they hold, only z[b][c][0 .. L) is written.
+ *    T2S_EINVAL, with nothing launched: as t2s_wg_noise_keyed, and col0 < 0 or col0 + L >= 2^40.
  *  t2s_noise_tile: host only, the columns of one row that a workgroup of the noise kernel makes (1024). */
 int t2s_bernoulli_mask_keyed(unsigned char* mask, int n_steps, int B, int row, const unsigned long long* seeds, float keep_prob,
                              void* stream);
 int t2s_noise_tile(void);
 int t2s_wg_noise_keyed(float* z, int B, int G, long L, const unsigned long long* seeds, float sigma, const float* sigmas, void* stream);
+int t2s_wg_noise_keyed_at(float* z, int B, int G, long L, long col0, const long long* col0s, const unsigned long long* seeds, float sigma,
+                          const float* sigmas, void* stream);
 
 #ifdef __cplusplus
 }

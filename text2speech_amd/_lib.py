@@ -123,7 +123,9 @@ SIGNATURES = {
     "t2s_bernoulli_mask_keyed": [c_vp, c_int, c_int, c_int, c_vp, c_float, c_vp],
     "t2s_noise_tile": [],
     "t2s_wg_noise_keyed": [c_vp, c_int, c_int, c_long, c_vp, c_float, c_vp, c_vp],
-    "t2s_sum_axis0": [c_vp, c_int, c_int, c_vp, c_vp],
+    "t2s_wg_noise_keyed_at": [c_vp, c_int, c_int, c_long, c_long, c_vp, c_vp, c_float, c_vp, c_vp],
+    "t2s_wg_audio_window": [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_long, c_long, c_vp],
+    "t2s_sum_axis0":[c_vp, c_int, c_int, c_vp, c_vp],
     "t2s_add3": [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp],
     "t2s_scale_by_scalar": [c_vp, ctypes.c_size_t, c_vp, c_float, c_vp, c_vp],
     "t2s_planes_to_f32": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp],

@@ -158,6 +158,13 @@ int t2s_wg_audio_squeeze(float* audio, float* z, int B, int T, int n_group, int 
     return T2S_OK;
 }
 
+int t2s_wg_audio_window(const float* z, int B, int G, int L, int k0, int k1, float* dst, long ld_dst, long dst_off, void* stream) {
+    if (!z || !dst || B <= 0 || B > 65535 || G <= 0 || L <= 0 || k0 < 0 || k0 >= k1 || k1 > L || dst_off < 0 || ld_dst <= 0) return T2S_EINVAL;
+    if ((long)(k1 - k0) * G > ld_dst - dst_off) return T2S_EINVAL;      // the kept samples must fit the row behind dst_off
+    T2S_CHECK_HIP(t2s_launch_audio_window(z, B, G, L, k0, k1, dst, ld_dst, dst_off, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 int t2s_wg_convinv(float* z, const float* W, int B, int n_group, int c_off, int n_rem, int L, void* stream) {
     if (!z || !W || B <= 0 || L <= 0 || n_rem <= 0 || n_rem > 16 || c_off < 0 || c_off + n_rem > n_group) return T2S_EINVAL;
     T2S_CHECK_HIP(t2s_launch_convinv(z, W, B, n_group, c_off, n_rem, L, (hipStream_t)stream));

@@ -157,6 +157,8 @@ hipError_t t2s_launch_upsample_squeeze(const float* mel, const float* W, const f
                                        u16* S_hi, u16* S_lo, hipStream_t stream, bool h16 = false);
 hipError_t t2s_launch_audio_squeeze(const float* audio, float* z, int B, int T, int n_group, int L, int unsqueeze,
                                     hipStream_t stream);
+hipError_t t2s_launch_audio_window(const float* z, int B, int n_group, int L, int k0, int k1, float* dst, long ld_dst, long dst_off,
+                                   hipStream_t stream);
 hipError_t t2s_launch_convinv(float* z, const float* W, int B, int n_group, int c_off, int n_rem, int L,
                               hipStream_t stream);
 struct SmallMatJob { const float* W; float* logdet_out; float* inv_out; long n; };   // mirrors t2s_small_mat_job

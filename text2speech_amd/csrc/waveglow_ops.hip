@@ -636,6 +636,27 @@ hipError_t t2s_launch_audio_squeeze(const float* audio, float* z, int B, int T, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The kept columns [k0, k1) of a vocoded window z [B][G][L] as samples of the caller's rows (streaming.py):
+// dst[b][dst_off + (k - k0) G + g] = z[b][g][k].  One thread per sample, so a wave stores 64 consecutive floats and reads G runs of
+// 64 / G; dst needs no alignment beyond the element.  The host checked 0 <= k0 < k1 <= L and dst_off + (k1 - k0) G <= ld_dst.
+__global__ __launch_bounds__(256) void audio_window_kernel(const float* __restrict__ z, int G, int L, int k0, long n, float* dst,
+                                                           long ld_dst, long dst_off) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int b = blockIdx.y;
+    const long kk = i / G;
+    const int g = (int)(i - kk * G);
+    dst[(size_t)b * ld_dst + dst_off + i] = z[((size_t)b * G + g) * (size_t)L + k0 + kk];
+}
+hipError_t t2s_launch_audio_window(const float* z, int B, int n_group, int L, int k0, int k1, float* dst, long ld_dst, long dst_off,
+                                   hipStream_t stream) {
+    const long n = (long)(k1 - k0) * n_group;
+    hipLaunchKernelGGL(audio_window_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, stream, z, n_group, L, k0, n, dst,
+                       ld_dst, dst_off);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // Invertible 1x1 conv applied in place to channels [c_off, c_off + n_rem) of z [B][G][L]
 // (reference glow.py:82-102; the reverse direction passes W^-1).
 __global__ void convinv_kernel(float* z, const float* __restrict__ W, int G, int c_off, int n, int L) {

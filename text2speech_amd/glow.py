@@ -600,9 +600,15 @@ class _Engine:
         self.packed["compose_key"] = self.packed_key
 
     # ------------------------------------------------------------------ workspaces
-    def workspace(self, B, L, device):
+    STREAM_SHAPES = 3       # workspaces a stream keeps resident: its first, regular and last window
+
+    def workspace(self, B, L, device, cache=None):
+        """The activation planes of a (B, L) call.  The engine keeps ONE shape resident and reallocates (zero-filled) on every
+        change.  cache (a dict owned by a stream, streaming.py): that call's workspaces live there instead, at most STREAM_SHAPES
+        of them, the oldest dropped first - a stream alternates between its first, regular and last window shapes - and the
+        engine's own resident shape is left alone, so what the calls around a stream allocate does not change."""
         key = (B, L, str(device))
-        w = self.ws.get(key)
+        w = (self.ws if cache is None else cache).get(key)
         if w is None:
             g = self.geom()
             Lp = _lib.plane_rows(L, g["halo"])
@@ -616,7 +622,12 @@ class _Engine:
                      z2=torch.empty(B, self.m.n_group, L, dtype=torch.float32, device=device),        # one-launch flow boundaries: the other z
                      fold_acc=torch.zeros(_lib.load().t2s_wg_gate_fold_slots(B, g["C"], L), B, 8, L, dtype=torch.float32,
                                           device=device))
-            self.ws = {key: w}      # keep one shape resident
+            if cache is None:
+                self.ws = {key: w}      # keep one shape resident
+            else:
+                while len(cache) >= self.STREAM_SHAPES:
+                    del cache[next(iter(cache))]
+                cache[key] = w
         return w
 
     # ------------------------------------------------------------------ stages
@@ -893,7 +904,14 @@ class _Engine:
         self._keep.append(lens)
         return audio, (lengths * stride).to(mel.device)
 
-    def _infer(self, mel, sigma, noise, lens, seeds=None, sigmas=None):
+    def infer_window(self, mel, col0, k0, k1, sigma, seeds, sigmas, out, out_off, ws_cache=None):
+        """_infer on ``mel``, a run of an utterance's frames that starts at column ``col0`` of its draws: the same launches, with
+        the keyed draws taken at that offset (t2s_wg_noise_keyed_at) and columns [k0, k1) of the result written into
+        out[:, out_off:] (t2s_wg_audio_window) in place of the whole-row unsqueeze."""
+        return self._infer(mel, sigma, None, None, seeds, sigmas, window=(int(col0), int(k0), int(k1), out, int(out_off)),
+                           ws_cache=ws_cache)
+
+    def _infer(self, mel, sigma, noise, lens, seeds=None, sigmas=None, window=None, ws_cache=None):
         m = self.m
         self._check_inputs(mel)
         dev = mel.device
@@ -912,7 +930,7 @@ class _Engine:
         path = plan.path
         self._keep = []
         plan = self._pack(plan, dev)
-        w = self.workspace(B, L, dev)
+        w = self.workspace(B, L, dev, ws_cache)
         st = _lib.current_stream()
         # Weights are packed once here, so the conditioning path can be composed with the upsampler (K = 640 -> 320 in the gate
         # GEMM, no upsampler launch) - wherever the grid is large enough for the 256-row ping-pong tiles anyway.  Opt-in
@@ -942,9 +960,13 @@ class _Engine:
         early_ks = self.early_flows()
         if seeds is not None:
             # keyed draws (csrc/sampling.hip): z[b] is a function of (seeds[b], channel, column) - one launch, scaled as it is stored
-            sampling.noise_keyed(z, seeds, sigma, sigmas)
+            if window is None:
+                sampling.noise_keyed(z, seeds, sigma, sigmas)
+            else:
+                sampling.noise_keyed_at(z, window[0], seeds, sigma, sigmas)
             self._keep += [seeds, sigmas]
         else:
+            assert window is None, "a window's draws are keyed"
             if noise is None:
                 noise_final = torch.randn(B, n_rem_final, L, dtype=torch.float32, device=dev)
                 noise_early = [torch.randn(B, m.n_early_size, L, dtype=torch.float32, device=dev) for _ in early_ks]
@@ -967,6 +989,12 @@ class _Engine:
             self._wn(plan, k, z, B, L, w, c_off, n_half)
             self._end_fold(k, z, None, w["fold_acc"], None, B, L, c_off, n_half, reverse=True, plan=plan)
             _lib.call("t2s_wg_convinv", _lib.ptr(z), _lib.ptr(fl["w_inv"]), B, G, c_off, n_rem, L, st)
+        if window is not None:
+            _, k0, k1, out, out_off = window
+            ld = out.stride(0) if B > 1 else out.size(1)        # (one row: its stride says nothing)
+            _lib.call("t2s_wg_audio_window", _lib.ptr(z), B, G, L, k0, k1, _lib.ptr(out), ld, out_off, st)
+            self._keep.append(z)
+            return out
         audio = torch.empty(B, L * G, dtype=torch.float32, device=dev)
         _lib.call("t2s_wg_audio_squeeze", _lib.ptr(audio), _lib.ptr(z), B, L * G, G, L, 1, st)
         return audio
@@ -1062,6 +1090,78 @@ class WaveGlow(torch.nn.Module):
         with torch.no_grad():
             out = self._eng().infer(spect, sigma, noise, seeds, sigmas)
         return self._finish(out, spect)
+
+    def infer_window(self, spect, f0, f1, sigma=1.0, seed=None, final=False, halo=None, out=None, out_offset=0, _region=None,
+                     _ws=None):
+        """The audio of frames [f0, f1) of an utterance whose frames 0 .. F_known - 1 are ``spect`` [B, n_mel, F_known]:
+        [B, stride (f1 - f0)], what ``infer(whole mel, sigma, seed=seed)[:, stride f0 : stride f1]`` holds - without the rest of the
+        mel, which may not be decoded yet (streaming.py).
+
+        The inverse flow runs on frames [max(0, f0 - left), min(F_known, f1 + right)) only, (left, right) =
+        ``streaming.vocoder_halo(self)`` - the flow's reach, (99, 96) frames at the defaults - through the launches ``infer`` issues
+        for a mel of that length: the same kernels and per-column arithmetic, whichever chain ``infer`` takes for the model
+        (split-bf16, or fp16 for ``.half()``, with the same overflow refusal).  The draws are the keyed ones of the window's own
+        columns (``t2s_wg_noise_keyed_at``), and the kept columns go straight into the result (``t2s_wg_audio_window``).  Against
+        the float64 oracle a window is as exact as the whole call; against ``infer`` it differs by float rounding only where the
+        GEMMs tile the two lengths differently.
+
+        ``seed`` is required (an int, or one per entry); there is no ``noise=``.  ``final=True`` says F_known is the utterance's
+        length; without it ``f1 + right > F_known`` raises T2SError before any launch, because frames not yet known would decide
+        the result.  ``halo=(l, r)`` smaller than the exact one is the caller's accuracy trade (the measured curve:
+        profiles/streaming.md); larger changes nothing.  ``out`` (float32 [B, >= out_offset + stride (f1 - f0)], unit stride
+        along a row): the samples are written at ``out[:, out_offset:]`` and that view is returned."""
+        from . import streaming
+        T2SError = _lib.T2SError
+        if seed is None:
+            raise T2SError("infer_window: a seed is required - a window's draws are keyed by (seed, channel, column)")
+        if not torch.is_tensor(spect) or not spect.is_cuda or spect.dim() != 3:
+            raise T2SError("infer_window: spect must be a [B, n_mel, F] CUDA/HIP tensor - there is no CPU fallback")
+        exact = streaming.vocoder_halo(self)            # (raises where stride % n_group != 0)
+        left, right = exact if halo is None else (int(halo[0]), int(halo[1]))
+        if left < 0 or right < 0:
+            raise ValueError("infer_window: halo must be (left, right) >= 0, got %r" % (halo,))
+        B, _, F_known = spect.shape
+        f0, f1 = int(f0), int(f1)
+        if not 0 <= f0 < f1 <= F_known:
+            raise T2SError("infer_window: need 0 <= f0 < f1 <= %d known frames, got [%d, %d)" % (F_known, f0, f1))
+        if f1 + right > F_known and not final:
+            raise T2SError("infer_window: frames [%d, %d) need %d frames behind them and only %d are known; pass final=True if "
+                           "the utterance ends there" % (f0, f1, right, F_known))
+        lo, hi = (max(0, f0 - left), min(F_known, f1 + right)) if _region is None else _region
+        assert 0 <= lo <= f0 and f1 <= hi <= F_known
+        stride, G = self.upsample.stride[0], self.n_group
+        cols, n = stride // G, stride * (f1 - f0)
+        given = out is not None
+        if given:
+            out_offset = int(out_offset)
+            if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.size(0) == B
+                    and out.stride(1) == 1 and (B == 1 or out.stride(0) >= out.size(1)) and 0 <= out_offset
+                    and out_offset + n <= out.size(1)):
+                raise T2SError("infer_window: out must be a float32 CUDA/HIP tensor [%d, >= %d] with unit stride along a row"
+                               % (B, int(out_offset) + n))
+        else:
+            out, out_offset = torch.empty(B, n, dtype=torch.float32, device=spect.device), 0
+        seeds, sigma, sigmas = self._keyed_args("infer_window", spect, sigma, None, seed)
+        with torch.no_grad():
+            self._eng().infer_window(spect[:, :, lo:hi], lo * cols, (f0 - lo) * cols, (f1 - lo) * cols, sigma, seeds, sigmas, out,
+                                     out_offset, _ws)
+        res = out[:, out_offset:out_offset + n]
+        fin = self._finish(res, spect)
+        return res if given else fin
+
+    def infer_stream(self, pieces, sigma=1.0, seed=None, first_frames=32, window_frames=128, halo=None):
+        """A generator over ``pieces``, an iterable of (mel piece [B, n_mel, n], last) in frame order (``last`` true on the final
+        one; n may be 0): yields audio pieces [B, stride f] whose concatenation is ``infer(the whole mel, sigma, seed=seed)``, of
+        length exactly stride F.  The first piece holds ``first_frames`` frames and is issued once first_frames + right frames
+        are known, the following ones ``window_frames`` each (``streaming.plan_windows``: every frame in exactly one window, a
+        window only when the frames that decide it are known or the end is).  Each window is an ``infer_window`` call; their
+        workspaces - at most three shapes: first, regular, last - stay resident for the life of the generator, and the engine's
+        own resident workspace is not touched.  The weights are packed once per parameter version, as for ``infer``.
+        ``seed`` is required; ``halo`` as ``infer_window`` takes it.  Arguments are checked here, before the first piece is
+        asked for."""
+        from . import streaming
+        halo = streaming._check_stream_args(self, seed, first_frames, window_frames, halo, "infer_stream")
+        return (w[0] for w in streaming.stream_windows(self, pieces, sigma, seed, first_frames, window_frames, halo))
 
     def _keyed_args(self, who, spect, sigma, noise, seeds):
         """(seeds int64 [B] on the device or None, sigma float, per-entry sigmas or None) of infer / infer_batch; raises before any

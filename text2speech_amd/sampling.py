@@ -74,3 +74,13 @@ def noise_keyed(z, seeds, sigma=1.0, sigmas=None):
     assert z.dtype == torch.float32 and z.is_contiguous()
     _lib.call("t2s_wg_noise_keyed", _lib.ptr(z), B, G, L, _lib.ptr(seeds), float(sigma), _lib.ptr(sigmas), _lib.current_stream())
     return z
+
+
+def noise_keyed_at(z, col0, seeds, sigma=1.0, sigmas=None, col0s=None):
+    """Fill the contiguous f32 ``z`` [B, G, L] with the draws ``noise_keyed`` puts at columns [col0, col0 + L) of a longer buffer -
+    a window of an utterance's noise (streaming.py).  ``col0s`` (int64 [B] on the device): one offset per entry instead."""
+    B, G, L = z.shape
+    assert z.dtype == torch.float32 and z.is_contiguous()
+    _lib.call("t2s_wg_noise_keyed_at", _lib.ptr(z), B, G, L, int(col0), _lib.ptr(col0s), _lib.ptr(seeds), float(sigma),
+              _lib.ptr(sigmas), _lib.current_stream())
+    return z

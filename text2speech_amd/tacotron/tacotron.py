@@ -904,6 +904,36 @@ class _TacoEngine:
         alignments [B, T, T_in]).  ``lengths`` (int32 [B] on the device): the attention of entry b sees its first lengths[b]
         positions only, and a fourth result is returned, each entry's output length (int64 [B] on the device: its stop step + 1,
         or max_decoder_steps); frames past it are not masked here."""
+        dec = self.m.decoder
+        T_cap = int(dec.max_decoder_steps)
+        n_mel = dec.n_mel_channels * dec.n_frames_per_step
+        n_done = T_cap
+        stopped = False
+        for mel_gate, S, s0, sv in self._decode_chunks(memory, prenet_masks, seed, chunk, train_masks, lengths, seeds):
+            if bool((sv >= 0).all()):
+                n_done = int(sv.max().item()) + 1
+                stopped = True
+                break
+        if not stopped:
+            print("Warning! Reached max decoder steps", file=sys.stderr)     # reference tacotron.py:458 (stdout there)
+        mel = mel_gate[:, :n_mel, :n_done].contiguous()
+        gate = mel_gate[:, n_mel, :n_done].unsqueeze(-1).contiguous()          # [B, T, 1] as the reference returns
+        align = S["align_out"][:, :n_done].contiguous()
+        if lengths is None:
+            return mel, gate, align
+        olen = torch.where(sv >= 0, sv + 1, torch.full_like(sv, T_cap)).to(device=memory.device, dtype=torch.int64)
+        return mel, gate, align, olen
+
+    def _decode_chunks(self, memory, prenet_masks=None, seed=None, chunk=64, train_masks=None, lengths=None, seeds=None,
+                       ahead=False):
+        """decode_free's chunk loop as a generator: sets the decode up as decode_free always did, then per chunk launches its steps
+        and the stop check, polls the stop steps once (one host sync per chunk, not per frame) and yields (mel_gate [B, n_mel + 1,
+        T_cap], the struct's buffers, frames decoded so far, stop steps int32 [B] on the host: -1 = not yet).  The consumer stops
+        iterating when every entry has stopped; the generator ends by itself at max_decoder_steps.
+        ahead (inference_stream): while no entry has stopped, chunk k + 1 is enqueued BEFORE chunk k's state is yielded and polled
+        after the consumer comes back, so that what the consumer enqueues for chunk k runs behind chunk k + 1 and the device does
+        not idle through the poll.  The yielded frame count is then chunk k's; frames of a chunk are never yielded before its own
+        poll, so nothing computed past a stop step is seen."""
         if seed is None:
             seed = self.fresh_seed()
         m = self.m
@@ -930,10 +960,10 @@ class _TacoEngine:
         self._query_plan(d, 0, min(chunk, T_cap), w16)
         self.last_decode_w16 = w16 is not None
         stop = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        st = _lib.current_stream()
-        s0 = 0
-        n_done = T_cap
-        while s0 < T_cap:
+
+        def launch(s0):
+            # (the current stream is read per chunk: the consumer of a generator may have changed it)
+            st = _lib.current_stream()
             n = min(chunk, T_cap - s0)
             if w16 is None:
                 _lib.call("t2s_taco_decode_steps", ctypes.byref(d), s0, n, st)
@@ -941,20 +971,64 @@ class _TacoEngine:
                 _lib.call("t2s_taco_decode_steps_w16", ctypes.byref(d), ctypes.byref(w16), s0, n, st)
             _lib.call("t2s_taco_stop_check", _lib.ptr(mel_gate), B, n_mel, T_cap, s0, n, float(dec.gate_threshold),
                       _lib.ptr(stop), st)
-            s0 += n
-            sv = stop.cpu()                     # sparse poll: one host sync per chunk, not per frame
-            if bool((sv >= 0).all()):
-                n_done = int(sv.max().item()) + 1
-                break
-        else:
-            print("Warning! Reached max decoder steps", file=sys.stderr)     # reference tacotron.py:458 (stdout there)
-        mel = mel_gate[:, :n_mel, :n_done].contiguous()
-        gate = mel_gate[:, n_mel, :n_done].unsqueeze(-1).contiguous()          # [B, T, 1] as the reference returns
-        align = S["align_out"][:, :n_done].contiguous()
-        if lengths is None:
-            return mel, gate, align
-        olen = torch.where(sv >= 0, sv + 1, torch.full_like(sv, T_cap)).to(device=dev, dtype=torch.int64)
-        return mel, gate, align, olen
+            return s0 + n
+
+        s0 = 0
+        if not ahead:
+            while s0 < T_cap:
+                s0 = launch(s0)
+                sv = stop.cpu()                     # sparse poll: one host sync per chunk, not per frame
+                yield mel_gate, S, s0, sv
+            return
+        s0 = launch(0)
+        sv = stop.cpu()
+        while s0 < T_cap and not bool((sv >= 0).all()):
+            s1 = launch(s0)
+            yield mel_gate, S, s0, sv               # chunk k's frames, with chunk k + 1 in flight
+            sv = stop.cpu()
+            s0 = s1
+        yield mel_gate, S, s0, sv
+
+    def inference_stream(self, ids, seed=None, chunk=64):
+        """inference() for one text in eval mode as a generator of pieces: after each chunk's stop poll, (mel, mel_post, gate, align,
+        last) for the frames that became final.  mel / gate / align pieces hold the frames decoded since the piece before;
+        mel_post lags them by the postnet's reach (5 layers x 2 frames): it is final up to 10 frames before the last decoded one,
+        or up to the end once the stop step is known.  The postnet runs on [lo - reach, hi + reach) clipped to [0, decoded) and the
+        centre is kept, so the utterance's own ends see the zero padding the whole call shows them.  A mel_post piece may be empty
+        ([1, n_mel, 0])."""
+        if seed is None:
+            seed = self.fresh_seed()
+        m = self.m
+        dec = m.decoder
+        dev = ids.device
+        self.prepare(dev)
+        memory, _ = self.encode(ids, None, None, seed)
+        T_cap = int(dec.max_decoder_steps)
+        n_mel = dec.n_mel_channels * dec.n_frames_per_step
+        reach = 2 * len(m.postnet.convolutions)
+        m_out = p_out = 0           # frames already yielded: mel / gate / align, and mel_post
+        for mel_gate, S, n_known, sv in self._decode_chunks(memory, None, seed, chunk, ahead=True):
+            stopped = bool((sv >= 0).all())
+            last = stopped or n_known >= T_cap
+            if stopped:
+                n_known = int(sv.max().item()) + 1
+            elif last:
+                print("Warning! Reached max decoder steps", file=sys.stderr)
+            mel = mel_gate[:, :n_mel, m_out:n_known].contiguous()
+            gate = mel_gate[:, n_mel, m_out:n_known].unsqueeze(-1).contiguous()
+            align = S["align_out"][:, m_out:n_known].contiguous()
+            p_hi = n_known if last else max(p_out, n_known - reach)
+            if p_hi > p_out:
+                lo, hi = max(0, p_out - reach), min(n_known, p_hi + reach)
+                win = mel_gate[:, :n_mel, lo:hi].contiguous()
+                post = self.postnet(win)
+                mel_post = (win + post)[:, :, p_out - lo:p_hi - lo].contiguous()
+            else:
+                mel_post = torch.empty(mel.size(0), n_mel, 0, dtype=torch.float32, device=dev)
+            m_out, p_out = n_known, p_hi
+            yield mel, mel_post, gate, align, last
+            if last:
+                return
 
     def forward(self, text, text_lengths, mels, output_lengths, prenet_masks=None, seed=None, train_masks=None, save=None,
                 max_len=None):
@@ -1164,6 +1238,39 @@ class Tacotron(nn.Module):
         with torch.no_grad():
             out = self._eng().inference(inputs, prenet_masks, seed=seed, train_masks=train_masks)
         return self._as_module_dtype(self.parse_output(out))
+
+    def inference_stream(self, inputs, speaker_id=None, seed=None, chunk=64):
+        """``inference`` for one text (B = 1, eval mode) as a generator: after every ``chunk`` decoder steps' stop poll it yields
+        ``(mel, mel_post, gate, align, last)`` for the frames that became final, so that a vocoder can start on the first frames
+        while the rest is still decoded (``streaming.synthesize_stream``).  mel [1, n_mel, n], gate [1, n, 1] and align [1, n, T_in]
+        hold the frames decoded since the piece before; mel_post [1, n_mel, n'] lags them by the postnet's reach, 5 layers x 2 = 10
+        frames, and catches up in the last piece (n' may be 0).  Concatenated along the frame axis the pieces are
+        ``inference(inputs, speaker_id, seed=seed)``: the same stop step, mel / gate / align equal, mel_post up to float rounding,
+        and the same "max decoder steps" warning.  Frames a chunk computed past the stop step are never yielded.  While no stop
+        has been seen the next chunk is enqueued before a piece is yielded, so the consumer's launches run behind it.
+        Arguments are checked here, before the first piece is asked for."""
+        self._check(inputs)
+        if self.training:
+            raise _lib.T2SError("inference_stream runs in eval mode only (call .eval())")
+        if inputs.dim() != 2 or inputs.size(0) != 1:
+            raise _lib.T2SError("inference_stream: inputs must be [1, T] ids, got %s" % (tuple(inputs.shape),))
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("inference_stream: chunk must be >= 1, got %d" % chunk)
+        if seed is not None:
+            seed = sampling.check_seed(seed, "inference_stream: seed")
+        return self._inference_stream(inputs, seed, chunk)
+
+    def _inference_stream(self, inputs, seed, chunk):
+        with torch.no_grad():
+            gen = self._eng().inference_stream(inputs, seed=seed, chunk=chunk)
+        while True:
+            with torch.no_grad():
+                try:
+                    piece = next(gen)
+                except StopIteration:
+                    return
+            yield tuple(self._as_module_dtype(list(piece[:4]))) + (piece[4],)
 
     def inference_batch(self, inputs, input_lengths, speaker_id=None, prenet_masks=None, seeds=None):
         """Autoregressive decode of a batch of texts of different lengths, in eval mode: ``inputs`` [B, T] padded ids,
