@@ -260,3 +260,74 @@ def padded_rows(rows):
 def current_stream():
     import torch
     return c_vp(torch.cuda.current_stream().cuda_stream)
+
+
+_orders = None         # every live StreamOrder (a weakref.WeakSet, made with the first one)
+
+
+class StreamOrder:
+    """Program order per object across streams (point 3).  The object remembers the stream of its last
+    call; a call that arrives on another stream makes that stream wait on the device for the last one before its first launch or
+    cache read.  On one stream it is a comparison: nothing is recorded and nothing is launched.
+
+    Parameters are shared between objects: an optimizer (``writer=True``) rewrites in place what the engines pack from.  So a
+    writer's call also waits for the latest call of every other object, and every object's call for the latest call of every
+    writer - once per such call, and only where the two streams differ.  Two engines never wait for each other: a Tacotron and a
+    WaveGlow on streams of their own stay independent."""
+    __slots__ = ("last", "calls", "seen", "writer", "switched", "__weakref__")
+
+    def __init__(self, writer=False):
+        import weakref
+        global _orders
+        if _orders is None:
+            _orders = weakref.WeakSet()
+        self.last = None
+        self.calls = 0
+        self.seen = weakref.WeakKeyDictionary()     # other object -> the count of its calls this one is ordered behind
+        self.writer = bool(writer)
+        self.switched = False       # whether the latest enter() came on another stream than the call before it
+        _orders.add(self)
+
+    def __deepcopy__(self, memo):
+        return StreamOrder(self.writer)     # a copied engine or optimizer has made no call yet
+
+    def enter(self, device=None):
+        """The caller's current stream, ordered behind the object's last call and behind the writers of what it reads."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        last = self.last
+        self.switched = last is not None and last != cur
+        if self.switched:
+            cur.wait_stream(last)
+        self.last = cur
+        self.calls += 1
+        for o in _orders:
+            if o is self or not (o.writer or self.writer) or o.last is None or self.seen.get(o) == o.calls:
+                continue
+            if o.last != cur:
+                cur.wait_stream(o.last)
+            self.seen[o] = o.calls
+        return cur
+
+
+def record_stream(obj, stream, _seen=None):
+    """tensor.record_stream(stream) for every device tensor reachable through dicts, lists, tuples and plain objects: a resident
+    buffer that was allocated on one stream and is now used on another must not be handed out again by the caching allocator,
+    once it is dropped, before that other stream has finished with it.  Called where a StreamOrder saw the stream change, never on
+    the single-stream path."""
+    import torch
+    seen = set() if _seen is None else _seen
+    if id(obj) in seen:
+        return
+    seen.add(id(obj))
+    if torch.is_tensor(obj):
+        if obj.is_cuda:
+            obj.record_stream(stream)
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            record_stream(v, stream, seen)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            record_stream(v, stream, seen)
+    elif hasattr(obj, "__dict__") and not isinstance(obj, (torch.nn.Module, torch.cuda.Stream, torch.cuda.Event, type)):
+        record_stream(vars(obj), stream, seen)

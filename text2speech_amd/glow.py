@@ -258,10 +258,23 @@ class _Engine:
         self.packed16_key = None
         self._keep = []             # the current call's temporaries whose pointers went to a kernel
         self._streams = {}
+        # program order across streams: a call on another stream than the engine's last one waits for it before it reads a
+        # cached pack, a workspace or the engine's side streams (nothing is recorded or launched on one stream)
+        self.order = _lib.StreamOrder()
         self.grad_sync = None       # distributed.GradSync: bucketed RCCL all-reduce issued from inside backward
         self.gemm_events = None     # bench.py: list of (start, end) torch.cuda.Event pairs around the gate GEMM
         self.gemm_event_stride = 1  # bench.py: time every n-th gate-GEMM launch (an event pair costs ~1.5 us of stream time)
         self._gemm_launch_no = 0
+
+    def _enter(self, device):
+        """The caller's stream, ordered behind the engine's last call.  Where the stream changed, the
+        resident buffers - allocated on whichever stream first needed them - are recorded as in use on this one too.  Returns (the
+        stream, whether it changed): workspace() wants both for a stream's own cache."""
+        cur = self.order.enter(device)
+        switched = self.order.switched
+        if switched:
+            _lib.record_stream((self.ws, self.packed, self.packed16, self._keep), cur)
+        return cur, switched
 
     # ------------------------------------------------------------------ geometry
     def geom(self):
@@ -602,12 +615,14 @@ class _Engine:
     # ------------------------------------------------------------------ workspaces
     STREAM_SHAPES = 3       # workspaces a stream keeps resident: its first, regular and last window
 
-    def workspace(self, B, L, device, cache=None):
+    def workspace(self, B, L, device, cache=None, switched=None):
         """The activation planes of a (B, L) call.  The engine keeps ONE shape resident and reallocates (zero-filled) on every
         change.  cache (a dict owned by a stream, streaming.py): that call's workspaces live there instead, at most STREAM_SHAPES
         of them, the oldest dropped first - a stream alternates between its first, regular and last window shapes - and the
         engine's own resident shape is left alone, so what the calls around a stream allocate does not change."""
         key = (B, L, str(device))
+        if cache is not None and switched is not None and switched[1]:
+            _lib.record_stream(cache, switched[0])          # a stream's own workspaces, as _enter() does for the engine's: what _enter() returned
         w = (self.ws if cache is None else cache).get(key)
         if w is None:
             g = self.geom()
@@ -742,6 +757,7 @@ class _Engine:
         WN.end folded in, residual GEMM), then WN.end's output (b ; log_s) without applying the coupling."""
         self._check_inputs(audio, spect)
         dev = audio.device
+        self._enter(dev)
         B, n_in, L = audio.shape
         c_off, n_rem, n_half = self._flow_geom(k)
         g = self.geom()
@@ -798,6 +814,7 @@ class _Engine:
         m = self.m
         self._check_inputs(mel, audio)
         dev = audio.device
+        self._enter(dev)
         B, T = audio.shape
         G = m.n_group
         L = T // G
@@ -915,6 +932,7 @@ class _Engine:
         m = self.m
         self._check_inputs(mel)
         dev = mel.device
+        entered = self._enter(dev)      # (infer_batch's lengths, uploaded ahead of this, are a tensor of that call's own)
         B, _, frames = mel.shape
         G = m.n_group
         up = m.upsample
@@ -930,7 +948,7 @@ class _Engine:
         path = plan.path
         self._keep = []
         plan = self._pack(plan, dev)
-        w = self.workspace(B, L, dev, ws_cache)
+        w = self.workspace(B, L, dev, ws_cache, entered)
         st = _lib.current_stream()
         # Weights are packed once here, so the conditioning path can be composed with the upsampler (K = 640 -> 320 in the gate
         # GEMM, no upsampler launch) - wherever the grid is large enough for the 256-row ping-pong tiles anyway.  Opt-in

@@ -205,6 +205,7 @@ def forward_train(eng, mel, audio):
     eng.train_check()
     eng._check_inputs(mel, audio)
     dev = audio.device
+    eng._enter(dev)             # behind the engine's last call, whichever stream that was on
     B, T = audio.shape
     G = m.n_group
     L = T // G
@@ -321,6 +322,7 @@ def backward_train(eng, ts, gz, g_log_s, g_log_det):
     B, L, Lp, nt = ts.B, ts.L, ts.Lp, ts.nt
     G = m.n_group
     dev = ts.z_final.device
+    eng._enter(dev)
     st = _lib.current_stream()
     grads = {}
     zb = ts.zero_bias

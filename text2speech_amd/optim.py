@@ -37,6 +37,7 @@ def _norm_scratch(device):
 
 
 _clip_table = None      # the job table of the last clip_grad_norm_ call, keyed on its gradient pointers
+_clip_order = _lib.StreamOrder()       # its reduction scratch is shared by every call: program order across streams
 
 
 def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False):
@@ -57,6 +58,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
         if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
             raise _lib.T2SError("clip_grad_norm_ needs contiguous float32 GPU gradients")
     global _clip_table
+    _clip_order.enter(grads[0].device)
     key = tuple(g.data_ptr() for g in grads) + tuple(g.numel() for g in grads)
     t = _clip_table
     if t is None or t["key"] != key:
@@ -99,6 +101,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._norm = None           # the job table over every group, the reduction scratch and out[4] of t2s_grad_norm_table
         self.grad_norm = None
         self.found_nonfinite = None
+        # a step on another stream than the last one waits for it (moments, job tables) and for the engines that read the
+        # parameters it rewrites; their next calls wait for this step
+        self.order = _lib.StreamOrder(writer=True)
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -171,6 +176,10 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        for group in self.param_groups:
+            if group["params"]:
+                self.order.enter(group["params"][0].device)
+                break
         active = [(gi, group) for gi, group in enumerate(self.param_groups) if any(p.grad is not None for p in group["params"])]
         tables = [self._table(gi, group) for gi, group in active]
         clip = self._grad_norm(tables) if self.max_grad_norm is not None and tables else None

@@ -76,6 +76,7 @@ class _Bwd:
         self.eng, self.sv = eng, sv
         self.m = eng.m
         self.dev = sv["memory"].device
+        eng._enter(self.dev)
         self.st = _lib.current_stream()
         self.grads = {}
         self.keep = []

@@ -384,6 +384,9 @@ class _TacoEngine:
         self.m = model
         self.prep = None
         self.prep_key = None
+        # program order across streams: every entry point starts with prepare(), which makes a call on another stream than the
+        # engine's last one wait for it before the prepared weights, the pool or the decoder state are touched
+        self.order = _lib.StreamOrder()
         self.lstm_xbufs = {}    # (direction of use, B, device) -> [split BiLSTM exchange buffer, epoch of its last launch]
         self.xbuf_errs = {}     # exchange buffer name -> (its int64 view, index of its error word): read by check_lstm_xbuf()
         self.decode_stream = True       # offer the streamed-gate buffers (gate_part, ploc, w_pre2T); False: the plain chain (A/B tests)
@@ -396,6 +399,14 @@ class _TacoEngine:
         self.last_decode_w16 = False    # whether the last decode_free went through t2s_taco_decode_steps_w16 ...
         self.last_decode_lstm_bytes = None      # ... and the bytes of LSTM weights one of its steps read (t2s_taco_decode_plan_w16)
         self.last_prenet_masks = None   # the mask buffer [n, B, 2, prenet_dim] the last decode_free read (tests compare batch and solo draws)
+
+    def _enter(self, dev):
+        """The caller's stream, ordered behind the engine's last call.  Where the stream changed, the
+        prepared weights and the pooled buffers are recorded as in use on this one too."""
+        cur = self.order.enter(dev)
+        if self.order.switched:
+            _lib.record_stream((self.prep, self.pool, self.lstm_xbufs), cur)
+        return cur
 
     # ------------------------------------------------------------------ weight preparation
     def _pack_conv_bn(self, seq, dev, halo):
@@ -420,6 +431,7 @@ class _TacoEngine:
 
     def prepare(self, dev):
         m = self.m
+        self._enter(dev)
         key = tuple(p._version for p in m.parameters()) + (str(dev), m.training)
         lstm_w = [m.decoder.attention_rnn.weight_ih, m.decoder.attention_rnn.weight_hh, m.decoder.decoder_rnn.weight_ih,
                   m.decoder.decoder_rnn.weight_hh]
@@ -755,6 +767,7 @@ class _TacoEngine:
         what it computes alone (inference_batch); the last layer's output there is not."""
         P = self.prep
         m = self.m
+        self._enter(mel.device)         # a piece of inference_stream may be asked for on another stream than the one before
         B, C, T = mel.shape
         halo = 2
         Lp = _lib.plane_rows(T, halo)
@@ -962,7 +975,9 @@ class _TacoEngine:
         stop = torch.full((B,), -1, dtype=torch.int32, device=dev)
 
         def launch(s0):
-            # (the current stream is read per chunk: the consumer of a generator may have changed it)
+            # (the current stream is read per chunk: the consumer of a generator may have changed it - and is then ordered behind
+            # the chunk before, as between two calls)
+            self._enter(dev)
             st = _lib.current_stream()
             n = min(chunk, T_cap - s0)
             if w16 is None:
