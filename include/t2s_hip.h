@@ -981,6 +981,52 @@ int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* tab
                     double rescaling_max, double peak_floor, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths,
                     void* stream);
 
+/* ---- joining the rows of padded batches into one utterance in device memory (additive to ABI version 4; audio.py join_batches,
+ *      longform.py synthesize_long) ----
+ * Sentence after sentence, a pause of zeros between them, a linear ramp at the joints; no length is read by the host.
+ *  - n segments are numbered by position p = 0 .. n-1.
+ *  - Segment p is row order[p] of the sources, or row p when order is NULL.
+ *  - Its length len_p is read from the device.  It is clamped to [0, N] of its row, so any value is safe.
+ *  - Its pause is g_p >= 0 samples, for p < n-1.  Pauses come from an int32 array by position, or one uniform gap.  g_{n-1} counts
+ *    as 0.
+ * With int64 arithmetic:
+ *     off_0 = 0,   off_{p+1} = off_p + len_p + g_p,   total = off_{n-1} + len_{n-1}
+ *     dst[off_p + i] = w_p(i) x_p[i]        0 <= i < len_p
+ *     dst[j] = +0                           every other j in [0, dst_cap)
+ * The fade is F >= 0 samples.
+ *  - The ramp is r(k) = (float)((double)(2k + 1) / (double)(2F)) for 0 <= k < F.  It is one double division, rounded once.
+ *  - The leading ramp applies to segment p when p > 0 or fade_ends is set.  The trailing ramp applies when p < n-1 or fade_ends is
+ *    set.
+ *  - y = x (f16 widened exactly).
+ *  - If the leading ramp applies and i < F: y = y r(i), one f32 multiply.
+ *  - Then, if the trailing ramp applies and len_p - 1 - i < F: y = y r(len_p - 1 - i).
+ *  - A segment shorter than 2F gets both factors, in that order.
+ *  - F = 0 copies bit for bit.
+ * Because of this, a segment's samples in the output depend on its own samples, F, and whether it is first or last.  They do not
+ * depend on the batch it came from or on its row.  Elements at or beyond dst_cap are never written.  offsets[0 .. n] is reported
+ * unclipped, with offsets[n] = total.  length = min(total, dst_cap) is reported as int32.
+ *  t2s_join_tile: host only, the samples of one row that one workgroup of the gather handles (2048).
+ *  t2s_join_offsets: the scan.  lengths, row_caps (the N of each row's batch): int32 [n] in device memory, by row; order: int32 [n],
+ *    position -> row, or NULL (an entry outside [0, n) counts as an empty segment); gaps: int32 [n - 1] by position (a negative one
+ *    counts as 0), or NULL: `gap` everywhere.  Writes offsets (int64 [n + 1], 8-byte aligned) and length (int32 [1]) from one
+ *    workgroup in integer arithmetic, for any n up to 65535.  It also stores +0 to all of dst[0 : dst_cap), on the same stream and
+ *    before the scan: the pauses and the tail are this call's business, so after it and the gathers every element of
+ *    dst[0 : dst_cap) is defined, whatever it held before.
+ *  t2s_join_gather: one source batch.  src: B rows of N samples, ldx elements apart (ldx >= N), src_kind 1 f32 or 2 f16 (as
+ *    t2s_trim_gather's); lengths: int32 [B] of these rows; pos: int32 [B], pos[b] the position of row b - a negative or >= n value
+ *    means the row is not part of the join and writes nothing; offsets: the scan's.  Row b's len samples (lengths[b] clamped to
+ *    [0, N]) go to dst[offsets[pos[b]] + i] with the ramps above, where that index lies in [0, dst_cap); nothing else is written
+ *    and samples at or behind a row's length are never read.  The grid is ceil(N / tile) x B workgroups.  Several batches are
+ *    several calls with the same offsets, n, fade and dst; their order does not matter.
+ *  T2S_EINVAL, with nothing launched: a NULL required pointer (all but order, gaps and stream); n, B, N or dst_cap <= 0; n or
+ *    B > 65535; dst_cap > 2^31 - 1; fade < 0 or > 65536; gap < 0; a src_kind other than 1 or 2; ldx < N; src overlapping dst; offsets
+ *    not 8-byte aligned.  No alignment is required beyond the element otherwise. */
+int t2s_join_tile(void);
+int t2s_join_offsets(const int* lengths, const int* row_caps, const int* order, const int* gaps, int gap, int n, float* dst,
+                     long dst_cap, long* offsets, int* length, void* stream);
+int t2s_join_gather(const void* src, int src_kind, int B, int N, long ldx, const int* lengths, const int* pos, const long* offsets,
+                    int n, int fade, int fade_ends, float* dst, long dst_cap, void* stream);
+
 /* ---- keyed sampling: random draws that are a function of (the entry's seed, the element's index) only (additive to ABI version 4;
  *      tacotron.py inference_batch(seeds=), glow.py infer(seed=) / infer_batch(seeds=) / draw_noise) ----
  * An entry of a batch draws the same bits alone and in any batch: nothing depends on B, on the entry's place, on the padded length

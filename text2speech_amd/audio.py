@@ -15,11 +15,15 @@ for bit, and zeros behind its end.  from_pcm16 is to_pcm1
 clips are text2speech_amd/data.py.  Resampler converts the sample rate of a batch (forward / resample_batch) or, through
 PcmPool.resample, of a pool: scipy.signal.resample_poly's polyphase filter with every sum in double precision (csrc/resample.hip).
 Trimmer cuts leading and trailing silence (librosa.effects.trim's decision) and rescales to a peak, on a batch (forward /
-trim_batch / bounds_batch) or, through PcmPool.rescale_trim, on a pool (csrc/trim.hip).
+trim_batch / bounds_batch) or, through PcmPool.rescale_trim, on a pool (csrc/trim.hip).  join_batches / join_batch turn the padded
+rows of such batches back into one utterance - pauses between them, ramps at the joints - with no length read back (csrc/join.hip;
+text2speech_amd/longform.py is the chain around it).
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
 window); the mel filterbank restates librosa.filters.mel's defaults (Slaney scale, area normalisation) because librosa is
 an unpinned dependency that this image does not have.
 """
+import operator
+
 import numpy as np
 import torch
 from scipy.signal import get_window
@@ -27,7 +31,8 @@ from scipy.signal import get_window
 from . import _lib
 
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
-           "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer"]
+           "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer", "join_batches",
+           "join_batch"]
 
 
 def _ru(a, b):
@@ -411,6 +416,146 @@ class Trimmer:
         return out.view(audio.shape), out_lens
 
 
+JOIN_MAX_FADE = 65536          # the library's limit on the fade (include/t2s_hip.h)
+JOIN_MAX_SAMPLES = 2 ** 31 - 1  # ... and on the joined row
+
+
+def _join_count(v, what, name):
+    """a host count of samples (or a row number) as an int >= 0; anything else raises ValueError"""
+    try:
+        n = None if isinstance(v, bool) else operator.index(v)
+    except TypeError:
+        n = None
+    if n is None:
+        raise ValueError("%s: %s must be an integer, got a %s" % (what, name, type(v).__name__))
+    if n < 0:
+        raise ValueError("%s: %s must not be negative, got %d" % (what, name, n))
+    return n
+
+
+def _join_rows(audio, lengths, k, what):
+    """One source batch of join_batches, checked -> (rows [B, N], B, N, lengths as given: a device tensor or a host one)"""
+    T2SError = _lib.T2SError
+    who = "%s: batch %d" % (what, k)
+    _need_cuda(audio, who)
+    if audio.dim() not in (2, 3) or (audio.dim() == 3 and audio.size(1) != 1) or audio.numel() == 0:
+        raise T2SError("%s: audio must be [B, N] or [B, 1, N] and hold samples, got %s" % (who, tuple(audio.shape)))
+    x = audio.detach()
+    if x.dtype not in (torch.float32, torch.float16):
+        raise T2SError("%s: expected float32 or float16, got %s (there is no silent cast)" % (who, x.dtype))
+    N = x.size(-1)
+    x = x.reshape(-1, N)
+    B = x.size(0)
+    try:
+        lens = torch.as_tensor(lengths)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise T2SError("%s: lengths must be a tensor or a sequence of integers (%s)" % (who, e))
+    if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+        raise T2SError("%s: lengths must be integers, got %s" % (who, lens.dtype))
+    if lens.dim() != 1 or lens.numel() != B:
+        raise T2SError("%s: lengths has shape %s, the batch holds %d entries" % (who, tuple(lens.shape), B))
+    if lens.device.type != "cpu" and lens.device != x.device:
+        raise T2SError("%s: lengths live on %s, the audio on %s" % (who, lens.device, x.device))
+    return x, B, N, lens.detach()
+
+
+def join_batches(batches, order=None, pause=0, pauses=None, fade=0, fade_ends=False):
+    """The rows of padded batches as ONE utterance in HBM: segment after segment, `pause` samples of silence between them, a linear
+    ramp of `fade` samples at the joints (csrc/join.hip; include/t2s_hip.h states the arithmetic).  `batches`: a list of
+    (audio [B, N] or [B, 1, N] float32 or float16 in HBM, lengths [B]) - WaveGlow.infer_batch's, Denoiser.denoise_batch's or
+    Trimmer.trim_batch's two results as returned.  A device tensor of lengths is used where it is (clamped to [0, N] on the device);
+    a host tensor or a sequence is copied over.  Rows are numbered through the batches in the order given, n in all.
+
+    order    a host sequence, a permutation of the n rows: position -> row (None: the rows as numbered)
+    pause    samples of silence behind every segment but the last; `pauses`: n - 1 host ints by position, instead
+    fade     samples of ramp r(k) = (2k + 1) / (2 fade) at the start of every segment but the first and at the end of every segment
+             but the last; `fade_ends`: at the utterance's own two ends as well.  A segment shorter than 2 fade gets both factors.
+
+    Returns (audio float32 [1, cap], length int32 [1] on the device, offsets int64 [n + 1] on the device): segment p is
+    audio[0, offsets[p] : offsets[p] + its length], offsets[n] = length the joined samples, and everything else up to
+    cap = sum B N + sum of the pauses - known on the host - is +0.  With fade = 0 a segment's samples are copied bit for bit (f16
+    widened exactly); whatever the fade they depend on the segment, the fade and whether it is first or last - not on its batch or
+    row.  Nothing is read back: one small host-to-device copy (the order, the pauses), one scan launch and one gather launch per
+    batch, all on the current stream."""
+    what = "join_batches"
+    T2SError = _lib.T2SError
+    try:
+        batches = [tuple(b) for b in batches]
+    except TypeError:
+        raise T2SError("%s: batches must be a list of (audio, lengths) pairs" % what) from None
+    if not batches or any(len(b) != 2 for b in batches):
+        raise T2SError("%s: batches must be a non-empty list of (audio, lengths) pairs" % what)
+    fade = _join_count(fade, what, "fade")
+    if fade > JOIN_MAX_FADE:
+        raise ValueError("%s: fade may be at most %d samples, got %d" % (what, JOIN_MAX_FADE, fade))
+    rows = [_join_rows(a, l, k, what) for k, (a, l) in enumerate(batches)]
+    dev = rows[0][0].device
+    for k, r in enumerate(rows):
+        if r[0].device != dev:
+            raise T2SError("%s: batch %d is on %s, batch 0 on %s" % (what, k, r[0].device, dev))
+    n = sum(r[1] for r in rows)
+    if n > 65535:
+        raise T2SError("%s: %d rows, the most is 65535" % (what, n))
+    if pauses is not None:
+        try:
+            gaps = [_join_count(g, what, "a pause") for g in pauses]
+        except TypeError:
+            raise ValueError("%s: pauses must be a sequence of integers" % what) from None
+        if len(gaps) != n - 1:
+            raise ValueError("%s: pauses holds %d values, %d segments need %d" % (what, len(gaps), n, n - 1))
+    else:
+        gaps = [_join_count(pause, what, "pause")] * (n - 1)
+    if order is None:
+        order = list(range(n))
+    else:
+        try:
+            order = [_join_count(r, what, "an entry of order") for r in order]
+        except TypeError:
+            raise ValueError("%s: order must be a sequence of integers" % what) from None
+        if sorted(order) != list(range(n)):
+            raise ValueError("%s: order must be a permutation of the %d rows, got %s" % (what, n, order))
+    cap = sum(r[1] * r[2] for r in rows) + sum(gaps)
+    if cap > JOIN_MAX_SAMPLES:
+        raise T2SError("%s: the joined row would hold %d samples, the most is %d" % (what, cap, JOIN_MAX_SAMPLES))
+    pos = [0] * n
+    for p, r in enumerate(order):
+        pos[r] = p
+    caps = [r[2] for r in rows for _ in range(r[1])]
+    # one table, one copy: order | pos | caps | pauses, then every host tensor of lengths
+    host = [torch.tensor(order + pos + caps + gaps, dtype=torch.int32)]
+    host += [r[3].to(torch.int64).clamp(0, r[2]).to(torch.int32) for r in rows if not r[3].is_cuda]
+    table = _to_device(torch.cat(host), dev)
+    order_d, pos_d, caps_d, gaps_d = table[:n], table[n:2 * n], table[2 * n:3 * n], table[3 * n:4 * n - 1]
+    at = 4 * n - 1
+    lens_d = []
+    for r in rows:
+        if r[3].is_cuda:
+            lens_d.append(r[3].clamp(0, r[2]).to(torch.int32))
+        else:
+            lens_d.append(table[at:at + r[1]])
+            at += r[1]
+    all_lens = lens_d[0] if len(rows) == 1 else torch.cat(lens_d)
+    out = torch.empty(1, cap, dtype=torch.float32, device=dev)
+    length = torch.empty(1, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    p, st = _lib.ptr, _lib.current_stream()
+    _lib.call("t2s_join_offsets", p(all_lens), p(caps_d), p(order_d), p(gaps_d) if n > 1 else None, 0, n, p(out), cap, p(offsets),
+              p(length), st)
+    r0 = 0
+    for (x, B, N, _), lens in zip(rows, lens_d):
+        if x.stride(1) != 1 or (B > 1 and x.stride(0) < N):
+            x = x.contiguous()
+        _lib.call("t2s_join_gather", p(x), _KINDS[x.dtype], B, N, x.stride(0) if B > 1 else N, p(lens), p(pos_d[r0:r0 + B]), p(offsets),
+                  n, fade, int(bool(fade_ends)), p(out), cap, st)
+        r0 += B
+    return out, length, offsets
+
+
+def join_batch(audio, lengths, order=None, pause=0, pauses=None, fade=0, fade_ends=False):
+    """join_batches for one batch: the rows of (audio, lengths) as one utterance."""
+    return join_batches([(audio, lengths)], order, pause, pauses, fade, fade_ends)
+
+
 def dynamic_range_compression(x, C=1, clip_val=1e-5):
     return torch.log(torch.clamp(x, min=clip_val) * C)
 
@@ -693,4 +838,4 @@ class Denoiser(torch.nn.Module):
         audio, lens = self.stft._batch_audio(audio, lengths, what)
         mag, ph, _, _, fl = self.stft._transform(audio.float(), lens)
         out = self.stft._inverse(mag, ph, fl, _bias=self.bias_spec.reshape(-1).contiguous(), _strength=strength)
-        return out, ((fl - 1) * self.stft.hop_length).to(out.device)
+        return out, _to_device((fl - 1) * self.stft.hop_length, out.device)

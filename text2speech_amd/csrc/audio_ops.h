@@ -82,3 +82,30 @@ hipError_t t2s_launch_trim_energy(const TrimEnergyArgs& a, int src_kind, int n_r
 hipError_t t2s_launch_trim_bounds(const TrimBoundsArgs& a, int n_rows, hipStream_t s);
 // (src_kind, dst_kind): int16 -> int16, f32 -> f32, f16 -> f32
 hipError_t t2s_launch_trim_gather(const TrimGatherArgs& a, int src_kind, int dst_kind, int n_rows, hipStream_t s);
+
+// joining the rows of padded batches into one utterance (join.hip): the scan of the lengths, then one gather per source batch
+#define T2S_JOIN_TILE 2048                      // samples of one row per workgroup of the gather
+struct JoinOffsetsArgs {
+    const int* lengths;         // [n] int32 on the device, by row; any value safe
+    const int* row_caps;        // [n] int32: the N of each row's batch
+    const int* order;           // [n] int32: position -> row, or NULL (the identity)
+    const int* gaps;            // [n - 1] int32 by position, or NULL: `gap` everywhere
+    int gap, n;
+    long dst_cap;
+    long* offsets;              // [n + 1] int64, unclipped; offsets[n] = total
+    int* length;                // [1] int32: min(total, dst_cap)
+};
+struct JoinGatherArgs {
+    const void* src;            // f32 / f16, B rows of N samples, ldx apart
+    long N, ldx;
+    const int* lengths;         // [B] int32
+    const int* pos;             // [B] int32: the row's position; outside [0, n): not part of the join
+    const long* offsets;        // the scan's
+    int n, fade, fade_ends;
+    float* dst;
+    long dst_cap;
+};
+// zeroes dst[0 : dst_cap) on the stream, then scans
+hipError_t t2s_launch_join_offsets(const JoinOffsetsArgs& a, float* dst, hipStream_t s);
+// src_kind 1 f32, 2 f16
+hipError_t t2s_launch_join_gather(const JoinGatherArgs& a, int src_kind, int B, hipStream_t s);

@@ -237,4 +237,36 @@ int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* tab
     return T2S_OK;
 }
 
+// ---- joining the rows of padded batches into one utterance: join.hip's two kernels --------------------------------------------------
+int t2s_join_tile(void) { return T2S_JOIN_TILE; }
+
+int t2s_join_offsets(const int* lengths, const int* row_caps, const int* order, const int* gaps, int gap, int n, float* dst,
+                     long dst_cap, long* offsets, int* length, void* stream) {
+    if (!lengths || !row_caps || !dst || !offsets || !length || !al8(offsets) || n <= 0 || n > 65535 || dst_cap <= 0 ||
+        dst_cap > 0x7fffffffL || gap < 0)
+        return T2S_EINVAL;
+    JoinOffsetsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.lengths = lengths; a.row_caps = row_caps; a.order = order; a.gaps = gaps; a.gap = gap; a.n = n; a.dst_cap = dst_cap;
+    a.offsets = offsets; a.length = length;
+    T2S_CHECK_HIP(t2s_launch_join_offsets(a, dst, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_join_gather(const void* src, int src_kind, int B, int N, long ldx, const int* lengths, const int* pos, const long* offsets,
+                    int n, int fade, int fade_ends, float* dst, long dst_cap, void* stream) {
+    if (!src || !lengths || !pos || !offsets || !dst || !al8(offsets) || (src_kind != 1 && src_kind != 2) || B <= 0 || B > 65535 ||
+        N <= 0 || ldx < N || n <= 0 || n > 65535 || fade < 0 || fade > 65536 || dst_cap <= 0 || dst_cap > 0x7fffffffL)
+        return T2S_EINVAL;
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + ((size_t)(B - 1) * ldx + N) * (src_kind == 1 ? 4 : 2);
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)dst_cap * 4;
+    if (s0 < d1 && d0 < s1) return T2S_EINVAL;                  // never in place
+    JoinGatherArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.N = N; a.ldx = ldx; a.lengths = lengths; a.pos = pos; a.offsets = offsets; a.n = n; a.fade = fade;
+    a.fade_ends = fade_ends != 0; a.dst = dst; a.dst_cap = dst_cap;
+    T2S_CHECK_HIP(t2s_launch_join_gather(a, src_kind, B, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 }  // extern "C"

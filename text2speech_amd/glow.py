@@ -914,12 +914,13 @@ class _Engine:
         self._check_inputs(mel)
         stride = m.upsample.stride[0]
         # columns per entry, once per call: the only host -> device copy, and the array every launch that takes lengths reads
-        lens = (lengths * (stride // m.n_group)).to(torch.int32).to(mel.device)
+        # (through page-locked memory, so that the host does not wait for the copy: long-form synthesis runs behind it unsynchronised)
+        lens = (lengths * (stride // m.n_group)).to(torch.int32).pin_memory().to(mel.device, non_blocking=True)
         audio = self._infer(mel, sigma, noise, lens, seeds, sigmas)
         B, T = audio.shape
         _lib.call("t2s_zero_rows_f32", _lib.ptr(audio), _lib.ptr(lens), B, T // m.n_group, m.n_group, _lib.current_stream())
         self._keep.append(lens)
-        return audio, (lengths * stride).to(mel.device)
+        return audio, (lengths * stride).pin_memory().to(mel.device, non_blocking=True)
 
     def infer_window(self, mel, col0, k0, k1, sigma, seeds, sigmas, out, out_off, ws_cache=None):
         """_infer on ``mel``, a run of an utterance's frames that starts at column ``col0`` of its draws: the same launches, with

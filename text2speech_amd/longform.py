@@ -1,0 +1,253 @@
+"""Long-form synthesis: a paragraph as one utterance in HBM.
+
+The decoder stops at max_decoder_steps frames (1000: 5.7 s at hop 256 and 44 800 Hz), so a text longer than a sentence or two is
+split into chunks (``split_text``), the chunks are decoded and vocoded in ragged batches (``Tacotron.inference_batch(seeds=)``,
+``WaveGlow.infer_batch(seeds=)``, optionally ``Denoiser.denoise_batch`` and ``Trimmer.trim_batch``), and the rows of those batches
+are joined - sentence after sentence, a pause between them, a short ramp at every joint - by ``audio.join_batches``
+(csrc/join.hip), optionally resampled and quantised.  Every chunk has a seed of its own (``chunk_seeds``), so its audio is a
+function of (seed, its index, its text) and not of the batch it was computed in.  ``synthesize_long`` is the chain."""
+import collections
+
+import torch
+
+from . import _lib, sampling
+from .text import text_to_sequence
+
+SAMPLING_RATE = 44800          # the project's rate (the reference's hparams.py); synthesize_long(sampling_rate=) overrides it
+MAX_SYMBOLS = 64               # split_text's default: a guess, see there
+PAUSE_MS, FADE_MS = 250.0, 5.0
+
+_MASK = (1 << 64) - 1
+GOLD = 0x9E3779B97F4A7C15
+SENTENCE_END = ".?!。．？！"               # . ? ! and the full-width 。 ． ？ ！
+CLAUSE_END = ",;:，；：、"                 # , ; : and the full-width ， ； ： 、
+
+LongForm = collections.namedtuple("LongForm", "audio length offsets chunks truncated")
+
+
+def mix(x):
+    """splitmix64's finaliser on a wrapping uint64, as include/t2s_hip.h states it for the keyed draws"""
+    x &= _MASK
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _MASK
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _MASK
+    x ^= x >> 31
+    return x
+
+
+def chunk_seeds(seed, n):
+    """One seed per chunk from the utterance's: s_i = mix((i + 1) GOLD + seed) >> 1 in wrapping uint64 arithmetic, n Python ints in
+    [0, 2^63).  Chunk i's draws then depend on (seed, i) alone - not on the batch size or on the order the chunks were grouped in."""
+    seed = sampling.check_seed(seed, "chunk_seeds: seed")
+    n = int(n)
+    if n < 0:
+        raise ValueError("chunk_seeds: n must be >= 0, got %d" % n)
+    return [mix((i + 1) * GOLD + seed) >> 1 for i in range(n)]
+
+
+def n_symbols(text):
+    """ids the text becomes, the end-of-sequence id included: what the encoder sees"""
+    return len(text_to_sequence(text))
+
+
+def _pack(tokens, max_symbols):
+    """Consecutive tokens joined by single spaces into as few pieces of at most max_symbols ids as a left-to-right pass gives;
+    a token that is too long alone is returned alone (the caller cuts it further or refuses it)."""
+    pieces, cur = [], None
+    for t in tokens:
+        cand = t if cur is None else cur + " " + t
+        if cur is None or n_symbols(cand) <= max_symbols:
+            cur = cand
+        else:
+            pieces.append(cur)
+            cur = t
+    if cur is not None:
+        pieces.append(cur)
+    return pieces
+
+
+def _runs(words, marks):
+    """the words grouped into runs that end behind a word whose last character is one of `marks` (it stays with the left part)"""
+    runs, cur = [], []
+    for w in words:
+        cur.append(w)
+        if w[-1] in marks:
+            runs.append(" ".join(cur))
+            cur = []
+    if cur:
+        runs.append(" ".join(cur))
+    return runs
+
+
+def split_text(text, max_symbols=MAX_SYMBOLS):
+    """A text as a list of chunks for ``synthesize_long``; host only.  It is cut behind ``. ? !`` and their full-width forms where
+    whitespace or the end follows: one sentence, one chunk.  A sentence of more than ``max_symbols`` ids
+    (``len(text_to_sequence(s))``, the end-of-sequence id included) is cut further behind ``, ; :`` (and their full-width forms), and
+    a clause that is still too long at whitespace; neighbouring parts of a sentence are put together again, left to right, as long
+    as they fit.  The punctuation stays with the part on its left.  A word that exceeds max_symbols alone raises ValueError; empty
+    pieces are dropped.  ``" ".join(split_text(t)) == " ".join(t.split())``: nothing but whitespace is lost.
+
+    The default max_symbols = 64 is a guess at what a decoder trained on sentence-length clips speaks inside its 1000 frames (about
+    14 jamo a second for 5.7 s, with room to spare); no trained checkpoint has been measured here.  A chunk that does run into
+    max_decoder_steps is reported by synthesize_long's ``truncated``."""
+    if not isinstance(text, str):
+        raise ValueError("split_text: text must be a str, got %s" % type(text).__name__)
+    max_symbols = int(max_symbols)
+    if max_symbols < 2:
+        raise ValueError("split_text: max_symbols must be at least 2 (one symbol and the end-of-sequence id), got %d" % max_symbols)
+    chunks = []
+    for sentence in _runs(text.split(), SENTENCE_END):
+        if n_symbols(sentence) <= max_symbols:
+            chunks.append(sentence)
+            continue
+        parts = []
+        for clause in _runs(sentence.split(" "), CLAUSE_END):
+            if n_symbols(clause) <= max_symbols:
+                parts.append(clause)
+                continue
+            for piece in _pack(clause.split(" "), max_symbols):
+                if n_symbols(piece) > max_symbols:
+                    raise ValueError("split_text: %r is %d symbols without whitespace to cut at, max_symbols is %d"
+                                     % (piece, n_symbols(piece), max_symbols))
+                parts.append(piece)
+        chunks += _pack(parts, max_symbols)
+    return chunks
+
+
+def ms_to_samples(ms, rate, what="ms_to_samples"):
+    """round(ms rate / 1000) as a host int; a negative or non-finite duration raises ValueError"""
+    try:
+        v = float(ms) * rate / 1000.0
+    except (TypeError, ValueError):
+        raise ValueError("%s: a duration in milliseconds must be a number, got %r" % (what, ms)) from None
+    if not (v >= 0.0 and v - v == 0.0):
+        raise ValueError("%s: a duration must be finite and not negative, got %r ms" % (what, ms))
+    return int(round(v))
+
+
+def _plan(n_ids, batch_size, sort_by_length):
+    """(groups of chunk indices, order: position -> row of the join) - rows are numbered through the groups"""
+    idx = list(range(len(n_ids)))
+    if sort_by_length:
+        idx.sort(key=lambda i: -n_ids[i])                       # (stable: equal counts keep their order)
+    groups = [idx[g:g + batch_size] for g in range(0, len(idx), batch_size)]
+    row_of = {c: r for r, c in enumerate(idx)}
+    return groups, [row_of[p] for p in range(len(idx))]
+
+
+def _check_long_args(tacotron, waveglow, text, chunks, seed, seeds, batch_size, max_symbols, pause_ms, pauses_ms, fade_ms, rate):
+    """Every check of synthesize_long that needs no device -> (chunks, ids per chunk, seeds, pauses in samples, fade in samples)"""
+    who = "synthesize_long"
+    T2SError = _lib.T2SError
+    if tacotron.training or waveglow.training:
+        raise T2SError("%s runs in eval mode only (call .eval() on both models)" % who)
+    if (text is None) == (chunks is None):
+        raise T2SError("%s: give text or chunks, exactly one" % who)
+    if (seed is None) == (seeds is None):
+        raise T2SError("%s: a seed is required, seed or seeds (one per chunk) - without one a chunk's draws depend on its batch"
+                       % who)
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError("%s: batch_size must be an integer >= 1, got %r" % (who, batch_size))
+    if int(rate) != rate or rate < 1:
+        raise ValueError("%s: sampling_rate must be a positive integer, got %r" % (who, rate))
+    if text is not None:
+        chunks = split_text(text, max_symbols)
+    else:
+        if isinstance(chunks, str):
+            raise T2SError("%s: chunks must be a sequence of strings, not one string (that is text=)" % who)
+        chunks = list(chunks)
+        if not all(isinstance(c, str) for c in chunks):
+            raise T2SError("%s: chunks must be strings" % who)
+    if not chunks:
+        raise T2SError("%s: nothing to say - the text holds no chunk" % who)
+    n = len(chunks)
+    if n > 65535:
+        raise T2SError("%s: %d chunks, the most is 65535" % (who, n))
+    ids = [text_to_sequence(c) for c in chunks]
+    if seeds is None:
+        seeds = chunk_seeds(seed, n)
+    else:
+        try:
+            seeds = [sampling.check_seed(s, "%s: seeds" % who) for s in seeds]
+        except TypeError:
+            raise ValueError("%s: seeds must be a sequence of integers" % who) from None
+        if len(seeds) != n:
+            raise ValueError("%s: seeds holds %d values, there are %d chunks" % (who, len(seeds), n))
+    if pauses_ms is not None:
+        try:
+            gaps = [ms_to_samples(ms, rate, who) for ms in pauses_ms]
+        except TypeError:
+            raise ValueError("%s: pauses_ms must be a sequence of numbers" % who) from None
+        if len(gaps) != n - 1:
+            raise ValueError("%s: pauses_ms holds %d values, %d chunks need %d" % (who, len(gaps), n, n - 1))
+    else:
+        gaps = [ms_to_samples(pause_ms, rate, who)] * (n - 1)
+    return chunks, ids, seeds, gaps, ms_to_samples(fade_ms, rate, who)
+
+
+def synthesize_long(tacotron, waveglow, text=None, *, chunks=None, seed=None, seeds=None, sigma=0.666, batch_size=8,
+                    max_symbols=MAX_SYMBOLS, sort_by_length=True, denoiser=None, strength=0.1, trimmer=None, pause_ms=PAUSE_MS,
+                    pauses_ms=None, fade_ms=FADE_MS, resampler=None, pcm16=False, sampling_rate=None):
+    """Text of any length -> one utterance in HBM.  ``text`` is split by ``split_text(text, max_symbols)``, or ``chunks`` (strings)
+    are taken as they are; each goes through ``text_to_sequence``.  Groups of ``batch_size`` chunks (8 is the largest batch on the
+    fp16 decode path) run ``tacotron.inference_batch(seeds=)`` -> ``waveglow.infer_batch(sigma, seeds=)`` -> ``denoiser.denoise_batch
+    (strength)`` and ``trimmer.trim_batch`` where given; with ``sort_by_length`` the groups are taken in order of decreasing id
+    count, so that chunks of similar length share a batch (both models also compute their padding).  One ``audio.join_batches`` over
+    all groups puts the chunks back in the text's order with ``pause_ms`` of silence between them (``pauses_ms``: one value per
+    joint) and ``fade_ms`` of ramp at every joint; then ``resampler.resample_batch`` and ``audio.to_pcm16`` where asked.
+    Milliseconds become samples at the vocoder's rate, round(ms rate / 1000) on the host; the rate is ``sampling_rate``, else the
+    resampler's orig_rate, else 44 800.
+
+    A seed is required: ``seed`` (chunk i gets ``chunk_seeds(seed, n)[i]`` for both its prenet masks and its vocoder noise) or
+    ``seeds``, one int in [0, 2^63) per chunk.  Chunk i's samples are then those of
+    ``infer(inference(ids_i, seed=s_i).mel_post, sigma, seed=s_i)`` up to float rounding, whatever batch_size and sort_by_length.
+    Eval mode only.
+
+    Returns LongForm(audio, length, offsets, chunks, truncated):
+      audio      [1, cap] float32 (int16 with pcm16), zeros behind ``length``
+      length     [1] on the device: the utterance's samples, at the output rate
+      offsets    int64 [n + 1] on the device: chunk i starts at offsets[i] and the joined samples end at offsets[n] - in samples
+                 at the VOCODER's rate, before any resampling
+      chunks     the chunk strings
+      truncated  bool [n] on the device: chunk i ran into max_decoder_steps without a stop (its audio is cut there; split finer)
+
+    The host reads one thing per group from the device: the output lengths, once, directly behind ``inference_batch`` (whose
+    decode loop polls the device anyway) - ``infer_batch`` and ``denoise_batch`` size their launches by them.  Behind that read
+    nothing in the group's chain, in the join or in the resampling reads the device; the lengths the trimmer finds never leave it."""
+    from . import audio as A
+    rate = sampling_rate if sampling_rate is not None else (resampler.orig_rate if resampler is not None else SAMPLING_RATE)
+    chunks, ids, seeds, gaps, fade = _check_long_args(tacotron, waveglow, text, chunks, seed, seeds, batch_size, max_symbols, pause_ms,
+                                                      pauses_ms, fade_ms, rate)
+    n = len(chunks)
+    n_ids = [len(s) for s in ids]
+    groups, order = _plan(n_ids, int(batch_size), sort_by_length)
+    dev = next(waveglow.parameters()).device
+    stride = int(waveglow.upsample.stride[0])
+    T_cap = int(tacotron.decoder.max_decoder_steps)
+    rows = [c for g in groups for c in g]                       # row -> chunk
+    seeds_d = A._to_device(torch.tensor([seeds[c] for c in rows], dtype=torch.int64), dev)
+    batches, flags, r0 = [], [], 0
+    for g in groups:
+        B, T = len(g), max(n_ids[c] for c in g)
+        padded = torch.zeros(B, T, dtype=torch.int64)
+        for b, c in enumerate(g):
+            padded[b, :n_ids[c]] = torch.from_numpy(ids[c]).to(torch.int64)
+        s_d = seeds_d[r0:r0 + B]
+        r0 += B
+        out = tacotron.inference_batch(A._to_device(padded, dev), torch.tensor([n_ids[c] for c in g]), seeds=s_d)
+        frames = out[4].cpu()                                   # the group's one read-back
+        flags.append(out[4] == T_cap)
+        wav, wav_lens = waveglow.infer_batch(out[1], frames, sigma=sigma, seeds=s_d)
+        if denoiser is not None:
+            wav, wav_lens = denoiser.denoise_batch(wav, frames * stride, strength)
+        if trimmer is not None:
+            wav, wav_lens = trimmer.trim_batch(wav, wav_lens)
+        batches.append((wav, wav_lens))
+    audio, length, offsets = A.join_batches(batches, order=order, pauses=gaps, fade=fade)
+    truncated = torch.cat(flags)[A._to_device(torch.tensor(order, dtype=torch.int64), dev)]
+    if resampler is not None:
+        audio, length = resampler.resample_batch(audio, length)
+    if pcm16:
+        audio = A.to_pcm16(audio)                               # (zeros behind `length` already)
+    return LongForm(audio, length, offsets, chunks, truncated)
