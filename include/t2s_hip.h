@@ -1061,6 +1061,69 @@ int t2s_wg_noise_keyed(float* z, int B, int G, long L, const unsigned long long*
 int t2s_wg_noise_keyed_at(float* z, int B, int G, long L, long col0, const long long* col0s, const unsigned long long* seeds, float sigma,
                           const float* sigmas, void* stream);
 
+/* ---- the alignment check: where every decoder frame attends, and whether that path is the text (additive to ABI version 4;
+ *      alignment.py alignment_report, longform.py synthesize_long(check=); csrc/align.hip) ----
+ * Inputs
+ *  - A: B entries of N rows of T_in columns.
+ *     - Row stride is ld_row >= T_in.
+ *     - Entry stride is ld_entry >= N * ld_row.
+ *     - src_kind is 1 for f32 or 2 for f16, as in t2s_join_gather.
+ *  - in_len, out_len: int32 [B] in device memory.
+ *     - out_len may be NULL, which means N.  in_len may be NULL, which means T_in.
+ *  - Clamped values: S_b = clamp(in_len[b], 1, T_in) and F_b = clamp(out_len[b], 0, N).
+ * Row pass (t2s_align_rows).  For every b and t < F_b:
+ *  - pos[b,t] is the smallest j in [0, S_b) at which A[b,t,j] is largest.
+ *     - The scan starts at best = -inf, j = 0 and updates on v > best.  A NaN is therefore never chosen, and a row of NaN gives
+ *       pos = 0 with peak -inf.
+ *  - peak[b,t] is that value, widened to f32 exactly.
+ *  - bad[b,t] = 1 if any of the S_b values is not finite, otherwise 0.
+ * For t >= F_b: pos = -1, peak = 0, bad = 0.  The row is not loaded, so the ragged tail costs nothing.
+ * Outputs: pos int32 [B, N], peak f32 [B, N], bad uint8 [B, N].
+ * One wave per row, lanes striding the columns, four rows per workgroup; the grid covers the B N rows.
+ * Entry pass (t2s_align_stats).  One workgroup per entry, walking t in blocks of 256 frames with a carry.  Outputs:
+ * stats, int32 [B, 8]:
+ *   0 frames         F_b
+ *   1 symbols        S_b
+ *   2 max_skip       max(pos_t - pos_{t-1}) over 1 <= t < F_b, not below 0.  0 if F_b < 2.
+ *   3 max_back       max(pos_{t-1} - pos_t), same convention
+ *   4 longest_stall  longest run of consecutive frames with equal pos.  0 if F_b = 0.
+ *   5 last_pos       pos_{F_b - 1}.  -1 if F_b = 0.
+ *   6 covered        number of j < S_b with dur[b,j] > 0
+ *   7 bad_rows       sum of bad
+ * focus, f64 [B]:
+ *  - The mean of peak over the entry's frames.  It is summed in double, in an order fixed by F_b alone (thread i of 256 adds frames
+ *    i, i + 256, ... in that order, then a fixed tree joins the 256 sums).  An entry's bits are then the same alone, in any batch
+ *    and at any place.
+ *  - 0 if F_b = 0.
+ *  - If a peak is not finite, the result is whatever IEEE gives.  bad_rows reports it.
+ * dur, int32 [B, T_in]:
+ *  - The number of frames with pos = j.
+ *  - 0 for j >= S_b.
+ * flags, int32 [B].  The thresholds reach the kernel in a by-value struct:
+ *     1 TRUNCATED   max_frames > 0 && F_b >= max_frames
+ *     2 SKIP        max_skip > skip_max
+ *     4 BACK        max_back > back_max
+ *     8 STALL       longest_stall > stall_max
+ *    16 UNFINISHED  last_pos < S_b - 1 - end_slack
+ *    32 DIFFUSE     !(focus >= min_focus), so a NaN sets it
+ *    64 NONFINITE   bad_rows > 0
+ *   128 EMPTY       F_b == 0
+ *  - A negative integer threshold switches its bit off.
+ *  - min_focus <= 0 switches DIFFUSE off (a NaN min_focus as well).
+ * t2s_align_stats reads the row pass's pos, peak and bad ([B, N], the first F_b of each entry) and the same two length arrays.  It
+ * stores +0 to all of dur on the same stream before its kernel.  It trusts no pos it reads: a value outside [0, S_b) is counted in no
+ * dur.
+ * Memory safety: every length is clamped; nothing outside the stated outputs is written; nothing is read past S_b columns or F_b
+ * rows.  T_in of any positive size works.  The one limit is B N <= 2^31 - 1 (rows are numbered in an int).
+ * T2S_EINVAL, with nothing launched: a NULL A, pos, peak, bad, stats, focus, dur or flags; a pointer that is not aligned to its
+ * element (A to 4 bytes for f32 and 2 for f16, the int32 and f32 arrays to 4, focus to 8; in_len and out_len where given); B, N or
+ * T_in < 1; B N > 2^31 - 1; ld_row < T_in; ld_entry < N ld_row; a src_kind other than 1 or 2. */
+int t2s_align_rows(const void* A, int src_kind, int B, int N, int T_in, long ld_row, long ld_entry, const int* in_len,
+                   const int* out_len, int* pos, float* peak, unsigned char* bad, void* stream);
+int t2s_align_stats(const int* pos, const float* peak, const unsigned char* bad, int B, int N, int T_in, const int* in_len,
+                    const int* out_len, int max_frames, int skip_max, int back_max, int stall_max, int end_slack, double min_focus,
+                    int* stats, double* focus, int* dur, int* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

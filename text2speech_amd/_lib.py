@@ -123,6 +123,9 @@ SIGNATURES = {
     "t2s_join_tile": [],
     "t2s_join_offsets": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_long, c_vp, c_vp, c_vp],
     "t2s_join_gather": [c_vp, c_int, c_int, c_int, c_long, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_long, c_vp],
+    "t2s_align_rows": [c_vp, c_int, c_int, c_int, c_int, c_long, c_long, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "t2s_align_stats": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_double, c_vp, c_vp,
+                        c_vp, c_vp, c_vp],
     "t2s_bernoulli_mask_keyed": [c_vp, c_int, c_int, c_int, c_vp, c_float, c_vp],
     "t2s_noise_tile": [],
     "t2s_wg_noise_keyed": [c_vp, c_int, c_int, c_long, c_vp, c_float, c_vp, c_vp],

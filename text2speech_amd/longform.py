@@ -5,7 +5,9 @@ split into chunks (``split_text``), the chunks are decoded and vocoded in ragged
 ``WaveGlow.infer_batch(seeds=)``, optionally ``Denoiser.denoise_batch`` and ``Trimmer.trim_batch``), and the rows of those batches
 are joined - sentence after sentence, a pause between them, a short ramp at every joint - by ``audio.join_batches``
 (csrc/join.hip), optionally resampled and quantised.  Every chunk has a seed of its own (``chunk_seeds``), so its audio is a
-function of (seed, its index, its text) and not of the batch it was computed in.  ``synthesize_long`` is the chain."""
+function of (seed, its index, its text) and not of the batch it was computed in.  ``synthesize_long`` is the chain; with
+``check=`` it looks at every chunk's attention path first (``alignment.alignment_report``) and, with ``max_attempts`` > 1, decodes a
+flagged chunk again under another seed (``plan_pass`` / ``settle_pass`` / ``plan_retries`` are the host planning)."""
 import collections
 
 import torch
@@ -23,6 +25,7 @@ SENTENCE_END = ".?!ã€‚ï¼Žï¼Ÿï¼"               # . ? ! and the full-width ã€‚ ï¼
 CLAUSE_END = ",;:ï¼Œï¼›ï¼šã€"                 # , ; : and the full-width ï¼Œ ï¼› ï¼š ã€
 
 LongForm = collections.namedtuple("LongForm", "audio length offsets chunks truncated")
+LongFormChecked = collections.namedtuple("LongFormChecked", LongForm._fields + ("flags", "attempts", "stats", "focus", "durations"))
 
 
 def mix(x):
@@ -136,6 +139,53 @@ def _plan(n_ids, batch_size, sort_by_length):
     return groups, [row_of[p] for p in range(len(idx))]
 
 
+def plan_pass(n_ids, seeds, pending, k, batch_size, sort_by_length):
+    """Pass k of synthesize_long(check=) over the chunks `pending` (chunk indices, ascending): they are grouped by ``_plan`` as a text
+    of their own would be -> [(the group's chunks, their seeds ``attempt_seeds(seeds[c], k)``)].  Host only."""
+    from .alignment import attempt_seeds
+    groups, _ = _plan([n_ids[c] for c in pending], batch_size, sort_by_length)
+    return [([pending[i] for i in g], [attempt_seeds(seeds[pending[i]], k) for i in g]) for g in groups]
+
+
+def settle_pass(flags, k, max_attempts):
+    """The rows of a group that are kept at attempt k, given their flags: those with flags 0, and every row at the last attempt"""
+    return [b for b, f in enumerate(flags) if f == 0 or k >= max_attempts - 1]
+
+
+def _run_passes(n_ids, seeds, batch_size, sort_by_length, max_attempts, decode, keep):
+    """The retry loop.  ``decode(k, chunks, seeds) -> (flags, handle)`` decodes one group and reports one int of flags per row;
+    ``keep(handle, rows, chunks, seeds)`` speaks the kept rows.  Kept rows are numbered through the passes and groups in the order
+    they are kept -> (passes: per pass a list of (chunks, seeds, kept rows), attempts per chunk, order: position -> row)."""
+    n = len(n_ids)
+    pending, attempts, row_of, passes = list(range(n)), [0] * n, {}, []
+    for k in range(max_attempts):
+        if not pending:
+            break
+        this, again = [], []
+        for chunks, s in plan_pass(n_ids, seeds, pending, k, batch_size, sort_by_length):
+            flags, handle = decode(k, chunks, s)
+            kept = settle_pass(flags, k, max_attempts)
+            for b in kept:
+                attempts[chunks[b]] = k
+                row_of[chunks[b]] = len(row_of)
+            again += [c for b, c in enumerate(chunks) if b not in kept]
+            if kept:
+                keep(handle, kept, chunks, s)
+            this.append((chunks, s, kept))
+        passes.append(this)
+        pending = sorted(again)
+    return passes, attempts, [row_of[p] for p in range(n)]
+
+
+def plan_retries(n_ids, seeds, flag_table, batch_size=8, sort_by_length=True, max_attempts=1):
+    """What synthesize_long(check=, max_attempts=) does, given the flags beforehand: ``flag_table[k][i]`` are the flags chunk i gets
+    at attempt k (0: it passes).  Chunk i is spoken with its first attempt that passes, or else with its last.  Returns (passes,
+    attempts, order): per pass the list of its groups as (chunks, seeds, rows of the group that are kept); the attempt every chunk is
+    spoken with; and position -> row of the join, the kept rows numbered through the passes and groups.  Host only."""
+    return _run_passes(n_ids, seeds, int(batch_size), sort_by_length, int(max_attempts),
+                       lambda k, chunks, s: ([flag_table[k][c] for c in chunks], None), lambda *a: None)
+
+
 def _check_long_args(tacotron, waveglow, text, chunks, seed, seeds, batch_size, max_symbols, pause_ms, pauses_ms, fade_ms, rate):
     """Every check of synthesize_long that needs no device -> (chunks, ids per chunk, seeds, pauses in samples, fade in samples)"""
     who = "synthesize_long"
@@ -188,7 +238,7 @@ def _check_long_args(tacotron, waveglow, text, chunks, seed, seeds, batch_size, 
 
 def synthesize_long(tacotron, waveglow, text=None, *, chunks=None, seed=None, seeds=None, sigma=0.666, batch_size=8,
                     max_symbols=MAX_SYMBOLS, sort_by_length=True, denoiser=None, strength=0.1, trimmer=None, pause_ms=PAUSE_MS,
-                    pauses_ms=None, fade_ms=FADE_MS, resampler=None, pcm16=False, sampling_rate=None):
+                    pauses_ms=None, fade_ms=FADE_MS, resampler=None, pcm16=False, sampling_rate=None, check=None, max_attempts=1):
     """Text of any length -> one utterance in HBM.  ``text`` is split by ``split_text(text, max_symbols)``, or ``chunks`` (strings)
     are taken as they are; each goes through ``text_to_sequence``.  Groups of ``batch_size`` chunks (8 is the largest batch on the
     fp16 decode path) run ``tacotron.inference_batch(seeds=)`` -> ``waveglow.infer_batch(sigma, seeds=)`` -> ``denoiser.denoise_batch
@@ -214,11 +264,39 @@ def synthesize_long(tacotron, waveglow, text=None, *, chunks=None, seed=None, se
 
     The host reads one thing per group from the device: the output lengths, once, directly behind ``inference_batch`` (whose
     decode loop polls the device anyway) - ``infer_batch`` and ``denoise_batch`` size their launches by them.  Behind that read
-    nothing in the group's chain, in the join or in the resampling reads the device; the lengths the trimmer finds never leave it."""
+    nothing in the group's chain, in the join or in the resampling reads the device; the lengths the trimmer finds never leave it.
+
+    ``check`` (an ``alignment.AlignmentCheck``) looks at every chunk's attention path before it is spoken, and ``max_attempts`` > 1
+    decodes a flagged chunk again.  Pass k = 0, 1, ... takes the chunks not yet accepted, groups them as above (``plan_pass``),
+    decodes each group with ``inference_batch(seeds=attempt_seeds(s_i, k))`` and runs ``alignment.alignment_report`` on the
+    alignments; the group's one read-back then brings the flags along with the output lengths (one stacked tensor, one copy).  A
+    chunk whose flags are 0 is accepted, and at pass max_attempts - 1 every remaining one is: chunk i is spoken with its first
+    attempt that passes, or else with its last, through ``infer_batch -> denoise_batch -> trim_batch`` under the same attempt seed -
+    the audio of its solo chain under ``attempt_seeds(s_i, a_i)`` up to float rounding, whatever batch_size and sort_by_length.
+    A group with a rejected row pays one index copy of its accepted rows' mel before the vocoder
+    (``mel_post[:, :, :N'].index_select(0, rows)``, N' their longest) and small ones of their lengths, seeds and report; a group
+    without one pays nothing.  The join takes the accepted rows of all passes through ``order``.  A check's ``max_frames=None``
+    is the decoder's max_decoder_steps.  The result is then LongFormChecked: LongForm's five fields (``truncated`` as before, of the
+    attempt kept), and
+      flags      int32 [n] on the device: the kept attempt's flags (0: it passed; alignment.FLAG_NAMES)
+      attempts   int64 [n] on the host: the attempt chunk i is spoken with
+      stats      int32 [n, 8], focus float64 [n], durations int32 [n, longest chunk's ids] on the device: the kept attempt's
+                 report in the text's order (durations: frames per symbol, before trimming and resampling)
+    ``check=None`` with ``max_attempts=1`` is the call without either: the same launches, a LongForm."""
     from . import audio as A
     rate = sampling_rate if sampling_rate is not None else (resampler.orig_rate if resampler is not None else SAMPLING_RATE)
     chunks, ids, seeds, gaps, fade = _check_long_args(tacotron, waveglow, text, chunks, seed, seeds, batch_size, max_symbols, pause_ms,
                                                       pauses_ms, fade_ms, rate)
+    if isinstance(max_attempts, bool) or not isinstance(max_attempts, int) or max_attempts < 1:
+        raise ValueError("synthesize_long: max_attempts must be an integer >= 1, got %r" % (max_attempts,))
+    if check is not None:
+        from .alignment import AlignmentCheck
+        if not isinstance(check, AlignmentCheck):
+            raise _lib.T2SError("synthesize_long: check must be an alignment.AlignmentCheck, got a %s" % type(check).__name__)
+        return _synthesize_checked(tacotron, waveglow, chunks, ids, seeds, gaps, fade, sigma, int(batch_size), sort_by_length, denoiser,
+                                   strength, trimmer, resampler, pcm16, check, max_attempts)
+    if max_attempts != 1:
+        raise ValueError("synthesize_long: max_attempts = %d needs a check to decide who goes again" % max_attempts)
     n = len(chunks)
     n_ids = [len(s) for s in ids]
     groups, order = _plan(n_ids, int(batch_size), sort_by_length)
@@ -251,3 +329,63 @@ def synthesize_long(tacotron, waveglow, text=None, *, chunks=None, seed=None, se
     if pcm16:
         audio = A.to_pcm16(audio)                               # (zeros behind `length` already)
     return LongForm(audio, length, offsets, chunks, truncated)
+
+
+def _synthesize_checked(tacotron, waveglow, chunks, ids, seeds, gaps, fade, sigma, batch_size, sort_by_length, denoiser, strength,
+                        trimmer, resampler, pcm16, check, max_attempts):
+    """synthesize_long with a check: the passes of ``_run_passes``, each group decoded, reported, read once and its kept rows spoken"""
+    from . import audio as A
+    from .alignment import alignment_report
+    n = len(chunks)
+    n_ids = [len(s) for s in ids]
+    dev = next(waveglow.parameters()).device
+    stride = int(waveglow.upsample.stride[0])
+    T_cap = int(tacotron.decoder.max_decoder_steps)
+    check = check.with_max_frames(T_cap)
+    batches, kept_reports = [], []
+
+    def decode(k, group, group_seeds):
+        B, T = len(group), max(n_ids[c] for c in group)
+        padded = torch.zeros(B, T, dtype=torch.int64)
+        for b, c in enumerate(group):
+            padded[b, :n_ids[c]] = torch.from_numpy(ids[c]).to(torch.int64)
+        in_lens = torch.tensor([n_ids[c] for c in group])
+        s_d = A._to_device(torch.tensor(group_seeds, dtype=torch.int64), dev)
+        out = tacotron.inference_batch(A._to_device(padded, dev), in_lens, seeds=s_d)
+        rep = alignment_report(out[3], in_lens, out[4], check)
+        both = torch.stack([out[4], rep.flags.to(torch.int64)]).cpu()          # the group's one read-back: lengths and flags
+        return both[1].tolist(), (out[1], out[4], both[0], s_d, rep)
+
+    def keep(handle, rows, group, group_seeds):
+        mel, olen, frames, s_d, rep = handle
+        fields = (rep.flags, rep.stats, rep.focus, rep.durations)
+        if len(rows) < len(group):                              # rejected rows leave the batch: index copies, no arithmetic
+            idx = A._to_device(torch.tensor(rows, dtype=torch.int64), dev)
+            frames = frames[rows]
+            mel = mel[:, :, :int(frames.max())].index_select(0, idx)
+            olen, s_d = olen.index_select(0, idx), s_d.index_select(0, idx)
+            fields = tuple(f.index_select(0, idx) for f in fields)
+        wav, wav_lens = waveglow.infer_batch(mel, frames, sigma=sigma, seeds=s_d)
+        if denoiser is not None:
+            wav, wav_lens = denoiser.denoise_batch(wav, frames * stride, strength)
+        if trimmer is not None:
+            wav, wav_lens = trimmer.trim_batch(wav, wav_lens)
+        batches.append((wav, wav_lens))
+        kept_reports.append((olen == T_cap,) + fields)
+
+    _, attempts, order = _run_passes(n_ids, seeds, batch_size, sort_by_length, max_attempts, decode, keep)
+    audio, length, offsets = A.join_batches(batches, order=order, pauses=gaps, fade=fade)
+    order_d = A._to_device(torch.tensor(order, dtype=torch.int64), dev)
+    truncated, flags, stats, focus = (torch.cat([r[i] for r in kept_reports])[order_d] for i in range(4))
+    durations = torch.zeros(n, max(n_ids), dtype=torch.int32, device=dev)
+    r0 = 0
+    for r in kept_reports:                                      # (a group's durations are as wide as its longest chunk)
+        durations[r0:r0 + r[4].size(0), :r[4].size(1)] = r[4]
+        r0 += r[4].size(0)
+    durations = durations[order_d]
+    if resampler is not None:
+        audio, length = resampler.resample_batch(audio, length)
+    if pcm16:
+        audio = A.to_pcm16(audio)
+    return LongFormChecked(audio, length, offsets, chunks, truncated, flags, torch.tensor(attempts, dtype=torch.int64), stats, focus,
+                           durations)
