@@ -1124,6 +1124,70 @@ int t2s_align_stats(const int* pos, const float* peak, const unsigned char* bad,
                     const int* out_len, int max_frames, int skip_max, int back_max, int stall_max, int end_slack, double min_focus,
                     int* stats, double* focus, int* dur, int* flags, void* stream);
 
+/* ---- speaking rate and symbol timestamps: a mel warped in time, and the spans of its symbols (additive to ABI version 4;
+ *      rate.py warp_mel / symbol_spans, longform.py synthesize_long_timed(speed=, timestamps=); csrc/warp.hip) ----
+ * Speed is changed between the two models: stretching the frame axis of the mel and letting the vocoder make more or fewer samples
+ * keeps pitch and timbre.  The same cumulative map that drives the warp tells where every symbol went.  Everything discrete is an
+ * exact integer, so it cannot differ between the device, a restatement, a solo run and a batch.
+ * Stretch per frame
+ *  - Q = 2^20.  Source frame f of entry b has a stretch s[b,f]: an int64 count of output frames in units of 1 / Q.
+ *  - One rate r for all, or one per entry: s = rint(Q / r), formed on the host in double.  It reaches the map kernel by value
+ *    (`stretch`) or as int64 [B] in device memory (`stretches`, each value clamped to [Q / 8, 8 Q] on the device).
+ *  - Per-symbol rates: `rates` f32 [B, T_in] and `path` int32 [B, F] (t2s_align_rows' pos).
+ *      s[b,f] = rint(Q / clamp((double)rates[b, path[b,f]], min_rate, max_rate)), formed on the device, ties to even.
+ *    A frame is at rate 1 (s = Q) when its path value lies outside [0, S_b), S_b = clamp(in_len[b], 1, T_in), or when its table value
+ *    is a NaN.  +-inf, 0 and negative values clamp.  min_rate <= max_rate are host doubles within [1 / 8, 8].
+ * Cumulative map
+ *  - F_b = clamp(lengths[b], 0, F).
+ *  - c[b,0] = 0, c[b,f+1] = c[b,f] + s[b,f] for f < F_b: int64 [B, F + 1].  Entries behind F_b repeat c[b,F_b].
+ * Output length
+ *  - F'_b = 0 if F_b = 0, else clamp((c[b,F_b] + Q / 2) >> 20, 1, cap).
+ * Output frame j < F'_b
+ *  - p = (2j + 1) Q, and m[f] = c[f] + c[f+1] is the doubled centre of source frame f.  Let f be the largest index with m[f] <= p.
+ *  - If there is none, out = x[0].  If f >= F_b - 1, out = x[F_b - 1].
+ *  - Otherwise a = (double)(p - m[f]) / (double)(m[f+1] - m[f]).  If a == 0, out = x[f] bit for bit and x[f+1] is not read.  Else
+ *    out = (T)((1 - a) (double)x[f] + a (double)x[f+1]): one double expression, rounded once to the mel's type T (f32 or f16).
+ *  - The same f and a serve all C channels.  Columns F'_b .. cap - 1 of the output are +0.
+ *  So rate 1 is the identity bit for bit (f = j, a = 0), any stretches give np.interp(j + 0.5, m / 2Q, x) with end clamping, and a
+ *  uniform rate r reads the coordinate (j + 0.5) r - 0.5.
+ * Symbol spans
+ *  - For symbol k < S_b: first is the smallest and last the largest f < F_b with path[b,f] == k; t0 = c[first], t1 = c[last + 1].
+ *  - In vocoder samples u = (t hop) >> 20.  With a monotone path neighbouring spans abut exactly.
+ *  - Then, for both ends, each step where its argument is given: u = clamp(u - trim_start[b], 0, trim_len[b]); u += offsets[b];
+ *    u = min((u up) / down, total), an integer floor division.
+ *  - spans int64 [B, T_in, 2] holds (-1, -1) for a symbol no frame attends to, for a symbol at or behind S_b and for every symbol of
+ *    an entry with F_b = 0.
+ *  t2s_warp_block: host only, the frames of one step of the map's walk and the output frames of one tile of the gather (256).
+ *  t2s_warp_map: one workgroup per entry walks the frames in blocks with a carried int64 sum, for any F.  lengths, in_len: int32 [B] in
+ *    device memory or NULL (F, T_in).  path rows are ld_path >= F apart, rates rows ld_rates >= T_in apart; rates needs path, takes
+ *    stretch = Q and no stretches.  Writes, each where its pointer is given (one at least): cum = c; out_len int32 [B] = F'_b;
+ *    first_last int32 [B, T_in, 2] = (first, last), (-1, -1) for a symbol without a frame (needs path; the call sets it to -1 on the
+ *    same stream before the kernel, whose integer minima and maxima are exact in any order).
+ *  t2s_warp_gather: x is B entries of C rows of F frames, rows ld_row >= F and entries ld_entry >= C ld_row elements apart (a view of a
+ *    wider mel goes in as it is), src_kind 1 f32 or 2 f16; cum and out_len are the map's.  Writes all of out [B, C, cap], dense and of
+ *    x's type.  The grid runs over tiles of output frames x entries x groups of 16 channels; a column finds its f once, by bisection
+ *    in the entry's row of c, and stores are coalesced along time.
+ *  t2s_warp_spans: one thread per (entry, symbol).  trim_start and trim_end (both or neither: a Trimmer's cut points, trim_len =
+ *    trim_end - trim_start), offsets, total_dev (int64 [1], in the place of `total`): int64 in device memory or NULL; no step is
+ *    skipped by a value, up = down = 1 and total = 2^62 leave u as it is.
+ * Memory safety: every length is clamped; a path value is used only inside [0, S_b); the gather's f lies in [0, F_b) whatever cum
+ * holds, samples at or behind F_b are never read and a store goes only inside [0, cap); first / last are used only inside [0, F_b).
+ * T2S_EINVAL, with nothing launched: a NULL x, cum (gather, spans), out_len (gather), out, first_last (spans) or spans; no output at
+ *    all (map); rates or first_last without path, rates with stretches or with stretch != Q; a pointer that is not aligned to its
+ *    element (int64 arrays to 8); B < 1 or > 65535; F < 1 or > 2^30; cap < 1; C < 1; T_in < 1 where a path or spans are asked for;
+ *    B T_in > 2^31 - 1; ld_path < F, ld_rates < T_in, ld_row < F, ld_entry < C ld_row; a src_kind other than 1 or 2; x overlapping
+ *    out; a stretch outside [Q / 8, 8 Q]; min_rate or max_rate outside [1 / 8, 8] or min_rate > max_rate; hop, up or down outside
+ *    [1, 2^20]; F hop > 2^39; total < 0; one of trim_start and trim_end without the other. */
+int t2s_warp_block(void);
+int t2s_warp_map(const int* lengths, int B, int F, long stretch, const long* stretches, const int* path, long ld_path,
+                 const float* rates, long ld_rates, const int* in_len, int T_in, double min_rate, double max_rate, int cap, long* cum,
+                 int* out_len, int* first_last, void* stream);
+int t2s_warp_gather(const void* x, int src_kind, int B, int C, int F, long ld_row, long ld_entry, const int* lengths, const long* cum,
+                    const int* out_len, void* out, int cap, void* stream);
+int t2s_warp_spans(const long* cum, const int* first_last, int B, int F, int T_in, const int* in_len, const int* lengths, int hop,
+                   const long* trim_start, const long* trim_end, const long* offsets, long up, long down, long total,
+                   const long* total_dev, long* spans, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,11 @@ SIGNATURES = {
     "t2s_align_rows": [c_vp, c_int, c_int, c_int, c_int, c_long, c_long, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "t2s_align_stats": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_double, c_vp, c_vp,
                         c_vp, c_vp, c_vp],
+    "t2s_warp_block": [],
+    "t2s_warp_map": [c_vp, c_int, c_int, c_long, c_vp, c_vp, c_long, c_vp, c_long, c_vp, c_int, c_double, c_double, c_int, c_vp, c_vp,
+                     c_vp, c_vp],
+    "t2s_warp_gather": [c_vp, c_int, c_int, c_int, c_int, c_long, c_long, c_vp, c_vp, c_vp, c_vp, c_int, c_vp],
+    "t2s_warp_spans": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_long, c_long, c_long, c_vp, c_vp, c_vp],
     "t2s_bernoulli_mask_keyed": [c_vp, c_int, c_int, c_int, c_vp, c_float, c_vp],
     "t2s_noise_tile": [],
     "t2s_wg_noise_keyed": [c_vp, c_int, c_int, c_long, c_vp, c_float, c_vp, c_vp],

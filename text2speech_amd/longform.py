@@ -7,7 +7,9 @@ are joined - sentence after sentence, a pause between them, a short ramp at ever
 (csrc/join.hip), optionally resampled and quantised.  Every chunk has a seed of its own (``chunk_seeds``), so its audio is a
 function of (seed, its index, its text) and not of the batch it was computed in.  ``synthesize_long`` is the chain; with
 ``check=`` it looks at every chunk's attention path first (``alignment.alignment_report``) and, with ``max_attempts`` > 1, decodes a
-flagged chunk again under another seed (``plan_pass`` / ``settle_pass`` / ``plan_retries`` are the host planning)."""
+flagged chunk again under another seed (``plan_pass`` / ``settle_pass`` / ``plan_retries`` are the host planning).
+``synthesize_long_timed`` is the same chain with a speaking rate and the time of every symbol (``rate.warp_mel``,
+``rate.symbol_spans``)."""
 import collections
 
 import torch
@@ -26,6 +28,9 @@ CLAUSE_END = ",;:ÔºåÔºõÔºö„ÄÅ"                 # , ; : and the full-width Ôºå Ôº
 
 LongForm = collections.namedtuple("LongForm", "audio length offsets chunks truncated")
 LongFormChecked = collections.namedtuple("LongFormChecked", LongForm._fields + ("flags", "attempts", "stats", "focus", "durations"))
+# ... and with timestamps=True: the same fields, then spans
+LongFormTimed = collections.namedtuple("LongFormTimed", LongForm._fields + ("spans",))
+LongFormCheckedTimed = collections.namedtuple("LongFormCheckedTimed", LongFormChecked._fields + ("spans",))
 
 
 def mix(x):
@@ -282,19 +287,55 @@ def synthesize_long(tacotron, waveglow, text=None, *, chunks=None, seed=None, se
       attempts   int64 [n] on the host: the attempt chunk i is spoken with
       stats      int32 [n, 8], focus float64 [n], durations int32 [n, longest chunk's ids] on the device: the kept attempt's
                  report in the text's order (durations: frames per symbol, before trimming and resampling)
-    ``check=None`` with ``max_attempts=1`` is the call without either: the same launches, a LongForm."""
+    ``check=None`` with ``max_attempts=1`` is the call without either: the same launches, a LongForm.
+
+    ``synthesize_long_timed`` is this call with two more keywords, ``speed`` and ``timestamps``: another speaking rate, and the
+    time of every symbol in the audio returned.  The keyword list of this one is pinned by a test, so they live there."""
+    return synthesize_long_timed(tacotron, waveglow, text, chunks=chunks, seed=seed, seeds=seeds, sigma=sigma, batch_size=batch_size,
+                                 max_symbols=max_symbols, sort_by_length=sort_by_length, denoiser=denoiser, strength=strength,
+                                 trimmer=trimmer, pause_ms=pause_ms, pauses_ms=pauses_ms, fade_ms=fade_ms, resampler=resampler,
+                                 pcm16=pcm16, sampling_rate=sampling_rate, check=check, max_attempts=max_attempts)
+
+
+def synthesize_long_timed(tacotron, waveglow, text=None, *, chunks=None, seed=None, seeds=None, sigma=0.666, batch_size=8,
+                          max_symbols=MAX_SYMBOLS, sort_by_length=True, denoiser=None, strength=0.1, trimmer=None, pause_ms=PAUSE_MS,
+                          pauses_ms=None, fade_ms=FADE_MS, resampler=None, pcm16=False, sampling_rate=None, check=None, max_attempts=1,
+                          speed=None, timestamps=False):
+    """``synthesize_long`` - every argument, default and result of it, see there - at another speaking rate and with the time of
+    every symbol.  Without the two keywords it is that call: the same launches, the same result.
+
+    ``speed`` (a float in [1 / 8, 8], or one per chunk; 2 is twice as fast) changes the speaking rate without touching pitch: every
+    group's ``mel_post`` goes through ``rate.warp_mel`` between ``inference_batch`` and ``infer_batch``, and the vocoder makes
+    ``rate.warped_length(frames_i, speed_i)`` frames of samples for chunk i - an integer the host forms from the frames the group's
+    one read-back already brought, so there is no second one.  Chunk i's samples are then those of
+    ``infer(warp_mel(inference(ids_i, seed=s_i).mel_post, None, speed_i).mel, sigma, seed=s_i)`` up to float rounding.  ``speed=1.0``
+    gives the audio of ``speed=None`` bit for bit (the warp is the identity); ``speed=None`` issues the launches it always did.
+    Per-symbol rates are reachable through ``warp_mel`` only.
+
+    ``timestamps=True`` adds ``spans`` to the result (a LongFormTimed, or a LongFormCheckedTimed with a check): int64
+    [n, longest chunk's ids, 2] on the device, in the text's order - symbol k of chunk i sounds in
+    ``audio[0, spans[i, k, 0] : spans[i, k, 1]]``, in samples of the audio RETURNED: behind the warp, the trimmer's cut, the join's
+    offsets and the resampler's ratio (``rate.symbol_spans`` states each step); (-1, -1) for a symbol no frame attends to and for
+    the padding behind a chunk's ids.  It runs ``alignment_report`` for the path where no check does, asks ``trimmer.bounds_batch``
+    for the cut points ``trim_batch`` will use (the same input, the same decision: one more energy pass), and without a ``speed``
+    runs the warp at rate 1.  Nothing more is read back.  The other fields keep their meaning; ``durations`` stays the frames per
+    symbol of the decoded mel."""
     from . import audio as A
     rate = sampling_rate if sampling_rate is not None else (resampler.orig_rate if resampler is not None else SAMPLING_RATE)
     chunks, ids, seeds, gaps, fade = _check_long_args(tacotron, waveglow, text, chunks, seed, seeds, batch_size, max_symbols, pause_ms,
                                                       pauses_ms, fade_ms, rate)
     if isinstance(max_attempts, bool) or not isinstance(max_attempts, int) or max_attempts < 1:
         raise ValueError("synthesize_long: max_attempts must be an integer >= 1, got %r" % (max_attempts,))
+    speeds = _check_speed(speed, len(chunks))
+    timing = _Timing(waveglow, trimmer, resampler) if timestamps else None
+    if speeds is None and timestamps:
+        speeds = [1.0] * len(chunks)
     if check is not None:
         from .alignment import AlignmentCheck
         if not isinstance(check, AlignmentCheck):
             raise _lib.T2SError("synthesize_long: check must be an alignment.AlignmentCheck, got a %s" % type(check).__name__)
         return _synthesize_checked(tacotron, waveglow, chunks, ids, seeds, gaps, fade, sigma, int(batch_size), sort_by_length, denoiser,
-                                   strength, trimmer, resampler, pcm16, check, max_attempts)
+                                   strength, trimmer, resampler, pcm16, check, max_attempts, speeds, timing)
     if max_attempts != 1:
         raise ValueError("synthesize_long: max_attempts = %d needs a check to decide who goes again" % max_attempts)
     n = len(chunks)
@@ -313,26 +354,98 @@ def synthesize_long(tacotron, waveglow, text=None, *, chunks=None, seed=None, se
             padded[b, :n_ids[c]] = torch.from_numpy(ids[c]).to(torch.int64)
         s_d = seeds_d[r0:r0 + B]
         r0 += B
-        out = tacotron.inference_batch(A._to_device(padded, dev), torch.tensor([n_ids[c] for c in g]), seeds=s_d)
+        in_lens = torch.tensor([n_ids[c] for c in g])
+        out = tacotron.inference_batch(A._to_device(padded, dev), in_lens, seeds=s_d)
+        path = None
+        if timing is not None:
+            from .alignment import alignment_report
+            path = alignment_report(out[3], in_lens, out[4]).path
         frames = out[4].cpu()                                   # the group's one read-back
         flags.append(out[4] == T_cap)
-        wav, wav_lens = waveglow.infer_batch(out[1], frames, sigma=sigma, seeds=s_d)
+        mel, src_frames, warped = out[1], frames, None
+        if speeds is not None:                                  # (frames: from here on the vocoder's, the warped ones)
+            from .rate import warp_mel
+            warped = warp_mel(mel, src_frames, [speeds[c] for c in g], path=path, input_lengths=in_lens, n_symbols=T)
+            mel, frames = warped.mel, warped.host_lengths
+        wav, wav_lens = waveglow.infer_batch(mel, frames, sigma=sigma, seeds=s_d)
         if denoiser is not None:
             wav, wav_lens = denoiser.denoise_batch(wav, frames * stride, strength)
+        if timing is not None:
+            timing.add(warped, in_lens, src_frames, wav, wav_lens)
         if trimmer is not None:
             wav, wav_lens = trimmer.trim_batch(wav, wav_lens)
         batches.append((wav, wav_lens))
     audio, length, offsets = A.join_batches(batches, order=order, pauses=gaps, fade=fade)
-    truncated = torch.cat(flags)[A._to_device(torch.tensor(order, dtype=torch.int64), dev)]
+    order_d = A._to_device(torch.tensor(order, dtype=torch.int64), dev)
+    truncated = torch.cat(flags)[order_d]
     if resampler is not None:
         audio, length = resampler.resample_batch(audio, length)
     if pcm16:
         audio = A.to_pcm16(audio)                               # (zeros behind `length` already)
+    if timing is not None:
+        return LongFormTimed(audio, length, offsets, chunks, truncated, timing.spans(order, order_d, offsets, length, max(n_ids)))
     return LongForm(audio, length, offsets, chunks, truncated)
 
 
+def _check_speed(speed, n):
+    """synthesize_long_timed's ``speed`` -> None, or one rate per chunk (each checked by ``rate.stretch_q``)"""
+    if speed is None:
+        return None
+    from .rate import stretch_q
+    if isinstance(speed, (list, tuple)):
+        if len(speed) != n:
+            raise ValueError("synthesize_long_timed: speed holds %d values, there are %d chunks" % (len(speed), n))
+        speeds = list(speed)
+    else:
+        speeds = [speed] * n
+    for v in speeds:
+        stretch_q(v)
+    return [float(v) for v in speeds]
+
+
+class _Timing:
+    """What synthesize_long_timed(timestamps=True) keeps of every spoken group, and the spans it makes of that behind the join."""
+
+    def __init__(self, waveglow, trimmer, resampler):
+        self.hop = int(waveglow.upsample.stride[0])
+        self.trimmer = trimmer
+        self.ratio = (1, 1) if resampler is None else (resampler.up, resampler.down)
+        self.groups = []
+
+    def add(self, warped, in_lens, src_frames, wav, wav_lens):
+        """behind the denoiser, in front of the trimmer: its cut points are found here, on what trim_batch will see.  Without a
+        trimmer the cut is (0, the samples made): a chunk's last span then ends with its audio, not in the pause behind it (the
+        warped length is rounded to whole frames, the map is not)"""
+        if self.trimmer is None:
+            made = wav_lens.to(torch.int64)
+            bounds = (torch.zeros_like(made), made)
+        else:
+            bounds = self.trimmer.bounds_batch(wav, wav_lens)
+        self.groups.append((warped, in_lens, src_frames, bounds))
+
+    def spans(self, order, order_d, offsets, length, T_max):
+        """int64 [n, T_max, 2] in the text's order; rows are numbered through the groups as the join numbers them"""
+        from . import audio as A
+        from .rate import symbol_spans
+        n = len(order)
+        dev = offsets.device
+        pos = [0] * n
+        for p, r in enumerate(order):
+            pos[r] = p
+        by_row = offsets.index_select(0, A._to_device(torch.tensor(pos, dtype=torch.int64), dev))
+        out = torch.full((n, T_max, 2), -1, dtype=torch.int64, device=dev)
+        r0 = 0
+        for warped, in_lens, src_frames, bounds in self.groups:
+            B = in_lens.numel()
+            sp = symbol_spans(warped, None, in_lens, src_frames, self.hop, trim_bounds=bounds, offsets=by_row[r0:r0 + B],
+                              ratio=self.ratio, total=length)
+            out[r0:r0 + B, :sp.size(1)] = sp
+            r0 += B
+        return out[order_d]
+
+
 def _synthesize_checked(tacotron, waveglow, chunks, ids, seeds, gaps, fade, sigma, batch_size, sort_by_length, denoiser, strength,
-                        trimmer, resampler, pcm16, check, max_attempts):
+                        trimmer, resampler, pcm16, check, max_attempts, speeds=None, timing=None):
     """synthesize_long with a check: the passes of ``_run_passes``, each group decoded, reported, read once and its kept rows spoken"""
     from . import audio as A
     from .alignment import alignment_report
@@ -354,20 +467,31 @@ def _synthesize_checked(tacotron, waveglow, chunks, ids, seeds, gaps, fade, sigm
         out = tacotron.inference_batch(A._to_device(padded, dev), in_lens, seeds=s_d)
         rep = alignment_report(out[3], in_lens, out[4], check)
         both = torch.stack([out[4], rep.flags.to(torch.int64)]).cpu()          # the group's one read-back: lengths and flags
-        return both[1].tolist(), (out[1], out[4], both[0], s_d, rep)
+        return both[1].tolist(), (out[1], out[4], both[0], s_d, rep, in_lens)
 
     def keep(handle, rows, group, group_seeds):
-        mel, olen, frames, s_d, rep = handle
+        mel, olen, frames, s_d, rep, in_lens = handle
         fields = (rep.flags, rep.stats, rep.focus, rep.durations)
+        path = rep.path
         if len(rows) < len(group):                              # rejected rows leave the batch: index copies, no arithmetic
             idx = A._to_device(torch.tensor(rows, dtype=torch.int64), dev)
             frames = frames[rows]
             mel = mel[:, :, :int(frames.max())].index_select(0, idx)
             olen, s_d = olen.index_select(0, idx), s_d.index_select(0, idx)
             fields = tuple(f.index_select(0, idx) for f in fields)
+            if speeds is not None:
+                in_lens, path = in_lens[rows], path.index_select(0, idx)
+        src_frames, warped = frames, None
+        if speeds is not None:                                  # (frames: from here on the vocoder's, the warped ones)
+            from .rate import warp_mel
+            warped = warp_mel(mel, src_frames, [speeds[group[b]] for b in rows], path=path if timing is not None else None,
+                              input_lengths=in_lens, n_symbols=rep.durations.size(1))
+            mel, frames = warped.mel, warped.host_lengths
         wav, wav_lens = waveglow.infer_batch(mel, frames, sigma=sigma, seeds=s_d)
         if denoiser is not None:
             wav, wav_lens = denoiser.denoise_batch(wav, frames * stride, strength)
+        if timing is not None:
+            timing.add(warped, in_lens, src_frames, wav, wav_lens)
         if trimmer is not None:
             wav, wav_lens = trimmer.trim_batch(wav, wav_lens)
         batches.append((wav, wav_lens))
@@ -387,5 +511,8 @@ def _synthesize_checked(tacotron, waveglow, chunks, ids, seeds, gaps, fade, sigm
         audio, length = resampler.resample_batch(audio, length)
     if pcm16:
         audio = A.to_pcm16(audio)
-    return LongFormChecked(audio, length, offsets, chunks, truncated, flags, torch.tensor(attempts, dtype=torch.int64), stats, focus,
-                           durations)
+    result = LongFormChecked(audio, length, offsets, chunks, truncated, flags, torch.tensor(attempts, dtype=torch.int64), stats, focus,
+                             durations)
+    if timing is not None:
+        return LongFormCheckedTimed(*result, timing.spans(order, order_d, offsets, length, max(n_ids)))
+    return result
