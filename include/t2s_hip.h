@@ -981,6 +981,55 @@ int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* tab
                     double rescaling_max, double peak_floor, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths,
                     void* stream);
 
+/* ---- programme loudness in device memory (additive to ABI version 4; audio.py Loudness, data.py PcmPool.loudness /
+ *      normalize_loudness, longform.py normalize_long) ----
+ * ITU-R BS.1770-4 / EBU R128 gated loudness of a mono row, and the gain that brings it to a target.  For a row of n samples x at
+ * the integer rate fs (an int16 row counts as x / 32768, an f16 row is widened exactly; the filter starts from zero state at the
+ * row's first sample, and only the row's own samples enter):
+ *  - K-weighting: y = the shelf biquad, then the high-pass biquad, applied to x in double (transposed direct form II).  The caller
+ *    forms the coefficients in double; audio.py loudness_coefficients states the formulas.
+ *  - Hops: h = floor(fs / 10 + 1 / 2) samples; z_k = the sum of y^2 over samples k h .. (k + 1) h - 1, for k < n / h (an incomplete
+ *    trailing hop is dropped).  Blocks: ms_j = (((z_j + z_(j+1)) + z_(j+2)) + z_(j+3)) / (4 h), j < J = max(0, n / h - 3).
+ *  - Gates, linear, in double: A = { j : ms_j > gate_abs }, R = { j in A : ms_j > 0.1 mean(A) }, ms = mean(R),
+ *    lufs = -0.691 + 10 log10(ms).  (gate_abs = 10^((-70 + 0.691) / 10) is the standard's.)
+ *  - Gain: g = sqrt(target_T / ms), target_T = 10^((target_lufs + 0.691) / 10) formed by the caller; peak = max |x| (in the units
+ *    above; a non-finite sample counts as +inf); with peak_limit > 0 and peak g > peak_limit: g = peak_limit / peak.
+ *  - flags: 1 J = 0 (the row is shorter than 0.4 s); 2 A is empty (J > 0, every sample finite); 4 the peak limit set the gain;
+ *    8 a non-finite sample lies inside the row (|A| and |R| then count as 0).  Any of 1, 2, 8 gives g = 1, ms = 0, lufs = -inf
+ *    (NaN with 8).
+ * The filter runs in parallel along the row (csrc/loudness.hip): segments of t2s_loud_segment() samples, 256 to a tile, every
+ * one counted from the row's first sample, and every sum in one order that depends on n and h alone; no atomics.  A row's
+ * statistics and samples are therefore the same bits alone and at any place of any batch or pool, at any alignment, whatever lies
+ * behind its length.  Tables are int64 in device memory and any value in them is safe, as t2s_trim_gather's: a negative src_count
+ * or a src_start outside [0, src_len) counts as no samples, a src_count that runs past src_len is cut there; nothing outside
+ * [0, src_len) is read.  src_kind 0 int16, 1 f32, 2 f16; no alignment beyond the element (tables, coef, scratch, stats: 8 bytes).
+ *  t2s_loud_tile / t2s_loud_segment: host only, the samples of one workgroup's tile (8192) and of one lane's segment (32).
+ *  t2s_loud_scratch: host only, the doubles of scratch t2s_loud_measure needs for n_rows rows of at most max_count samples
+ *    (-1 for arguments t2s_loud_measure would refuse).
+ *  t2s_loud_measure: table [n_rows][2] = (src_start, src_count); a row longer than max_count is cut there.  fs_hop is h.
+ *    coef: 160 doubles in device memory - [0, 5) b0 b1 b2 a1 a2 of the shelf, [5, 10) of the high-pass, [10, 16) unused,
+ *    [16 + 16 k, 32 + 16 k) for k = 0 .. 7 the 4 x 4 row-major matrix P_S^(2^k), [144, 160) P_tile = P_S^256, where P_S = M^S and M
+ *    is the zero-input map of one sample on the state (s1, s2 of the shelf, s1, s2 of the high-pass).  stats: double [n_rows][4] =
+ *    (ms, lufs, peak, g); counts: int32 [n_rows][4] = (J, |A|, |R|, flags).  Four launches on the stream; nothing waits across
+ *    workgroups.  peak_limit <= 0: none.
+ *  t2s_loud_apply: table [n_rows][4] = (src_start, src_count, dst_start, dst_cap), as t2s_trim_gather's; g is stats[r][3].
+ *    int16 -> int16 stores rint((double)x g), ties to even, saturated; f32 / f16 -> f32 stores (float)((double)x g); g = 1 copies
+ *    bit for bit (f16 widened exactly).  The row gets min(n, dst_cap) samples at dst_start and +0 behind them up to dst_cap; dst_cap
+ *    is cut to max_out and to what dst holds; out_lengths: NULL or int32 [n_rows] that receives the count.
+ *  T2S_EINVAL, with nothing launched: a NULL src, table, coef, scratch, stats, counts or dst; src_len, dst_len, n_rows, max_count or
+ *    max_out <= 0; n_rows > 65535; max_count > 2^31 - 1; max_out > 2^40; fs_hop outside [400, 38400] or below the segment; a kind
+ *    out of range or a pair other than int16 -> int16, f32 -> f32, f16 -> f32; gate_abs negative or not finite; target_T not
+ *    finite or <= 0; peak_limit NaN; a misaligned table, coef, scratch, stats or counts; scratch_len below t2s_loud_scratch's;
+ *    overlapping src and dst. */
+int t2s_loud_tile(void);
+int t2s_loud_segment(void);
+long t2s_loud_scratch(int n_rows, long max_count);
+int t2s_loud_measure(const void* src, int src_kind, long src_len, const long* table, int n_rows, long max_count, int fs_hop,
+                     const double* coef, double* scratch, long scratch_len, double gate_abs, double target_T, double peak_limit,
+                     double* stats, int* counts, void* stream);
+int t2s_loud_apply(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* stats, void* dst,
+                   int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream);
+
 /* ---- joining the rows of padded batches into one utterance in device memory (additive to ABI version 4; audio.py join_batches,
  *      longform.py synthesize_long) ----
  * Sentence after sentence, a pause of zeros between them, a linear ramp at the joints; no length is read by the host.

@@ -15,13 +15,16 @@ for bit, and zeros behind its end.  from_pcm16 is to_pcm1
 clips are text2speech_amd/data.py.  Resampler converts the sample rate of a batch (forward / resample_batch) or, through
 PcmPool.resample, of a pool: scipy.signal.resample_poly's polyphase filter with every sum in double precision (csrc/resample.hip).
 Trimmer cuts leading and trailing silence (librosa.effects.trim's decision) and rescales to a peak, on a batch (forward /
-trim_batch / bounds_batch) or, through PcmPool.rescale_trim, on a pool (csrc/trim.hip).  join_batches / join_batch turn the padded
+trim_batch / bounds_batch) or, through PcmPool.rescale_trim, on a pool (csrc/trim.hip).  Loudness measures BS.1770 / EBU R128 gated
+loudness and brings rows to a target level (measure_batch / normalize_batch; PcmPool.loudness / normalize_loudness for a pool;
+csrc/loudness.hip).  join_batches / join_batch turn the padded
 rows of such batches back into one utterance - pauses between them, ramps at the joints - with no length read back (csrc/join.hip;
 text2speech_amd/longform.py is the chain around it).
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
 window); the mel filterbank restates librosa.filters.mel's defaults (Slaney scale, area normalisation) because librosa is
 an unpinned dependency that this image does not have.
 """
+import collections
 import operator
 
 import numpy as np
@@ -31,8 +34,8 @@ from scipy.signal import get_window
 from . import _lib
 
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
-           "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer", "join_batches",
-           "join_batch"]
+           "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer", "Loudness", "LoudnessReport",
+           "loudness_coefficients", "join_batches", "join_batch"]
 
 
 def _ru(a, b):
@@ -265,6 +268,39 @@ TRIM_MAX_FRAME = 8192          # the library's limit on frame_length (include/t2
 _KINDS = {torch.int16: 0, torch.float32: 1, torch.float16: 2}
 
 
+def _float_rows(audio, lengths, what, int16_way="PcmPool.rescale_trim"):
+    """audio [N], [B, N] or [B, 1, N] f32 / f16 in HBM and lengths (None: every row whole) -> (flat view over the rows, B, N,
+    ldx, int64 lengths on the device clamped to [0, N]); nothing is read back"""
+    _need_cuda(audio, what)
+    if audio.dim() not in (1, 2, 3) or (audio.dim() == 3 and audio.size(1) != 1) or audio.numel() == 0:
+        raise _lib.T2SError("%s: audio must be [N], [B, N] or [B, 1, N] and hold samples, got %s" % (what, tuple(audio.shape)))
+    x = audio.detach()
+    if x.dtype not in (torch.float32, torch.float16):
+        raise _lib.T2SError("%s: expected float32 or float16, got %s (int16 pools go through %s)" % (what, x.dtype, int16_way))
+    N = x.size(-1)
+    x = x.reshape(-1, N)
+    B = x.size(0)
+    if B > 65535:
+        raise _lib.T2SError("%s: %d rows, the most is 65535" % (what, B))
+    if x.stride(1) != 1 or (B > 1 and x.stride(0) < N):
+        x = x.contiguous()
+    ldx = x.stride(0) if B > 1 else N
+    if lengths is None:
+        lens_d = torch.full((B,), N, dtype=torch.int64, device=x.device)
+    else:
+        try:
+            lens = torch.as_tensor(lengths)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise _lib.T2SError("%s: lengths must be a tensor or a sequence of integers (%s)" % (what, e))
+        if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+            raise _lib.T2SError("%s: lengths must be integers, got %s" % (what, lens.dtype))
+        if lens.dim() != 1 or lens.numel() != B:
+            raise _lib.T2SError("%s: lengths has shape %s, the batch holds %d entries" % (what, tuple(lens.shape), B))
+        lens = lens.detach().to(torch.int64).clamp(0, N)
+        lens_d = lens if lens.is_cuda else _to_device(lens.contiguous(), x.device)
+    return torch.as_strided(x, ((B - 1) * ldx + N,), (1,)), B, N, ldx, lens_d
+
+
 class Trimmer:
     """Silence trimming and peak rescaling in HBM (csrc/trim.hip): librosa.effects.trim(x, top_db, frame_length, hop_length)'s cut
     points - the first and the last frame whose RMS lies less than top_db below the loudest frame's, frames centred with
@@ -330,36 +366,7 @@ class Trimmer:
                   _lib.current_stream())
 
     def _rows(self, audio, lengths, what):
-        """audio [N], [B, N] or [B, 1, N] f32 / f16 in HBM and lengths (None: every row whole) -> (flat view over the rows, B, N,
-        ldx, int64 lengths on the device clamped to [0, N]); nothing is read back"""
-        _need_cuda(audio, what)
-        if audio.dim() not in (1, 2, 3) or (audio.dim() == 3 and audio.size(1) != 1) or audio.numel() == 0:
-            raise _lib.T2SError("%s: audio must be [N], [B, N] or [B, 1, N] and hold samples, got %s" % (what, tuple(audio.shape)))
-        x = audio.detach()
-        if x.dtype not in (torch.float32, torch.float16):
-            raise _lib.T2SError("%s: expected float32 or float16, got %s (int16 pools go through PcmPool.rescale_trim)" % (what, x.dtype))
-        N = x.size(-1)
-        x = x.reshape(-1, N)
-        B = x.size(0)
-        if B > 65535:
-            raise _lib.T2SError("%s: %d rows, the most is 65535" % (what, B))
-        if x.stride(1) != 1 or (B > 1 and x.stride(0) < N):
-            x = x.contiguous()
-        ldx = x.stride(0) if B > 1 else N
-        if lengths is None:
-            lens_d = torch.full((B,), N, dtype=torch.int64, device=x.device)
-        else:
-            try:
-                lens = torch.as_tensor(lengths)
-            except (TypeError, ValueError, RuntimeError) as e:
-                raise _lib.T2SError("%s: lengths must be a tensor or a sequence of integers (%s)" % (what, e))
-            if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
-                raise _lib.T2SError("%s: lengths must be integers, got %s" % (what, lens.dtype))
-            if lens.dim() != 1 or lens.numel() != B:
-                raise _lib.T2SError("%s: lengths has shape %s, the batch holds %d entries" % (what, tuple(lens.shape), B))
-            lens = lens.detach().to(torch.int64).clamp(0, N)
-            lens_d = lens if lens.is_cuda else _to_device(lens.contiguous(), x.device)
-        return torch.as_strided(x, ((B - 1) * ldx + N,), (1,)), B, N, ldx, lens_d
+        return _float_rows(audio, lengths, what)
 
     def _batch_bounds(self, flat, B, N, ldx, lens_d):
         """(stats, bounds, row index) of a padded batch; the tables are built on the device"""
@@ -414,6 +421,153 @@ class Trimmer:
             raise _lib.T2SError("%s: audio must be [B, T] or [B, 1, T], got %s" % (what, tuple(getattr(audio, "shape", ()))))
         out, out_lens = self._trim(audio, lengths, what)
         return out.view(audio.shape), out_lens
+
+
+LOUD_MIN_RATE, LOUD_MAX_RATE = 4000, 384000    # the library's limits on the hop, as rates (include/t2s_hip.h)
+LOUD_GATE_ABS = 10.0 ** ((-70.0 + 0.691) / 10.0)       # BS.1770's absolute gate, as a mean square
+LOUD_FLAG_SHORT, LOUD_FLAG_SILENT, LOUD_FLAG_PEAK, LOUD_FLAG_NONFINITE = 1, 2, 4, 8
+
+LoudnessReport = collections.namedtuple("LoudnessReport", "ms lufs peak gain blocks flags")
+
+
+def loudness_coefficients(sampling_rate):
+    """BS.1770's K-weighting at any rate, float64: ((b, a) of the shelf, (b, a) of the high-pass), a[0] = 1.  The analogue
+    prototypes behind the standard's 48 kHz table, bilinear-transformed: at 48 000 Hz these give the printed table to 1e-15."""
+    fs = float(sampling_rate)
+
+    def stage(f0, Q, shelf_db):
+        K = np.tan(np.pi * f0 / fs)
+        a0 = 1.0 + K / Q + K * K
+        a = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+        if shelf_db is None:
+            return np.array([1.0, -2.0, 1.0]), a
+        Vh = 10.0 ** (shelf_db / 20.0)
+        Vb = Vh ** 0.4996667741545416
+        return np.array([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0]), a
+
+    return stage(1681.974450955533, 0.7071752369554196, 3.999843853973347), stage(38.13547087602444, 0.5003270373238773, None)
+
+
+def loudness_hop(sampling_rate):
+    """samples of BS.1770's 100 ms hop at an integer rate: floor(fs / 10 + 1 / 2)"""
+    return (2 * int(sampling_rate) + 10) // 20
+
+
+def loudness_table(sampling_rate, segment, lanes=256):
+    """t2s_loud_measure's `coef` (include/t2s_hip.h states the layout), float64 [160]: both biquads, then the zero-input map of
+    `segment` samples on the cascade's state raised to 2^k, k = 0 .. log2(lanes) - 1, then that of a tile of lanes segments."""
+    (b1, a1), (b2, a2) = loudness_coefficients(sampling_rate)
+    # one sample with x = 0: y1 = s0; s0' = -a1[1] y1 + s1; s1' = -a1[2] y1; y2 = b2[0] y1 + s2; s2' = b2[1] y1 - a2[1] y2 + s3; ...
+    M = np.zeros((4, 4))
+    M[0] = [-a1[1], 1.0, 0.0, 0.0]
+    M[1] = [-a1[2], 0.0, 0.0, 0.0]
+    M[2] = [b2[1] - a2[1] * b2[0], 0.0, -a2[1], 1.0]
+    M[3] = [b2[2] - a2[2] * b2[0], 0.0, -a2[2], 0.0]
+    steps = int(lanes).bit_length() - 1
+    assert 1 << steps == lanes and steps == 8
+    out = np.zeros(16 + 16 * steps + 16)
+    out[0:5] = [b1[0], b1[1], b1[2], a1[1], a1[2]]
+    out[5:10] = [b2[0], b2[1], b2[2], a2[1], a2[2]]
+    P = np.linalg.matrix_power(M, int(segment))
+    for k in range(steps):
+        out[16 + 16 * k:32 + 16 * k] = P.reshape(-1)
+        P = P @ P
+    out[16 + 16 * steps:] = P.reshape(-1)
+    return out
+
+
+class Loudness:
+    """Programme loudness in HBM (csrc/loudness.hip): ITU-R BS.1770-4 / EBU R128 gated loudness of every row - K-weighting, 400 ms
+    blocks on a 100 ms hop, the absolute gate at -70 LUFS and the relative one 10 LU below the gated mean - and the gain that brings
+    the row to `target_lufs` (-23: EBU R128's programme level, a convention), limited so that no sample exceeds `peak_limit` (a
+    sample peak, not a true peak; None: no limit).  include/t2s_hip.h states the arithmetic.  A row shorter than 0.4 s, one with
+    nothing above -70 LUFS and one with a non-finite sample are flagged (LOUD_FLAG_*) and left as they are (gain 1).  Mono; nothing
+    is read back, everything runs on the caller's current stream, and a row's result does not depend on the batch around it."""
+
+    def __init__(self, sampling_rate, target_lufs=-23.0, peak_limit=None, device="cuda"):
+        T2SError = _lib.T2SError
+        try:
+            whole = not isinstance(sampling_rate, bool) and int(sampling_rate) == sampling_rate
+        except (TypeError, ValueError, OverflowError):
+            whole = False
+        if not whole or not LOUD_MIN_RATE <= sampling_rate <= LOUD_MAX_RATE:
+            raise T2SError("Loudness: sampling_rate must be an integer in [%d, %d], got %r" % (LOUD_MIN_RATE, LOUD_MAX_RATE, sampling_rate))
+        if not isinstance(target_lufs, (int, float, np.floating, np.integer)) or not np.isfinite(target_lufs):
+            raise T2SError("Loudness: target_lufs must be finite, got %r" % (target_lufs,))
+        if peak_limit is not None and (not isinstance(peak_limit, (int, float, np.floating, np.integer)) or not np.isfinite(peak_limit)
+                                       or peak_limit <= 0):
+            raise T2SError("Loudness: peak_limit must be None or finite and positive, got %r" % (peak_limit,))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise T2SError("Loudness: the filter table lives in HBM (cuda); there is no CPU path")
+        self.sampling_rate, self.hop = int(sampling_rate), loudness_hop(sampling_rate)
+        self.target_lufs = float(target_lufs)
+        self.target_T = 10.0 ** ((self.target_lufs + 0.691) / 10.0)
+        self.peak_limit = None if peak_limit is None else float(peak_limit)
+        self.device = dev
+        self._coef = None           # uploaded by the first call (1.3 KB, a blocking copy): constructing needs no device
+
+    def _table(self, dev):
+        if self._coef is None or self._coef.device != dev:
+            lib = _lib.load()
+            # (blocking, so that the table is whole before any stream can read it)
+            self._coef = torch.from_numpy(loudness_table(self.sampling_rate, lib.t2s_loud_segment(),
+                                                         lib.t2s_loud_tile() // lib.t2s_loud_segment())).to(dev)
+        return self._coef
+
+    def _measure(self, src, table2, n_rows, max_count, stats=None, counts=None):
+        """t2s_loud_measure over `table2` (device int64 [n_rows, 2]: src_start, src_count) of the flat device tensor `src`
+        -> (stats float64 [n_rows, 4], counts int32 [n_rows, 4])"""
+        p, dev = _lib.ptr, src.device
+        max_count = max(1, int(max_count))
+        if max_count > 2 ** 31 - 1:
+            raise _lib.T2SError("Loudness: a row of %d samples, the most is 2^31 - 1" % max_count)
+        if stats is None:
+            stats = torch.empty(n_rows, 4, dtype=torch.float64, device=dev)
+            counts = torch.empty(n_rows, 4, dtype=torch.int32, device=dev)
+        need = _lib.load().t2s_loud_scratch(n_rows, max_count)
+        scratch = torch.empty(need, dtype=torch.float64, device=dev)
+        _lib.call("t2s_loud_measure", p(src), _KINDS[src.dtype], src.numel(), p(table2), n_rows, max_count, self.hop, p(self._table(dev)),
+                  p(scratch), need, LOUD_GATE_ABS, self.target_T, self.peak_limit or 0.0, p(stats), p(counts), _lib.current_stream())
+        return stats, counts
+
+    @staticmethod
+    def _apply(src, table4, n_rows, stats, dst, max_out):
+        p = _lib.ptr
+        _lib.call("t2s_loud_apply", p(src), _KINDS[src.dtype], src.numel(), p(table4), n_rows, p(stats), p(dst), _KINDS[dst.dtype],
+                  dst.numel(), max(1, int(max_out)), None, _lib.current_stream())
+
+    @staticmethod
+    def _report(stats, counts):
+        return LoudnessReport(stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3], counts[:, 0], counts[:, 3])
+
+    def _batch(self, audio, lengths, what):
+        flat, B, N, ldx, lens_d = _float_rows(audio, lengths, what, "PcmPool.normalize_loudness")
+        rows = torch.arange(B, dtype=torch.int64, device=flat.device)
+        stats, counts = self._measure(flat, torch.stack([rows * ldx, lens_d], 1).contiguous(), B, N)
+        return flat, B, N, ldx, lens_d, rows, stats, counts
+
+    def measure_batch(self, audio, lengths=None):
+        """audio [N], [B, N] or [B, 1, N] float32 or float16 in HBM (strided rows are taken where they are) and lengths [B] (the
+        int32 device tensor infer_batch / trim_batch return is used where it is; None: whole rows) -> LoudnessReport(ms, lufs, peak,
+        gain float64 [B], blocks, flags int32 [B]), all on the device.  Samples at and behind lengths[b] are never read."""
+        return self._report(*self._batch(audio, lengths, "Loudness.measure_batch")[-2:])
+
+    def normalize_batch(self, audio, lengths=None):
+        """-> (audio float32 of audio's shape, lengths as given): entry b's first lengths[b] samples times its gain - forward(
+        audio[b, :lengths[b]])'s bit for bit - and zeros behind them.  A flagged row is copied.  Nothing is read back."""
+        what = "Loudness.normalize_batch"
+        flat, B, N, ldx, lens_d, rows, stats, _ = self._batch(audio, lengths, what)
+        out = torch.empty(B, N, dtype=torch.float32, device=flat.device)
+        table4 = torch.stack([rows * ldx, lens_d, rows * N, torch.full_like(rows, N)], 1).contiguous()
+        self._apply(flat, table4, B, stats, out.view(-1), N)
+        return out.view(audio.shape), lengths
+
+    def forward(self, audio):
+        """One clip [N] / [1, N], or whole rows [B, N] / [B, 1, N], float32 or float16 in HBM -> float32 of the same shape"""
+        return self.normalize_batch(audio, None)[0]
+
+    __call__ = forward
 
 
 JOIN_MAX_FADE = 65536          # the library's limit on the fade (include/t2s_hip.h)

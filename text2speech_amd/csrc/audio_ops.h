@@ -83,6 +83,45 @@ hipError_t t2s_launch_trim_bounds(const TrimBoundsArgs& a, int n_rows, hipStream
 // (src_kind, dst_kind): int16 -> int16, f32 -> f32, f16 -> f32
 hipError_t t2s_launch_trim_gather(const TrimGatherArgs& a, int src_kind, int dst_kind, int n_rows, hipStream_t s);
 
+// programme loudness (loudness.hip): K-weighting by tiles and segments, hop energies, both gates, the gain; then the gain applied
+#define T2S_LOUD_SEGMENT 32                     // consecutive samples one lane filters
+#define T2S_LOUD_TILE (256 * T2S_LOUD_SEGMENT)  // consecutive samples of one row per workgroup
+#define T2S_LOUD_MIN_HOP 400                    // 100 ms at 4 kHz
+#define T2S_LOUD_MAX_HOP 38400                  // ... at 384 kHz
+#define T2S_LOUD_HOPS (T2S_LOUD_TILE / T2S_LOUD_MIN_HOP + 2)    // the most hops that touch one tile
+#define T2S_LOUD_TILE_DOUBLES (5 + T2S_LOUD_HOPS)               // scratch per tile: state [4], peak, the hops' parts
+#define T2S_LOUD_COEF_POW 16                    // coef: [0, 10) the biquads, [16, 144) P_S^(2^k) k = 0 .. 7, [144, 160) P_tile
+#define T2S_LOUD_COEF_TILE (T2S_LOUD_COEF_POW + 8 * 16)
+#define T2S_LOUD_COEF_DOUBLES (T2S_LOUD_COEF_TILE + 16)
+struct LoudMeasureArgs {
+    const void* src;            // int16 / f32 / f16 [src_len]
+    long src_len;
+    const long* table;          // [n_rows][2] int64 on the device: src_start, src_count
+    int n_rows, h;
+    long max_count;             // samples the grid and the scratch cover per row; a longer row is cut there
+    long tiles_max, hops_max;   // ceil(max_count / tile), max_count / T2S_LOUD_MIN_HOP + 1
+    long row_doubles;           // tiles_max T2S_LOUD_TILE_DOUBLES + hops_max: the scratch of one row
+    const double* coef;         // [T2S_LOUD_COEF_DOUBLES]
+    double* scratch;            // [n_rows][row_doubles]
+    double unit;                // 1 / 32768 for int16 sources, 1 for floats
+    double gate_abs, target_T, peak_limit;
+    double* stats;              // [n_rows][4]: ms, lufs, peak, g
+    int* counts;                // [n_rows][4]: J, |A|, |R|, flags
+};
+struct LoudApplyArgs {
+    const void* src;
+    long src_len;
+    const long* table;          // [n_rows][4] int64 on the device: src_start, src_count, dst_start, dst_cap
+    const double* stats;        // the measure's
+    void* dst;                  // int16 / f32 [dst_len]
+    long dst_len;
+    long max_out;               // outputs the grid covers per row
+    int* out_lengths;           // [n_rows] int32 or NULL
+};
+hipError_t t2s_launch_loud_measure(const LoudMeasureArgs& a, int src_kind, hipStream_t s);
+// (src_kind, dst_kind): int16 -> int16, f32 -> f32, f16 -> f32
+hipError_t t2s_launch_loud_apply(const LoudApplyArgs& a, int src_kind, int dst_kind, int n_rows, hipStream_t s);
+
 // joining the rows of padded batches into one utterance (join.hip): the scan of the lengths, then one gather per source batch
 #define T2S_JOIN_TILE 2048                      // samples of one row per workgroup of the gather
 struct JoinOffsetsArgs {

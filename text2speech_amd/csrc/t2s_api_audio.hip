@@ -237,6 +237,54 @@ int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* tab
     return T2S_OK;
 }
 
+// ---- programme loudness: loudness.hip's measure (four launches) and apply -----------------------------------------------------------
+int t2s_loud_tile(void) { return T2S_LOUD_TILE; }
+int t2s_loud_segment(void) { return T2S_LOUD_SEGMENT; }
+
+long t2s_loud_scratch(int n_rows, long max_count) {
+    if (n_rows <= 0 || n_rows > 65535 || max_count <= 0 || max_count > 0x7fffffffL) return -1;
+    const long tiles = (max_count + T2S_LOUD_TILE - 1) / T2S_LOUD_TILE, hops = max_count / T2S_LOUD_MIN_HOP + 1;
+    return (long)n_rows * (tiles * T2S_LOUD_TILE_DOUBLES + hops);
+}
+
+int t2s_loud_measure(const void* src, int src_kind, long src_len, const long* table, int n_rows, long max_count, int fs_hop,
+                     const double* coef, double* scratch, long scratch_len, double gate_abs, double target_T, double peak_limit,
+                     double* stats, int* counts, void* stream) {
+    // (a comparison with NaN is false, the subtraction is NaN for an infinity)
+    if (!src || !table || !coef || !scratch || !stats || !counts || !al8(table) || !al8(coef) || !al8(scratch) || !al8(stats) ||
+        ((uintptr_t)counts & 3) || src_kind < 0 || src_kind > 2 || src_len <= 0 || n_rows <= 0 || n_rows > 65535 || max_count <= 0 ||
+        max_count > 0x7fffffffL || fs_hop < T2S_LOUD_MIN_HOP || fs_hop > T2S_LOUD_MAX_HOP || T2S_LOUD_SEGMENT > fs_hop ||
+        !finite_nonneg(gate_abs) || !(target_T > 0.0) || target_T - target_T != 0.0 || peak_limit != peak_limit ||
+        scratch_len < t2s_loud_scratch(n_rows, max_count))
+        return T2S_EINVAL;
+    LoudMeasureArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.src_len = src_len; a.table = table; a.n_rows = n_rows; a.h = fs_hop; a.max_count = max_count;
+    a.tiles_max = (max_count + T2S_LOUD_TILE - 1) / T2S_LOUD_TILE; a.hops_max = max_count / T2S_LOUD_MIN_HOP + 1;
+    a.row_doubles = a.tiles_max * T2S_LOUD_TILE_DOUBLES + a.hops_max;
+    a.coef = coef; a.scratch = scratch; a.unit = src_kind == 0 ? 1.0 / 32768.0 : 1.0;
+    a.gate_abs = gate_abs; a.target_T = target_T; a.peak_limit = peak_limit > 0.0 ? peak_limit : 0.0; a.stats = stats; a.counts = counts;
+    T2S_CHECK_HIP(t2s_launch_loud_measure(a, src_kind, (hipStream_t)stream));
+    return T2S_OK;
+}
+
+int t2s_loud_apply(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* stats, void* dst,
+                   int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream) {
+    if (!src || !table || !stats || !dst || !al8(table) || !al8(stats) || src_kind < 0 || src_kind > 2 ||
+        dst_kind != (src_kind == 0 ? 0 : 1) || src_len <= 0 || dst_len <= 0 || n_rows <= 0 || n_rows > 65535 || max_out <= 0 ||
+        max_out > (1L << 40))
+        return T2S_EINVAL;
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)src_len * (src_kind == 1 ? 4 : 2);
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)dst_len * (dst_kind == 1 ? 4 : 2);
+    if (s0 < d1 && d0 < s1) return T2S_EINVAL;                  // never in place
+    LoudApplyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = src; a.src_len = src_len; a.table = table; a.stats = stats; a.dst = dst; a.dst_len = dst_len; a.max_out = max_out;
+    a.out_lengths = out_lengths;
+    T2S_CHECK_HIP(t2s_launch_loud_apply(a, src_kind, dst_kind, n_rows, (hipStream_t)stream));
+    return T2S_OK;
+}
+
 // ---- joining the rows of padded batches into one utterance: join.hip's two kernels --------------------------------------------------
 int t2s_join_tile(void) { return T2S_JOIN_TILE; }
 

@@ -4,6 +4,7 @@ a list of clip indices into the tensors `WaveGlow.forward` / `Tacotron.forward` 
   PcmPool(clips, sampling_rate)                 the clips back to back in one int16 device tensor; .from_wav_files(paths, rate);
                                                 .resample(new_rate) / from_wav_files(..., resample=True): rate conversion in HBM;
                                                 .rescale_trim(rescaling_max, top_db): the reference's peak rescaling and silence trim
+                                                .loudness() / .normalize_loudness(target_lufs): BS.1770 gated loudness per clip
   Mel2SampBatch(pool, segment_length, ...)      waveglow/mel2samp.py:60-105 (Mel2Samp.__getitem__ + the default collate): (mel, audio)
   TextMelBatch(pool, sequences, ...)            utils/data_utils.py:46-150 (TextMelLoader + TextMelCollate) and Tacotron.parse_batch
 
@@ -22,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import Resampler, TacotronSTFT, Trimmer, _pcm16_gather, _to_device
+from .audio import (LOUD_FLAG_NONFINITE, LOUD_FLAG_SHORT, LOUD_FLAG_SILENT, Loudness, Resampler, TacotronSTFT, Trimmer, _pcm16_gather,
+                    _to_device)
 
 __all__ = ["PcmPool", "Mel2SampBatch", "TextMelBatch", "gather_width"]
 
@@ -137,6 +139,49 @@ class PcmPool:
             sl = slice(r0, min(n, r0 + chunk))
             tr._gather(self.pcm, table4[sl], sl.stop - r0, None if bounds_d is None else bounds_d[sl], stats[sl], pool.pcm,
                        int(pool.lengths[sl].max()))
+        return pool
+
+    def _loudness(self, target_lufs, peak_limit):
+        """(Loudness, stats float64 [n, 4], counts int32 [n, 4]) of every clip, 65535 rows a launch"""
+        ld = Loudness(self.sampling_rate, target_lufs, peak_limit, device=self.pcm.device)
+        n, dev, chunk = len(self), self.pcm.device, 65535
+        stats = torch.empty(n, 4, dtype=torch.float64, device=dev)
+        counts = torch.empty(n, 4, dtype=torch.int32, device=dev)
+        table2 = _to_device(torch.stack([self.offsets, self.lengths], 1).contiguous(), dev)
+        for r0 in range(0, n, chunk):
+            sl = slice(r0, min(n, r0 + chunk))
+            ld._measure(self.pcm, table2[sl], sl.stop - r0, int(self.lengths[sl].max()), stats[sl], counts[sl])
+        return ld, stats, counts
+
+    def loudness(self, target_lufs=-23.0):
+        """BS.1770 / EBU R128 gated loudness of every clip (audio.Loudness states the rule; a sample counts as x / 32768):
+        LoudnessReport(ms, lufs, peak, gain, blocks, flags), one entry per clip, on the device; `gain` is what brings the clip to
+        target_lufs.  Nothing is read back."""
+        _, stats, counts = self._loudness(target_lufs, None)
+        return Loudness._report(stats, counts)
+
+    def normalize_loudness(self, target_lufs=-23.0, peak_limit=32767 / 32768, allow_unmeasured=False):
+        """Every clip brought to target_lufs, as a new pool at the same rate with the same lengths, int16 to int16 in HBM:
+        rint(x gain), ties to even, saturated; the gain is cut so that the clip's largest sample stays within peak_limit (of full
+        scale; None: no limit).  A clip shorter than 0.4 s, one with nothing above -70 LUFS and one that... cannot hold a non-finite
+        sample, being int16: the first two have no loudness, and raise T2SError naming the clips - unless allow_unmeasured is set: then
+        they are copied.  The flags are read back once (this is corpus preparation)."""
+        ld, stats, counts = self._loudness(target_lufs, peak_limit)
+        if not allow_unmeasured:
+            flags = counts[:, 3].cpu()
+            short = torch.nonzero(flags & LOUD_FLAG_SHORT).flatten().tolist()
+            silent = torch.nonzero(flags & LOUD_FLAG_SILENT).flatten().tolist()
+            bad = torch.nonzero(flags & LOUD_FLAG_NONFINITE).flatten().tolist()
+            if short or silent or bad:
+                raise T2SError("PcmPool.normalize_loudness: clips %s are shorter than 0.4 s, clips %s hold nothing above -70 LUFS, "
+                               "clips %s a non-finite sample: they have no loudness (allow_unmeasured=True copies them)"
+                               % (short, silent, bad))
+        n, dev, chunk = len(self), self.pcm.device, 65535
+        pool = self._of(torch.empty_like(self.pcm), self.lengths, self.sampling_rate)
+        table4 = _to_device(torch.stack([self.offsets, self.lengths, pool.offsets, pool.lengths], 1).contiguous(), dev)
+        for r0 in range(0, n, chunk):
+            sl = slice(r0, min(n, r0 + chunk))
+            ld._apply(self.pcm, table4[sl], sl.stop - r0, stats[sl], pool.pcm, int(self.lengths[sl].max()))
         return pool
 
     @classmethod

@@ -387,6 +387,20 @@ def synthesize_long_timed(tacotron, waveglow, text=None, *, chunks=None, seed=No
     return LongForm(audio, length, offsets, chunks, truncated)
 
 
+def normalize_long(result, loudness):
+    """A ``LongForm`` / ``LongFormChecked`` / ``LongFormTimed`` / ``LongFormCheckedTimed`` with its whole utterance brought to
+    ``loudness``'s target (``audio.Loudness.normalize_batch`` over ``result.audio`` and ``result.length``): the same tuple with
+    ``audio`` replaced.  One gain for the utterance moves no sample in time, so ``length``, ``offsets``, ``spans`` and every other
+    field are the objects given.  Nothing is read back.  An int16 result is refused: level first, quantise afterwards."""
+    if not isinstance(result, (LongForm, LongFormChecked, LongFormTimed, LongFormCheckedTimed)):
+        raise _lib.T2SError("normalize_long: expected a LongForm result of synthesize_long, got a %s" % type(result).__name__)
+    if not torch.is_tensor(result.audio) or result.audio.dtype != torch.float32:
+        raise _lib.T2SError("normalize_long: the audio is %s; synthesize with pcm16=False, normalize, then audio.to_pcm16"
+                            % getattr(result.audio, "dtype", type(result.audio).__name__))
+    audio, _ = loudness.normalize_batch(result.audio, result.length)
+    return result._replace(audio=audio)
+
+
 def _check_speed(speed, n):
     """synthesize_long_timed's ``speed`` -> None, or one rate per chunk (each checked by ``rate.stretch_q``)"""
     if speed is None:
