@@ -1030,6 +1030,57 @@ int t2s_loud_measure(const void* src, int src_kind, long src_len, const long* ta
 int t2s_loud_apply(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* stats, void* dst,
                    int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream);
 
+/* ---- true-peak metering and a look-ahead limiter in device memory (additive to ABI version 4; audio.py Limiter, data.py
+ *      PcmPool.true_peak / limit, longform.py limit_long) ----
+ * The last stage of a delivery chain: no output sample above a ceiling, the gain taken down smoothly around each peak only.  For a
+ * mono row of n samples x and a row gain g (gains[r], or 1 without gains; an int16 row counts as x / 32768, an f16 row is widened
+ * exactly), all in double: u[i] = (double)x[i] g inside the row and 0 outside it (zero extension, as t2s_resample_table's).
+ *  1. Envelope.  os is 1, 2 or 4; h is the caller's interpolation filter of n_taps = 2 half_width os + 1 taps, half = half_width os
+ *     (audio.py resample_filter(1, os, half_width, beta): scipy.signal.resample_poly(x, os, 1)'s own filter - the project's filter,
+ *     not the 48-tap table printed in BS.1770 Annex 2, which is one admissible interpolator among others).
+ *     y[m] = sum_j u[j] h[m - os j + half] over the j whose tap index lies in [0, n_taps), in ascending j, one fused multiply-add a
+ *     tap; p[i] = max(|u[i]|, max_(q < os) |y[os i + q]|).  With os = 1: p[i] = |u[i]| and h is not read.
+ *  2. Required gain.  r[i] = c / p[i] where p[i] > c, else 1; r = 1 outside the row.  c is the ceiling, a float32 value.
+ *  3. Look-ahead.  m[i] = min over |k| <= L of r[i + k], for every i (outside the row too).  0 <= L <= t2s_limit_max_lookahead().
+ *  4. Smoothing.  s[i] = min(r[i], sum_(k = -L .. L) w[k] m[i + k]), in ascending k, one fused multiply-add a tap.  w is the
+ *     caller's window of 2 L + 1 doubles, w[k] = 1/2 + 1/2 cos(pi k / (L + 1)) normalised; its sum in ascending order must not come
+ *     out below 1 (audio.py limiter_window sees to that), so that s is exactly 1 wherever every m in reach is 1: the kernels skip
+ *     the sum for a tile with no r below 1 in reach, and for a row with none at all.
+ *  5. Output.  o[i] = u[i] s[i].  f32 / f16 -> f32 stores (float)o[i]; int16 -> int16 stores rint(32768 o[i]), ties to even,
+ *     saturated.  The row gets min(n, dst_cap) samples at dst_start and +0 behind them up to dst_cap (cut to max_out and to what dst
+ *     holds), as t2s_loud_apply's.  With g = 1 a row with nothing over the ceiling is copied bit for bit.
+ *  6. stats: double [n_rows][4] = (true_peak = max p, sample_peak = max |u|, s_min = min s, 0); counts: int32 [n_rows][2] =
+ *     (the number of i with p[i] > c, flags).  flags: 1 the row was limited (the count is not 0); 8 a u inside the row is not
+ *     finite: then both peaks are +inf, s_min 1, the count 0, and t2s_limit_apply copies the row WITHOUT its gain.
+ * Guaranteed: |stored sample| <= c, exactly (s <= r <= c / |u| up to one rounding in double, and rounding to float32 is monotone
+ * and c is a float32; int16: |code| <= rint(32768 c)).  NOT guaranteed: the true peak of the output - a gain that moves changes
+ * the values between the samples; profiles/limiter_tests.md records what it came to.  o[i] depends on x over
+ * [i - R, i + R] only, R = 2 L + half_width.  Every sum has one order that depends on the row alone, min and max are order-free and
+ * tiles are counted from the row's first sample: a row's statistics and samples are the same bits alone and at any place of any
+ * batch or pool, at any alignment, whatever lies behind its length.  Tables are int64 in device memory and any value in them is
+ * safe, as t2s_loud_apply's; nothing outside [0, src_len) is read and stores land only inside [dst_start, dst_start + dst_cap).
+ *  t2s_limit_tile / t2s_limit_max_lookahead / t2s_limit_max_half_width: host only; the outputs of one workgroup (1024), the largest L
+ *    (1024) and the largest half_width (32).
+ *  t2s_limit_scratch: host only, the doubles of scratch t2s_limit_measure needs (four per tile; -1 for arguments it would refuse).
+ *  t2s_limit_measure: table [n_rows][2] = (src_start, src_count); a row longer than max_count is cut there.  Two launches.
+ *  t2s_limit_apply: table [n_rows][4] = (src_start, src_count, dst_start, dst_cap); counts are the measure call's; the envelope is
+ *    computed again, not stored in between.  out_lengths: NULL or int32 [n_rows] that receives the count.  One launch.
+ *  T2S_EINVAL, with nothing launched: a NULL src, table, h, w, scratch, stats, counts or dst; src_len, dst_len, n_rows, max_count or
+ *    max_out <= 0; n_rows > 65535; max_count > 2^31 - 1; max_out > 2^40; os not 1, 2 or 4; half_width outside [1, max];
+ *    n_taps != 2 half_width os + 1; L outside [0, max]; c not finite, <= 0 or not a float32 value; a kind out of range or a pair
+ *    other than int16 -> int16, f32 -> f32, f16 -> f32; a misaligned table, gains, h, w, scratch, stats (8 bytes) or counts (4);
+ *    scratch_len below t2s_limit_scratch's; overlapping src and dst. */
+int t2s_limit_tile(void);
+int t2s_limit_max_lookahead(void);
+int t2s_limit_max_half_width(void);
+long t2s_limit_scratch(int n_rows, long max_count);
+int t2s_limit_measure(const void* src, int src_kind, long src_len, const long* table, int n_rows, long max_count, const double* gains,
+                      const double* h, int n_taps, int os, int half_width, const double* w, int lookahead, double ceiling,
+                      double* scratch, long scratch_len, double* stats, int* counts, void* stream);
+int t2s_limit_apply(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* gains, const double* h,
+                    int n_taps, int os, int half_width, const double* w, int lookahead, double ceiling, const int* counts, void* dst,
+                    int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream);
+
 /* ---- joining the rows of padded batches into one utterance in device memory (additive to ABI version 4; audio.py join_batches,
  *      longform.py synthesize_long) ----
  * Sentence after sentence, a pause of zeros between them, a linear ramp at the joints; no length is read by the host.

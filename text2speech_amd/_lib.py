@@ -126,6 +126,14 @@ SIGNATURES = {
     "t2s_loud_measure": [c_vp, c_int, c_long, c_vp, c_int, c_long, c_int, c_vp, c_vp, c_long, c_double, c_double, c_double, c_vp, c_vp,
                          c_vp],
     "t2s_loud_apply": [c_vp, c_int, c_long, c_vp, c_int, c_vp, c_vp, c_int, c_long, c_long, c_vp, c_vp],
+    "t2s_limit_tile": [],
+    "t2s_limit_max_lookahead": [],
+    "t2s_limit_max_half_width": [],
+    "t2s_limit_scratch": [c_int, c_long],
+    "t2s_limit_measure": [c_vp, c_int, c_long, c_vp, c_int, c_long, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_double, c_vp, c_long,
+                          c_vp, c_vp, c_vp],
+    "t2s_limit_apply": [c_vp, c_int, c_long, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_double, c_vp, c_vp, c_int, c_long,
+                        c_long, c_vp, c_vp],
     "t2s_join_tile": [],
     "t2s_join_offsets": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_long, c_vp, c_vp, c_vp],
     "t2s_join_gather": [c_vp, c_int, c_int, c_int, c_long, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_long, c_vp],
@@ -186,7 +194,8 @@ for _n in ("t2s_wg_start", "t2s_wg_in_cond_gate_fold", "t2s_wg_res_only"):
     SIGNATURES[_n + "_h16_ragged"] = SIGNATURES[_n + "_h16"][:-1] + [c_vp, c_vp]
 del _n
 _RESTYPE = {"t2s_error_string": ctypes.c_char_p, "t2s_last_hip_error": ctypes.c_char_p,
-            "t2s_small_wgrad_scratch": ctypes.c_long, "t2s_taco_lstm_xbuf_bytes": ctypes.c_long, "t2s_loud_scratch": ctypes.c_long}
+            "t2s_small_wgrad_scratch": ctypes.c_long, "t2s_taco_lstm_xbuf_bytes": ctypes.c_long, "t2s_loud_scratch": ctypes.c_long,
+            "t2s_limit_scratch": ctypes.c_long}
 
 
 class T2SError(RuntimeError):

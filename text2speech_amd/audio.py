@@ -17,7 +17,8 @@ PcmPool.resample, of a pool: scipy.signal.resample_poly's polyphase filter with 
 Trimmer cuts leading and trailing silence (librosa.effects.trim's decision) and rescales to a peak, on a batch (forward /
 trim_batch / bounds_batch) or, through PcmPool.rescale_trim, on a pool (csrc/trim.hip).  Loudness measures BS.1770 / EBU R128 gated
 loudness and brings rows to a target level (measure_batch / normalize_batch; PcmPool.loudness / normalize_loudness for a pool;
-csrc/loudness.hip).  join_batches / join_batch turn the padded
+csrc/loudness.hip).  Limiter is the chain's last stage, a true-peak meter and look-ahead limiter (true_peak_batch / limit_batch;
+Loudness.normalize_limit_batch; PcmPool.true_peak / limit; csrc/limiter.hip).  join_batches / join_batch turn the padded
 rows of such batches back into one utterance - pauses between them, ramps at the joints - with no length read back (csrc/join.hip;
 text2speech_amd/longform.py is the chain around it).
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
@@ -35,7 +36,8 @@ from . import _lib
 
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
            "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer", "Loudness", "LoudnessReport",
-           "loudness_coefficients", "join_batches", "join_batch"]
+           "loudness_coefficients", "Limiter", "LimiterReport", "limiter_window", "LIMIT_FLAG_LIMITED", "LIMIT_FLAG_NONFINITE",
+           "LIMIT_MAX_LOOKAHEAD", "join_batches", "join_batch"]
 
 
 def _ru(a, b):
@@ -566,6 +568,203 @@ class Loudness:
     def forward(self, audio):
         """One clip [N] / [1, N], or whole rows [B, N] / [B, 1, N], float32 or float16 in HBM -> float32 of the same shape"""
         return self.normalize_batch(audio, None)[0]
+
+    __call__ = forward
+
+    def normalize_limit_batch(self, audio, lengths, limiter):
+        """normalize_batch with `limiter` (a Limiter at this rate) in place of a lowered row gain: measure_batch, then
+        limiter.limit_batch(audio, lengths, gain=report.gain) - the loudness gain and the limiter in one pass over the samples, no
+        buffer in between, nothing read back.  A row keeps its loudness gain and only the surroundings of its peaks are taken down
+        to the limiter's ceiling.  Construct this Loudness with peak_limit=None for that; a peak_limit still lowers the row gain
+        first.  -> (audio float32 of audio's shape, lengths as given)"""
+        if not isinstance(limiter, Limiter):
+            raise _lib.T2SError("Loudness.normalize_limit_batch: limiter must be an audio.Limiter, got a %s" % type(limiter).__name__)
+        if limiter.sampling_rate != self.sampling_rate:
+            raise _lib.T2SError("Loudness.normalize_limit_batch: the limiter is built for %d Hz, this Loudness for %d"
+                                % (limiter.sampling_rate, self.sampling_rate))
+        report = self.measure_batch(audio, lengths)
+        return limiter.limit_batch(audio, lengths, gain=report.gain)
+
+
+LIMIT_MAX_LOOKAHEAD = 1024     # the library's limits (include/t2s_hip.h)
+LIMIT_MAX_HALF_WIDTH = 32
+LIMIT_FLAG_LIMITED, LIMIT_FLAG_NONFINITE = 1, 8
+
+LimiterReport = collections.namedtuple("LimiterReport", "true_peak sample_peak min_gain limited flags")
+
+
+def limiter_window(lookahead):
+    """t2s_limit_measure's `w`, float64 [2 L + 1]: w[k] = 1/2 + 1/2 cos(pi k / (L + 1)) for k = -L .. L, normalised to sum 1 - and
+    the centre tap raised by the few ulps it may take for the sum in ASCENDING order, as the kernel adds it, to be no less than 1:
+    the smoothed gain is then exactly 1 wherever every minimum in reach is 1, which is what lets an untouched stretch keep its
+    bits."""
+    L = int(lookahead)
+    w = 0.5 + 0.5 * np.cos(np.pi * np.arange(-L, L + 1, dtype=np.float64) / (L + 1))
+    w = w / w.sum()
+
+    def asc():
+        acc = 0.0
+        for v in w:
+            acc += float(v)
+        return acc
+
+    while asc() < 1.0:
+        w[L] += max(1.0 - asc(), np.spacing(w[L]))
+    return w
+
+
+def _real(v):
+    return isinstance(v, (int, float, np.floating, np.integer)) and not isinstance(v, bool) and np.isfinite(v)
+
+
+class Limiter:
+    """A true-peak meter and look-ahead limiter in HBM (csrc/limiter.hip), the last stage of a delivery chain: resample first,
+    limit last at the delivery rate, then to_pcm16.  include/t2s_hip.h states the arithmetic: the row's envelope `oversample`
+    times oversampled with resample_filter(1, oversample, half_width, beta) - scipy.signal.resample_poly's own filter, the
+    project's interpolator, not BS.1770 Annex 2's printed 48-tap table, which is one admissible choice - the gain ceiling / peak
+    each sample needs, its minimum over +-lookahead samples, that smoothed by a normalised Hann window, and the row times the
+    result.  `ceiling` is 10^(ceiling_db / 20) rounded to float32; `lookahead` = round(sampling_rate lookahead_ms / 1000)
+    samples; an output sample depends on the input over +-`reach` = 2 lookahead + half_width samples only.  GUARANTEED: no output
+    sample exceeds `ceiling` in magnitude, exactly.  NOT guaranteed: the output's true peak - a moving gain changes the values
+    between the samples; at oversample=4 and the default look-ahead it came to about 1 + 2e-5 of the ceiling and less
+    (profiles/limiter_tests.md).  Mono; nothing is read back, everything runs on the caller's current stream, and a row's result
+    does not depend on the batch around it.  A row with a non-finite sample is flagged (LIMIT_FLAG_NONFINITE) and copied."""
+
+    def __init__(self, sampling_rate, ceiling_db=-1.0, lookahead_ms=1.5, oversample=4, half_width=10, beta=5.0, device="cuda"):
+        T2SError = _lib.T2SError
+        try:
+            whole = not isinstance(sampling_rate, bool) and int(sampling_rate) == sampling_rate
+        except (TypeError, ValueError, OverflowError):
+            whole = False
+        if not whole or sampling_rate < 1:
+            raise T2SError("Limiter: sampling_rate must be a positive integer, got %r" % (sampling_rate,))
+        if not _real(ceiling_db) or ceiling_db > 0:
+            raise T2SError("Limiter: ceiling_db must be finite and at most 0 (dB relative to full scale), got %r" % (ceiling_db,))
+        if not _real(lookahead_ms) or lookahead_ms < 0:
+            raise T2SError("Limiter: lookahead_ms must be finite and not negative, got %r" % (lookahead_ms,))
+        lookahead = int(round(int(sampling_rate) * float(lookahead_ms) / 1000.0))
+        if lookahead > LIMIT_MAX_LOOKAHEAD:
+            raise T2SError("Limiter: lookahead_ms = %r is %d samples at %d Hz, the most is %d"
+                           % (lookahead_ms, lookahead, sampling_rate, LIMIT_MAX_LOOKAHEAD))
+        if isinstance(oversample, bool) or oversample not in (1, 2, 4):
+            raise T2SError("Limiter: oversample must be 1, 2 or 4, got %r" % (oversample,))
+        if isinstance(half_width, bool) or not isinstance(half_width, (int, np.integer)) or not 1 <= half_width <= LIMIT_MAX_HALF_WIDTH:
+            raise T2SError("Limiter: half_width must be an integer in [1, %d], got %r" % (LIMIT_MAX_HALF_WIDTH, half_width))
+        if not _real(beta) or beta < 0:
+            raise T2SError("Limiter: beta must be finite and not negative, got %r" % (beta,))
+        ceiling = float(np.float32(10.0 ** (float(ceiling_db) / 20.0)))
+        if not ceiling > 0.0:
+            raise T2SError("Limiter: ceiling_db = %r gives a ceiling of 0 in float32" % (ceiling_db,))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise T2SError("Limiter: the filter and the window live in HBM (cuda); there is no CPU path")
+        self.sampling_rate = int(sampling_rate)
+        self.ceiling_db, self.ceiling = float(ceiling_db), ceiling
+        self.lookahead, self.oversample, self.half_width, self.beta = lookahead, int(oversample), int(half_width), float(beta)
+        self.reach = 2 * lookahead + self.half_width
+        self.n_taps = 2 * self.half_width * self.oversample + 1
+        self.device = dev
+        self._tables = None         # uploaded by the first call (a blocking copy): constructing needs no device
+
+    def _hw(self, dev):
+        """(h, w) on the device: the interpolation filter and the smoothing window, one upload"""
+        if self._tables is None or self._tables.device != dev:
+            h = resample_filter(1, self.oversample, self.half_width, self.beta)[2]
+            assert h.size == self.n_taps
+            # (blocking, so that the tables are whole before any stream can read them)
+            self._tables = torch.from_numpy(np.concatenate([h, limiter_window(self.lookahead)])).to(dev)
+        return self._tables[:self.n_taps], self._tables[self.n_taps:]
+
+    def _params(self, dev):
+        h, w = self._hw(dev)
+        return _lib.ptr(h), self.n_taps, self.oversample, self.half_width, _lib.ptr(w), self.lookahead, self.ceiling
+
+    def _measure(self, src, table2, n_rows, max_count, gains=None, stats=None, counts=None):
+        """t2s_limit_measure over `table2` (device int64 [n_rows, 2]: src_start, src_count) of the flat device tensor `src`
+        -> (stats float64 [n_rows, 4], counts int32 [n_rows, 2])"""
+        p, dev = _lib.ptr, src.device
+        max_count = max(1, int(max_count))
+        if max_count > 2 ** 31 - 1:
+            raise _lib.T2SError("Limiter: a row of %d samples, the most is 2^31 - 1" % max_count)
+        if stats is None:
+            stats = torch.empty(n_rows, 4, dtype=torch.float64, device=dev)
+            counts = torch.empty(n_rows, 2, dtype=torch.int32, device=dev)
+        need = _lib.load().t2s_limit_scratch(n_rows, max_count)
+        scratch = torch.empty(need, dtype=torch.float64, device=dev)
+        _lib.call("t2s_limit_measure", p(src), _KINDS[src.dtype], src.numel(), p(table2), n_rows, max_count, p(gains),
+                  *self._params(dev), p(scratch), need, p(stats), p(counts), _lib.current_stream())
+        return stats, counts
+
+    def _apply(self, src, table4, n_rows, gains, counts, dst, max_out):
+        p = _lib.ptr
+        _lib.call("t2s_limit_apply", p(src), _KINDS[src.dtype], src.numel(), p(table4), n_rows, p(gains), *self._params(src.device),
+                  p(counts), p(dst), _KINDS[dst.dtype], dst.numel(), max(1, int(max_out)), None, _lib.current_stream())
+
+    @staticmethod
+    def _report(stats, counts):
+        return LimiterReport(stats[:, 0], stats[:, 1], stats[:, 2], counts[:, 0], counts[:, 1])
+
+    @staticmethod
+    def _check(audio, lengths, gain, what):
+        """what needs no device to refuse: the shapes and types of audio, lengths and gain (the messages of _float_rows)"""
+        T2SError = _lib.T2SError
+        if not torch.is_tensor(audio):
+            raise T2SError("%s: audio must be a tensor, got a %s" % (what, type(audio).__name__))
+        if audio.dim() not in (1, 2, 3) or (audio.dim() == 3 and audio.size(1) != 1) or audio.numel() == 0:
+            raise T2SError("%s: audio must be [N], [B, N] or [B, 1, N] and hold samples, got %s" % (what, tuple(audio.shape)))
+        if audio.dtype not in (torch.float32, torch.float16):
+            raise T2SError("%s: expected float32 or float16, got %s (int16 pools go through PcmPool.limit)" % (what, audio.dtype))
+        B = audio.numel() // audio.size(-1)
+        if B > 65535:
+            raise T2SError("%s: %d rows, the most is 65535" % (what, B))
+        if lengths is not None:
+            try:
+                lens = torch.as_tensor(lengths)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise T2SError("%s: lengths must be a tensor or a sequence of integers (%s)" % (what, e))
+            if lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+                raise T2SError("%s: lengths must be integers, got %s" % (what, lens.dtype))
+            if lens.dim() != 1 or lens.numel() != B:
+                raise T2SError("%s: lengths has shape %s, the batch holds %d entries" % (what, tuple(lens.shape), B))
+        if gain is not None:
+            if not torch.is_tensor(gain) or gain.dtype != torch.float64:
+                raise T2SError("%s: gain must be None or a float64 tensor in HBM (e.g. LoudnessReport.gain), got %s"
+                               % (what, gain.dtype if torch.is_tensor(gain) else "a %s" % type(gain).__name__))
+            if gain.dim() != 1 or gain.numel() != B:
+                raise T2SError("%s: gain has shape %s, the batch holds %d entries" % (what, tuple(gain.shape), B))
+            if gain.device != audio.device:
+                raise T2SError("%s: gain is on %s, audio on %s" % (what, gain.device, audio.device))
+
+    def _batch(self, audio, lengths, gain, what):
+        self._check(audio, lengths, gain, what)
+        flat, B, N, ldx, lens_d = _float_rows(audio, lengths, what, "PcmPool.limit")
+        gains = None if gain is None else gain.detach().contiguous()    # (a strided view such as LoudnessReport.gain: packed here)
+        rows = torch.arange(B, dtype=torch.int64, device=flat.device)
+        stats, counts = self._measure(flat, torch.stack([rows * ldx, lens_d], 1).contiguous(), B, N, gains)
+        return flat, B, N, ldx, lens_d, rows, gains, stats, counts
+
+    def true_peak_batch(self, audio, lengths=None, gain=None):
+        """audio [N], [B, N] or [B, 1, N] float32 or float16 in HBM (strided rows are read where they are), lengths [B] (an int32
+        or int64 device tensor is used where it is, a host sequence is copied over; None: whole rows) and gain (None, or a float64
+        device tensor [B] the rows are multiplied by first) -> LimiterReport(true_peak, sample_peak, min_gain float64 [B],
+        limited, flags int32 [B]), all on the device: the peaks of the INPUT times its gain, the smallest gain limit_batch would
+        apply and the number of samples over the ceiling.  Samples at and behind lengths[b] are never read."""
+        return self._report(*self._batch(audio, lengths, gain, "Limiter.true_peak_batch")[-2:])
+
+    def limit_batch(self, audio, lengths=None, gain=None):
+        """-> (audio float32 of audio's shape, lengths as given): entry b's first lengths[b] samples times its gain, limited -
+        forward(audio[b, :lengths[b]])'s bit for bit - and zeros behind them.  A row with nothing over the ceiling and no gain is
+        copied bit for bit.  Nothing is read back."""
+        what = "Limiter.limit_batch"
+        flat, B, N, ldx, lens_d, rows, gains, _, counts = self._batch(audio, lengths, gain, what)
+        out = torch.empty(B, N, dtype=torch.float32, device=flat.device)
+        table4 = torch.stack([rows * ldx, lens_d, rows * N, torch.full_like(rows, N)], 1).contiguous()
+        self._apply(flat, table4, B, gains, counts, out.view(-1), N)
+        return out.view(audio.shape), lengths
+
+    def forward(self, audio):
+        """One clip [N] / [1, N], or whole rows [B, N] / [B, 1, N], float32 or float16 in HBM -> float32 of the same shape"""
+        return self.limit_batch(audio, None)[0]
 
     __call__ = forward
 

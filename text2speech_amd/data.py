@@ -5,6 +5,7 @@ a list of clip indices into the tensors `WaveGlow.forward` / `Tacotron.forward` 
                                                 .resample(new_rate) / from_wav_files(..., resample=True): rate conversion in HBM;
                                                 .rescale_trim(rescaling_max, top_db): the reference's peak rescaling and silence trim
                                                 .loudness() / .normalize_loudness(target_lufs): BS.1770 gated loudness per clip
+                                                .true_peak(limiter) / .limit(limiter, loudness): true peak and look-ahead limiter
   Mel2SampBatch(pool, segment_length, ...)      waveglow/mel2samp.py:60-105 (Mel2Samp.__getitem__ + the default collate): (mel, audio)
   TextMelBatch(pool, sequences, ...)            utils/data_utils.py:46-150 (TextMelLoader + TextMelCollate) and Tacotron.parse_batch
 
@@ -23,8 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import (LOUD_FLAG_NONFINITE, LOUD_FLAG_SHORT, LOUD_FLAG_SILENT, Loudness, Resampler, TacotronSTFT, Trimmer, _pcm16_gather,
-                    _to_device)
+from .audio import (LOUD_FLAG_NONFINITE, LOUD_FLAG_SHORT, LOUD_FLAG_SILENT, Limiter, Loudness, Resampler, TacotronSTFT, Trimmer,
+                    _pcm16_gather, _to_device)
 
 __all__ = ["PcmPool", "Mel2SampBatch", "TextMelBatch", "gather_width"]
 
@@ -182,6 +183,56 @@ class PcmPool:
         for r0 in range(0, n, chunk):
             sl = slice(r0, min(n, r0 + chunk))
             ld._apply(self.pcm, table4[sl], sl.stop - r0, stats[sl], pool.pcm, int(self.lengths[sl].max()))
+        return pool
+
+    def _limiter(self, limiter, loudness, what):
+        """(gains float64 [n] or None, stats float64 [n, 4], counts int32 [n, 2]) of every clip, 65535 rows a launch"""
+        if not isinstance(limiter, Limiter):
+            raise T2SError("%s: limiter must be an audio.Limiter, got a %s" % (what, type(limiter).__name__))
+        if loudness is not None and not isinstance(loudness, Loudness):
+            raise T2SError("%s: loudness must be None or an audio.Loudness, got a %s" % (what, type(loudness).__name__))
+        for stage in (limiter, loudness):
+            if stage is not None and stage.sampling_rate != self.sampling_rate:
+                raise T2SError("%s: the %s is built for %d Hz, the pool holds %d Hz"
+                               % (what, type(stage).__name__, stage.sampling_rate, self.sampling_rate))
+        n, dev, chunk = len(self), self.pcm.device, 65535
+        table2 = _to_device(torch.stack([self.offsets, self.lengths], 1).contiguous(), dev)
+        gains = None
+        if loudness is not None:
+            lstats = torch.empty(n, 4, dtype=torch.float64, device=dev)
+            lcounts = torch.empty(n, 4, dtype=torch.int32, device=dev)
+            for r0 in range(0, n, chunk):
+                sl = slice(r0, min(n, r0 + chunk))
+                loudness._measure(self.pcm, table2[sl], sl.stop - r0, int(self.lengths[sl].max()), lstats[sl], lcounts[sl])
+            gains = lstats[:, 3].contiguous()
+        stats = torch.empty(n, 4, dtype=torch.float64, device=dev)
+        counts = torch.empty(n, 2, dtype=torch.int32, device=dev)
+        for r0 in range(0, n, chunk):
+            sl = slice(r0, min(n, r0 + chunk))
+            limiter._measure(self.pcm, table2[sl], sl.stop - r0, int(self.lengths[sl].max()), None if gains is None else gains[sl],
+                             stats[sl], counts[sl])
+        return gains, stats, counts
+
+    def true_peak(self, limiter):
+        """The true peak of every clip as `limiter` (an audio.Limiter at the pool's rate) meters it, a sample counting as
+        x / 32768: LimiterReport(true_peak, sample_peak, min_gain, limited, flags), one entry per clip, on the device.  Nothing is
+        read back."""
+        _, stats, counts = self._limiter(limiter, None, "PcmPool.true_peak")
+        return Limiter._report(stats, counts)
+
+    def limit(self, limiter, loudness=None):
+        """Every clip through `limiter` (audio.Limiter states the rule), as a new pool at the same rate with the same lengths in
+        the same order, int16 to int16 in HBM: rint(32768 o), ties to even, saturated, so no code exceeds rint(32768 ceiling).  With
+        `loudness` (an audio.Loudness at the pool's rate; build it with peak_limit=None) each clip is brought to its target first -
+        the gain and the limiter in one pass; a clip that has no loudness (too short, silent) keeps gain 1.  Nothing is read back."""
+        gains, _, counts = self._limiter(limiter, loudness, "PcmPool.limit")
+        n, dev, chunk = len(self), self.pcm.device, 65535
+        pool = self._of(torch.empty_like(self.pcm), self.lengths, self.sampling_rate)
+        table4 = _to_device(torch.stack([self.offsets, self.lengths, pool.offsets, pool.lengths], 1).contiguous(), dev)
+        for r0 in range(0, n, chunk):
+            sl = slice(r0, min(n, r0 + chunk))
+            limiter._apply(self.pcm, table4[sl], sl.stop - r0, None if gains is None else gains[sl], counts[sl], pool.pcm,
+                           int(self.lengths[sl].max()))
         return pool
 
     @classmethod

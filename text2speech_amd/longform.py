@@ -401,6 +401,24 @@ def normalize_long(result, loudness):
     return result._replace(audio=audio)
 
 
+def limit_long(result, limiter, loudness=None):
+    """A ``LongForm`` / ``LongFormChecked`` / ``LongFormTimed`` / ``LongFormCheckedTimed`` with its whole utterance through
+    ``limiter`` (``audio.Limiter.limit_batch`` over ``result.audio`` and ``result.length``; with ``loudness``, an
+    ``audio.Loudness``, ``normalize_limit_batch``: brought to the target first, in the same pass): the same tuple with ``audio``
+    replaced.  A limiter moves no sample in time, so ``length``, ``offsets``, ``spans`` and every other field are the objects
+    given.  Nothing is read back.  An int16 result is refused: limit first, quantise afterwards."""
+    if not isinstance(result, (LongForm, LongFormChecked, LongFormTimed, LongFormCheckedTimed)):
+        raise _lib.T2SError("limit_long: expected a LongForm result of synthesize_long, got a %s" % type(result).__name__)
+    if not torch.is_tensor(result.audio) or result.audio.dtype != torch.float32:
+        raise _lib.T2SError("limit_long: the audio is %s; synthesize with pcm16=False, limit, then audio.to_pcm16"
+                            % getattr(result.audio, "dtype", type(result.audio).__name__))
+    if loudness is None:
+        audio, _ = limiter.limit_batch(result.audio, result.length)
+    else:
+        audio, _ = loudness.normalize_limit_batch(result.audio, result.length, limiter)
+    return result._replace(audio=audio)
+
+
 def _check_speed(speed, n):
     """synthesize_long_timed's ``speed`` -> None, or one rate per chunk (each checked by ``rate.stretch_q``)"""
     if speed is None:
