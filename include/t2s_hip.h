@@ -1081,6 +1081,62 @@ int t2s_limit_apply(const void* src, int src_kind, long src_len, const long* tab
                     int n_taps, int os, int half_width, const double* w, int lookahead, double ceiling, const int* counts, void* dst,
                     int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream);
 
+/* ---- delivery inside a stream: the resampler and the limiter window by window, G.711 (additive to ABI version 4; audio.py
+ *      DeliveryStream, to_ulaw / to_alaw; streaming.py synthesize_stream(delivery=); csrc/delivery.hip) ----
+ * A stream hands over the row of an utterance piece by piece.  Both stages are local, so a stream keeps the last C samples of what
+ * it has seen - the carry, f32 [B][C], packed - and each output is the whole-row entry point's own loop over carry | piece: the
+ * windows of a stream, concatenated, are t2s_resample_batch's / t2s_limit_apply's row bit for bit, for any piece lengths.  All
+ * positions are global sample indices of the stream's row, host scalars; the host knows every piece length and nothing is read
+ * back.  Rows: carry_in / carry_out [B][C]; piece f32 (is_half = 0) or f16 [B] rows of n samples, ldp elements apart, at global
+ * position K0 (N0); out f32 [B] rows, ldo apart.  carry_in holds the samples K0 - C .. K0 - 1 and is only read; carry_out (another
+ * buffer: ping-pong) receives the last C samples of carry | piece, an f16 sample widened exactly; a piece shorter than C shifts the
+ * old carry.  Samples below index 0 do not exist (they are never read: a new stream's carry may hold anything); with `final`,
+ * samples at or beyond K0 + n do not exist either.  n = 0 is allowed (piece may then be NULL), and with `final` flushes what the
+ * carry still owes.  One launch each; a workgroup makes 1024 outputs, one more per row writes the carry.
+ *  t2s_resample_window_carry: host only.  C_r = ceil(n_taps / up); -1 for n_taps < 3 or up < 1.
+ *  t2s_resample_window_end: host only.  The M1 of a window that ends at source sample K1 = K0 + n:
+ *    not final  M1 = max(M0, ceil((K1 up - half) / down)), half = n_taps / 2 - every output whose last tap lies below K1;
+ *    final      M1 = max(M0, ceil(K1 up / down)) - t2s_resample_table's n_out.           -1 for arguments the call would refuse.
+ *  t2s_resample_window: writes y[m], M0 <= m < M1, to out[b][m - M0]: t2s_resample_table's sum - k ascending, one double fused
+ *    multiply-add per tap from +0, rounded to f32 once - over the samples that exist.  M0 is the M1 of the window before (0 at
+ *    first).
+ *  t2s_limit_window_carry: host only.  C_l = 2 (2 lookahead + half_width) = 2 reach; -1 outside the limits.
+ *  t2s_limit_window_end: host only.  not final: O1 = max(O0, N1 - reach); final: O1 = max(O0, N1), N1 = N0 + n.
+ *  t2s_limit_window: writes o[i], O0 <= i < O1, to out[b][i - O0]: steps 1 - 5 of the limiter above over [O0 - reach, N1) - the same
+ *    sums in the same order, the same sliding minimum and window sum, r = 1 outside the row; f32 / f16 -> f32.  gains: double [B] in
+ *    device memory or NULL; h, n_taps, os, half_width, w, lookahead, ceiling as t2s_limit_apply's.  There is no measure pass and no
+ *    counts: a window sum is skipped only for a tile with no r < 1 in reach, where s is exactly 1.
+ *    state: 40 bytes a row, 8-byte aligned, kept by the caller from window to window and updated through integer atomics only:
+ *    words 0 - 2 the bit patterns of the largest p, the largest |u| and the smallest s over the delivered i (non-negative doubles
+ *    order as their bit patterns), word 3 zero, then int32 the number of delivered i with p[i] > c and int32 flags.  A new stream
+ *    sets it to (0, 0, the bits of 1.0, 0, 0, 0).  After the final window, read as double [4] and int32 [2], it is
+ *    t2s_limit_measure's stats and counts of the whole row.
+ *    NOT FINITE: the whole-row call copies such a row; a stream has already delivered, so it mutes instead.  A u that is not
+ *    finite, or an interpolated y that is not, counts as p = +inf: r = 0 there, the gain goes to 0 around it, o[i] = +0 where u[i]
+ *    itself is not finite, every stored sample is finite, and flag 8 is raised (the recorded peaks are then +inf and s_min 0).
+ *  t2s_g711: int16 codes [n] -> bytes [n], ITU-T G.711.  law 0, mu-law: v = x >> 2 (arithmetic, 14 bits); v < 0: v = -v and the
+ *    sign mask is 0x7F, else 0xFF; v = min(v, 8159) + 33 (the 16-bit form's clip 32635 and bias 132, >> 2); seg = the first of the
+ *    ends 0x3F, 0x7F, 0xFF .. 0x1FFF with v <= end; byte = ((seg << 4) | ((v >> (seg + 1)) & 15)) ^ mask, and 0x7F ^ mask where no
+ *    end holds v.  law 1, A-law: v = x >> 3 (13 bits); v >= 0: mask 0xD5, else v = -v - 1 and mask 0x55; seg = the first of the ends
+ *    0x1F, 0x3F, 0x7F .. 0xFFF with v <= end; byte = ((seg << 4) | ((v >> (seg < 2 ? 1 : seg)) & 15)) ^ mask.  No alignment beyond
+ *    the element.
+ *  T2S_EINVAL, with nothing launched and nothing written: a NULL carry_in, carry_out, h, w or state, a NULL piece with n > 0, a NULL
+ *    out where the window has outputs; carry_in and carry_out overlapping; B <= 0 or > 65535; n < 0 or > 2^31 - 1; ldp < n; a
+ *    position below 0 or above 2^40; O0 > N1; more outputs than out_cap or ldo; the filter, window and ceiling conditions of
+ *    t2s_resample_table / t2s_limit_apply; a misaligned h, w, gains, state (8 bytes), carry or out (4), piece (its element);
+ *    t2s_g711: a NULL pcm or out, n <= 0 or > 2^40, law other than 0 or 1. */
+int t2s_resample_window_carry(int n_taps, int up);
+long t2s_resample_window_end(long K1, long M0, int n_taps, int up, int down, int final);
+int t2s_resample_window(const float* carry_in, float* carry_out, const void* piece, int is_half, int B, long n, long ldp, long K0,
+                        long M0, int final, const double* h, int n_taps, int up, int down, float* out, long out_cap, long ldo,
+                        void* stream);
+int t2s_limit_window_carry(int lookahead, int half_width);
+long t2s_limit_window_end(long N1, long O0, int lookahead, int half_width, int final);
+int t2s_limit_window(const float* carry_in, float* carry_out, const void* piece, int is_half, int B, long n, long ldp, long N0, long O0,
+                     int final, const double* gains, const double* h, int n_taps, int os, int half_width, const double* w,
+                     int lookahead, double ceiling, float* out, long out_cap, long ldo, void* state, void* stream);
+int t2s_g711(const short* pcm, long n, int law, unsigned char* out, void* stream);
+
 /* ---- joining the rows of padded batches into one utterance in device memory (additive to ABI version 4; audio.py join_batches,
  *      longform.py synthesize_long) ----
  * Sentence after sentence, a pause of zeros between them, a linear ramp at the joints; no length is read by the host.

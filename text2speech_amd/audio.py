@@ -18,7 +18,9 @@ Trimmer cuts leading and trailing silence (librosa.effects.trim's decision) and 
 trim_batch / bounds_batch) or, through PcmPool.rescale_trim, on a pool (csrc/trim.hip).  Loudness measures BS.1770 / EBU R128 gated
 loudness and brings rows to a target level (measure_batch / normalize_batch; PcmPool.loudness / normalize_loudness for a pool;
 csrc/loudness.hip).  Limiter is the chain's last stage, a true-peak meter and look-ahead limiter (true_peak_batch / limit_batch;
-Loudness.normalize_limit_batch; PcmPool.true_peak / limit; csrc/limiter.hip).  join_batches / join_batch turn the padded
+Loudness.normalize_limit_batch; PcmPool.true_peak / limit; csrc/limiter.hip).  DeliveryStream is that chain inside a stream: resample,
+gain, limit and encode (float32, int16, G.711 through to_ulaw / to_alaw) piece by piece, the pieces' concatenation being the
+whole-utterance chain's result bit for bit (csrc/delivery.hip; synthesize_stream(delivery=)).  join_batches / join_batch turn the padded
 rows of such batches back into one utterance - pauses between them, ramps at the joints - with no length read back (csrc/join.hip;
 text2speech_amd/longform.py is the chain around it).
 Bases are built on the host at construction exactly as the reference builds them (numpy FFT of the identity, pinv, scipy
@@ -37,7 +39,7 @@ from . import _lib
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
            "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer", "Loudness", "LoudnessReport",
            "loudness_coefficients", "Limiter", "LimiterReport", "limiter_window", "LIMIT_FLAG_LIMITED", "LIMIT_FLAG_NONFINITE",
-           "LIMIT_MAX_LOOKAHEAD", "join_batches", "join_batch"]
+           "LIMIT_MAX_LOOKAHEAD", "DeliveryStream", "DELIVERY_ENCODINGS", "to_ulaw", "to_alaw", "join_batches", "join_batch"]
 
 
 def _ru(a, b):
@@ -767,6 +769,214 @@ class Limiter:
         return self.limit_batch(audio, None)[0]
 
     __call__ = forward
+
+
+DELIVERY_ENCODINGS = ("f32", "pcm16", "ulaw", "alaw")
+
+
+def _g711(audio, lengths, law):
+    pcm = to_pcm16(audio, lengths)
+    out = torch.empty(pcm.shape, dtype=torch.uint8, device=pcm.device)
+    _lib.call("t2s_g711", _lib.ptr(pcm), pcm.numel(), law, _lib.ptr(out), _lib.current_stream())
+    return out
+
+
+def to_ulaw(audio, lengths=None):
+    """Waveform in [-1, 1) -> G.711 mu-law bytes on the device: to_pcm16 (its arguments, its saturation) and then ITU-T G.711's
+    integer algorithm on the int16 codes (t2s_g711, include/t2s_hip.h).  Returns a uint8 tensor of audio's shape."""
+    return _g711(audio, lengths, 0)
+
+
+def to_alaw(audio, lengths=None):
+    """... -> G.711 A-law bytes (uint8 of audio's shape)"""
+    return _g711(audio, lengths, 1)
+
+
+class DeliveryStream:
+    """The delivery chain inside a stream (csrc/delivery.hip): pieces of an utterance at `src_rate` in, pieces at `out_rate` out -
+    resampled, multiplied by `gain`, limited by `limiter` and encoded - whose concatenation is, bit for bit,
+
+        enc(limiter.limit_batch(Resampler(src_rate, out_rate).forward(whole), gain=gain)[0])
+
+    for rows whose samples are finite and for ANY piece lengths, 0 and 1 included.  Both stages are local, so the stream keeps a
+    short tail of each (ceil(n_taps / up) source samples; 2 limiter.reach delivery samples) in HBM from push to push; a piece is
+    never resampled or limited alone, which would put a filter transient at every cut and lose the look-ahead across it.
+
+    `out_rate` None or equal to src_rate skips the resampler.  `limiter` is an audio.Limiter built for the DELIVERY rate; `gain` a
+    float or a float64 device tensor [B] (e.g. LoudnessReport.gain of a calibration utterance - the gated loudness of a programme
+    is not known before it ends, so a stream cannot measure its own) and needs a limiter, as limit_batch(gain=) does.  `encoding`:
+    "f32", "pcm16" (to_pcm16), "ulaw", "alaw" (to_ulaw / to_alaw).  At least one stage must be asked for.
+
+    push(piece [B, n] float32 or float16 in HBM, last=False) -> [B, m] (float32 / int16 / uint8; m may be 0).  Until the piece
+    flagged `last`, the stream holds back up to `latency` delivery samples: what the filters still need to see.  `delivered` counts
+    the samples returned so far; both are host integers.  report() is the limiter's running LimiterReport on the device: after the
+    last push it equals limiter.true_peak_batch's of the whole row.  A sample that is not finite cannot make the stream copy the
+    row, as limit_batch does - it has already delivered - so the stream mutes around it (the gain goes to 0, what is stored is
+    finite) and raises LIMIT_FLAG_NONFINITE.  Nothing is read back; every launch goes to the caller's current stream; B is fixed by
+    the first push (or open()).  Not here: measured loudness, ragged batches, one launch for both stages."""
+
+    def __init__(self, src_rate, out_rate=None, limiter=None, gain=None, encoding="f32"):
+        T2SError = _lib.T2SError
+        what = "DeliveryStream"
+        for name, v in (("src_rate", src_rate),) + ((("out_rate", out_rate),) if out_rate is not None else ()):
+            try:
+                whole = not isinstance(v, bool) and int(v) == v and v >= 1
+            except (TypeError, ValueError, OverflowError):
+                whole = False
+            if not whole:
+                raise T2SError("%s: %s must be a positive integer, got %r" % (what, name, v))
+        self.src_rate = int(src_rate)
+        self.out_rate = self.src_rate if out_rate is None else int(out_rate)
+        if encoding not in DELIVERY_ENCODINGS:
+            raise T2SError("%s: encoding must be one of %s, got %r" % (what, ", ".join(DELIVERY_ENCODINGS), encoding))
+        if limiter is not None and not isinstance(limiter, Limiter):
+            raise T2SError("%s: limiter must be an audio.Limiter or None, got a %s" % (what, type(limiter).__name__))
+        if limiter is not None and limiter.sampling_rate != self.out_rate:
+            raise T2SError("%s: the limiter was built for %d Hz, the delivery rate is %d Hz (limit last, at the rate delivered)"
+                           % (what, limiter.sampling_rate, self.out_rate))
+        if gain is not None:
+            if limiter is None:
+                raise T2SError("%s: gain needs a limiter (the gain is applied inside it, as limit_batch(gain=) does)" % what)
+            if torch.is_tensor(gain):
+                if gain.dtype != torch.float64 or gain.dim() != 1 or gain.numel() == 0:
+                    raise T2SError("%s: a gain tensor must be float64 [B], got %s %s" % (what, gain.dtype, tuple(gain.shape)))
+            elif not _real(gain):
+                raise T2SError("%s: gain must be a finite number or a float64 tensor [B], got %r" % (what, gain))
+        self.up = self.down = 1
+        self._h_host = None
+        if self.out_rate != self.src_rate:
+            self.up, self.down, self._h_host = resample_filter(self.src_rate, self.out_rate)
+            if max(self.up, self.down) > RESAMPLE_MAX_FACTOR:
+                raise T2SError("%s: %d -> %d Hz is the ratio %d / %d; max(up, down) may be at most %d"
+                               % (what, self.src_rate, self.out_rate, self.up, self.down, RESAMPLE_MAX_FACTOR))
+        if self._h_host is None and limiter is None and encoding == "f32":
+            raise T2SError("%s: nothing to do - ask for another rate, a limiter or an encoding" % what)
+        self.limiter, self.gain, self.encoding = limiter, gain, encoding
+        self.n_taps = 0 if self._h_host is None else int(self._h_host.size)
+        # the carries: host arithmetic (the library's t2s_*_window_carry restate it and the tests compare)
+        self.resample_carry = 0 if self._h_host is None else -(-self.n_taps // self.up)
+        self.limit_carry = 0 if limiter is None else 2 * limiter.reach
+        # delivery samples a push may hold back: the outputs whose last tap the source has not reached, and the limiter's reach
+        self.latency = (0 if self._h_host is None else -(-(self.n_taps // 2) // self.down)) + (0 if limiter is None else limiter.reach)
+        self.delivered = 0
+        self.B = None
+        self._ended = False
+        self._K = self._M = self._N = self._O = 0      # source samples seen, resampled; delivery samples seen, limited
+        self._order = _lib.StreamOrder()
+
+    def open(self, B, device="cuda"):
+        """Allocates the stream's state for B rows and uploads the tables (the one blocking copy, where the limiter has not
+        uploaded its own yet).  push() calls it with the first piece's B; call it first where not even that push may block."""
+        if self.B is not None:
+            return self
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.T2SError("DeliveryStream: the stream's state lives in HBM (cuda); there is no CPU path")
+        B = int(B)
+        if not 1 <= B <= 65535:
+            raise _lib.T2SError("DeliveryStream: %d rows, from 1 to 65535" % B)
+        if dev.index is None:                                   # ("cuda": the current device, named as a piece's .device names it)
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self._gains = None
+        if self.gain is not None:
+            if torch.is_tensor(self.gain):
+                if self.gain.numel() != B or self.gain.device.type != "cuda":
+                    raise _lib.T2SError("DeliveryStream: gain holds %d values on %s, the stream has %d rows in HBM"
+                                        % (self.gain.numel(), self.gain.device, B))
+                self._gains = self.gain.detach().contiguous()
+            else:
+                self._gains = torch.full((B,), float(self.gain), dtype=torch.float64, device=dev)
+        self._h = None if self._h_host is None else _to_device(torch.from_numpy(self._h_host), dev)
+        # (ping-pong: a window reads one carry and writes the other; zeros, though samples below index 0 are never read)
+        self._rc = [torch.zeros(B, self.resample_carry, dtype=torch.float32, device=dev) for _ in range(2)] if self._h is not None else None
+        self._lc = self._state = None
+        if self.limiter is not None:
+            self.limiter._hw(dev)
+            self._lc = [torch.zeros(B, self.limit_carry, dtype=torch.float32, device=dev) for _ in range(2)]
+            self._state = torch.zeros(B, 5, dtype=torch.int64, device=dev)
+            self._state[:, 2].fill_(0x3FF0000000000000)         # the bits of 1.0: the smallest gain so far
+        self._ri = self._li = 0
+        self.B, self.device = B, dev
+        return self
+
+    def report(self):
+        """The limiter's running state as a LimiterReport of views into it (float64 [B] x 3, int32 [B] x 2), on the device"""
+        if self.limiter is None:
+            raise _lib.T2SError("DeliveryStream.report: the stream has no limiter")
+        if self.B is None:
+            raise _lib.T2SError("DeliveryStream.report: nothing has been pushed yet")
+        return Limiter._report(self._state[:, :4].view(torch.float64), self._state[:, 4:].view(torch.int32))
+
+    def _resample(self, x, n, ldp, final):
+        lib, p = _lib.load(), _lib.ptr
+        M1 = lib.t2s_resample_window_end(self._K + n, self._M, self.n_taps, self.up, self.down, int(final))
+        m = M1 - self._M
+        out = torch.empty(self.B, m, dtype=torch.float32, device=self.device)
+        if n or m:
+            i = self._ri
+            _lib.call("t2s_resample_window", p(self._rc[i]), p(self._rc[1 - i]), p(x) if n else None, int(x.dtype == torch.float16),
+                      self.B, n, ldp, self._K, self._M, int(final), p(self._h), self.n_taps, self.up, self.down,
+                      p(out) if m else None, m, m, _lib.current_stream())
+            self._ri = 1 - i
+        self._K += n
+        self._M = M1
+        return out, m, m
+
+    def _limit(self, x, n, ldp, final):
+        lib, p, lim = _lib.load(), _lib.ptr, self.limiter
+        O1 = lib.t2s_limit_window_end(self._N + n, self._O, lim.lookahead, lim.half_width, int(final))
+        m = O1 - self._O
+        out = torch.empty(self.B, m, dtype=torch.float32, device=self.device)
+        if n or m:
+            i = self._li
+            _lib.call("t2s_limit_window", p(self._lc[i]), p(self._lc[1 - i]), p(x) if n else None, int(x.dtype == torch.float16),
+                      self.B, n, ldp, self._N, self._O, int(final), p(self._gains), *lim._params(self.device),
+                      p(out) if m else None, m, m, p(self._state), _lib.current_stream())
+            self._li = 1 - i
+        self._N += n
+        self._O = O1
+        return out, m, m
+
+    def push(self, piece, last=False):
+        """piece [B, n] float32 or float16 in HBM (n may be 0; strided rows are read where they are) -> what can be delivered now,
+        [B, m] in the stream's encoding, m >= 0.  `last` ends the row: what was held back comes out, and no further piece is
+        taken.  One launch a stage and one or two for the encoding, on the caller's current stream; the host never waits."""
+        T2SError = _lib.T2SError
+        what = "DeliveryStream.push"
+        if self._ended:
+            raise T2SError("%s: a piece arrived behind the one flagged last" % what)
+        if not torch.is_tensor(piece) or piece.dim() != 2:
+            raise T2SError("%s: a piece must be a tensor [B, n], got %s" % (what, tuple(piece.shape) if torch.is_tensor(piece)
+                                                                            else "a %s" % type(piece).__name__))
+        if piece.dtype not in (torch.float32, torch.float16):
+            raise T2SError("%s: expected float32 or float16, got %s" % (what, piece.dtype))
+        _need_cuda(piece, what)
+        B, n = piece.shape
+        self.open(B, piece.device)
+        if B != self.B or piece.device != self.device:
+            raise T2SError("%s: the stream was opened for %d rows on %s, the piece has %d on %s"
+                           % (what, self.B, self.device, B, piece.device))
+        x = piece.detach()
+        if n and (x.stride(1) != 1 or (B > 1 and x.stride(0) < n)):
+            x = x.contiguous()
+        ld = x.stride(0) if (B > 1 and n) else n
+        cur = self._order.enter(self.device)
+        if self._order.switched:
+            _lib.record_stream((self._rc, self._lc, self._state, self._h, self._gains), cur)
+        final = bool(last)
+        if self._h is not None:
+            x, n, ld = self._resample(x, n, ld, final)
+        if self.limiter is not None:
+            x, n, ld = self._limit(x, n, ld, final)
+        self._ended = final
+        self.delivered += n
+        if self.encoding == "f32":
+            return x
+        if n == 0:
+            return torch.empty(B, 0, dtype=torch.int16 if self.encoding == "pcm16" else torch.uint8, device=self.device)
+        if self.encoding == "pcm16":
+            return to_pcm16(x)
+        return to_ulaw(x) if self.encoding == "ulaw" else to_alaw(x)
 
 
 JOIN_MAX_FADE = 65536          # the library's limit on the fade (include/t2s_hip.h)

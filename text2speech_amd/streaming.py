@@ -112,11 +112,12 @@ def _check_stream_args(waveglow, seed, first_frames, window_frames, halo, who):
     return halo
 
 
-def stream_windows(waveglow, pieces, sigma, seed, first_frames, window_frames, halo, margin=0, who="infer_stream"):
+def stream_windows(waveglow, pieces, sigma, seed, first_frames, window_frames, halo, margin=0, who="infer_stream", flag_last=False):
     """The generator behind ``WaveGlow.infer_stream``: over (mel piece [B, n_mel, n], last) it yields (audio [B, stride (g1 - g0)],
     f0, f1, g0, g1) per window, where the window delivers frames [f0, f1) and the audio covers [g0, g1) = [f0 - margin, f1 + margin)
-    clipped to the utterance (margin > 0: synthesize_stream's denoiser wants its STFT's reach around every inner edge).  The
-    workspaces of the windows' shapes live in a dict of this generator, at most three (``_Engine.workspace``)."""
+    clipped to the utterance (margin > 0: synthesize_stream's denoiser wants its STFT's reach around every inner edge).  With
+    ``flag_last`` a sixth value says whether the window is the utterance's last.  The workspaces of the windows' shapes live in a
+    dict of this generator, at most three (``_Engine.workspace``)."""
     left, right = halo
     plan_halo = (left + margin, right + margin)
     mel = _MelBuffer()
@@ -142,13 +143,13 @@ def stream_windows(waveglow, pieces, sigma, seed, first_frames, window_frames, h
             audio = waveglow.infer_window(mel.known(), g0, g1, sigma=sigma, seed=seed, final=ended, halo=halo, _region=(lo, hi),
                                           _ws=ws)
             start = f1
-            yield audio, f0, f1, g0, g1
+            yield (audio, f0, f1, g0, g1, ended and f1 >= mel.n) if flag_last else (audio, f0, f1, g0, g1)
     if not ended:
         raise _lib.T2SError("%s: the pieces ended without one flagged last" % who)
 
 
 def synthesize_stream(tacotron, waveglow, ids, speaker_id=None, seed=None, sigma=0.666, denoiser=None, strength=0.1, first_frames=32,
-                      window_frames=128, halo=None, pcm16=False):
+                      window_frames=128, halo=None, pcm16=False, delivery=None):
     """Text to audio pieces: ``tacotron.inference_stream`` feeding ``waveglow.infer_stream`` on one stream.  A generator of audio
     pieces [1, n] (float32, or int16 with ``pcm16``) whose concatenation is the utterance; the first one exists once
     first_frames + halo frames are decoded, not after the last frame.  ``seed`` (required) keys both the prenet masks and the
@@ -159,9 +160,26 @@ def synthesize_stream(tacotron, waveglow, ids, speaker_id=None, seed=None, sigma
     widened by the STFT's reach, ceil(filter_length / stride) = 4 frames per inner edge; ``denoiser.forward(., strength)`` runs on
     the widened window and the centre is kept, so every kept sample sees the samples the whole-utterance call shows it, and the
     utterance's own ends keep their reflect padding.  B = 1, eval mode; ``halo`` as ``infer_window`` takes it.  Arguments are
-    checked here, before the first piece is asked for."""
+    checked here, before the first piece is asked for.
+
+    ``delivery``: an ``audio.DeliveryStream`` (one per utterance), or a callable without arguments that makes one.  Every piece -
+    denoised where there is a denoiser - is pushed through it, the last one flagged, and what comes out is yielded: resampled,
+    limited and encoded audio whose concatenation is the whole-utterance chain applied to the plain stream's concatenation, bit
+    for bit.  A push that gives nothing yields nothing.  Not together with ``pcm16`` (the stream has its own encoding); the
+    speaking rate, timestamps and the alignment check are not part of a stream."""
     if tacotron.training or waveglow.training:
         raise _lib.T2SError("synthesize_stream runs in eval mode only (call .eval() on both models)")
+    if delivery is not None:
+        if pcm16:
+            raise _lib.T2SError("synthesize_stream: delivery= and pcm16=True exclude each other (ask the DeliveryStream for \"pcm16\")")
+        from .audio import DeliveryStream
+        if not isinstance(delivery, DeliveryStream):
+            if not callable(delivery):
+                raise _lib.T2SError("synthesize_stream: delivery must be an audio.DeliveryStream or a callable that makes one, got a %s"
+                                    % type(delivery).__name__)
+            delivery = delivery()
+            if not isinstance(delivery, DeliveryStream):
+                raise _lib.T2SError("synthesize_stream: delivery() returned a %s, not an audio.DeliveryStream" % type(delivery).__name__)
     halo = _check_stream_args(waveglow, seed, first_frames, window_frames, halo, "synthesize_stream")
     stride = int(waveglow.upsample.stride[0])
     margin = 0
@@ -171,15 +189,22 @@ def synthesize_stream(tacotron, waveglow, ids, speaker_id=None, seed=None, sigma
                                 % (denoiser.stft.hop_length, stride))
         margin = -(-denoiser.stft.filter_length // stride)
     mels = tacotron.inference_stream(ids, speaker_id, seed=seed)
-    return _synthesize(mels, waveglow, seed, sigma, denoiser, strength, first_frames, window_frames, halo, margin, stride, pcm16)
+    return _synthesize(mels, waveglow, seed, sigma, denoiser, strength, first_frames, window_frames, halo, margin, stride, pcm16,
+                       delivery)
 
 
-def _synthesize(mels, waveglow, seed, sigma, denoiser, strength, first_frames, window_frames, halo, margin, stride, pcm16):
+def _synthesize(mels, waveglow, seed, sigma, denoiser, strength, first_frames, window_frames, halo, margin, stride, pcm16,
+                delivery=None):
     from . import audio as A
     pieces = ((p[1], p[4]) for p in mels)
-    for audio, f0, f1, g0, g1 in stream_windows(waveglow, pieces, sigma, seed, first_frames, window_frames, halo, margin,
-                                                "synthesize_stream"):
+    for audio, f0, f1, g0, g1, last in stream_windows(waveglow, pieces, sigma, seed, first_frames, window_frames, halo, margin,
+                                                      "synthesize_stream", flag_last=True):
         if denoiser is not None:
             with torch.no_grad():
                 audio = denoiser(audio, strength)[:, 0, stride * (f0 - g0):stride * (f1 - g0)]
-        yield A.to_pcm16(audio) if pcm16 else audio
+        if delivery is None:
+            yield A.to_pcm16(audio) if pcm16 else audio
+            continue
+        out = delivery.push(audio, last)
+        if out.size(1):
+            yield out
