@@ -2,13 +2,13 @@
 // limiter window by window, and G.711 bytes.  include/t2s_hip.h states the arithmetic.  Both stages are local - an output of the
 // resampler reads ceil(n_taps / up) source samples, an output of the limiter 2 L + half_width samples to either side - so a stream
 // keeps a short tail of its row, the carry, from window to window and every output is computed from carry | piece by the loop the
-// whole-row kernel runs (csrc/resample.hip, csrc/limiter.hip; restated here, so that neither file is compiled differently): the
-// concatenation of a stream's windows is the whole-row result bit for bit.
+// whole-row kernel runs - one statement of each, csrc/resample_tap.h for csrc/resample.hip and this file, csrc/limit_tile.h for
+// csrc/limiter.hip and this file: the concatenation of a stream's windows is the whole-row result bit for bit.
 //
 //   resample_window_kernel  grid (tiles + 1) x rows.  A workgroup makes T2S_RESAMPLE_TILE outputs counted from the window's first:
 //                           the filter phase by phase in LDS, then per output one loop over k ascending, one double fma a tap
 //                           from +0, over the carry and then the piece.  The last workgroup of a row writes the next carry.
-//   limit_window_kernel     grid (tiles + 1) x rows.  A workgroup makes DV_TILE outputs: samples staged in LDS as floats, r over
+//   limit_window_kernel     grid (tiles + 1) x rows.  A workgroup makes LM_TILE outputs: samples staged in LDS as floats, r over
 //                           the tile and 2 L to either side, the sliding minimum by doubling, the window sum; a tile with no r below
 //                           1 in reach skips both.  Its peaks, smallest s, count and flags go into the row's running state by
 //                           integer atomics (max / min of the bit patterns of non-negative doubles, add, or): order-free, so the
@@ -20,29 +20,22 @@
 //
 // Memory safety: a sample at global index i is read from the piece when K0 <= i < K0 + n, from the carry when K0 - C <= i < K0 and
 // i >= 0, and is 0 otherwise - whatever K0, M0 / O0 hold; an output index lies in [0, M1 - M0), which the entry point has checked
-// against out_cap; the state index is the row.  LDS of the limiter as in limiter.hip: 144 + 8 E + 4 (E + 2 half_width) bytes.
+// against out_cap; the state index is the row.  The LDS of both kernels is laid out and sized by the shared headers.
 #include "../../include/t2s_hip.h"
 #include "t2s_common.h"
 #include "t2s_api_common.h"
 #include "audio_ops.h"
+#include "limit_tile.h"
+#include "resample_tap.h"
 
 #include <limits.h>
 #include <math.h>
 #include <string.h>
 
 #define DV_THREADS 256
-#define DV_TILE 1024                            // outputs of one row per workgroup of the limiter: t2s_limit_tile()
-#define DV_MAX_L 1024
-#define DV_MAX_HW 32
-#define DV_OUT (DV_TILE / DV_THREADS)
-#define DV_EPT ((DV_TILE + 4 * DV_MAX_L) / DV_THREADS)
-#define DV_RED (4 * (DV_THREADS / 64))
-#define DV_HEAD (DV_RED + 2)
 #define DV_MAX_POS (1L << 40)                   // the largest sample index of a stream's row
 
-static_assert(DV_TILE % DV_THREADS == 0 && (4 * DV_MAX_L) % DV_THREADS == 0, "whole elements per thread");
-static_assert(8 * DV_HEAD + 8 * (DV_TILE + 4 * DV_MAX_L) + 4 * (DV_TILE + 4 * DV_MAX_L + 2 * DV_MAX_HW) <= 65536, "the staging fits 64 KB of LDS");
-static_assert(DV_HEAD % 2 == 0, "the staging starts 16-byte aligned");
+static_assert(DV_THREADS == RS_THREADS && DV_THREADS == LM_THREADS, "one workgroup size: the carry's roll serves both kernels");
 
 // the two-segment source of a window: carry [C] holds the samples K0 - C .. K0 - 1, piece [n] the samples K0 .. K0 + n - 1
 template <typename TPiece>
@@ -51,6 +44,7 @@ struct DvSource {
     const TPiece* piece;
     long K0, K1;
     int C;
+    __device__ __forceinline__ long end() const { return K1; }
     __device__ __forceinline__ float at(long i) const {
         if (i < 0 || i >= K1) return 0.f;
         if (i >= K0) return (float)piece[i - K0];
@@ -97,29 +91,14 @@ __global__ __launch_bounds__(DV_THREADS) void resample_window_kernel(const RsWin
         return;
     }
     const long m0 = a.M0 + (long)blockIdx.x * T2S_RESAMPLE_TILE;
-    const int n_taps = a.n_taps, lp = a.lp;
-    for (int j = tid; j < n_taps; j += DV_THREADS) dv_hp[(j % a.up) * lp + j / a.up] = a.h[j];
-    __syncthreads();
+    rs_stage_phases(dv_hp, a.h, a.n_taps, a.up, a.lp, tid);
 
-    const long up = a.up, down = a.down;
-    const int L = (n_taps + a.up - 1) / a.up;                   // taps of the longest phase
-    const long c0 = (long)(n_taps / 2) + m0 * down;             // h's index under source sample 0, for output m0
-    const long q0 = c0 / up;
-    const unsigned r0 = (unsigned)(c0 % up);
+    const RsTile tile(m0, a.n_taps, a.up, a.down, a.lp);
     float* out = a.out + (size_t)r * a.ldo;
     for (int o = tid; o < T2S_RESAMPLE_TILE; o += DV_THREADS) {
         const long m = m0 + o;
         if (m >= a.M1) break;
-        const unsigned e = r0 + (unsigned)o * (unsigned)a.down;
-        const unsigned p = e % (unsigned)a.up;
-        const long kc = q0 + e / (unsigned)a.up;                // the sample under tap p; tap p + i up is under kc - i
-        const int cnt = L - ((long)p + (long)(L - 1) * up >= n_taps ? 1 : 0);
-        const long k_lo = kc - (cnt - 1) > 0 ? kc - (cnt - 1) : 0;
-        const long k_hi = kc < src.K1 - 1 ? kc : src.K1 - 1;
-        const double* hrow = dv_hp + (size_t)p * lp;
-        double acc = 0.0;
-        for (long k = k_lo; k <= k_hi; ++k) acc = fma((double)src.at(k), hrow[kc - k], acc);
-        out[m - a.M0] = (float)acc;                             // one rounding
+        out[m - a.M0] = (float)tile.output(o, src, dv_hp);         // one rounding
     }
 }
 
@@ -153,7 +132,6 @@ struct LmWindowArgs {
 template <typename TPiece, int OS>
 __global__ __launch_bounds__(DV_THREADS) void limit_window_kernel(const LmWindowArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dv_smem[];
-    double (*s_red)[DV_THREADS / 64] = (double (*)[DV_THREADS / 64])dv_smem;
     const int tid = threadIdx.x, r = blockIdx.y;
     DvSource<TPiece> src;
     src.carry = a.carry_in + (size_t)r * a.C;
@@ -163,20 +141,20 @@ __global__ __launch_bounds__(DV_THREADS) void limit_window_kernel(const LmWindow
         src.roll(a.carry_out + (size_t)r * a.C, tid);
         return;
     }
-    const long base = a.O0 + (long)blockIdx.x * DV_TILE;
+    const long base = a.O0 + (long)blockIdx.x * LM_TILE;
     const long N1 = src.K1;
     const int L = a.L, hw = a.hw;
-    const int E = DV_TILE + 4 * L, X = E + 2 * hw;
-    int* s_any = (int*)(dv_smem + DV_RED);
-    double* A = dv_smem + DV_HEAD;                              // [E]: r over base - 2 L .., then the minima in place
-    float* xs = (float*)(A + E);                                // [X]: x over base - 2 L - hw ..
+    const int E = LM_TILE + 4 * L, X = E + 2 * hw;
+    const LmTileLds lds = lm_tile_lds(dv_smem, E);
+    double* A = lds.A;
+    float* xs = lds.xs;
     const double gu = a.gains ? a.gains[r] : 1.0;
     const double c = a.c;
 
     // ---- stage the samples: every one once; zeros outside the row (and behind what the stream has seen) ----
     const long x0 = base - 2 * L - hw;
     for (int q = tid; q < X; q += DV_THREADS) xs[q] = src.at(x0 + q);
-    if (tid == 0) *s_any = 0;
+    if (tid == 0) *lds.any = 0;
     __syncthreads();
 
     // ---- r over the tile and 2 L to either side; the peaks and the count of what this tile delivers ----
@@ -187,88 +165,33 @@ __global__ __launch_bounds__(DV_THREADS) void limit_window_kernel(const LmWindow
         const long i = base - 2 * L + q;
         double rv = 1.0;
         if (i >= 0 && i < N1) {
-            const double uc = (double)xs[q + hw] * gu;
-            double p = fabs(uc);
-            int nf = !(p < (double)INFINITY);
-            if (OS > 1) {
-                double acc[OS];
-#pragma unroll
-                for (int ph = 0; ph < OS; ++ph) acc[ph] = 0.0;
-                const double* hh = a.h + OS * 2 * hw;           // tap ph + os (2 hw - d) meets sample i - hw + d
-                for (int d = 0; d <= 2 * hw; ++d) {
-                    const double uv = (double)xs[q + d] * gu;
-#pragma unroll
-                    for (int ph = 0; ph < OS; ++ph)
-                        if (ph == 0 || d > 0) acc[ph] = fma(uv, hh[ph - OS * d], acc[ph]);
-                }
-#pragma unroll
-                for (int ph = 0; ph < OS; ++ph) {
-                    p = fmax(p, fabs(acc[ph]));
-                    nf |= !(fabs(acc[ph]) < (double)INFINITY);
-                }
-            }
-            if (nf) p = (double)INFINITY;                       // a sample or an interpolated value that is not finite mutes
+            // (a sample or an interpolated value that is not finite mutes: p is +inf there)
+            const double p = lm_envelope<OS, true>(xs + q, hw, gu, a.h);
             if (p > c) rv = c / p;
-            if (q >= 2 * L && q < 2 * L + DV_TILE && i < a.O1) {
-                const double au = fabs(uc);
+            if (q >= 2 * L && q < 2 * L + LM_TILE && i < a.O1) {
+                const double au = fabs((double)xs[q + hw] * gu);
                 tp = fmax(tp, p);
                 sp = fmax(sp, au < (double)INFINITY ? au : (double)INFINITY);
                 cnt += p > c ? 1 : 0;
-                bad |= nf;
+                bad |= !(p < (double)INFINITY);
             }
         }
         A[q] = rv;
         any |= rv < 1.0;
     }
-    if (any) *s_any = 1;
+    if (any) *lds.any = 1;
     __syncthreads();                                            // (A is whole)
-    any = *s_any;
+    any = *lds.any;
 
-    double s[DV_OUT];
+    double s[LM_OUT];
 #pragma unroll
-    for (int e = 0; e < DV_OUT; ++e) s[e] = 1.0;
-    if (any) {
-        double rs[DV_OUT];
-#pragma unroll
-        for (int e = 0; e < DV_OUT; ++e) rs[e] = A[2 * L + tid + e * DV_THREADS];
-        // ---- the minimum over 2 L + 1 by doubling, in place: read, barrier, write, barrier ----
-        const int W = 2 * L + 1;
-        double v[DV_EPT];
-        int win = 1;
-        while (win < W) {
-            const int sh = 2 * win <= W ? win : W - win;        // the last step overlaps
-#pragma unroll
-            for (int e = 0; e < DV_EPT; ++e) {
-                const int q = tid + e * DV_THREADS;
-                if (q + sh < E) v[e] = fmin(A[q], A[q + sh]);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < DV_EPT; ++e) {
-                const int q = tid + e * DV_THREADS;
-                if (q + sh < E) A[q] = v[e];
-            }
-            __syncthreads();
-            win += sh;
-        }
-        // ---- A[b] is now m at base - L + b: the window sum of the thread's outputs, in ascending k ----
-        double acc[DV_OUT];
-#pragma unroll
-        for (int e = 0; e < DV_OUT; ++e) acc[e] = 0.0;
-        const double* m = A + tid;
-        for (int k = 0; k < W; ++k) {
-            const double wk = a.w[k];
-#pragma unroll
-            for (int e = 0; e < DV_OUT; ++e) acc[e] = fma(wk, m[k + e * DV_THREADS], acc[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < DV_OUT; ++e) s[e] = fmin(rs[e], acc[e]);
-    }
+    for (int e = 0; e < LM_OUT; ++e) s[e] = 1.0;
+    if (any) lm_min_window_sum(A, E, L, a.w, tid, s);
 
     float* out = a.out + (size_t)r * a.ldo;
     double smin = 1.0;
 #pragma unroll
-    for (int e = 0; e < DV_OUT; ++e) {
+    for (int e = 0; e < LM_OUT; ++e) {
         const int o = tid + e * DV_THREADS;
         const long i = base + o;
         if (i < a.O1) {
@@ -278,28 +201,10 @@ __global__ __launch_bounds__(DV_THREADS) void limit_window_kernel(const LmWindow
         }
     }
 
-    // ---- the tile's statistics: order-free reductions over the workgroup, then into the row's state ----
-    double dcnt = (double)cnt;
-    for (int off = 32; off; off >>= 1) {
-        tp = fmax(tp, __shfl_xor(tp, off));
-        sp = fmax(sp, __shfl_xor(sp, off));
-        smin = fmin(smin, __shfl_xor(smin, off));
-        dcnt += __shfl_xor(dcnt, off);                          // (integers below 2^53: exact in any order)
-        bad |= __shfl_xor(bad, off);
-    }
-    if ((tid & 63) == 0) {
-        s_red[0][tid >> 6] = tp; s_red[1][tid >> 6] = sp; s_red[2][tid >> 6] = smin; s_red[3][tid >> 6] = bad ? -1.0 - dcnt : dcnt;
-    }
-    __syncthreads();
+    // ---- the tile's statistics into the row's state: order-free, whatever order the workgroups arrive in ----
+    double total = (double)cnt;
+    lm_reduce(lds.red, tid, tp, sp, smin, total, bad);
     if (tid == 0) {
-        double total = 0.0;
-        bad = 0;
-        for (int wv = 0; wv < DV_THREADS / 64; ++wv) {
-            tp = fmax(tp, s_red[0][wv]); sp = fmax(sp, s_red[1][wv]); smin = fmin(smin, s_red[2][wv]);
-            const double cw = s_red[3][wv];
-            if (cw < 0.0) { bad = 1; total += -1.0 - cw; }
-            else total += cw;
-        }
         unsigned long long* st = a.state + 5 * (size_t)r;
         int* ct = (int*)(st + 4);
         // (non-negative doubles order as their bit patterns; a tile that changes nothing issues no atomic)
@@ -312,15 +217,10 @@ __global__ __launch_bounds__(DV_THREADS) void limit_window_kernel(const LmWindow
     }
 }
 
-static size_t dv_lds(int L, int hw) {
-    const size_t E = DV_TILE + 4 * (size_t)L;
-    return 8 * DV_HEAD + 8 * E + 4 * ((E + 2 * (size_t)hw + 3) & ~(size_t)3);
-}
-
 template <typename TPiece>
 static hipError_t dv_launch_limit(const LmWindowArgs& a, int os, int B, hipStream_t s) {
     const dim3 grid(a.tiles + 1, B), block(DV_THREADS);
-    const size_t lds = dv_lds(a.L, a.hw);
+    const size_t lds = lm_tile_lds_bytes(a.L, a.hw);
     if (os == 1) hipLaunchKernelGGL((limit_window_kernel<TPiece, 1>), grid, block, lds, s, a);
     else if (os == 2) hipLaunchKernelGGL((limit_window_kernel<TPiece, 2>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((limit_window_kernel<TPiece, 4>), grid, block, lds, s, a);
@@ -355,7 +255,6 @@ __global__ __launch_bounds__(DV_THREADS) void g711_kernel(const short* pcm, long
 }
 
 // ---- the extern "C" boundary ----------------------------------------------------------------------------------------------------------
-static inline bool dv_al(const void* p, unsigned m) { return ((uintptr_t)p & (m - 1)) == 0; }
 static long dv_gcd(long a, long b) { while (b) { const long t = a % b; a = b; b = t; } return a; }
 
 static bool dv_overlap(const void* a, const void* b, size_t bytes) {
@@ -369,7 +268,7 @@ static bool dv_rows_ok(const float* carry_in, float* carry_out, const void* piec
     if (!carry_in || !carry_out || B <= 0 || B > 65535 || n < 0 || n > 0x7fffffffL || (n > 0 && (!piece || ldp < n)) ||
         pos0 < 0 || out0 < 0 || pos0 > DV_MAX_POS - n || out0 > DV_MAX_POS || C < 1 || ldo < 0)
         return false;
-    if (!dv_al(carry_in, 4) || !dv_al(carry_out, 4) || !dv_al(out, 4) || !dv_al(piece, is_half ? 2 : 4)) return false;
+    if (!aligned_to(carry_in, 4) || !aligned_to(carry_out, 4) || !aligned_to(out, 4) || !aligned_to(piece, is_half ? 2 : 4)) return false;
     return !dv_overlap(carry_in, carry_out, (size_t)B * C * sizeof(float));
 }
 
@@ -389,7 +288,7 @@ long t2s_resample_window_end(long K1, long M0, int n_taps, int up, int down, int
 int t2s_resample_window(const float* carry_in, float* carry_out, const void* piece, int is_half, int B, long n, long ldp, long K0,
                         long M0, int final, const double* h, int n_taps, int up, int down, float* out, long out_cap, long ldo,
                         void* stream) {
-    if (!h || !dv_al(h, 8) || up < 1 || down < 1 || up > 512 || down > 512 || dv_gcd(up, down) != 1 || n_taps < 3 || !(n_taps & 1) ||
+    if (!h || !aligned_to(h, 8) || up < 1 || down < 1 || up > 512 || down > 512 || dv_gcd(up, down) != 1 || n_taps < 3 || !(n_taps & 1) ||
         t2s_resample_lds_bytes(n_taps, up) > T2S_RESAMPLE_LDS_MAX)
         return T2S_EINVAL;
     const int C = t2s_resample_window_carry(n_taps, up);
@@ -406,7 +305,7 @@ int t2s_resample_window(const float* carry_in, float* carry_out, const void* pie
 }
 
 int t2s_limit_window_carry(int lookahead, int half_width) {
-    if (lookahead < 0 || lookahead > DV_MAX_L || half_width < 1 || half_width > DV_MAX_HW) return -1;
+    if (lookahead < 0 || lookahead > LM_MAX_L || half_width < 1 || half_width > LM_MAX_HW) return -1;
     return 2 * (2 * lookahead + half_width);
 }
 
@@ -419,12 +318,7 @@ long t2s_limit_window_end(long N1, long O0, int lookahead, int half_width, int f
 int t2s_limit_window(const float* carry_in, float* carry_out, const void* piece, int is_half, int B, long n, long ldp, long N0, long O0,
                      int final, const double* gains, const double* h, int n_taps, int os, int half_width, const double* w,
                      int lookahead, double ceiling, float* out, long out_cap, long ldo, void* state, void* stream) {
-    if (!h || !w || !state || !dv_al(h, 8) || !dv_al(w, 8) || !dv_al(gains, 8) || !dv_al(state, 8)) return T2S_EINVAL;
-    if (os != 1 && os != 2 && os != 4) return T2S_EINVAL;
-    if (half_width < 1 || half_width > DV_MAX_HW || n_taps != 2 * half_width * os + 1 || lookahead < 0 || lookahead > DV_MAX_L)
-        return T2S_EINVAL;
-    // (a comparison with NaN is false, the subtraction is NaN for an infinity)
-    if (!(ceiling > 0.0 && ceiling - ceiling == 0.0 && (double)(float)ceiling == ceiling)) return T2S_EINVAL;
+    if (!state || !aligned_to(state, 8) || !lm_params_ok(gains, h, n_taps, os, half_width, w, lookahead, ceiling)) return T2S_EINVAL;
     const int C = t2s_limit_window_carry(lookahead, half_width);
     if (!dv_rows_ok(carry_in, carry_out, piece, is_half, B, n, ldp, N0, O0, C, out, ldo)) return T2S_EINVAL;
     const long O1 = t2s_limit_window_end(N0 + n, O0, lookahead, half_width, final);
@@ -434,13 +328,13 @@ int t2s_limit_window(const float* carry_in, float* carry_out, const void* piece,
     a.carry_in = carry_in; a.carry_out = carry_out; a.piece = piece; a.n = n; a.ldp = ldp; a.N0 = N0; a.O0 = O0; a.O1 = O1;
     a.gains = gains; a.h = h; a.w = w; a.c = ceiling; a.hw = half_width; a.L = lookahead; a.C = C; a.out = out; a.ldo = ldo;
     a.state = (unsigned long long*)state;
-    a.tiles = (unsigned)((O1 - O0 + DV_TILE - 1) / DV_TILE);
+    a.tiles = (unsigned)((O1 - O0 + LM_TILE - 1) / LM_TILE);
     T2S_CHECK_HIP(is_half ? dv_launch_limit<_Float16>(a, os, B, (hipStream_t)stream) : dv_launch_limit<float>(a, os, B, (hipStream_t)stream));
     return T2S_OK;
 }
 
 int t2s_g711(const short* pcm, long n, int law, unsigned char* out, void* stream) {
-    if (!pcm || !out || !dv_al(pcm, 2) || n <= 0 || n > DV_MAX_POS || (law != 0 && law != 1)) return T2S_EINVAL;
+    if (!pcm || !out || !aligned_to(pcm, 2) || n <= 0 || n > DV_MAX_POS || (law != 0 && law != 1)) return T2S_EINVAL;
     hipLaunchKernelGGL(g711_kernel, dim3((unsigned)((n + DV_THREADS - 1) / DV_THREADS)), dim3(DV_THREADS), 0, (hipStream_t)stream, pcm, n,
                        law, out);
     T2S_CHECK_HIP(hipGetLastError());

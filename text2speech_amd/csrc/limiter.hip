@@ -21,28 +21,20 @@
 //
 // Memory safety: src_count is cut to what lies inside [0, src_len) (and, measuring, to max_count, which sizes the grid and the
 // scratch); the destination to [dst_start, dst_start + dst_cap) inside [0, dst_len) and to max_out; all in 64-bit, whatever the
-// tables hold.  LDS, all dynamic: 144 + 8 E + 4 (E + 2 half_width) bytes, E = LM_TILE + 4 L: 61.8 KB at L = 1024 and half_width = 32, two
-// workgroups to a CU; 15.7 KB at L = 67.
+// tables hold (csrc/pcm_rows.h).  LDS, all dynamic (csrc/limit_tile.h): 61.8 KB at L = 1024 and half_width = 32, two workgroups to a
+// CU; 15.7 KB at L = 67.
+//
+// The tile's geometry, its LDS layout, the envelope, the minimum with the window sum and the workgroup's reduction are
+// csrc/limit_tile.h's, which the stream's window kernel (csrc/delivery.hip) runs too.
 #include "../../include/t2s_hip.h"
 #include "t2s_common.h"
 #include "t2s_api_common.h"
+#include "limit_tile.h"
+#include "pcm_rows.h"
 
 #include <limits.h>
 #include <math.h>
 #include <string.h>
-
-#define LM_THREADS 256
-#define LM_TILE 1024                            // outputs of one row per workgroup
-#define LM_MAX_L 1024
-#define LM_MAX_HW 32
-#define LM_OUT (LM_TILE / LM_THREADS)           // outputs a thread makes
-#define LM_EPT ((LM_TILE + 4 * LM_MAX_L) / LM_THREADS)          // elements of r a thread holds at most
-#define LM_RED (4 * (LM_THREADS / 64))          // doubles in front of the staging: the partial results of the reductions,
-#define LM_HEAD (LM_RED + 2)                    // ... and the workgroup's "some r is below 1" word
-
-static_assert(LM_TILE % LM_THREADS == 0 && (4 * LM_MAX_L) % LM_THREADS == 0, "whole elements per thread");
-static_assert(8 * LM_HEAD + 8 * (LM_TILE + 4 * LM_MAX_L) + 4 * (LM_TILE + 4 * LM_MAX_L + 2 * LM_MAX_HW) <= 65536, "the staging fits 64 KB of LDS");
-static_assert(LM_HEAD % 2 == 0, "the staging starts 16-byte aligned");
 
 struct LimitArgs {
     const void* src;            // int16 / f32 / f16 [src_len]
@@ -64,36 +56,22 @@ struct LimitArgs {
     int* out_lengths;           // apply: [n_rows] int32 or NULL
 };
 
-static __device__ __forceinline__ long lm_count(long s0, long n, long src_len, long max_count) {
-    if (n < 0 || s0 < 0 || s0 >= src_len) return 0;
-    if (n > src_len - s0) n = src_len - s0;
-    return n > max_count ? max_count : n;
-}
-
-static __device__ __forceinline__ short lm_round16(double v) {
-    const double q = rint(v);                                   // ties to even
-    if (q >= 32767.0) return 32767;
-    if (q <= -32768.0) return -32768;
-    return q == q ? (short)(int)q : (short)0;                   // NaN: 0
-}
-static __device__ __forceinline__ void lm_store(short* p, double o) { *p = lm_round16(32768.0 * o); }
+static __device__ __forceinline__ void lm_store(short* p, double o) { *p = pcm_round16(32768.0 * o); }
 static __device__ __forceinline__ void lm_store(float* p, double o) { *p = (float)o; }
 
 template <typename TSrc, typename TDst, int OS, bool APPLY>
 __global__ __launch_bounds__(LM_THREADS) void limit_tile_kernel(const LimitArgs a) {
-    // (all LDS in the dynamic region, 16-byte aligned: a static in front of it would shift the base of the doubles)
     extern __shared__ __attribute__((aligned(16))) double lm_smem[];
-    double (*s_red)[LM_THREADS / 64] = (double (*)[LM_THREADS / 64])lm_smem;        // [4][waves]: the workgroup's reductions
     const int tid = threadIdx.x, r = blockIdx.y;
     const long base = (long)blockIdx.x * LM_TILE;
     const int L = a.L, hw = a.hw;
     const int E = LM_TILE + 4 * L, X = E + 2 * hw;
-    int* s_any = (int*)(lm_smem + LM_RED);
-    double* A = lm_smem + LM_HEAD;                              // [E]: r over base - 2 L .., then the minima in place
-    float* xs = (float*)(A + E);                                // [X]: x over base - 2 L - hw ..
+    const LmTileLds lds = lm_tile_lds(lm_smem, E);
+    double* A = lds.A;
+    float* xs = lds.xs;
     const long* t = a.table + (APPLY ? 4 : 2) * (size_t)r;
     const long s0 = t[0];
-    const long n = lm_count(s0, t[1], a.src_len, APPLY ? LONG_MAX : a.max_count);
+    const long n = pcm_src_count(s0, t[1], a.src_len, APPLY ? LONG_MAX : a.max_count);
     const TSrc* x = (const TSrc*)a.src + (n > 0 ? s0 : 0);
     double gu = (a.gains ? a.gains[r] : 1.0) * a.unit;          // (g / 32768 is exact: u = (x / 32768) g bit for bit)
     const double c = a.c;
@@ -102,10 +80,7 @@ __global__ __launch_bounds__(LM_THREADS) void limit_tile_kernel(const LimitArgs 
     TDst* out = nullptr;
     if (APPLY) {
         const long d0 = t[2];
-        cap = t[3];
-        if (cap > a.max_out) cap = a.max_out;
-        if (cap < 0 || d0 < 0 || d0 >= a.dst_len) cap = 0;
-        else if (cap > a.dst_len - d0) cap = a.dst_len - d0;
+        cap = pcm_dst_cap(t[3], a.max_out, d0, a.dst_len);
         valid = n < cap ? n : cap;
         if (blockIdx.x == 0 && tid == 0 && a.out_lengths) a.out_lengths[r] = valid > INT_MAX ? INT_MAX : (int)valid;
         if (base >= cap) return;                                // (the whole workgroup)
@@ -131,7 +106,7 @@ __global__ __launch_bounds__(LM_THREADS) void limit_tile_kernel(const LimitArgs 
         const long i = x0 + q;
         xs[q] = (i >= 0 && i < n) ? (float)x[i] : 0.f;
     }
-    if (tid == 0) *s_any = 0;
+    if (tid == 0) *lds.any = 0;
     __syncthreads();
 
     // ---- r over the tile and 2 L to either side; the tile's own peaks and count ----
@@ -142,77 +117,28 @@ __global__ __launch_bounds__(LM_THREADS) void limit_tile_kernel(const LimitArgs 
         const long i = base - 2 * L + q;
         double rv = 1.0;
         if (i >= 0 && i < n) {
-            const double uc = (double)xs[q + hw] * gu;
-            double p = fabs(uc);
-            if (OS > 1) {
-                double acc[OS];
-#pragma unroll
-                for (int ph = 0; ph < OS; ++ph) acc[ph] = 0.0;
-                const double* hh = a.h + OS * 2 * hw;           // tap ph + os (2 hw - d) meets sample i - hw + d
-                for (int d = 0; d <= 2 * hw; ++d) {
-                    const double uv = (double)xs[q + d] * gu;
-#pragma unroll
-                    for (int ph = 0; ph < OS; ++ph)
-                        if (ph == 0 || d > 0) acc[ph] = fma(uv, hh[ph - OS * d], acc[ph]);
-                }
-#pragma unroll
-                for (int ph = 0; ph < OS; ++ph) p = fmax(p, fabs(acc[ph]));
-            }
+            // (the sample alone decides "not finite" here: the measure flags the whole row, and the apply then copies it)
+            const double p = lm_envelope<OS, false>(xs + q, hw, gu, a.h);
             if (p > c) rv = c / p;
             if (!APPLY && q >= 2 * L && q < 2 * L + LM_TILE) {
+                const double au = fabs((double)xs[q + hw] * gu);
                 tp = fmax(tp, p);
-                sp = fmax(sp, fabs(uc));
+                sp = fmax(sp, au);
                 cnt += p > c ? 1.0 : 0.0;
-                bad |= !(fabs(uc) < (double)INFINITY);
+                bad |= !(au < (double)INFINITY);
             }
         }
         A[q] = rv;
         any |= rv < 1.0;
     }
-    if (any) *s_any = 1;
+    if (any) *lds.any = 1;
     __syncthreads();                                            // (A is whole)
-    any = *s_any;
+    any = *lds.any;
 
     double s[LM_OUT];
 #pragma unroll
     for (int e = 0; e < LM_OUT; ++e) s[e] = 1.0;
-    if (any) {
-        double rs[LM_OUT];
-#pragma unroll
-        for (int e = 0; e < LM_OUT; ++e) rs[e] = A[2 * L + tid + e * LM_THREADS];
-        // ---- the minimum over 2 L + 1 by doubling, in place: read, barrier, write, barrier ----
-        const int W = 2 * L + 1;
-        double v[LM_EPT];
-        int win = 1;
-        while (win < W) {
-            const int sh = 2 * win <= W ? win : W - win;        // the last step overlaps
-#pragma unroll
-            for (int e = 0; e < LM_EPT; ++e) {
-                const int q = tid + e * LM_THREADS;
-                if (q + sh < E) v[e] = fmin(A[q], A[q + sh]);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < LM_EPT; ++e) {
-                const int q = tid + e * LM_THREADS;
-                if (q + sh < E) A[q] = v[e];
-            }
-            __syncthreads();
-            win += sh;
-        }
-        // ---- A[b] is now m at base - L + b: the window sum of the thread's outputs, in ascending k ----
-        double acc[LM_OUT];
-#pragma unroll
-        for (int e = 0; e < LM_OUT; ++e) acc[e] = 0.0;
-        const double* m = A + tid;
-        for (int k = 0; k < W; ++k) {
-            const double wk = a.w[k];
-#pragma unroll
-            for (int e = 0; e < LM_OUT; ++e) acc[e] = fma(wk, m[k + e * LM_THREADS], acc[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < LM_OUT; ++e) s[e] = fmin(rs[e], acc[e]);
-    }
+    if (any) lm_min_window_sum(A, E, L, a.w, tid, s);
 
     if (APPLY) {
 #pragma unroll
@@ -230,30 +156,17 @@ __global__ __launch_bounds__(LM_THREADS) void limit_tile_kernel(const LimitArgs 
 #pragma unroll
     for (int e = 0; e < LM_OUT; ++e)
         if (base + tid + e * LM_THREADS < n) smin = fmin(smin, s[e]);
-    if (bad) cnt = -(double)(1L << 40);
-    for (int off = 32; off; off >>= 1) {
-        tp = fmax(tp, __shfl_xor(tp, off));
-        sp = fmax(sp, __shfl_xor(sp, off));
-        smin = fmin(smin, __shfl_xor(smin, off));
-        cnt += __shfl_xor(cnt, off);                            // (integers below 2^53: exact in any order)
-    }
-    if ((tid & 63) == 0) {
-        s_red[0][tid >> 6] = tp; s_red[1][tid >> 6] = sp; s_red[2][tid >> 6] = smin; s_red[3][tid >> 6] = cnt;
-    }
-    __syncthreads();
+    lm_reduce(lds.red, tid, tp, sp, smin, cnt, bad);
     if (tid == 0) {
-        for (int wv = 1; wv < LM_THREADS / 64; ++wv) {
-            tp = fmax(tp, s_red[0][wv]); sp = fmax(sp, s_red[1][wv]); smin = fmin(smin, s_red[2][wv]); cnt += s_red[3][wv];
-        }
         double* o = a.scratch + ((size_t)r * a.tiles_max + blockIdx.x) * 4;
-        o[0] = tp; o[1] = sp; o[2] = smin; o[3] = cnt < 0.0 ? -1.0 : cnt;
+        o[0] = tp; o[1] = sp; o[2] = smin; o[3] = bad ? -1.0 : cnt;
     }
 }
 
 __global__ __launch_bounds__(64) void limit_reduce_kernel(const LimitArgs a) {
     const int tid = threadIdx.x, r = blockIdx.x;
     const long* t = a.table + 2 * (size_t)r;
-    const long n = lm_count(t[0], t[1], a.src_len, a.max_count);
+    const long n = pcm_src_count(t[0], t[1], a.src_len, a.max_count);
     const long nt = (n + LM_TILE - 1) / LM_TILE;                // <= tiles_max, since n <= max_count
     const double* tiles = a.scratch + (size_t)r * a.tiles_max * 4;
     double tp = 0.0, sp = 0.0, smin = 1.0, cnt = 0.0;
@@ -283,15 +196,10 @@ __global__ __launch_bounds__(64) void limit_reduce_kernel(const LimitArgs a) {
     }
 }
 
-static size_t lm_lds(const LimitArgs& a) {
-    const size_t E = LM_TILE + 4 * (size_t)a.L;
-    return 8 * LM_HEAD + 8 * E + 4 * ((E + 2 * (size_t)a.hw + 3) & ~(size_t)3);
-}
-
 template <typename TSrc, typename TDst, bool APPLY>
 static void lm_launch(const LimitArgs& a, dim3 grid, hipStream_t s) {
     const dim3 block(LM_THREADS);
-    const size_t lds = lm_lds(a);
+    const size_t lds = lm_tile_lds_bytes(a.L, a.hw);
     if (a.os == 1) hipLaunchKernelGGL((limit_tile_kernel<TSrc, TDst, 1, APPLY>), grid, block, lds, s, a);
     else if (a.os == 2) hipLaunchKernelGGL((limit_tile_kernel<TSrc, TDst, 2, APPLY>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((limit_tile_kernel<TSrc, TDst, 4, APPLY>), grid, block, lds, s, a);
@@ -324,19 +232,6 @@ static hipError_t lm_launch_apply(const LimitArgs& a, int src_kind, hipStream_t 
 }
 
 // ---- the extern "C" boundary ----------------------------------------------------------------------------------------------------------
-static inline bool lm_al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-
-// what both entry points refuse about the filter, the window and the ceiling
-static bool lm_params_ok(const double* gains, const double* h, int n_taps, int os, int half_width, const double* w, int lookahead,
-                         double ceiling) {
-    if (!h || !w || !lm_al8(h) || !lm_al8(w) || !lm_al8(gains)) return false;
-    if (os != 1 && os != 2 && os != 4) return false;
-    if (half_width < 1 || half_width > LM_MAX_HW || n_taps != 2 * half_width * os + 1) return false;
-    if (lookahead < 0 || lookahead > LM_MAX_L) return false;
-    // (a comparison with NaN is false, the subtraction is NaN for an infinity)
-    return ceiling > 0.0 && ceiling - ceiling == 0.0 && (double)(float)ceiling == ceiling;
-}
-
 extern "C" {
 
 int t2s_limit_tile(void) { return LM_TILE; }
@@ -351,7 +246,7 @@ long t2s_limit_scratch(int n_rows, long max_count) {
 int t2s_limit_measure(const void* src, int src_kind, long src_len, const long* table, int n_rows, long max_count, const double* gains,
                       const double* h, int n_taps, int os, int half_width, const double* w, int lookahead, double ceiling,
                       double* scratch, long scratch_len, double* stats, int* counts, void* stream) {
-    if (!src || !table || !scratch || !stats || !counts || !lm_al8(table) || !lm_al8(scratch) || !lm_al8(stats) ||
+    if (!src || !table || !scratch || !stats || !counts || !aligned_to(table, 8) || !aligned_to(scratch, 8) || !aligned_to(stats, 8) ||
         ((uintptr_t)counts & 3) || src_kind < 0 || src_kind > 2 || src_len <= 0 || n_rows <= 0 || n_rows > 65535 || max_count <= 0 ||
         max_count > 0x7fffffffL || !lm_params_ok(gains, h, n_taps, os, half_width, w, lookahead, ceiling) ||
         scratch_len < t2s_limit_scratch(n_rows, max_count))
@@ -368,7 +263,7 @@ int t2s_limit_measure(const void* src, int src_kind, long src_len, const long* t
 int t2s_limit_apply(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* gains, const double* h,
                     int n_taps, int os, int half_width, const double* w, int lookahead, double ceiling, const int* counts, void* dst,
                     int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream) {
-    if (!src || !table || !counts || !dst || !lm_al8(table) || ((uintptr_t)counts & 3) || ((uintptr_t)out_lengths & 3) || src_kind < 0 ||
+    if (!src || !table || !counts || !dst || !aligned_to(table, 8) || ((uintptr_t)counts & 3) || ((uintptr_t)out_lengths & 3) || src_kind < 0 ||
         src_kind > 2 || dst_kind != (src_kind == 0 ? 0 : 1) || src_len <= 0 || dst_len <= 0 || n_rows <= 0 || n_rows > 65535 ||
         max_out <= 0 || max_out > (1L << 40) || !lm_params_ok(gains, h, n_taps, os, half_width, w, lookahead, ceiling))
         return T2S_EINVAL;

@@ -28,9 +28,11 @@
 // batch or pool, at any alignment, whatever lies behind its length.
 //
 // Memory safety: src_count is cut to what lies inside [0, src_len) and to max_count, which sizes the grid and the scratch; the
-// destination to [dst_start, dst_start + dst_cap) inside [0, dst_len); all of it in 64-bit, whatever the tables hold.
+// destination to [dst_start, dst_start + dst_cap) inside [0, dst_len); all of it in 64-bit, whatever the tables hold
+// (csrc/pcm_rows.h).
 #include "t2s_common.h"
 #include "audio_ops.h"
+#include "pcm_rows.h"
 
 #include <limits.h>
 #include <math.h>
@@ -46,12 +48,6 @@ static_assert(LD_THREADS * LD_S == T2S_LOUD_TILE, "a tile is one segment per lan
 static_assert((1 << LD_STEPS) == LD_THREADS, "the scan covers the workgroup");
 static_assert(T2S_LOUD_TILE % (LD_THREADS * LD_UNROLL) == 0, "staging loop");
 static_assert(T2S_LOUD_HOPS <= LD_THREADS, "one thread per hop of a tile");
-
-static __device__ __forceinline__ long ld_count(long s0, long n, long src_len, long max_count) {
-    if (n < 0 || s0 < 0 || s0 >= src_len) return 0;
-    if (n > src_len - s0) n = src_len - s0;
-    return n > max_count ? max_count : n;
-}
 
 static __device__ __forceinline__ double ld_abs(float v) {
     const double a = fabs((double)v);
@@ -83,7 +79,7 @@ __global__ __launch_bounds__(LD_THREADS) void loud_tile_kernel(const LoudMeasure
     const int tid = threadIdx.x, r = blockIdx.y;
     const long* t = a.table + 2 * (size_t)r;
     const long s0 = t[0];
-    const long n = ld_count(s0, t[1], a.src_len, a.max_count);
+    const long n = pcm_src_count(s0, t[1], a.src_len, a.max_count);
     const long base = (long)blockIdx.x * T2S_LOUD_TILE;
     if (base >= n) return;                                      // (the whole workgroup)
     const int m = n - base < T2S_LOUD_TILE ? (int)(n - base) : T2S_LOUD_TILE;
@@ -203,7 +199,7 @@ __global__ __launch_bounds__(64) void loud_chain_kernel(const LoudMeasureArgs a)
     const int r = blockIdx.x * 64 + threadIdx.x;
     if (r >= a.n_rows) return;
     const long* t = a.table + 2 * (size_t)r;
-    const long n = ld_count(t[0], t[1], a.src_len, a.max_count);
+    const long n = pcm_src_count(t[0], t[1], a.src_len, a.max_count);
     const long nt = (n + T2S_LOUD_TILE - 1) / T2S_LOUD_TILE;    // <= tiles_max, since n <= max_count
     double* tile = a.scratch + (size_t)r * a.row_doubles;
     const double* P = a.coef + T2S_LOUD_COEF_TILE;
@@ -231,7 +227,7 @@ __global__ __launch_bounds__(LD_THREADS) void loud_gate_kernel(const LoudMeasure
     __shared__ double s_b[2];
     const int tid = threadIdx.x, r = blockIdx.x;
     const long* t = a.table + 2 * (size_t)r;
-    const long n = ld_count(t[0], t[1], a.src_len, a.max_count);
+    const long n = pcm_src_count(t[0], t[1], a.src_len, a.max_count);
     const long h = a.h;
     const long nt = (n + T2S_LOUD_TILE - 1) / T2S_LOUD_TILE;
     long nh = n / h;
@@ -332,13 +328,7 @@ __global__ __launch_bounds__(LD_THREADS) void loud_gate_kernel(const LoudMeasure
     ct[0] = (int)J; ct[1] = (int)nA; ct[2] = (int)nR; ct[3] = flags;
 }
 
-static __device__ __forceinline__ short ld_round16(double v) {
-    const double q = rint(v);                                   // ties to even
-    if (q >= 32767.0) return 32767;
-    if (q <= -32768.0) return -32768;
-    return q == q ? (short)(int)q : (short)0;                   // NaN: 0
-}
-static __device__ __forceinline__ void ld_put(short* p, short x, bool scaled, double g) { *p = scaled ? ld_round16((double)x * g) : x; }
+static __device__ __forceinline__ void ld_put(short* p, short x, bool scaled, double g) { *p = scaled ? pcm_round16((double)x * g) : x; }
 static __device__ __forceinline__ void ld_put(float* p, float x, bool scaled, double g) { *p = scaled ? (float)((double)x * g) : x; }
 static __device__ __forceinline__ void ld_put(float* p, _Float16 x, bool scaled, double g) { ld_put(p, (float)x, scaled, g); }
 
@@ -348,11 +338,8 @@ __global__ __launch_bounds__(LD_THREADS) void loud_apply_kernel(const LoudApplyA
     const long m0 = (long)blockIdx.x * LD_APPLY_TILE;
     const long* t = a.table + 4 * (size_t)r;
     const long s0 = t[0], d0 = t[2];
-    long cap = t[3];
-    const long n = ld_count(s0, t[1], a.src_len, LONG_MAX);
-    if (cap > a.max_out) cap = a.max_out;
-    if (cap < 0 || d0 < 0 || d0 >= a.dst_len) cap = 0;
-    else if (cap > a.dst_len - d0) cap = a.dst_len - d0;
+    const long cap = pcm_dst_cap(t[3], a.max_out, d0, a.dst_len);
+    const long n = pcm_src_count(s0, t[1], a.src_len);
     const long valid = n < cap ? n : cap;
     if (blockIdx.x == 0 && tid == 0 && a.out_lengths) a.out_lengths[r] = valid > INT_MAX ? INT_MAX : (int)valid;
     if (m0 >= cap) return;

@@ -16,22 +16,19 @@
 // clip's bits are the same alone and in any batch, and the int16 result is the rounding of the float64 sum.
 //
 // Memory safety: a row's (src_start, src_count, dst_start, dst_cap) are clamped so that only [0, src_len) is read and only
-// [dst_start, dst_start + dst_cap) inside [0, dst_len) is written, whatever the table or lengths hold; all of it in 64-bit.
+// [dst_start, dst_start + dst_cap) inside [0, dst_len) is written, whatever the table or lengths hold; all of it in 64-bit
+// (csrc/pcm_rows.h).
+//
+// The phase table and the loop of one output are csrc/resample_tap.h's, which the stream's window kernel (csrc/delivery.hip) runs
+// too.
 #include "t2s_common.h"
 #include "audio_ops.h"
+#include "pcm_rows.h"
+#include "resample_tap.h"
 
 #include <limits.h>
 
-#define RS_THREADS 256
-
-static __device__ __forceinline__ void rs_put(short* p, double v) {
-    const double r = rint(v);                               // ties to even
-    short s = 0;                                            // NaN
-    if (r >= 32767.0) s = 32767;
-    else if (r <= -32768.0) s = -32768;
-    else if (r == r) s = (short)(int)r;
-    *p = s;
-}
+static __device__ __forceinline__ void rs_put(short* p, double v) { *p = pcm_round16(v); }
 static __device__ __forceinline__ void rs_put(float* p, double v) { *p = (float)v; }      // one rounding
 
 template <typename TSrc, typename TDst>
@@ -50,11 +47,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const ResampleArgs
         d0 = (long)r * a.ldo;
         cap = a.N_out;
     }
-    if (n_in < 0 || s0 < 0 || s0 >= a.src_len) n_in = 0;
-    else if (n_in > a.src_len - s0) n_in = a.src_len - s0;
-    if (cap > a.max_out) cap = a.max_out;
-    if (cap < 0 || d0 < 0 || d0 >= a.dst_len) cap = 0;
-    else if (cap > a.dst_len - d0) cap = a.dst_len - d0;
+    n_in = pcm_src_count(s0, n_in, a.src_len);
+    cap = pcm_dst_cap(cap, a.max_out, d0, a.dst_len);
     const long up = a.up, down = a.down;
     const long n_out = n_in > (LONG_MAX - down) / up ? LONG_MAX : (n_in * up + down - 1) / down;
     const long valid = n_out < cap ? n_out : cap;
@@ -66,30 +60,14 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const ResampleArgs
         for (int o = tid; o < T2S_RESAMPLE_TILE && m0 + o < cap; o += RS_THREADS) out[m0 + o] = (TDst)0;
         return;
     }
-    const int n_taps = a.n_taps, lp = a.lp;
-    for (int j = tid; j < n_taps; j += RS_THREADS) rs_hp[(j % a.up) * lp + j / a.up] = a.h[j];
-    __syncthreads();
+    rs_stage_phases(rs_hp, a.h, a.n_taps, a.up, a.lp, tid);
 
-    const int L = (n_taps + a.up - 1) / a.up;               // taps of the longest phase
-    const long c0 = (long)(n_taps / 2) + m0 * down;         // h's index under input sample 0, for output m0
-    const long q0 = c0 / up;
-    const unsigned r0 = (unsigned)(c0 % up);
-    const TSrc* x = (const TSrc*)a.src + s0;
+    const RsTile tile(m0, a.n_taps, a.up, a.down, a.lp);
+    const RsRow<TSrc> row{(const TSrc*)a.src + s0, n_in};
     for (int o = tid; o < T2S_RESAMPLE_TILE; o += RS_THREADS) {
         const long m = m0 + o;
         if (m >= cap) break;
-        double acc = 0.0;
-        if (m < valid) {
-            const unsigned e = r0 + (unsigned)o * (unsigned)a.down;          // < 512 + 1023 * 512
-            const unsigned p = e % (unsigned)a.up;
-            const long kc = q0 + e / (unsigned)a.up;                          // the sample under tap p; tap p + i up is under kc - i
-            const int cnt = L - ((long)p + (long)(L - 1) * up >= n_taps ? 1 : 0);
-            const long k_lo = kc - (cnt - 1) > 0 ? kc - (cnt - 1) : 0;
-            const long k_hi = kc < n_in - 1 ? kc : n_in - 1;
-            const double* hrow = rs_hp + (size_t)p * lp;
-            for (long k = k_lo; k <= k_hi; ++k) acc = fma((double)x[k], hrow[kc - k], acc);
-        }
-        rs_put(out + m, acc);
+        rs_put(out + m, m < valid ? tile.output(o, row, rs_hp) : 0.0);
     }
 }
 

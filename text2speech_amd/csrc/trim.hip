@@ -20,9 +20,10 @@
 //
 // Memory safety: src_count is cut to what lies inside [0, src_len), the frame count to max_frames and to what the scratch holds
 // behind energy_start, the destination to [dst_start, dst_start + dst_cap) inside [0, dst_len), bounds to [0, src_count]; all of it
-// in 64-bit, whatever the tables hold.
+// in 64-bit, whatever the tables hold (csrc/pcm_rows.h).
 #include "t2s_common.h"
 #include "audio_ops.h"
+#include "pcm_rows.h"
 
 #include <limits.h>
 #include <math.h>
@@ -34,11 +35,6 @@
 #define TR_GATHER_TILE 2048                     // outputs of one row per workgroup of the gather
 
 static_assert(TR_LDS_FLOATS >= T2S_TRIM_MAX_FRAME, "one frame must fit");
-
-static __device__ __forceinline__ long tr_count(long s0, long n, long src_len) {
-    if (n < 0 || s0 < 0 || s0 >= src_len) return 0;
-    return n > src_len - s0 ? src_len - s0 : n;
-}
 
 // frames of a row of n samples that the scratch holds: 1 + (n + 2 pad - fl) / h, none for a reflect row of at most pad samples
 static __device__ __forceinline__ long tr_frames(long n, int fl, int h, int reflect, long e0, long energy_len, long max_frames) {
@@ -66,7 +62,7 @@ __global__ __launch_bounds__(TR_THREADS) void trim_energy_kernel(const TrimEnerg
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.y;
     const long* t = a.table + 3 * (size_t)r;
     const long s0 = t[0], e0 = t[2];
-    const long n = tr_count(s0, t[1], a.src_len);
+    const long n = pcm_src_count(s0, t[1], a.src_len);
     const int fl = a.frame_length, h = a.hop, pad = fl / 2, reflect = a.reflect;
     const long nf = a.energy ? tr_frames(n, fl, h, reflect, e0, a.energy_len, a.max_frames) : 0;
     const TSrc* x = (const TSrc*)a.src + (n > 0 ? s0 : 0);
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(TR_THREADS) void trim_bounds_kernel(const TrimBound
     const int tid = threadIdx.x, r = blockIdx.x;
     const long* t = a.table + 3 * (size_t)r;
     const long e0 = t[2];
-    const long n = tr_count(t[0], t[1], a.src_len);
+    const long n = pcm_src_count(t[0], t[1], a.src_len);
     const long nf = tr_frames(n, a.frame_length, a.hop, a.reflect, e0, a.energy_len, a.max_frames);
     const double peak = a.stats[2 * (size_t)r], e_max = a.stats[2 * (size_t)r + 1];
     long first = LONG_MAX, last = -1;
@@ -185,13 +181,7 @@ __global__ __launch_bounds__(TR_THREADS) void trim_bounds_kernel(const TrimBound
     }
 }
 
-static __device__ __forceinline__ short tr_round16(double v) {
-    const double q = rint(v);                                   // ties to even
-    if (q >= 32767.0) return 32767;
-    if (q <= -32768.0) return -32768;
-    return q == q ? (short)(int)q : (short)0;                   // NaN: 0
-}
-static __device__ __forceinline__ void tr_put(short* p, short x, int scaled, double s) { *p = scaled ? tr_round16((double)x * s) : x; }
+static __device__ __forceinline__ void tr_put(short* p, short x, int scaled, double s) { *p = scaled ? pcm_round16((double)x * s) : x; }
 static __device__ __forceinline__ void tr_put(float* p, float x, int scaled, double s) { *p = scaled ? (float)((double)x * s) : x; }
 static __device__ __forceinline__ void tr_put(float* p, _Float16 x, int scaled, double s) { tr_put(p, (float)x, scaled, s); }
 
@@ -200,11 +190,9 @@ __global__ __launch_bounds__(TR_THREADS) void trim_gather_kernel(const TrimGathe
     const int tid = threadIdx.x, r = blockIdx.y;
     const long m0 = (long)blockIdx.x * TR_GATHER_TILE;
     const long* t = a.table + 4 * (size_t)r;
-    long s0 = t[0], d0 = t[2], cap = t[3];
-    long n = tr_count(s0, t[1], a.src_len);
-    if (cap > a.max_out) cap = a.max_out;
-    if (cap < 0 || d0 < 0 || d0 >= a.dst_len) cap = 0;
-    else if (cap > a.dst_len - d0) cap = a.dst_len - d0;
+    long s0 = t[0];
+    const long d0 = t[2], cap = pcm_dst_cap(t[3], a.max_out, d0, a.dst_len);
+    long n = pcm_src_count(s0, t[1], a.src_len);
     if (a.bounds) {                                             // the kept range of the row, cut to the row
         long b0 = a.bounds[2 * (size_t)r], b1 = a.bounds[2 * (size_t)r + 1];
         if (b0 < 0) b0 = 0;
