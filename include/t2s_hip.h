@@ -1344,6 +1344,60 @@ int t2s_warp_spans(const long* cum, const int* first_last, int B, int F, int T_i
                    const long* trim_start, const long* trim_end, const long* offsets, long up, long down, long total,
                    const long* total_dev, long* spans, void* stream);
 
+/* ---- control inside a stream: the alignment check and the time warp, pushed piece by piece (additive to ABI version 4;
+ *      alignment.py AlignmentStream, rate.py WarpStream, streaming.py synthesize_stream(control=); csrc/stream_ctl.hip) ----
+ * Both computations above are prefix computations, so a stream carries them in HBM.  Notation: all buffers hold N_cap frames (the
+ * decoder's max_decoder_steps); n0 frames were seen before this push and n after it, 0 <= n0 <= n <= N_cap.  The guarantee: after
+ * every push the outputs are what the whole-row entry points give for the prefix [0, n), bit for bit, whatever the cuts.
+ * t2s_align_window
+ *  - A: B entries of n - n0 rows of T_in columns, the frames [n0, n); rows ld_row >= T_in and entries ld_entry >= (n - n0) ld_row
+ *    elements apart; src_kind 1 f32, 2 f16.  NULL is allowed where n == n0.  S_b = clamp(in_len[b], 1, T_in), in_len NULL: T_in.
+ *  - Row pass: t2s_align_rows' scan (ties to the smaller column, a NaN is never chosen) writes pos / peak / bad at columns [n0, n) of
+ *    the [B, N_cap] buffers, which persist over the stream.  Columns at and behind n are not written.
+ *  - Entry pass: one workgroup per entry walks the new frames 256 at a time.  Its running values live in a state block per entry
+ *    (t2s_align_window_state() bytes each, 8-byte aligned): the run-start carry, the maxima of skip / back / stall, covered and
+ *    bad_rows, and 256 double partial sums of the peaks.  A push with n0 == 0 initialises the block, and stores +0 to all of dur on
+ *    the same stream before its kernels; later pushes add to dur by the same integer atomics.
+ *  - Peak sums: frame t is added into partial t % 256 in ascending t, whatever the cuts; the 256-way tree of t2s_align_stats is
+ *    formed on every push from the current partials.  focus is therefore t2s_align_stats' bits for the prefix on every push.
+ *  - Stall: a run still open at frame n - 1 counts with its current length, as t2s_align_stats counts its last run.
+ *  - Outputs, rewritten on every push: stats [B, 8], focus [B] and flags [B] of the prefix [0, n), F_b = n.  On a push with
+ *    last == 0, flags carries only the live bits SKIP, BACK, STALL and NONFINITE; with last == 1 all eight, max_frames for TRUNCATED.
+ *  - An empty push (n == n0) launches the entry pass alone: the outputs are rewritten, e.g. with the bits of last == 1.
+ *  Memory safety as t2s_align_stats: every length is clamped, n0 and n as well; no pos that was read back is trusted.
+ *  T2S_EINVAL, with nothing launched and nothing written: a NULL pos, peak, bad, state, stats, focus, dur or flags; A NULL with n > n0;
+ *  a pointer not aligned to its element (state and focus to 8); B, T_in or N_cap < 1; N_cap > 2^30; B N_cap > 2^31 - 1; n0 < 0, n < n0
+ *  or n > N_cap; ld_row < T_in; ld_entry < (n - n0) ld_row; a src_kind other than 1 or 2; a last other than 0 or 1.
+ * t2s_warp_window_map
+ *  - t2s_warp_map's step over the frames [n0, n), one stretch per entry for this push: `stretch`, or stretches int64 [B] in device
+ *    memory, each clamped to [Q / 8, 8 Q] on the device.  It may differ from push to push.
+ *  - cum int64 [B, N_cap + 1] persists and is the carry: cum[b, n0 + 1 .. n] is extended from the stored cum[b, n0]; n0 == 0 writes
+ *    cum[b, 0] = 0.  Entries behind n are not written.
+ *  - With path (int32, rows ld_path >= n apart - t2s_align_window's pos) and first_last int32 [B, T_in, 2]: frames [n0, n) apply
+ *    t2s_warp_map's two tests with F_b = n.  A run's first frame is f == 0 or path[f - 1] != k, its last frame so far f == n - 1 or
+ *    path[f + 1] != k; first only ever decreases, last only ever increases, so after any push first_last is t2s_warp_map's for the
+ *    prefix.  The call sets first_last to -1 where n0 == 0 only.  t2s_warp_spans reads cum and first_last as they are, with F =
+ *    N_cap and lengths = n.
+ *  T2S_EINVAL: a NULL cum; first_last without path; path with T_in < 1 or ld_path < n; a pointer not aligned to its element; B < 1 or
+ *  > 65535; B T_in > 2^31 - 1; the frames as above; without stretches, a stretch outside [Q / 8, 8 Q].
+ * t2s_warp_window_gather
+ *  - Writes output columns [j0, j1) of the warped mel to out [B, C, j1 - j0], dense and of x's type: t2s_warp_gather's expression
+ *    exactly, with F_b = n.  x is the mel known so far, B entries of C rows of >= n frames, rows ld_row >= n and entries ld_entry >=
+ *    C ld_row elements apart.  A column j is settled - no later frame changes it - when (2j + 1) Q <= c[n - 1] + c[n]; a caller who
+ *    asks only for settled columns never reaches the clamp at F_b - 1 before the utterance's last push.
+ *  - j1 == j0 launches nothing.
+ *  T2S_EINVAL: a NULL cum; j0 < 0, j1 < j0, j1 > 2^31 - 1; and where j1 > j0: a NULL x or out, n < 1, ld_row < n, ld_entry < C ld_row,
+ *  misaligned x or out, x overlapping out; C < 1; a src_kind other than 1 or 2; B and the frames as above. */
+int t2s_align_window_state(void);
+int t2s_align_window(const void* A, int src_kind, int B, int N_cap, int T_in, int n0, int n, int last, long ld_row, long ld_entry,
+                     const int* in_len, int max_frames, int skip_max, int back_max, int stall_max, int end_slack, double min_focus,
+                     int* pos, float* peak, unsigned char* bad, void* state, int* stats, double* focus, int* dur, int* flags,
+                     void* stream);
+int t2s_warp_window_map(int B, int N_cap, int n0, int n, long stretch, const long* stretches, const int* path, long ld_path,
+                        const int* in_len, int T_in, long* cum, int* first_last, void* stream);
+int t2s_warp_window_gather(const void* x, int src_kind, int B, int C, int N_cap, int n, long ld_row, long ld_entry, const long* cum,
+                           long j0, long j1, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,11 @@ SIGNATURES = {
                      c_vp, c_vp],
     "t2s_warp_gather": [c_vp, c_int, c_int, c_int, c_int, c_long, c_long, c_vp, c_vp, c_vp, c_vp, c_int, c_vp],
     "t2s_warp_spans": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_long, c_long, c_long, c_vp, c_vp, c_vp],
+    "t2s_align_window_state": [],
+    "t2s_align_window": [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_vp, c_int, c_int, c_int, c_int, c_int,
+                         c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "t2s_warp_window_map": [c_int, c_int, c_int, c_int, c_long, c_vp, c_vp, c_long, c_vp, c_int, c_vp, c_vp, c_vp],
+    "t2s_warp_window_gather": [c_vp, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_vp, c_long, c_long, c_vp, c_vp],
     "t2s_bernoulli_mask_keyed": [c_vp, c_int, c_int, c_int, c_vp, c_float, c_vp],
     "t2s_noise_tile": [],
     "t2s_wg_noise_keyed": [c_vp, c_int, c_int, c_long, c_vp, c_float, c_vp, c_vp],

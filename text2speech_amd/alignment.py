@@ -5,7 +5,9 @@ looks at the alignments that ``Tacotron.inference`` / ``inference_batch`` / ``fo
 include/t2s_hip.h states the arithmetic): per frame the symbol it attends to, per entry the largest forward and backward step, the
 longest stall, the last symbol reached, the frames each symbol got (its duration) and the mean attention peak - and the flag bits that
 an ``AlignmentCheck``'s thresholds make of them.  ``synthesize_long(check=, max_attempts=)`` decodes a flagged chunk again under
-``attempt_seeds``: the prenet dropout is live in eval mode, so another seed is another attention path."""
+``attempt_seeds``: the prenet dropout is live in eval mode, so another seed is another attention path.  ``AlignmentStream`` is the same
+report pushed piece by piece while an utterance is still decoded (csrc/stream_ctl.hip): the watchdog of
+``synthesize_stream(control=StreamControl(check=))``, which ends a stream whose attention fails instead of speaking it out."""
 import collections
 
 import torch
@@ -13,7 +15,7 @@ import torch
 from . import _lib, sampling
 from .longform import _MASK, mix
 
-__all__ = ["AlignmentCheck", "AlignmentReport", "alignment_report", "attempt_seeds", "FLAG_NAMES", "STAT_NAMES"]
+__all__ = ["AlignmentCheck", "AlignmentReport", "alignment_report", "AlignmentStream", "attempt_seeds", "FLAG_NAMES", "STAT_NAMES", "LIVE"]
 
 TRUNCATED, SKIP, BACK, STALL, UNFINISHED, DIFFUSE, NONFINITE, EMPTY = 1, 2, 4, 8, 16, 32, 64, 128
 FLAG_NAMES = {TRUNCATED: "TRUNCATED", SKIP: "SKIP", BACK: "BACK", STALL: "STALL", UNFINISHED: "UNFINISHED", DIFFUSE: "DIFFUSE",
@@ -165,3 +167,125 @@ def alignment_report(alignments, input_lengths=None, output_lengths=None, check=
         _lib.call("t2s_align_stats", p(path), p(peak), p(bad), B, N, T, p(in_len), p(out_len), *check.thresholds(), p(stats),
                   p(focus), p(dur), p(flags), st)
     return AlignmentReport(flags, stats, focus, dur, path)
+
+
+LIVE = SKIP | BACK | STALL | NONFINITE      # the bits a stream's prefix can already decide; the others wait for its last push
+
+
+class AlignmentStream:
+    """``alignment_report`` pushed piece by piece while the utterance is still decoded (csrc/stream_ctl.hip): the watchdog of a stream.
+
+    ``check`` an ``AlignmentCheck`` (None: the defaults; its ``max_frames=None`` is ``capacity``), ``n_symbols`` the columns of an
+    alignment row, ``capacity`` the most frames there can be (the decoder's max_decoder_steps), ``B`` entries that grow together,
+    ``input_lengths`` their symbols (None: n_symbols).
+
+    ``push(align_piece [B, n, n_symbols], last)`` - float32 or float16, what ``Tacotron.inference_stream`` yields as ``piece[3]`` -
+    enqueues the window kernels and an asynchronous copy of flags and stats into page-locked memory, with an event behind it: no
+    wait, and nothing is read on the host.  After every push the buffers on the device hold what ``alignment_report`` gives for the
+    frames seen so far, bit for bit (the running maxima, the counts and the 256 partial sums of the peaks are carried in HBM); the
+    flags of a push not flagged ``last`` carry only the ``LIVE`` bits - SKIP, BACK, STALL, NONFINITE - and those of the last push
+    all eight.  A stall counts while it is still open, so it is seen while it happens.
+
+    ``report()``: an ``AlignmentReport`` of the prefix, on the device (copies; ``path`` holds the frames seen).  ``poll()``: the host
+    ``(flags int32 [B], stats int32 [B, 8])`` of the latest push whose copy has completed, or None; ``wait()``: the same for the
+    latest push, after ``event.synchronize()``.  ``path`` int32 [B, capacity] is the persistent buffer a ``WarpStream`` reads."""
+    SLOTS = 4
+
+    def __init__(self, check, n_symbols, capacity, device, B=1, input_lengths=None):
+        who = "AlignmentStream"
+        T2SError = _lib.T2SError
+        if check is None:
+            check = AlignmentCheck()
+        elif not isinstance(check, AlignmentCheck):
+            raise T2SError("%s: check must be an AlignmentCheck, got a %s" % (who, type(check).__name__))
+        for name, v in (("n_symbols", n_symbols), ("capacity", capacity), ("B", B)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError("%s: %s must be an integer >= 1, got %r" % (who, name, v))
+        if capacity > 2 ** 30 or B * capacity > 2 ** 31 - 1:
+            raise T2SError("%s: %d x %d frames, the most is 2^31 - 1 (2^30 an entry)" % (who, B, capacity))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise T2SError("%s: the stream lives in HBM (cuda); there is no CPU path" % who)
+        self.check, self.n_symbols, self.capacity, self.device, self.B = check, n_symbols, capacity, dev, B
+        self._thr = check.thresholds(capacity)
+        self._in_len = _lengths(input_lengths, B, dev, "input_lengths")
+        nbytes = _lib.load().t2s_align_window_state()
+        with torch.cuda.device(dev):
+            self.path = torch.empty(B, capacity, dtype=torch.int32, device=dev)
+            self._peak = torch.empty(B, capacity, dtype=torch.float32, device=dev)
+            self._bad = torch.empty(B, capacity, dtype=torch.uint8, device=dev)
+            self._state = torch.empty(B, nbytes // 8, dtype=torch.int64, device=dev)
+            self._out = torch.empty(B, 9, dtype=torch.int32, device=dev).view(-1)       # stats [B, 8], then flags [B]
+            self._focus = torch.empty(B, dtype=torch.float64, device=dev)
+            self._dur = torch.empty(B, n_symbols, dtype=torch.int32, device=dev)
+        self._host = [torch.empty(B * 9, dtype=torch.int32).pin_memory() for _ in range(self.SLOTS)]
+        self._events = [None] * self.SLOTS
+        self.frames = 0
+        self.pushes = 0
+        self.ended = False
+        self._order = _lib.StreamOrder()
+
+    def push(self, align_piece, last):
+        who = "AlignmentStream.push"
+        T2SError = _lib.T2SError
+        if self.ended:
+            raise T2SError("%s: a piece arrived behind the one flagged last" % who)
+        if not (torch.is_tensor(align_piece) and align_piece.is_cuda and align_piece.device == self.device):
+            raise T2SError("%s: expected alignments on %s" % (who, self.device))
+        A = align_piece.detach()
+        if A.dim() != 3 or A.size(0) != self.B or A.size(2) != self.n_symbols:
+            raise T2SError("%s: a piece must be [%d, n, %d], got %s" % (who, self.B, self.n_symbols, tuple(A.shape)))
+        if A.dtype not in _KINDS:
+            raise T2SError("%s: expected float32 or float16, got %s (there is no silent cast)" % (who, A.dtype))
+        m, T, B = A.size(1), self.n_symbols, self.B
+        n0, n = self.frames, self.frames + m
+        if n > self.capacity:
+            raise T2SError("%s: %d frames, the stream was made for %d" % (who, n, self.capacity))
+        ld_row = A.stride(1) if m > 1 else T
+        ld_entry = A.stride(0) if B > 1 else m * ld_row
+        if m and (A.stride(2) != 1 or ld_row < T or ld_entry < m * ld_row):
+            A = A.contiguous()
+            ld_row, ld_entry = T, m * T
+        cur = self._order.enter(self.device)
+        if self._order.switched:
+            _lib.record_stream((self.path, self._peak, self._bad, self._state, self._out, self._focus, self._dur, self._in_len), cur)
+        p = _lib.ptr
+        slot = self.pushes % self.SLOTS
+        with torch.cuda.device(self.device):
+            _lib.call("t2s_align_window", p(A) if m else None, _KINDS[A.dtype], B, self.capacity, T, n0, n, int(bool(last)), ld_row,
+                      ld_entry, p(self._in_len), *self._thr, p(self.path), p(self._peak), p(self._bad), p(self._state),
+                      p(self._out), p(self._focus), p(self._dur), p(self._out[8 * B:]), _lib.current_stream())
+            self._host[slot].copy_(self._out, non_blocking=True)
+            ev = self._events[slot]
+            if ev is None:
+                ev = self._events[slot] = torch.cuda.Event()
+            ev.record(cur)
+        self.frames = n
+        self.pushes += 1
+        self.ended = bool(last)
+
+    def _read(self, slot):
+        h = self._host[slot]
+        return h[8 * self.B:].clone(), h[:8 * self.B].view(self.B, 8).clone()
+
+    def poll(self):
+        """host (flags, stats) of the latest push whose copy has completed; None where there is none yet"""
+        for k in range(self.pushes - 1, max(-1, self.pushes - 1 - self.SLOTS), -1):
+            if self._events[k % self.SLOTS].query():
+                return self._read(k % self.SLOTS)
+        return None
+
+    def wait(self):
+        """host (flags, stats) of the latest push, after waiting for its copy"""
+        if not self.pushes:
+            return None
+        slot = (self.pushes - 1) % self.SLOTS
+        self._events[slot].synchronize()
+        return self._read(slot)
+
+    def report(self):
+        if not self.pushes:
+            raise _lib.T2SError("AlignmentStream.report: nothing has been pushed yet")
+        B, n = self.B, self.frames
+        return AlignmentReport(self._out[8 * B:].clone(), self._out[:8 * B].view(B, 8).clone(), self._focus.clone(), self._dur.clone(),
+                               self.path[:, :n].clone())

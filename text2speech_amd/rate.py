@@ -8,7 +8,11 @@ optionally carried through a ``Trimmer``'s cut, ``join_batches``' offsets and a 
 ``warped_length`` are the host's side of the definition: a caller who knows the frames and a uniform rate knows the warped length
 without a read-back.  ``synthesize_long_timed(speed=, timestamps=)`` is the chain.
 
-Not covered: rates that vary inside a symbol, pitch or energy control, speed inside ``synthesize_stream``."""
+``WarpStream`` is the same warp pushed piece by piece (csrc/stream_ctl.hip): the cumulative map persists in HBM and is its own carry,
+``settled_length`` says which output frames no later frame can change, and the pieces are ``warp_mel``'s frames bit for bit -
+``synthesize_stream(control=StreamControl(speed=))`` is that chain.
+
+Not covered: rates that vary inside a symbol, pitch or energy control, per-symbol rate tables inside a stream."""
 import collections
 import operator
 
@@ -16,7 +20,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["Q", "WarpedMel", "stretch_q", "warped_length", "warp_mel", "symbol_spans"]
+__all__ = ["Q", "WarpedMel", "stretch_q", "warped_length", "settled_length", "warp_mel", "symbol_spans", "WarpStream"]
 
 Q = 1 << 20                    # a stretch counts output frames in units of 1 / Q
 RATE_LO, RATE_HI = 0.125, 8.0  # the library's limits on a rate (include/t2s_hip.h)
@@ -59,6 +63,25 @@ def warped_length(frames, rate, cap=None):
     if frames is None or frames < 0:
         raise ValueError("warped_length: frames must be an integer >= 0")
     return _warped(frames, stretch_q(rate), cap)
+
+
+def settled_length(cum_before_last, cum_last, final=False):
+    """The output frames of a streamed warp that no later source frame can change, over exact Python integers.  With n source frames
+    seen, ``cum_before_last`` = c[n - 1] and ``cum_last`` = c[n] of the cumulative map (both 0 for n = 0; c[0] = 0 for n = 1):
+    output frame j interpolates between the source frames whose doubled centres m[f] = c[f] + c[f + 1] enclose (2j + 1) Q, so it is
+    settled once (2j + 1) Q <= m[n - 1] - the count is #{j >= 0 : (2j + 1) Q <= c[n - 1] + c[n]} = (c[n - 1] + c[n] + Q) // 2Q.
+    At rate 1 that is n: no lag.  ``final``: the utterance ends at frame n, and the count is ``warped_length``'s integer, 0 for
+    c[n] = 0 and else max(1, (c[n] + Q / 2) >> 20).  The host mirrors c from the stretches it passed (``stretch_q``), so it knows
+    every count without a read-back."""
+    try:
+        a, b = (None if isinstance(v, bool) else operator.index(v) for v in (cum_before_last, cum_last))
+    except TypeError:
+        a = b = None
+    if a is None or b is None or not 0 <= a <= b:
+        raise ValueError("settled_length: needs integers 0 <= c[n - 1] <= c[n], got %r and %r" % (cum_before_last, cum_last))
+    if final:
+        return 0 if b == 0 else max(1, (b + Q // 2) >> 20)
+    return 0 if b == 0 else (a + b + Q) // (2 * Q)
 
 
 def _lengths(lengths, B, hi, dev, who, what):
@@ -323,3 +346,102 @@ def symbol_spans(warped_or_cum, path, input_lengths, lengths, hop, *, trim_bound
         _lib.call("t2s_warp_spans", p(cum), p(fl), B, F, T_in, p(in_len), p(lens_d), hop, p(t0), p(t1), p(off), up, down, total,
                   p(total_d), p(spans), _lib.current_stream())
     return spans
+
+
+class WarpStream:
+    """``warp_mel`` at one rate for all entries, pushed piece by piece while the mel is still decoded (csrc/stream_ctl.hip).
+
+    ``n_mel`` channels, ``capacity`` source frames at most (the decoder's max_decoder_steps), ``dtype`` float32 or float16,
+    ``rate`` in [1 / 8, 8].  ``push(mel_piece [B, n_mel, n], last, rate=None)`` returns the warped frames that became settled -
+    [B, n_mel, n'], possibly empty - and on the push flagged ``last`` everything up to ``warped_length``; the concatenation of the
+    pieces is ``warp_mel(whole, None, rate).mel`` bit for bit, and the input itself at rate 1.  ``rate=`` applies to the frames of
+    this push and of later ones, so the rate can change while the stream runs: the pieces are then ``warp_mel(whole, path=piece
+    index of every frame, symbol_rates=the rates)``.  The host mirrors the cumulative map in exact integers from the stretches it
+    passed, so it knows ``settled_length`` - and with it every shape - without a read-back: a push is two launches on the caller's
+    current stream and no wait.
+
+    Attributes: ``frames_in``, ``frames_out``; ``cum`` int64 [B, capacity + 1] on the device, valid up to column ``frames_in``;
+    ``first_last`` int32 [B, n_symbols, 2] where a ``path`` was given (int32 [B, >= capacity] on the device, e.g. an
+    ``AlignmentStream``'s, which must hold a frame's symbol before the frame is pushed here): ``symbol_spans`` reads both, with
+    lengths = ``frames_in``.  The source mel known so far is kept in HBM (``streaming._MelBuffer``, as ``stream_windows`` keeps it)."""
+
+    def __init__(self, n_mel, capacity, dtype, device, rate=1.0, *, B=1, path=None, n_symbols=None, input_lengths=None):
+        from .streaming import _MelBuffer
+        who = "WarpStream"
+        T2SError = _lib.T2SError
+        try:
+            n_mel, capacity, B = (None if isinstance(v, bool) else operator.index(v) for v in (n_mel, capacity, B))
+        except TypeError:
+            n_mel = None
+        if n_mel is None or n_mel < 1 or capacity < 1 or capacity > 2 ** 30 or not 1 <= B <= 65535:
+            raise ValueError("%s: n_mel, capacity and B must be integers >= 1, capacity at most 2^30 and B at most 65535" % who)
+        if dtype not in _KINDS:
+            raise T2SError("%s: expected float32 or float16, got %s (there is no silent cast)" % (who, dtype))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise T2SError("%s: the stream lives in HBM (cuda); there is no CPU path" % who)
+        self.n_mel, self.capacity, self.dtype, self.device, self.B = n_mel, capacity, dtype, dev, B
+        self.rate = rate
+        self._path, self._ld_path, self._in_len, self.n_symbols = None, 0, None, 0
+        self.first_last = None
+        if path is not None:
+            self._path, self._ld_path, _, _, self._in_len, self.n_symbols = _path_args(path, None, input_lengths, n_symbols, B, capacity,
+                                                                                      dev, who)
+            if self._path.data_ptr() != path.data_ptr():
+                raise T2SError("%s: path must be dense along the frames (it is read again at every push)" % who)
+        with torch.cuda.device(dev):
+            self.cum = torch.empty(B, capacity + 1, dtype=torch.int64, device=dev)
+            if path is not None:
+                self.first_last = torch.empty(B, self.n_symbols, 2, dtype=torch.int32, device=dev)
+        self._mel = _MelBuffer()
+        self._c = [0, 0]                # c[n - 1], c[n] of the map, mirrored on the host
+        self.frames_in = self.frames_out = 0
+        self.ended = False
+        self._order = _lib.StreamOrder()
+
+    @property
+    def rate(self):
+        return self._rate
+
+    @rate.setter
+    def rate(self, value):
+        self._stretch = stretch_q(value)
+        self._rate = float(value)
+
+    def push(self, mel_piece, last, rate=None):
+        who = "WarpStream.push"
+        T2SError = _lib.T2SError
+        if self.ended:
+            raise T2SError("%s: a piece arrived behind the one flagged last" % who)
+        if rate is not None:
+            self.rate = rate
+        if not (torch.is_tensor(mel_piece) and mel_piece.is_cuda and mel_piece.device == self.device):
+            raise T2SError("%s: expected a mel piece on %s" % (who, self.device))
+        x = mel_piece.detach()
+        if x.dim() != 3 or x.size(0) != self.B or x.size(1) != self.n_mel or x.dtype != self.dtype:
+            raise T2SError("%s: a mel piece must be [%d, %d, n] %s, got %s %s" % (who, self.B, self.n_mel, self.dtype, tuple(x.shape), x.dtype))
+        n0 = self.frames_in
+        n = n0 + x.size(2)
+        if n > self.capacity:
+            raise T2SError("%s: %d frames, the stream was made for %d" % (who, n, self.capacity))
+        cur = self._order.enter(self.device)
+        if self._order.switched:
+            _lib.record_stream((self.cum, self.first_last, self._mel.buf), cur)
+        p, st, s = _lib.ptr, _lib.current_stream(), self._stretch
+        with torch.cuda.device(self.device):
+            if n > n0:
+                self._mel.append(x)
+                _lib.call("t2s_warp_window_map", self.B, self.capacity, n0, n, s, None, p(self._path), self._ld_path, p(self._in_len),
+                          self.n_symbols, p(self.cum), p(self.first_last), st)
+                self._c = [self._c[1] + (n - n0 - 1) * s, self._c[1] + (n - n0) * s]
+            self.frames_in = n
+            j0 = self.frames_out
+            j1 = max(j0, settled_length(self._c[0], self._c[1], final=bool(last)))
+            out = torch.empty(self.B, self.n_mel, j1 - j0, dtype=self.dtype, device=self.device)
+            if j1 > j0:
+                buf = self._mel.buf
+                _lib.call("t2s_warp_window_gather", p(buf), _KINDS[self.dtype], self.B, self.n_mel, self.capacity, n, buf.stride(1),
+                          buf.stride(0), p(self.cum), j0, j1, p(out), st)
+        self.frames_out = j1
+        self.ended = bool(last)
+        return out

@@ -4,7 +4,8 @@ WaveGlow's inverse flow has a finite reach, and every keyed noise value is a fun
 (sampling.py), so a window of an utterance's frames, vocoded alone with enough frames on either side - the halo - and the draws of
 its own columns, gives the audio the whole call gives for those frames.  ``vocoder_halo`` is that reach in frames, ``plan_windows``
 the schedule (pure host arithmetic), ``WaveGlow.infer_window`` / ``infer_stream`` the vocoder side, ``Tacotron.inference_stream`` the
-decoder side and ``synthesize_stream`` the two chained on one stream."""
+decoder side and ``synthesize_stream`` the two chained on one stream.  ``StreamControl`` is what its ``control=`` takes: the speaking
+rate (``rate.WarpStream``), symbol timestamps and the alignment watchdog (``alignment.AlignmentStream``) inside the stream."""
 import torch
 
 from . import _lib
@@ -148,8 +149,142 @@ def stream_windows(waveglow, pieces, sigma, seed, first_frames, window_frames, h
         raise _lib.T2SError("%s: the pieces ended without one flagged last" % who)
 
 
+class StreamControl:
+    """What ``synthesize_stream(control=)`` takes - one per utterance, or a callable without arguments that makes one - and the side
+    channel the caller reads between pieces and afterwards; the stream keeps yielding bare audio tensors.
+
+      speed       None, or a rate in [1 / 8, 8]: every mel_post piece goes through a ``rate.WarpStream`` between the two models, and
+                  the audio is ``infer(warp_mel(mel_post, speed).mel)``'s.  ``ctl.speed = x`` between pieces takes effect from the
+                  next mel piece on (a stream that began with ``speed=None`` and without timestamps has no warp to change)
+      check       None, or an ``alignment.AlignmentCheck``: every alignment piece goes through an ``alignment.AlignmentStream``,
+                  whose live flags - SKIP, BACK, STALL, NONFINITE - are copied to page-locked memory behind every piece.  The
+                  flags of piece k are read before anything of piece k + 1 is issued; the decoder's stop poll in between has
+                  already waited for that stream, so the read adds no wait
+      on_fail     "stop": on non-zero flags piece k + 1 is discarded, the decoder is closed and the utterance ends at the last
+                  frame whose mel_post had been yielded through piece k - the vocoder's last windows and the delivery are flushed
+                  as at an utterance's end, and ``aborted`` is True.  "flag": the flags are only recorded
+      timestamps  True: the warp's cumulative map and every symbol's first and last frame are kept on the device, and ``spans()``
+                  reads them
+
+    Readable at any time: ``frames_in`` / ``frames_out`` (mel_post frames taken and frames handed to the vocoder), ``flags`` (host
+    int, the latest read), ``aborted``, ``path`` (int32 [1, frames] on the device), ``report()`` (an ``AlignmentReport`` of the
+    prefix, on the device) and ``spans(ratio, total)``."""
+
+    def __init__(self, speed=None, check=None, on_fail="stop", timestamps=False):
+        from .alignment import AlignmentCheck
+        if check is not None and not isinstance(check, AlignmentCheck):
+            raise _lib.T2SError("StreamControl: check must be an alignment.AlignmentCheck or None, got a %s" % type(check).__name__)
+        if on_fail not in ("stop", "flag"):
+            raise ValueError("StreamControl: on_fail must be \"stop\" or \"flag\", got %r" % (on_fail,))
+        if not isinstance(timestamps, bool):
+            raise ValueError("StreamControl: timestamps must be True or False, got %r" % (timestamps,))
+        self.check, self.on_fail, self.timestamps = check, on_fail, timestamps
+        self._speed = None
+        self._align = self._warp = None
+        self._began = False
+        self.speed = speed
+        self.frames_in = self.frames_out = 0
+        self.flags = 0
+        self.aborted = False
+
+    @property
+    def speed(self):
+        return self._speed
+
+    @speed.setter
+    def speed(self, value):
+        from .rate import stretch_q
+        if value is None:
+            if self._began and self._warp is not None:
+                raise ValueError("StreamControl: the stream warps already; speed=None cannot be set while it runs (1.0 is the identity)")
+        else:
+            stretch_q(value)                # (raises ValueError on anything but a rate in [1 / 8, 8])
+            if self._began and self._speed is None and not self.timestamps:
+                raise _lib.T2SError("StreamControl: the stream began with speed=None and has no warp to change; begin it with speed=1.0")
+            value = float(value)
+        self._speed = value
+
+    def _begin(self, capacity, stride):
+        if self._began:
+            raise _lib.T2SError("synthesize_stream: a StreamControl serves one utterance (pass a callable that makes one per call)")
+        self._began = True
+        self._capacity, self._stride = int(capacity), int(stride)
+
+    def _feed(self, piece):
+        """one decoder piece -> the mel piece the vocoder takes"""
+        from .alignment import AlignmentCheck, AlignmentStream
+        from .rate import WarpStream
+        _, mel, _, align, last = piece
+        dev = mel.device
+        if self._align is None and (self.check is not None or self.timestamps):
+            off = AlignmentCheck(-1, -1, -1, -1, 0.0, 0)           # timestamps alone: the path is wanted, no bit is
+            self._align = AlignmentStream(self.check if self.check is not None else off, align.size(2), self._capacity, dev)
+        if self._align is not None:
+            self._align.push(align, last)
+        if self._warp is None and (self._speed is not None or self.timestamps):
+            path = self._align.path if self.timestamps else None
+            self._warp = WarpStream(mel.size(1), self._capacity, mel.dtype, dev, 1.0 if self._speed is None else self._speed,
+                                    path=path, n_symbols=align.size(2) if self.timestamps else None)
+        self._empty = mel[:, :, :0]
+        out = mel if self._warp is None else self._warp.push(mel, last, rate=self._speed)
+        self.frames_in += mel.size(2)
+        self.frames_out += out.size(2)
+        return out
+
+    def _read_flags(self):
+        """the flags of the latest alignment piece, from page-locked memory -> whether the stream has to stop"""
+        if self._align is None or self.check is None or not self._align.pushes:
+            return False
+        self.flags = int(self._align.wait()[0][0])
+        self.aborted = bool(self.flags) and self.on_fail == "stop" and not self._align.ended
+        return self.aborted
+
+    def _flush(self):
+        """the utterance ends here: what the warp still holds back"""
+        if self._warp is None:
+            return self._empty
+        out = self._warp.push(self._empty, True)
+        self.frames_out += out.size(2)
+        return out
+
+    @property
+    def path(self):
+        if self._align is None:
+            raise _lib.T2SError("StreamControl.path: needs check= or timestamps=True, and a first piece")
+        return self._align.path[:, :self._align.frames]
+
+    def report(self):
+        if self._align is None:
+            raise _lib.T2SError("StreamControl.report: needs check= or timestamps=True, and a first piece")
+        return self._align.report()
+
+    def spans(self, ratio=(1, 1), total=None):
+        """int64 [1, T_in, 2] on the device: every symbol's [start, end) so far, in samples of the audio the stream delivers -
+        ``rate.symbol_spans`` over the stream's own map with hop = the vocoder's stride, ``ratio`` = (up, down) of the delivery's
+        resampler and ``total`` its length where known.  A symbol no frame has attended to yet is (-1, -1)."""
+        from .rate import WarpedMel, symbol_spans
+        if not self.timestamps:
+            raise _lib.T2SError("StreamControl.spans: the control was made with timestamps=False")
+        if self._warp is None:
+            raise _lib.T2SError("StreamControl.spans: no piece has been decoded yet")
+        w = self._warp
+        return symbol_spans(WarpedMel(None, None, w.cum, w.first_last, None), None, None, [w.frames_in], self._stride, ratio=ratio,
+                            total=total)
+
+
+def _control_pieces(mels, ctl):
+    """inference_stream's pieces through a StreamControl -> (mel piece, last) for stream_windows"""
+    for piece in mels:
+        if ctl._read_flags():               # piece k's flags, before anything of piece k + 1 is issued: k + 1 is discarded
+            mels.close()
+            yield ctl._flush(), True
+            return
+        yield ctl._feed(piece), piece[4]
+    ctl._read_flags()
+
+
 def synthesize_stream(tacotron, waveglow, ids, speaker_id=None, seed=None, sigma=0.666, denoiser=None, strength=0.1, first_frames=32,
-                      window_frames=128, halo=None, pcm16=False, delivery=None):
+                      window_frames=128, halo=None, pcm16=False, delivery=None, control=None):
     """Text to audio pieces: ``tacotron.inference_stream`` feeding ``waveglow.infer_stream`` on one stream.  A generator of audio
     pieces [1, n] (float32, or int16 with ``pcm16``) whose concatenation is the utterance; the first one exists once
     first_frames + halo frames are decoded, not after the last frame.  ``seed`` (required) keys both the prenet masks and the
@@ -165,10 +300,23 @@ def synthesize_stream(tacotron, waveglow, ids, speaker_id=None, seed=None, sigma
     ``delivery``: an ``audio.DeliveryStream`` (one per utterance), or a callable without arguments that makes one.  Every piece -
     denoised where there is a denoiser - is pushed through it, the last one flagged, and what comes out is yielded: resampled,
     limited and encoded audio whose concatenation is the whole-utterance chain applied to the plain stream's concatenation, bit
-    for bit.  A push that gives nothing yields nothing.  Not together with ``pcm16`` (the stream has its own encoding); the
-    speaking rate, timestamps and the alignment check are not part of a stream."""
+    for bit.  A push that gives nothing yields nothing.  Not together with ``pcm16`` (the stream has its own encoding).
+
+    ``control``: a ``StreamControl`` (one per utterance), or a callable without arguments that makes one: the speaking rate, symbol
+    timestamps and the alignment watchdog inside the stream.  The chain is then inference_stream -> ``WarpStream.push`` of every
+    mel_post piece -> the vocoder's windows -> denoiser -> delivery, with every alignment piece pushed into an ``AlignmentStream``;
+    the control object is the side channel, the stream keeps yielding bare audio.  With ``control=None`` the call issues the
+    launches it issued before.  Not part of a stream: per-symbol rate tables (their settled count is data on the device), a
+    reaction inside the piece that failed (a host wait per chunk), decoding a failed stream again, B > 1, trimming."""
     if tacotron.training or waveglow.training:
         raise _lib.T2SError("synthesize_stream runs in eval mode only (call .eval() on both models)")
+    if control is not None and not isinstance(control, StreamControl):
+        if not callable(control):
+            raise _lib.T2SError("synthesize_stream: control must be a streaming.StreamControl or a callable that makes one, got a %s"
+                                % type(control).__name__)
+        control = control()
+        if not isinstance(control, StreamControl):
+            raise _lib.T2SError("synthesize_stream: control() returned a %s, not a streaming.StreamControl" % type(control).__name__)
     if delivery is not None:
         if pcm16:
             raise _lib.T2SError("synthesize_stream: delivery= and pcm16=True exclude each other (ask the DeliveryStream for \"pcm16\")")
@@ -189,14 +337,16 @@ def synthesize_stream(tacotron, waveglow, ids, speaker_id=None, seed=None, sigma
                                 % (denoiser.stft.hop_length, stride))
         margin = -(-denoiser.stft.filter_length // stride)
     mels = tacotron.inference_stream(ids, speaker_id, seed=seed)
+    if control is not None:
+        control._begin(tacotron.decoder.max_decoder_steps, stride)
     return _synthesize(mels, waveglow, seed, sigma, denoiser, strength, first_frames, window_frames, halo, margin, stride, pcm16,
-                       delivery)
+                       delivery, control)
 
 
 def _synthesize(mels, waveglow, seed, sigma, denoiser, strength, first_frames, window_frames, halo, margin, stride, pcm16,
-                delivery=None):
+                delivery=None, control=None):
     from . import audio as A
-    pieces = ((p[1], p[4]) for p in mels)
+    pieces = ((p[1], p[4]) for p in mels) if control is None else _control_pieces(mels, control)
     for audio, f0, f1, g0, g1, last in stream_windows(waveglow, pieces, sigma, seed, first_frames, window_frames, halo, margin,
                                                       "synthesize_stream", flag_last=True):
         if denoiser is not None:
@@ -206,5 +356,10 @@ def _synthesize(mels, waveglow, seed, sigma, denoiser, strength, first_frames, w
             yield A.to_pcm16(audio) if pcm16 else audio
             continue
         out = delivery.push(audio, last)
+        if out.size(1):
+            yield out
+    if delivery is not None and control is not None and control.aborted and not delivery._ended:
+        # (the watchdog cut the utterance at a frame the windows had already delivered: the delivery still ends as one ends)
+        out = delivery.push(control._empty.new_empty(control._empty.size(0), 0, dtype=torch.float32), True)
         if out.size(1):
             yield out
