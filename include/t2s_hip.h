@@ -1398,6 +1398,69 @@ int t2s_warp_window_map(int B, int N_cap, int n0, int n, long stretch, const lon
 int t2s_warp_window_gather(const void* x, int src_kind, int B, int C, int N_cap, int n, long ld_row, long ld_entry, const long* cum,
                            long j0, long j1, void* out, void* stream);
 
+/* ---- IIR filtering in device memory: cascades of second-order sections (additive to ABI version 4; audio.py SosFilter /
+ *      FilterStream, data.py PcmPool.filter, DeliveryStream(pre_filter=, post_filter=), longform.py filter_long; csrc/sosfilt.hip) ----
+ * A filter is n sections, 1 <= n <= t2s_sos_max_sections() (8: order 16), scipy.signal.sosfilt's: rows b0 b1 b2 a0 a1 a2 with
+ * a0 = 1.  For a mono row of samples v[i] (int16, f32 or f16, each widened to double exactly) and a row gain g (gains[r], or 1
+ * without gains), all in double:
+ *     x[i] = v[i] g, and +0.0 where that product is not finite (a NaN or an infinity would otherwise reach the end of the row, and
+ *            a stream cannot take back what it has delivered).  Each such i is counted in the row's `nonfinite`.
+ *     every section, transposed direct form II, from a zero state at the row's first sample:
+ *            y = b0 x + s1,    s1 = b1 x - a1 y + s2,    s2 = b2 x - a2 y        (each product-and-sum one fused multiply-add)
+ *     the output of section j is the input of section j + 1.
+ *     f32 destination: (float)y, one rounding.  int16 destination: rint(y), ties to even, saturated to [-32768, 32767]; each i with
+ *            rint(y) outside that range is counted in the row's `clipped`.  An int16 row is filtered in the code domain unless a
+ *            gain scales it (1 / 32768 brings it to [-1, 1) for an f32 destination).
+ * The recursion runs in parallel along the row (csrc/sosfilt.hip): segments of t2s_sos_segment() samples, 256 to a tile of
+ * t2s_sos_tile(), counted from the row's first sample.  Section by section, every segment is filtered from a zero state, the 256
+ * end states are chained by a scan with the powers of the section's zero-input map, and the segment is filtered again from the
+ * state in front of it; tiles are chained by the cascade's 2n x 2n zero-input map across a kernel boundary.  This is NOT the
+ * sequential recursion's rounding: the result differs from scipy.signal.sosfilt in double by the reordering, which
+ * profiles/filter_tests.md records (a pole pair at a few Hz, e.g. a 5 Hz high-pass at 48 kHz, is the kind of filter that direct-form
+ * double arithmetic itself does not hold to a float32 ulp).  Every sum has one order that depends on the row's length alone, so a
+ * row's samples and counts are the same bits alone and at any place of any batch or pool, at any alignment, whatever lies behind
+ * its length.  The kernels do not judge stability; audio.py refuses a pole of radius >= 1.
+ *  tab: t2s_sos_table_doubles() (552) doubles in device memory, built on the host in double by running the recurrence on unit states
+ *    with zero input (audio.py sos_table): [5 j, 5 j + 5) b0 b1 b2 a1 a2 of section j; [40 + 32 j + 4 k, + 4) the 2 x 2 row-major
+ *    zero-input map of section j's state (s1, s2) over segment 2^k samples, k = 0 .. 7; [296, 296 + (2 n)^2) the 2n x 2n row-major
+ *    map of the cascade's state (s1, s2 of section 0, s1, s2 of section 1, ...) over a tile.
+ *  t2s_sos_tile / t2s_sos_segment / t2s_sos_max_sections / t2s_sos_table_doubles: host only (4096, 16, 8, 552).
+ *  t2s_sos_scratch: host only, the doubles of scratch for n_rows rows of at most max_count samples: 2 n per tile (-1 for arguments
+ *    the call would refuse).
+ *  t2s_sos_filter: table [n_rows][4] = (src_start, src_count, dst_start, dst_cap), int64 in device memory, any value safe as
+ *    t2s_loud_apply's: nothing outside [0, src_len) is read, a row longer than max_count is cut there, stores land only inside
+ *    [dst_start, dst_start + dst_cap) cut to max_out and to [0, dst_len).  The row gets min(count, dst_cap) samples and +0 behind
+ *    them up to dst_cap.  src_kind 0 int16, 1 f32, 2 f16; dst_kind 0 int16 (from int16 only), 1 f32.  counts: int32 [n_rows][2] =
+ *    (nonfinite over the row's samples, clipped over the stored ones); the call zeroes them on the stream first.  Two or three
+ *    launches (no tile pass where max_count is below a tile); nothing waits across workgroups.
+ *  The stream form.  carry: t2s_sos_window_carry(n) bytes a row (16 n + 4 tile), 8-byte aligned, [B] rows packed: the cascade's state
+ *    at the start of the row's current tile (2n doubles), then the row's samples since then as f32 (fewer than a tile).  A new
+ *    stream's carry is all zero bytes; its counts are zero and accumulate.
+ *  t2s_sos_window: piece f32 (is_half 0) or f16 [B] rows of n >= 0 samples, ldp apart, at global position N0 of the row (the host
+ *    knows it: the sum of the pieces so far); out f32 [B] rows of n, ldo apart.  The window stages carry | piece from the tile's
+ *    start, N0 % tile samples back, and runs the same kernels, the chain starting from the carried state; a scanned state depends
+ *    only on the lanes in front of it and an output only on the samples in front of it, so the piece's outputs are the whole row's
+ *    bits for ANY piece lengths, and after the last piece counts are the whole row's.  carry_out (another buffer: ping-pong)
+ *    receives the next carry; n = 0 copies it.  scratch: t2s_sos_scratch(B, N0 % tile + n, n_sections) doubles.  A causal filter
+ *    holds nothing back: there is no final flag.
+ *  T2S_EINVAL, with nothing launched and nothing written: a NULL src, table, tab, scratch, dst, counts, carry_in or carry_out, a NULL
+ *    piece or out with n > 0; src_len, dst_len, n_rows, B, max_count or max_out <= 0; n_rows or B > 65535; max_count or N0 % tile + n
+ *    > 2^31 - 1; max_out or N0 > 2^40; n < 0; ldp or ldo < n; n_sections outside [1, 8]; a kind out of range or f32 / f16 -> int16;
+ *    scratch_len below t2s_sos_scratch's; a misaligned table, gains, tab, scratch, carry (8 bytes), counts or out (4), src, dst or
+ *    piece (its element); src overlapping dst; carry_in overlapping carry_out. */
+int t2s_sos_tile(void);
+int t2s_sos_segment(void);
+int t2s_sos_max_sections(void);
+int t2s_sos_table_doubles(void);
+long t2s_sos_scratch(int n_rows, long max_count, int n_sections);
+int t2s_sos_filter(const void* src, int src_kind, long src_len, const long* table, int n_rows, long max_count, const double* gains,
+                   const double* tab, int n_sections, double* scratch, long scratch_len, void* dst, int dst_kind, long dst_len,
+                   long max_out, int* counts, void* stream);
+int t2s_sos_window_carry(int n_sections);
+int t2s_sos_window(const void* carry_in, void* carry_out, const void* piece, int is_half, int B, long n, long ldp, long N0,
+                   const double* gains, const double* tab, int n_sections, double* scratch, long scratch_len, float* out, long ldo,
+                   int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

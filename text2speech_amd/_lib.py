@@ -143,6 +143,14 @@ SIGNATURES = {
     "t2s_limit_window": [c_vp, c_vp, c_vp, c_int, c_int, c_long, c_long, c_long, c_long, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int,
                          c_double, c_vp, c_long, c_long, c_vp, c_vp],
     "t2s_g711": [c_vp, c_long, c_int, c_vp, c_vp],
+    "t2s_sos_tile": [],
+    "t2s_sos_segment": [],
+    "t2s_sos_max_sections": [],
+    "t2s_sos_table_doubles": [],
+    "t2s_sos_scratch": [c_int, c_long, c_int],
+    "t2s_sos_filter": [c_vp, c_int, c_long, c_vp, c_int, c_long, c_vp, c_vp, c_int, c_vp, c_long, c_vp, c_int, c_long, c_long, c_vp, c_vp],
+    "t2s_sos_window_carry": [c_int],
+    "t2s_sos_window": [c_vp, c_vp, c_vp, c_int, c_int, c_long, c_long, c_long, c_vp, c_vp, c_int, c_vp, c_long, c_vp, c_long, c_vp, c_vp],
     "t2s_join_tile": [],
     "t2s_join_offsets": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_long, c_vp, c_vp, c_vp],
     "t2s_join_gather": [c_vp, c_int, c_int, c_int, c_long, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_long, c_vp],
@@ -209,7 +217,8 @@ for _n in ("t2s_wg_start", "t2s_wg_in_cond_gate_fold", "t2s_wg_res_only"):
 del _n
 _RESTYPE = {"t2s_error_string": ctypes.c_char_p, "t2s_last_hip_error": ctypes.c_char_p,
             "t2s_small_wgrad_scratch": ctypes.c_long, "t2s_taco_lstm_xbuf_bytes": ctypes.c_long, "t2s_loud_scratch": ctypes.c_long,
-            "t2s_limit_scratch": ctypes.c_long, "t2s_resample_window_end": ctypes.c_long, "t2s_limit_window_end": ctypes.c_long}
+            "t2s_limit_scratch": ctypes.c_long, "t2s_resample_window_end": ctypes.c_long, "t2s_limit_window_end": ctypes.c_long,
+            "t2s_sos_scratch": ctypes.c_long}
 
 
 class T2SError(RuntimeError):

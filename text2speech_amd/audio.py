@@ -39,7 +39,8 @@ from . import _lib
 __all__ = ["STFT", "TacotronSTFT", "Denoiser", "griffin_lim", "mel_filterbank", "dynamic_range_compression",
            "dynamic_range_decompression", "to_pcm16", "from_pcm16", "Resampler", "resample_filter", "Trimmer", "Loudness", "LoudnessReport",
            "loudness_coefficients", "Limiter", "LimiterReport", "limiter_window", "LIMIT_FLAG_LIMITED", "LIMIT_FLAG_NONFINITE",
-           "LIMIT_MAX_LOOKAHEAD", "DeliveryStream", "DELIVERY_ENCODINGS", "to_ulaw", "to_alaw", "join_batches", "join_batch"]
+           "LIMIT_MAX_LOOKAHEAD", "DeliveryStream", "DELIVERY_ENCODINGS", "to_ulaw", "to_alaw", "join_batches", "join_batch",
+           "SosFilter", "FilterStream", "FilterReport", "sos_table", "sos_preemphasis", "sos_deemphasis", "sos_butter", "SOS_MAX_SECTIONS"]
 
 
 def _ru(a, b):
@@ -771,6 +772,303 @@ class Limiter:
     __call__ = forward
 
 
+SOS_MAX_SECTIONS = 8           # the library's limits and geometry (include/t2s_hip.h)
+SOS_TABLE_DOUBLES = 552
+
+FilterReport = collections.namedtuple("FilterReport", "nonfinite clipped")
+
+
+def _check_sos(sos, what="SosFilter"):
+    """`sos` as a validated float64 [n, 6] array (scipy.signal.sosfilt's layout, a0 = 1, every pole inside the unit circle);
+    anything else raises T2SError naming the offending value.  Host only."""
+    T2SError = _lib.T2SError
+    try:
+        s = np.array(sos, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise T2SError("%s: sos must be an array [n, 6] of numbers (%s)" % (what, e))
+    if s.ndim != 2 or s.shape[1] != 6:
+        raise T2SError("%s: sos must have shape [n, 6] (b0 b1 b2 a0 a1 a2), got %s" % (what, tuple(s.shape)))
+    n = s.shape[0]
+    if not 1 <= n <= SOS_MAX_SECTIONS:
+        raise T2SError("%s: %d sections, from 1 to %d" % (what, n, SOS_MAX_SECTIONS))
+    for j in range(n):
+        if not np.all(np.isfinite(s[j])):
+            raise T2SError("%s: section %d holds a coefficient that is not finite: %s" % (what, j, s[j].tolist()))
+        if s[j, 3] != 1.0:
+            raise T2SError("%s: section %d has a0 = %r, it must be exactly 1 (normalise the section)" % (what, j, float(s[j, 3])))
+        radius = float(np.max(np.abs(np.roots(s[j, 3:]))))
+        if not radius < 1.0:
+            raise T2SError("%s: section %d has a pole of radius %.17g, it must lie inside the unit circle" % (what, j, radius))
+    return s
+
+
+def _sos_zero_input(sos, steps, marks):
+    """The cascade `sos` [n, 6] run for `steps` samples with zero input from each unit state of its 2n-vector (s1, s2 of section 0,
+    s1, s2 of section 1, ...), in float64, one column per unit state: {m: the 2n x 2n map after m samples} for m in marks."""
+    n = sos.shape[0]
+    st = np.eye(2 * n)                                          # st[2 j], st[2 j + 1]: s1, s2 of section j, one column per start
+    out = {}
+    for t in range(1, steps + 1):
+        x = np.zeros(2 * n)
+        for j in range(n):
+            b0, b1, b2, _, a1, a2 = sos[j]
+            y = b0 * x + st[2 * j]
+            st[2 * j] = (b1 * x + st[2 * j + 1]) - a1 * y
+            st[2 * j + 1] = b2 * x - a2 * y
+            x = y
+        if t in marks:
+            out[t] = st.copy()
+    return out
+
+
+def sos_table(sos, segment, lanes=256):
+    """t2s_sos_filter's `tab` (include/t2s_hip.h states the layout), float64 [552]: the sections' coefficients, every section's 2 x 2
+    zero-input map over segment 2^k samples, k = 0 .. log2(lanes) - 1, and the cascade's 2n x 2n map over a tile of `lanes`
+    segments - each formed by running the recurrence itself on unit states with zero input, so the kernel, the restatement in
+    tests/filter_ref.py and this table agree on the numbers."""
+    s = _check_sos(sos, "sos_table")
+    n, segment = s.shape[0], int(segment)
+    steps = int(lanes).bit_length() - 1
+    assert 1 << steps == lanes and steps == 8 and segment >= 1
+    out = np.zeros(SOS_TABLE_DOUBLES)
+    marks = [segment << k for k in range(steps)]
+    for j in range(n):
+        out[5 * j:5 * j + 5] = [s[j, 0], s[j, 1], s[j, 2], s[j, 4], s[j, 5]]
+        maps = _sos_zero_input(s[j:j + 1], marks[-1], set(marks))
+        for k, m in enumerate(marks):
+            out[40 + 32 * j + 4 * k:44 + 32 * j + 4 * k] = maps[m].reshape(-1)
+    tile = segment * lanes
+    out[296:296 + 4 * n * n] = _sos_zero_input(s, tile, {tile})[tile].reshape(-1)
+    return out
+
+
+def sos_preemphasis(k=0.97):
+    """The reference's preemphasis (utils/audio.py:24-27), scipy.signal.lfilter([1, -k], [1], x), as one section: float64 [1, 6]"""
+    if not _real(k):
+        raise _lib.T2SError("sos_preemphasis: k must be a finite number, got %r" % (k,))
+    return np.array([[1.0, -float(k), 0.0, 1.0, 0.0, 0.0]])
+
+
+def sos_deemphasis(k=0.97):
+    """The reference's inv_preemphasis (utils/audio.py:30-33), scipy.signal.lfilter([1], [1, -k], x), as one section"""
+    if not _real(k) or not abs(k) < 1.0:
+        raise _lib.T2SError("sos_deemphasis: k must be a number inside (-1, 1) (the pole), got %r" % (k,))
+    return np.array([[1.0, 0.0, 0.0, 1.0, -float(k), 0.0]])
+
+
+def sos_butter(order, cutoff_hz, kind, sampling_rate):
+    """A Butterworth design as sections, scipy.signal.butter(order, cutoff_hz, kind, fs=sampling_rate, output="sos"): float64
+    [n, 6].  kind "highpass" or "lowpass" with one cutoff, "bandpass" with (low, high); a band-pass of order N has 2N poles."""
+    from scipy.signal import butter
+    T2SError = _lib.T2SError
+    what = "sos_butter"
+    if kind not in ("highpass", "lowpass", "bandpass"):
+        raise T2SError("%s: kind must be 'highpass', 'lowpass' or 'bandpass', got %r" % (what, kind))
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order < 1:
+        raise T2SError("%s: order must be a positive integer, got %r" % (what, order))
+    if not _real(sampling_rate) or sampling_rate <= 0:
+        raise T2SError("%s: sampling_rate must be a positive number, got %r" % (what, sampling_rate))
+    cut = [cutoff_hz] if _real(cutoff_hz) else (list(cutoff_hz) if isinstance(cutoff_hz, (list, tuple, np.ndarray)) else None)
+    if cut is None or len(cut) != (2 if kind == "bandpass" else 1) or not all(_real(c) and 0 < c < sampling_rate / 2 for c in cut) \
+            or (len(cut) == 2 and not cut[0] < cut[1]):
+        raise T2SError("%s: a %s needs %s inside (0, %g) Hz, got %r"
+                       % (what, kind, "(low, high) cutoffs, low < high," if kind == "bandpass" else "one cutoff", sampling_rate / 2,
+                          cutoff_hz))
+    sections = int(order) if kind == "bandpass" else -(-int(order) // 2)
+    if sections > SOS_MAX_SECTIONS:
+        raise T2SError("%s: order %d as a %s is %d sections, the most is %d" % (what, order, kind, sections, SOS_MAX_SECTIONS))
+    return np.ascontiguousarray(butter(int(order), cut if len(cut) == 2 else cut[0], kind, fs=float(sampling_rate), output="sos"),
+                                dtype=np.float64)
+
+
+class SosFilter:
+    """An IIR filter in HBM (csrc/sosfilt.hip): a cascade of second-order sections, `sos` float64 [n, 6] in scipy.signal.sosfilt's
+    layout (1 <= n <= 8, a0 = 1, every pole inside the unit circle: anything else raises T2SError here, on the host, before
+    anything is uploaded).  include/t2s_hip.h states the arithmetic: every section in double from a zero state at the row's first
+    sample, a sample that is not finite entering as +0 and counted.  The recursion runs in parallel along the row, so the result
+    is scipy's to a rounding-reordering error that profiles/filter_tests.md records, not bit for bit - but a row's bits are the same
+    alone, in any batch or pool, and cut into the pieces of a stream (stream()).  `sampling_rate` (optional) names the rate the design
+    is for: a pool or a DeliveryStream at another rate then refuses it.  Mono; nothing is read back; every launch goes to the
+    caller's current stream."""
+
+    def __init__(self, sos, sampling_rate=None, device="cuda"):
+        self.sos = _check_sos(sos, "SosFilter")
+        if sampling_rate is not None and (not _real(sampling_rate) or sampling_rate <= 0):
+            raise _lib.T2SError("SosFilter: sampling_rate must be None or a positive number, got %r" % (sampling_rate,))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.T2SError("SosFilter: the filter table lives in HBM (cuda); there is no CPU path")
+        self.n_sections = int(self.sos.shape[0])
+        self.sampling_rate = sampling_rate
+        self.device = dev
+        self._tab_host = self._tab_dev = None       # uploaded by the first call (4.4 KB, a blocking copy): constructing needs no device
+
+    def table(self):
+        """The host table (sos_table at the library's segment and tile), float64 [552]"""
+        if self._tab_host is None:
+            lib = _lib.load()
+            self._tab_host = sos_table(self.sos, lib.t2s_sos_segment(), lib.t2s_sos_tile() // lib.t2s_sos_segment())
+        return self._tab_host
+
+    def _tab(self, dev):
+        if self._tab_dev is None or self._tab_dev.device != dev:
+            # (blocking, so that the table is whole before any stream can read it)
+            self._tab_dev = torch.from_numpy(self.table()).to(dev)
+        return self._tab_dev
+
+    def _filter(self, src, table4, n_rows, max_count, gains, dst, max_out, counts=None):
+        """t2s_sos_filter over `table4` (device int64 [n_rows, 4]) of the flat device tensor `src` into the flat `dst` -> counts
+        int32 [n_rows, 2] (nonfinite, clipped)"""
+        p, dev = _lib.ptr, src.device
+        max_count = max(1, int(max_count))
+        if max_count > 2 ** 31 - 1:
+            raise _lib.T2SError("SosFilter: a row of %d samples, the most is 2^31 - 1" % max_count)
+        if counts is None:
+            counts = torch.empty(n_rows, 2, dtype=torch.int32, device=dev)
+        need = _lib.load().t2s_sos_scratch(n_rows, max_count, self.n_sections)
+        scratch = torch.empty(need, dtype=torch.float64, device=dev)
+        _lib.call("t2s_sos_filter", p(src), _KINDS[src.dtype], src.numel(), p(table4), n_rows, max_count, p(gains), p(self._tab(dev)),
+                  self.n_sections, p(scratch), need, p(dst), _KINDS[dst.dtype], dst.numel(), max(1, int(max_out)), p(counts),
+                  _lib.current_stream())
+        return counts
+
+    def filter_batch(self, audio, lengths=None, gain=None):
+        """audio [N], [B, N] or [B, 1, N] float32 or float16 in HBM (strided rows are read where they are), lengths [B] (a device
+        tensor is used where it is; None: whole rows) and gain (None, a float64 device tensor [B] or a number the samples are
+        multiplied by first) -> (audio float32 of audio's shape, FilterReport(nonfinite, clipped int32 [B]) on the device): entry
+        b's first lengths[b] samples filtered - forward(audio[b, :lengths[b]])'s bit for bit - and zeros behind them.  Samples at
+        and behind lengths[b] are never read.  Nothing is read back."""
+        what = "SosFilter.filter_batch"
+        T2SError = _lib.T2SError
+        if not torch.is_tensor(audio):
+            raise T2SError("%s: audio must be a tensor, got a %s" % (what, type(audio).__name__))
+        if torch.is_tensor(gain):
+            if gain.dtype != torch.float64 or gain.dim() != 1 or gain.numel() != audio.numel() // max(1, audio.size(-1) if audio.dim() else 1):
+                raise T2SError("%s: a gain tensor must be float64 [B], got %s %s" % (what, gain.dtype, tuple(gain.shape)))
+            if gain.device != audio.device:
+                raise T2SError("%s: gain is on %s, audio on %s" % (what, gain.device, audio.device))
+        elif gain is not None and not _real(gain):
+            raise T2SError("%s: gain must be None, a finite number or a float64 tensor [B] in HBM, got %r" % (what, gain))
+        flat, B, N, ldx, lens_d = _float_rows(audio, lengths, what, "PcmPool.filter")
+        if gain is None:
+            gains = None
+        elif torch.is_tensor(gain):
+            gains = gain.detach().contiguous()
+        else:
+            gains = torch.full((B,), float(gain), dtype=torch.float64, device=flat.device)
+        rows = torch.arange(B, dtype=torch.int64, device=flat.device)
+        out = torch.empty(B, N, dtype=torch.float32, device=flat.device)
+        table4 = torch.stack([rows * ldx, lens_d, rows * N, torch.full_like(rows, N)], 1).contiguous()
+        counts = self._filter(flat, table4, B, N, gains, out.view(-1), N)
+        return out.view(audio.shape), FilterReport(counts[:, 0], counts[:, 1])
+
+    def forward(self, audio):
+        """One clip [N] / [1, N], or whole rows [B, N] / [B, 1, N], float32 or float16 in HBM -> float32 of the same shape"""
+        return self.filter_batch(audio, None)[0]
+
+    __call__ = forward
+
+    def stream(self):
+        """A FilterStream of this filter: the row piece by piece, the pieces' outputs being forward(whole)'s bit for bit"""
+        return FilterStream(self)
+
+
+class FilterStream:
+    """A SosFilter inside a stream: push(piece [B, n] float32 or float16 in HBM, last=False) -> [B, n] float32, for ANY piece
+    lengths, 0 and 1 included; the concatenation of the outputs is filt.forward(whole) bit for bit, and after the last push report()
+    is filter_batch's of the whole rows.  A causal filter holds nothing back: a push returns exactly n samples, and `last` only
+    closes the stream.  The stream carries, in HBM and in two buffers used in turn, the cascade's state at the start of the row's
+    current tile and the row's samples since then; a push filters carry | piece from the tile's start, which gives the whole row's
+    bits because a lane's state in the scan depends on the lanes in front of it only (DESIGN.md section 6b).  Nothing is read back;
+    every launch goes to the caller's current stream; B is fixed by the first push (or open())."""
+
+    def __init__(self, filt):
+        if not isinstance(filt, SosFilter):
+            raise _lib.T2SError("FilterStream: filt must be an audio.SosFilter, got a %s" % type(filt).__name__)
+        self.filter = filt
+        self.B = None
+        self.position = 0           # samples of the row seen so far (a host integer)
+        self._ended = False
+        self._order = _lib.StreamOrder()
+
+    def open(self, B, device="cuda"):
+        """Allocates the stream's carry for B rows and uploads the filter's table (the one blocking copy, where the filter has not
+        uploaded it yet).  push() calls it with the first piece's B."""
+        if self.B is not None:
+            return self
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.T2SError("FilterStream: the stream's state lives in HBM (cuda); there is no CPU path")
+        B = int(B)
+        if not 1 <= B <= 65535:
+            raise _lib.T2SError("FilterStream: %d rows, from 1 to 65535" % B)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        self._tile = lib.t2s_sos_tile()
+        words = lib.t2s_sos_window_carry(self.filter.n_sections) // 8
+        self._tab = self.filter._tab(dev)
+        self._carry = [torch.zeros(B, words, dtype=torch.float64, device=dev) for _ in range(2)]
+        self._counts = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        self._ci = 0
+        self.B, self.device = B, dev
+        return self
+
+    def report(self):
+        """The running FilterReport (views of the stream's counts, int32 [B]) on the device"""
+        if self.B is None:
+            raise _lib.T2SError("FilterStream.report: nothing has been pushed yet")
+        return FilterReport(self._counts[:, 0], self._counts[:, 1])
+
+    def _tensors(self):
+        return (self._carry, self._counts, self._tab)
+
+    def _window(self, x, n, ldp):
+        """The rows x (n samples each, ldp apart; opened, on the stream's device) -> out float32 [B, n]; no checks"""
+        out = torch.empty(self.B, n, dtype=torch.float32, device=self.device)
+        if n:
+            lib, p, i = _lib.load(), _lib.ptr, self._ci
+            need = lib.t2s_sos_scratch(self.B, self.position % self._tile + n, self.filter.n_sections)
+            if need < 0:
+                raise _lib.T2SError("FilterStream: a piece of %d samples, the most is 2^31 - 1 less a tile" % n)
+            scratch = torch.empty(need, dtype=torch.float64, device=self.device)
+            _lib.call("t2s_sos_window", p(self._carry[i]), p(self._carry[1 - i]), p(x), int(x.dtype == torch.float16), self.B, n, ldp,
+                      self.position, None, p(self._tab), self.filter.n_sections, p(scratch), need, p(out), n, p(self._counts),
+                      _lib.current_stream())
+            self._ci = 1 - i
+            self.position += n
+        return out
+
+    def push(self, piece, last=False):
+        """piece [B, n] float32 or float16 in HBM (n may be 0; strided rows are read where they are) -> [B, n] float32.  Two
+        launches (three where carry | piece fills a tile), on the caller's current stream; the host never waits."""
+        T2SError = _lib.T2SError
+        what = "FilterStream.push"
+        if self._ended:
+            raise T2SError("%s: a piece arrived behind the one flagged last" % what)
+        if not torch.is_tensor(piece) or piece.dim() != 2:
+            raise T2SError("%s: a piece must be a tensor [B, n], got %s" % (what, tuple(piece.shape) if torch.is_tensor(piece)
+                                                                            else "a %s" % type(piece).__name__))
+        if piece.dtype not in (torch.float32, torch.float16):
+            raise T2SError("%s: expected float32 or float16, got %s" % (what, piece.dtype))
+        _need_cuda(piece, what)
+        B, n = piece.shape
+        self.open(B, piece.device)
+        if B != self.B or piece.device != self.device:
+            raise T2SError("%s: the stream was opened for %d rows on %s, the piece has %d on %s"
+                           % (what, self.B, self.device, B, piece.device))
+        x = piece.detach()
+        if n and (x.stride(1) != 1 or (B > 1 and x.stride(0) < n)):
+            x = x.contiguous()
+        ld = x.stride(0) if (B > 1 and n) else n
+        cur = self._order.enter(self.device)
+        if self._order.switched:
+            _lib.record_stream(self._tensors(), cur)
+        out = self._window(x, n, ld)
+        self._ended = bool(last)
+        return out
+
+
 DELIVERY_ENCODINGS = ("f32", "pcm16", "ulaw", "alaw")
 
 
@@ -807,6 +1105,14 @@ class DeliveryStream:
     is not known before it ends, so a stream cannot measure its own) and needs a limiter, as limit_batch(gain=) does.  `encoding`:
     "f32", "pcm16" (to_pcm16), "ulaw", "alaw" (to_ulaw / to_alaw).  At least one stage must be asked for.
 
+    `pre_filter` and `post_filter` are audio.SosFilter cascades: the first runs at src_rate in front of the resampler (de-emphasis
+    belongs here), the second at out_rate behind it and in front of the limiter (a filter changes peaks, so the limiter stays
+    last; a telephone band in front of "ulaw" belongs here).  With them the concatenation is
+
+        enc(limiter.limit_batch(post_filter.forward(Resampler(src_rate, out_rate).forward(pre_filter.forward(whole))), gain=gain)[0])
+
+    bit for bit.  A causal filter holds nothing back: `latency` does not change.  filter_report() gives their counts.
+
     push(piece [B, n] float32 or float16 in HBM, last=False) -> [B, m] (float32 / int16 / uint8; m may be 0).  Until the piece
     flagged `last`, the stream holds back up to `latency` delivery samples: what the filters still need to see.  `delivered` counts
     the samples returned so far; both are host integers.  report() is the limiter's running LimiterReport on the device: after the
@@ -815,7 +1121,7 @@ class DeliveryStream:
     finite) and raises LIMIT_FLAG_NONFINITE.  Nothing is read back; every launch goes to the caller's current stream; B is fixed by
     the first push (or open()).  Not here: measured loudness, ragged batches, one launch for both stages."""
 
-    def __init__(self, src_rate, out_rate=None, limiter=None, gain=None, encoding="f32"):
+    def __init__(self, src_rate, out_rate=None, limiter=None, gain=None, encoding="f32", pre_filter=None, post_filter=None):
         T2SError = _lib.T2SError
         what = "DeliveryStream"
         for name, v in (("src_rate", src_rate),) + ((("out_rate", out_rate),) if out_rate is not None else ()):
@@ -849,9 +1155,19 @@ class DeliveryStream:
             if max(self.up, self.down) > RESAMPLE_MAX_FACTOR:
                 raise T2SError("%s: %d -> %d Hz is the ratio %d / %d; max(up, down) may be at most %d"
                                % (what, self.src_rate, self.out_rate, self.up, self.down, RESAMPLE_MAX_FACTOR))
-        if self._h_host is None and limiter is None and encoding == "f32":
+        for name, filt, rate in (("pre_filter", pre_filter, self.src_rate), ("post_filter", post_filter, self.out_rate)):
+            if filt is None:
+                continue
+            if not isinstance(filt, SosFilter):
+                raise T2SError("%s: %s must be an audio.SosFilter or None, got a %s" % (what, name, type(filt).__name__))
+            if filt.sampling_rate is not None and filt.sampling_rate != rate:
+                raise T2SError("%s: %s was designed for %g Hz, it runs at %d Hz (pre_filter at src_rate, post_filter at out_rate)"
+                               % (what, name, filt.sampling_rate, rate))
+        if self._h_host is None and limiter is None and encoding == "f32" and pre_filter is None and post_filter is None:
             raise T2SError("%s: nothing to do - ask for another rate, a limiter or an encoding" % what)
         self.limiter, self.gain, self.encoding = limiter, gain, encoding
+        self.pre_filter, self.post_filter = pre_filter, post_filter
+        self._pre = self._post = None       # their FilterStreams, made by open()
         self.n_taps = 0 if self._h_host is None else int(self._h_host.size)
         # the carries: host arithmetic (the library's t2s_*_window_carry restate it and the tests compare)
         self.resample_carry = 0 if self._h_host is None else -(-self.n_taps // self.up)
@@ -896,6 +1212,10 @@ class DeliveryStream:
             self._state = torch.zeros(B, 5, dtype=torch.int64, device=dev)
             self._state[:, 2].fill_(0x3FF0000000000000)         # the bits of 1.0: the smallest gain so far
         self._ri = self._li = 0
+        if self.pre_filter is not None:
+            self._pre = self.pre_filter.stream().open(B, dev)
+        if self.post_filter is not None:
+            self._post = self.post_filter.stream().open(B, dev)
         self.B, self.device = B, dev
         return self
 
@@ -906,6 +1226,12 @@ class DeliveryStream:
         if self.B is None:
             raise _lib.T2SError("DeliveryStream.report: nothing has been pushed yet")
         return Limiter._report(self._state[:, :4].view(torch.float64), self._state[:, 4:].view(torch.int32))
+
+    def filter_report(self):
+        """(pre_filter's running FilterReport or None, post_filter's or None), views on the device"""
+        if self.B is None:
+            raise _lib.T2SError("DeliveryStream.filter_report: nothing has been pushed yet")
+        return tuple(None if fs is None else fs.report() for fs in (self._pre, self._post))
 
     def _resample(self, x, n, ldp, final):
         lib, p = _lib.load(), _lib.ptr
@@ -963,9 +1289,16 @@ class DeliveryStream:
         cur = self._order.enter(self.device)
         if self._order.switched:
             _lib.record_stream((self._rc, self._lc, self._state, self._h, self._gains), cur)
+            for fs in (self._pre, self._post):
+                if fs is not None:
+                    _lib.record_stream(fs._tensors(), cur)
         final = bool(last)
+        if self._pre is not None:
+            x, ld = self._pre._window(x, n, ld), n
         if self._h is not None:
             x, n, ld = self._resample(x, n, ld, final)
+        if self._post is not None:
+            x, ld = self._post._window(x, n, ld), n
         if self.limiter is not None:
             x, n, ld = self._limit(x, n, ld, final)
         self._ended = final

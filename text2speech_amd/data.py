@@ -24,8 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import (LOUD_FLAG_NONFINITE, LOUD_FLAG_SHORT, LOUD_FLAG_SILENT, Limiter, Loudness, Resampler, TacotronSTFT, Trimmer,
-                    _pcm16_gather, _to_device)
+from .audio import (LOUD_FLAG_NONFINITE, LOUD_FLAG_SHORT, LOUD_FLAG_SILENT, Limiter, Loudness, Resampler, SosFilter, TacotronSTFT,
+                    Trimmer, _pcm16_gather, _to_device)
 
 __all__ = ["PcmPool", "Mel2SampBatch", "TextMelBatch", "gather_width"]
 
@@ -233,6 +233,28 @@ class PcmPool:
             sl = slice(r0, min(n, r0 + chunk))
             limiter._apply(self.pcm, table4[sl], sl.stop - r0, None if gains is None else gains[sl], counts[sl], pool.pcm,
                            int(self.lengths[sl].max()))
+        return pool
+
+    def filter(self, filt):
+        """Every clip through `filt` (an audio.SosFilter, which states the rule), as a new pool at the same rate with the same
+        lengths in the same order, int16 to int16 in HBM: each clip alone from a zero state, filtered in the code domain in double
+        and stored as rint(y), ties to even, saturated.  The new pool's `.clipped` and `.nonfinite` are int32 device tensors, one
+        count per clip (the saturated samples; an int16 sample is always finite, so the second is zero).  A filter built with a
+        sampling_rate other than the pool's is refused.  Nothing is read back."""
+        what = "PcmPool.filter"
+        if not isinstance(filt, SosFilter):
+            raise T2SError("%s: filt must be an audio.SosFilter, got a %s" % (what, type(filt).__name__))
+        if filt.sampling_rate is not None and filt.sampling_rate != self.sampling_rate:
+            raise T2SError("%s: the filter was designed for %g Hz, the pool holds %g Hz" % (what, filt.sampling_rate, self.sampling_rate))
+        n, dev, chunk = len(self), self.pcm.device, 65535
+        pool = self._of(torch.empty_like(self.pcm), self.lengths, self.sampling_rate)
+        table4 = _to_device(torch.stack([self.offsets, self.lengths, pool.offsets, pool.lengths], 1).contiguous(), dev)
+        counts = torch.empty(n, 2, dtype=torch.int32, device=dev)
+        for r0 in range(0, n, chunk):
+            sl = slice(r0, min(n, r0 + chunk))
+            filt._filter(self.pcm, table4[sl], sl.stop - r0, int(self.lengths[sl].max()), None, pool.pcm, int(self.lengths[sl].max()),
+                         counts[sl])
+        pool.nonfinite, pool.clipped = counts[:, 0], counts[:, 1]
         return pool
 
     @classmethod

@@ -419,6 +419,25 @@ def limit_long(result, limiter, loudness=None):
     return result._replace(audio=audio)
 
 
+def filter_long(result, filt):
+    """A ``LongForm`` / ``LongFormChecked`` / ``LongFormTimed`` / ``LongFormCheckedTimed`` with its whole utterance through ``filt``
+    (``audio.SosFilter.filter_batch`` over ``result.audio`` and ``result.length``): the same tuple with ``audio`` replaced.  A
+    causal filter stores output i at index i, so ``length``, ``offsets``, ``spans`` and every other field are the objects given -
+    but it does delay what it passes: its group delay is NOT compensated, and a span marks where a symbol's samples went in, not
+    where the filter's response to them peaks.  Nothing is read back.  An int16 result is refused: filter first, quantise
+    afterwards."""
+    from .audio import SosFilter
+    if not isinstance(result, (LongForm, LongFormChecked, LongFormTimed, LongFormCheckedTimed)):
+        raise _lib.T2SError("filter_long: expected a LongForm result of synthesize_long, got a %s" % type(result).__name__)
+    if not isinstance(filt, SosFilter):
+        raise _lib.T2SError("filter_long: filt must be an audio.SosFilter, got a %s" % type(filt).__name__)
+    if not torch.is_tensor(result.audio) or result.audio.dtype != torch.float32:
+        raise _lib.T2SError("filter_long: the audio is %s; synthesize with pcm16=False, filter, then audio.to_pcm16"
+                            % getattr(result.audio, "dtype", type(result.audio).__name__))
+    audio, _ = filt.filter_batch(result.audio, result.length)
+    return result._replace(audio=audio)
+
+
 def _check_speed(speed, n):
     """synthesize_long_timed's ``speed`` -> None, or one rate per chunk (each checked by ``rate.stretch_q``)"""
     if speed is None:
