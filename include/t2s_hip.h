@@ -1345,7 +1345,7 @@ int t2s_warp_spans(const long* cum, const int* first_last, int B, int F, int T_i
                    const long* total_dev, long* spans, void* stream);
 
 /* ---- control inside a stream: the alignment check and the time warp, pushed piece by piece (additive to ABI version 4;
- *      alignment.py AlignmentStream, rate.py WarpStream, streaming.py synthesize_stream(control=); csrc/stream_ctl.hip) ----
+ *      alignment.py AlignmentStream, rate.py WarpStream, streaming.py synthesize_stream(control=); csrc/align.hip, csrc/warp.hip) ----
  * Both computations above are prefix computations, so a stream carries them in HBM.  Notation: all buffers hold N_cap frames (the
  * decoder's max_decoder_steps); n0 frames were seen before this push and n after it, 0 <= n0 <= n <= N_cap.  The guarantee: after
  * every push the outputs are what the whole-row entry points give for the prefix [0, n), bit for bit, whatever the cuts.

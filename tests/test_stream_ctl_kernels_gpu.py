@@ -1,4 +1,4 @@
-"""t2s_align_window / t2s_warp_window_map / t2s_warp_window_gather (csrc/stream_ctl.hip, csrc/t2s_api_stream_ctl.hip) called
+"""t2s_align_window / t2s_warp_window_map / t2s_warp_window_gather (the window kernels of csrc/align.hip and csrc/warp.hip) called
 directly on guarded, pattern-filled buffers; behind every length - and between the rows and the entries - the sources hold NaN and
 1e4, which must never be seen.
 

@@ -6,7 +6,7 @@ include/t2s_hip.h states the arithmetic): per frame the symbol it attends to, pe
 longest stall, the last symbol reached, the frames each symbol got (its duration) and the mean attention peak - and the flag bits that
 an ``AlignmentCheck``'s thresholds make of them.  ``synthesize_long(check=, max_attempts=)`` decodes a flagged chunk again under
 ``attempt_seeds``: the prenet dropout is live in eval mode, so another seed is another attention path.  ``AlignmentStream`` is the same
-report pushed piece by piece while an utterance is still decoded (csrc/stream_ctl.hip): the watchdog of
+report pushed piece by piece while an utterance is still decoded (csrc/align.hip): the watchdog of
 ``synthesize_stream(control=StreamControl(check=))``, which ends a stream whose attention fails instead of speaking it out."""
 import collections
 
@@ -173,7 +173,7 @@ LIVE = SKIP | BACK | STALL | NONFINITE      # the bits a stream's prefix can alr
 
 
 class AlignmentStream:
-    """``alignment_report`` pushed piece by piece while the utterance is still decoded (csrc/stream_ctl.hip): the watchdog of a stream.
+    """``alignment_report`` pushed piece by piece while the utterance is still decoded (csrc/align.hip): the watchdog of a stream.
 
     ``check`` an ``AlignmentCheck`` (None: the defaults; its ``max_frames=None`` is ``capacity``), ``n_symbols`` the columns of an
     alignment row, ``capacity`` the most frames there can be (the decoder's max_decoder_steps), ``B`` entries that grow together,

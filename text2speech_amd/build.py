@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libt2s_hip.so")
 SOURCES = ["conv_gemm.hip", "gate_gemm_pp.hip", "wgrad_cl.hip", "waveglow_ops.hip", "tacotron_ops.hip", "sbgemm.hip", "train_ops.hip", "taco_bwd_ops.hip", "t2s_api_taco_bwd.hip", "t2s_api.hip", "t2s_api_taco.hip",
            "t2s_api_train.hip", "audio_ops.hip", "t2s_api_audio.hip", "loss_ops.hip", "resample.hip", "trim.hip", "loudness.hip", "limiter.hip", "delivery.hip", "join.hip", "sampling.hip", "align.hip", "t2s_api_align.hip", "warp.hip",
-           "t2s_api_warp.hip", "stream_ctl.hip", "t2s_api_stream_ctl.hip", "sosfilt.hip", "t2s_api_sosfilt.hip"]
+           "t2s_api_warp.hip", "sosfilt.hip", "t2s_api_sosfilt.hip"]
 
 
 def _newest(paths):

@@ -184,14 +184,14 @@ static bool trim_frames_ok(int frame_length, int hop, int pad_mode, long max_fra
     return frame_length >= 2 && frame_length <= T2S_TRIM_MAX_FRAME && hop >= 1 && hop <= frame_length && (pad_mode == 0 || pad_mode == 1) &&
            max_frames > 0 && max_frames <= (1L << 40);
 }
-static bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
 int t2s_trim_tile(void) { return T2S_TRIM_TILE; }
 
 int t2s_trim_energy(const void* src, int src_kind, long src_len, const long* table, int n_rows, int frame_length, int hop, int pad_mode,
                     long max_frames, double* energy, long energy_len, double* stats, void* stream) {
-    if (!src || !table || !stats || !al8(table) || !al8(stats) || !al8(energy) || src_kind < 0 || src_kind > 2 || src_len <= 0 ||
-        n_rows <= 0 || n_rows > 65535 || (energy && energy_len <= 0) || !trim_frames_ok(frame_length, hop, pad_mode, max_frames))
+    if (!src || !table || !stats || !aligned_to(table, 8) || !aligned_to(stats, 8) || !aligned_to(energy, 8) || src_kind < 0 ||
+        src_kind > 2 || src_len <= 0 || n_rows <= 0 || n_rows > 65535 || (energy && energy_len <= 0) ||
+        !trim_frames_ok(frame_length, hop, pad_mode, max_frames))
         return T2S_EINVAL;
     TrimEnergyArgs a;
     memset(&a, 0, sizeof(a));
@@ -204,8 +204,8 @@ int t2s_trim_energy(const void* src, int src_kind, long src_len, const long* tab
 int t2s_trim_bounds(const long* table, int n_rows, int src_kind, long src_len, int frame_length, int hop, int pad_mode, long max_frames,
                     const double* energy, long energy_len, const double* stats, double top_db, int rescale, double rescaling_max,
                     double peak_floor, long* bounds, void* stream) {
-    if (!table || !energy || !stats || !bounds || !al8(table) || !al8(energy) || !al8(stats) || !al8(bounds) || src_kind < 0 ||
-        src_kind > 2 || src_len <= 0 || n_rows <= 0 || n_rows > 65535 || energy_len <= 0 ||
+    if (!table || !energy || !stats || !bounds || !aligned_to(table, 8) || !aligned_to(energy, 8) || !aligned_to(stats, 8) ||
+        !aligned_to(bounds, 8) || src_kind < 0 || src_kind > 2 || src_len <= 0 || n_rows <= 0 || n_rows > 65535 || energy_len <= 0 ||
         !trim_frames_ok(frame_length, hop, pad_mode, max_frames) || !finite_nonneg(top_db) || !finite_nonneg(rescaling_max) ||
         !finite_nonneg(peak_floor) || (rescale != 0 && rescale != 1) || (rescale && !(rescaling_max > 0.0)))
         return T2S_EINVAL;
@@ -221,9 +221,10 @@ int t2s_trim_bounds(const long* table, int n_rows, int src_kind, long src_len, i
 int t2s_trim_gather(const void* src, int src_kind, long src_len, const long* table, int n_rows, const long* bounds, const double* stats,
                     double rescaling_max, double peak_floor, void* dst, int dst_kind, long dst_len, long max_out, int* out_lengths,
                     void* stream) {
-    if (!src || !table || !dst || !al8(table) || !al8(bounds) || !al8(stats) || src_kind < 0 || src_kind > 2 ||
-        dst_kind != (src_kind == 0 ? 0 : 1) || src_len <= 0 || dst_len <= 0 || n_rows <= 0 || n_rows > 65535 || max_out <= 0 ||
-        max_out > (1L << 40) || !finite_nonneg(rescaling_max) || !finite_nonneg(peak_floor) || (stats && !(rescaling_max > 0.0)))
+    if (!src || !table || !dst || !aligned_to(table, 8) || !aligned_to(bounds, 8) || !aligned_to(stats, 8) || src_kind < 0 ||
+        src_kind > 2 || dst_kind != (src_kind == 0 ? 0 : 1) || src_len <= 0 || dst_len <= 0 || n_rows <= 0 || n_rows > 65535 ||
+        max_out <= 0 || max_out > (1L << 40) || !finite_nonneg(rescaling_max) || !finite_nonneg(peak_floor) ||
+        (stats && !(rescaling_max > 0.0)))
         return T2S_EINVAL;
     const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)src_len * (src_kind == 1 ? 4 : 2);
     const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)dst_len * (dst_kind == 1 ? 4 : 2);
@@ -251,11 +252,11 @@ int t2s_loud_measure(const void* src, int src_kind, long src_len, const long* ta
                      const double* coef, double* scratch, long scratch_len, double gate_abs, double target_T, double peak_limit,
                      double* stats, int* counts, void* stream) {
     // (a comparison with NaN is false, the subtraction is NaN for an infinity)
-    if (!src || !table || !coef || !scratch || !stats || !counts || !al8(table) || !al8(coef) || !al8(scratch) || !al8(stats) ||
-        ((uintptr_t)counts & 3) || src_kind < 0 || src_kind > 2 || src_len <= 0 || n_rows <= 0 || n_rows > 65535 || max_count <= 0 ||
-        max_count > 0x7fffffffL || fs_hop < T2S_LOUD_MIN_HOP || fs_hop > T2S_LOUD_MAX_HOP || T2S_LOUD_SEGMENT > fs_hop ||
-        !finite_nonneg(gate_abs) || !(target_T > 0.0) || target_T - target_T != 0.0 || peak_limit != peak_limit ||
-        scratch_len < t2s_loud_scratch(n_rows, max_count))
+    if (!src || !table || !coef || !scratch || !stats || !counts || !aligned_to(table, 8) || !aligned_to(coef, 8) ||
+        !aligned_to(scratch, 8) || !aligned_to(stats, 8) || ((uintptr_t)counts & 3) || src_kind < 0 || src_kind > 2 || src_len <= 0 ||
+        n_rows <= 0 || n_rows > 65535 || max_count <= 0 || max_count > 0x7fffffffL || fs_hop < T2S_LOUD_MIN_HOP ||
+        fs_hop > T2S_LOUD_MAX_HOP || T2S_LOUD_SEGMENT > fs_hop || !finite_nonneg(gate_abs) || !(target_T > 0.0) ||
+        target_T - target_T != 0.0 || peak_limit != peak_limit || scratch_len < t2s_loud_scratch(n_rows, max_count))
         return T2S_EINVAL;
     LoudMeasureArgs a;
     memset(&a, 0, sizeof(a));
@@ -270,7 +271,7 @@ int t2s_loud_measure(const void* src, int src_kind, long src_len, const long* ta
 
 int t2s_loud_apply(const void* src, int src_kind, long src_len, const long* table, int n_rows, const double* stats, void* dst,
                    int dst_kind, long dst_len, long max_out, int* out_lengths, void* stream) {
-    if (!src || !table || !stats || !dst || !al8(table) || !al8(stats) || src_kind < 0 || src_kind > 2 ||
+    if (!src || !table || !stats || !dst || !aligned_to(table, 8) || !aligned_to(stats, 8) || src_kind < 0 || src_kind > 2 ||
         dst_kind != (src_kind == 0 ? 0 : 1) || src_len <= 0 || dst_len <= 0 || n_rows <= 0 || n_rows > 65535 || max_out <= 0 ||
         max_out > (1L << 40))
         return T2S_EINVAL;
@@ -290,7 +291,7 @@ int t2s_join_tile(void) { return T2S_JOIN_TILE; }
 
 int t2s_join_offsets(const int* lengths, const int* row_caps, const int* order, const int* gaps, int gap, int n, float* dst,
                      long dst_cap, long* offsets, int* length, void* stream) {
-    if (!lengths || !row_caps || !dst || !offsets || !length || !al8(offsets) || n <= 0 || n > 65535 || dst_cap <= 0 ||
+    if (!lengths || !row_caps || !dst || !offsets || !length || !aligned_to(offsets, 8) || n <= 0 || n > 65535 || dst_cap <= 0 ||
         dst_cap > 0x7fffffffL || gap < 0)
         return T2S_EINVAL;
     JoinOffsetsArgs a;
@@ -303,8 +304,8 @@ int t2s_join_offsets(const int* lengths, const int* row_caps, const int* order, 
 
 int t2s_join_gather(const void* src, int src_kind, int B, int N, long ldx, const int* lengths, const int* pos, const long* offsets,
                     int n, int fade, int fade_ends, float* dst, long dst_cap, void* stream) {
-    if (!src || !lengths || !pos || !offsets || !dst || !al8(offsets) || (src_kind != 1 && src_kind != 2) || B <= 0 || B > 65535 ||
-        N <= 0 || ldx < N || n <= 0 || n > 65535 || fade < 0 || fade > 65536 || dst_cap <= 0 || dst_cap > 0x7fffffffL)
+    if (!src || !lengths || !pos || !offsets || !dst || !aligned_to(offsets, 8) || (src_kind != 1 && src_kind != 2) || B <= 0 ||
+        B > 65535 || N <= 0 || ldx < N || n <= 0 || n > 65535 || fade < 0 || fade > 65536 || dst_cap <= 0 || dst_cap > 0x7fffffffL)
         return T2S_EINVAL;
     const uintptr_t s0 = (uintptr_t)src, s1 = s0 + ((size_t)(B - 1) * ldx + N) * (src_kind == 1 ? 4 : 2);
     const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)dst_cap * 4;

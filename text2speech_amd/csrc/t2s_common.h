@@ -88,6 +88,9 @@ static __device__ __forceinline__ float fast_tanh(float x) {
     return 1.0f - 2.0f / (__expf(2.0f * x) + 1.0f);
 }
 
+// a length or an index brought into [lo, hi] before it addresses anything
+static __device__ __forceinline__ int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // wave-wide sum (64 lanes)
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -8,7 +8,7 @@ optionally carried through a ``Trimmer``'s cut, ``join_batches``' offsets and a 
 ``warped_length`` are the host's side of the definition: a caller who knows the frames and a uniform rate knows the warped length
 without a read-back.  ``synthesize_long_timed(speed=, timestamps=)`` is the chain.
 
-``WarpStream`` is the same warp pushed piece by piece (csrc/stream_ctl.hip): the cumulative map persists in HBM and is its own carry,
+``WarpStream`` is the same warp pushed piece by piece (csrc/warp.hip): the cumulative map persists in HBM and is its own carry,
 ``settled_length`` says which output frames no later frame can change, and the pieces are ``warp_mel``'s frames bit for bit -
 ``synthesize_stream(control=StreamControl(speed=))`` is that chain.
 
@@ -349,7 +349,7 @@ def symbol_spans(warped_or_cum, path, input_lengths, lengths, hop, *, trim_bound
 
 
 class WarpStream:
-    """``warp_mel`` at one rate for all entries, pushed piece by piece while the mel is still decoded (csrc/stream_ctl.hip).
+    """``warp_mel`` at one rate for all entries, pushed piece by piece while the mel is still decoded (csrc/warp.hip).
 
     ``n_mel`` channels, ``capacity`` source frames at most (the decoder's max_decoder_steps), ``dtype`` float32 or float16,
     ``rate`` in [1 / 8, 8].  ``push(mel_piece [B, n_mel, n], last, rate=None)`` returns the warped frames that became settled -

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Control inside the stream on one MI355X (streaming.StreamControl, alignment.AlignmentStream, rate.WarpStream;
-csrc/stream_ctl.hip).
+the window kernels of csrc/align.hip and csrc/warp.hip).
 
     python tools/bench_stream_control.py [--runs 12] [--out-dir profiles]
 
